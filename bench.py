@@ -1,7 +1,7 @@
 # -*- coding: utf-8 -*-
 """Headline benchmark: GP log-likelihoods / second on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 Workload (BASELINE.json configs[2] per GPU; configs[3] = the same on 8 GPUs):
     B = 1024 independent (series x hyper-parameter draw) problems per GPU,
@@ -42,6 +42,12 @@ input family at the headline shape (sparse sampling: the plan runs the warm-star
 of the scan); `sharded_product_path` times the product's own sharding (one process, one host thread + plan
 per shard: batch.ShardedBatchedGP) next to the process-per-GPU number `--gpus N` reports; `value_steady` is
 the 2.5 s steady-state leg of the real loop.
+
+`--dump-outputs DIR` writes what the LAST of the K timed steps returned -- loglike, logdet, quad and status of every
+problem -- to DIR/<name>.npy in float64 (status cast from its int32 codes).  The inputs are seeded and the timed loop's
+last step always evaluates the same draw for a given K, so two builds run with the same arguments can be compared
+output for output.  Above DUMP_MAX_BYTES in all a fixed, seeded sample of the problems is written instead, with their
+indices in DIR/index.npy.  With several ranks every rank writes its own slice as <name>_rank<r>.npy.
 """
 import argparse
 import json
@@ -251,6 +257,25 @@ def real_loop(plan, draws, steps, offset=0):
             plan.enqueue()
             out = plan.results()
     return out
+
+
+DUMP_NAMES = ("loglike", "logdet", "quad", "status")   # the order real_loop's results come in
+DUMP_MAX_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(directory, results, rank=0, world=1):
+    """--dump-outputs: the (loglike, logdet, quad, status) arrays of one step as float64 .npy files in `directory`."""
+    os.makedirs(directory, exist_ok=True)
+    arrays = [np.asarray(a, dtype=np.float64) for a in results]
+    suffix = "" if world == 1 else "_rank%d" % rank
+    n = len(arrays[0])
+    per_problem = 8 * (len(arrays) + 1)           # (+ the index array when sampled)
+    if n * 8 * len(arrays) > DUMP_MAX_BYTES:
+        keep = np.sort(np.random.RandomState(0).choice(n, (DUMP_MAX_BYTES - 4096) // per_problem, replace=False))
+        arrays = [a[keep] for a in arrays]
+        np.save(os.path.join(directory, "index%s.npy" % suffix), keep.astype(np.float64))
+    for name, a in zip(DUMP_NAMES, arrays):
+        np.save(os.path.join(directory, name + suffix + ".npy"), a)
 
 
 def roofline_block(per_kernel_ms, B, N, W, traffic=None):
@@ -661,7 +686,12 @@ def main(argv=None):
     ap.add_argument("--no-config3", action="store_true", help="skip the 8-shard B = 8192 leg (20 GB of host arrays)")
     ap.add_argument("--steady-seconds", type=float, default=2.5)
     ap.add_argument("--settle-seconds", type=float, default=0.5, help="untimed extra warm-up before the K timed steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the results of the last timed step to DIR/<name>.npy")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1 (it is the number of timed steps)")
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)     # (fails before any GPU work, not after the timed region)
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         from celerite_amd import batch as _b
@@ -692,7 +722,7 @@ def main(argv=None):
     #  on a one-GPU box; the numbers of such a run mean nothing)
     B, N, JR, JC = args.batch, args.nsamples, args.jreal, args.jcomp
     W = JR + 2 * JC
-    K, Wm = max(args.steps, 1), max(args.warmup, 0)
+    K, Wm = args.steps, max(args.warmup, 0)
 
     try:  # the fp64 rate / clock of this box (rank 0's device stands for all; a few ms, outside every timed region)
         tf, mhz, cyc = batch.measure_fp64(2, 20000, device=dist.local_rank % ndev)   # (every rank on its own GPU)
@@ -724,10 +754,12 @@ def main(argv=None):
     dist.barrier()
     batch.device_synchronize()
     t0 = time.perf_counter()
-    real_loop(plan, draws, K, offset=1)
+    last_step = real_loop(plan, draws, K, offset=1)
     batch.device_synchronize()
     dist.barrier()
     dt = dist.max(time.perf_counter() - t0)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last_step, dist.rank, dist.world)
     dominant_ms, nrec_dom = plan.profile()
     plan.set_profiling(True)
     real_loop(plan, draws, K, offset=1)

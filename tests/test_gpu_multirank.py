@@ -105,6 +105,41 @@ def test_bench_one_gpu_line_as_the_driver_parses_it():
     assert whole["value"] == pytest.approx(out["value"], rel=1e-5) and "configs" in whole and "materialize" in whole
 
 
+@pytest.mark.timeout(900)
+def test_bench_dump_outputs_are_the_last_timed_step(tmp_path):
+    """``bench.py --dump-outputs DIR`` writes what the last of the ``--steps`` timed steps returned: two runs with the
+    same arguments write the same arrays, and they are the oracle's values for the draw that step evaluated."""
+    import bench
+
+    B, N, K = 64, 10000, 3
+    args = ["--gpus", "1", "--steps", str(K), "--warmup", "1", "--batch", str(B), "--nsamples", str(N),
+            "--steady-seconds", "0.2", "--settle-seconds", "0.1", "--no-configs", "--no-shared-series", "--no-cpu-baseline",
+            "--no-accuracy-family", "--no-gradient", "--no-object-api", "--sharded", "0"]
+    dumps = []
+    for run in range(2):
+        d = str(tmp_path / ("dump%d" % run))
+        env = dict(os.environ)
+        env["CLR_BENCH_FULL"] = str(tmp_path / ("full%d.json" % run))
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args + ["--dump-outputs", d], cwd=ROOT,
+                           env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=840)
+        assert r.returncode == 0, r.stderr.decode()[-3000:]
+        out = json.loads(r.stdout.decode().strip().splitlines()[-1])
+        assert out["steps"] == K and abs(out["ms_per_step"] - out["timed_region_s"] / K * 1e3) <= 1e-4 * out["ms_per_step"]
+        dumps.append({n: np.load(os.path.join(d, n + ".npy")) for n in bench.DUMP_NAMES})
+    for n in bench.DUMP_NAMES:
+        assert dumps[0][n].dtype == np.float64 and dumps[0][n].shape == (B,)
+        assert np.array_equal(dumps[0][n], dumps[1][n]), n
+    # the timed loop starts at draw 1 of the 8 (bench.real_loop(..., offset=1)): its last step evaluates draw K % 8
+    coeffs, t, diag, y = bench.make_inputs(B, N, 2, 3, seed=42)
+    draw = ([coeffs] + bench.fresh_draws(coeffs, 7, seed=1042))[K % 8]
+    nchk = 4
+    ll0, ld0, q0, st0 = ref.batch_log_likelihood(0.0, *[c[:nchk] for c in draw], t[:nchk], diag[:nchk], y[:nchk])
+    got = dumps[0]
+    assert np.array_equal(got["status"][:nchk], st0) and (got["status"] == 0).all()
+    for name, want in (("loglike", ll0), ("logdet", ld0), ("quad", q0)):
+        assert np.max(np.abs(got[name][:nchk] - want) / np.abs(want)) <= REL, name
+
+
 def test_sharded_plan_over_every_visible_device():
     """``ShardedBatchedGP`` with one shard per visible device (distinct devices, not one device listed several times):
     on the 8-GPU node this is BASELINE configs[3]'s partitioning; on a one-GPU box a single shard.  Bit-identical to

@@ -323,6 +323,36 @@ def test_bench_headline_line_is_small_strict_json():
     check(lean)
 
 
+def test_bench_dump_outputs_writes_float64_arrays_within_the_size_cap(tmp_path, monkeypatch):
+    """``bench.py --dump-outputs DIR``: one float64 .npy per result array of the step (the int32 status codes included);
+    above the size cap a fixed, seeded sample of the problems with its indices, the same sample on every run; several
+    ranks write one file per rank."""
+    import bench
+
+    rng = np.random.RandomState(3)
+    B = 1000
+    step = (rng.randn(B), rng.randn(B), rng.rand(B), rng.randint(0, 3, B).astype(np.int32))
+    bench.dump_outputs(str(tmp_path / "all"), step)
+    for name, a in zip(bench.DUMP_NAMES, step):
+        got = np.load(str(tmp_path / "all" / (name + ".npy")))
+        assert got.dtype == np.float64 and np.array_equal(got, a)
+    assert not (tmp_path / "all" / "index.npy").exists()
+    bench.dump_outputs(str(tmp_path / "ranks"), step, rank=1, world=2)
+    assert sorted(p.name for p in (tmp_path / "ranks").iterdir()) == sorted(n + "_rank1.npy" for n in bench.DUMP_NAMES)
+
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4096 + 40 * 100)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), step)
+    idx = np.load(str(tmp_path / "a" / "index.npy"))
+    assert len(idx) == 100 and np.all(np.diff(idx) > 0) and np.array_equal(idx, np.load(str(tmp_path / "b" / "index.npy")))
+    total = 0
+    for name, a in zip(bench.DUMP_NAMES, step):
+        got = np.load(str(tmp_path / "a" / (name + ".npy")))
+        assert got.dtype == np.float64 and np.array_equal(got, a[idx.astype(np.int64)])
+        total += got.nbytes
+    assert total + idx.nbytes <= bench.DUMP_MAX_BYTES
+
+
 def test_import_celerite_resolves_to_this_build():
     """The north star's "keeping the existing ... API as a drop-in": ``import celerite`` (the reference's package name,
     celerite/__init__.py:20-33) is this build -- package, public names and submodules."""
