@@ -6,8 +6,6 @@
 
 extern "C" {
 
-static void mp_release(clr_batch* h);
-
 /* ---- batched log-likelihood ---------------------------------------------------- */
 clr_batch* clr_batch_create(int B, int N, int J_real, int J_comp, int device) {
   if (B < 1 || N < 1 || J_real < 0 || J_comp < 0) {
@@ -29,7 +27,7 @@ clr_batch* clr_batch_create(int B, int N, int J_real, int J_comp, int device) {
   h->J_comp = J_comp;
   h->J = J_real + 2 * J_comp;
   h->launch = L;  // null: widths 9..64, one wave per problem (wide_kernels.hip)
-  if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
+  if (clr::create_stream(h->stream) != hipSuccess) {
     fail(CLR_HIP_ERROR, "hipStreamCreate failed");
     delete h;
     return nullptr;
@@ -41,33 +39,7 @@ clr_batch* clr_batch_create(int B, int N, int J_real, int J_comp, int device) {
   return h;
 }
 
-void clr_batch_destroy(clr_batch* h) {
-  if (!h) return;
-  (void)hipSetDevice(h->device);
-  if (h->stream) (void)hipStreamSynchronize(h->stream);
-  mp_release(h);
-  if (h->rescue) clr_batch_destroy(h->rescue);
-  h->rescue = nullptr;
-  if (h->rescue_idx) (void)hipFree(h->rescue_idx);
-  for (DevBuf* b : {&h->coeffs, &h->t, &h->diag, &h->y, &h->tT, &h->dT, &h->yT,
-                    &h->elems, &h->starts, &h->part, &h->partx, &h->cond, &h->out, &h->phi, &h->u, &h->W, &h->D,
-                    &h->fphi, &h->fu, &h->fW, &h->fD, &h->lvl_elems, &h->lvl_starts, &h->wstarts, &h->wends,
-                    &h->wpart, &h->wresid, &h->wT, &h->wD, &h->wY, &h->gA, &h->gU, &h->gV, &h->g_riders, &h->g_out,
-                    &h->g_res, &h->g_rec, &h->g_ck, &h->bs_rm, &h->bs_x, &h->bs_M, &h->bs_off, &h->bs_starts, &h->bs_decay, &h->bs_y, &h->ends, &h->sT, &h->sD, &h->sY})
-    b->release();
-  if (h->flags) (void)hipFree(h->flags);
-  if (h->wints) (void)hipFree(h->wints);
-  if (h->g_ckflag) (void)hipFree(h->g_ckflag);
-  for (hipEvent_t e : h->prof_events) (void)hipEventDestroy(e);
-  for (hipEvent_t& e : h->bs_ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
-  if (h->pin) (void)hipHostFree(h->pin);
-  clr::staging_destroy(h->staging);
-  h->scan.release();
-  for (DevBuf* b : {&h->gen_elems, &h->gen_starts, &h->gen_part, &h->gen_cond, &h->gen_scan}) b->release();
-  if (h->gen_flags) (void)hipFree(h->gen_flags);
-  if (h->stream) (void)hipStreamDestroy(h->stream);
-  delete h;
-}
+void clr_batch_destroy(clr_batch* h) { delete h; }
 
 static int warm_plan_chunks(clr_batch* h);
 static int warm_resolve(clr_batch* h, bool* pin_current);
@@ -173,13 +145,12 @@ int clr_batch_set_chunks(clr_batch* h, int nchunk) {
   if ((st = h->partx.reserve(pc * 2)) != CLR_OK) return st;
   if ((st = h->cond.reserve(pc * 4)) != CLR_OK) return st;  // gamma, mu, residual per chunk | measured G error
   if ((st = h->out.reserve((size_t)h->B * 3 + ((size_t)h->B + 1) / 2)) != CLR_OK) return st;
-  if (h->flags) (void)hipFree(h->flags);
-  h->flags = nullptr;
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&h->flags), (2 * pc + (size_t)h->B) * sizeof(int)));
+  h->flags.release();
+  if ((st = h->flags.reserve(2 * pc + (size_t)h->B)) != CLR_OK) return st;
   // a single-chunk plan launches no prefix / correct kernel: nothing else would ever clear need_exact or fill
   // the conditioning record
-  HIP_TRY(hipMemsetAsync(h->flags, 0, (2 * pc + (size_t)h->B) * sizeof(int), h->stream));
-  HIP_TRY(hipMemsetAsync(h->cond.p, 0, pc * 4 * sizeof(double), h->stream));
+  HIP_TRY(hipMemsetAsync(h->flags.p, 0, (2 * pc + (size_t)h->B) * sizeof(int), h->stream.get()));
+  HIP_TRY(hipMemsetAsync(h->cond.p, 0, pc * 4 * sizeof(double), h->stream.get()));
   h->evaluated = false;
   if ((st = warm_plan_chunks(h)) != CLR_OK) return st;
   if (h->J_general > 0 && (st = plan_general_chunks(h)) != CLR_OK) return st;  // (its chunking follows the plan's settings)
@@ -214,13 +185,8 @@ static int warm_plan_chunks(clr_batch* h) {
   if ((st = h->wpart.reserve(pc * 2)) != CLR_OK) return st;
   if ((st = h->wresid.reserve((size_t)h->B)) != CLR_OK) return st;
   const size_t ints = pc + 2 * (size_t)h->B;
-  if (ints > h->wints_cap) {
-    if (h->wints) (void)hipFree(h->wints);
-    h->wints = nullptr;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&h->wints), ints * sizeof(int)));
-    h->wints_cap = ints;
-  }
-  HIP_TRY(hipMemsetAsync(h->wints, 0, ints * sizeof(int), h->stream));
+  if ((st = h->wints.reserve(ints)) != CLR_OK) return st;
+  HIP_TRY(hipMemsetAsync(h->wints.p, 0, ints * sizeof(int), h->stream.get()));
   if (h->have_series) {  // the spans and the warm-ups follow the new chunking (the series are resident)
     if ((st = warm_scan_spans(h)) != CLR_OK) return st;
     warm_select(h);
@@ -241,10 +207,10 @@ static int warm_scan_spans(clr_batch* h) {
   clr::WarmCands cands;
   cands.nk = clr_batch::WARM_NK;
   for (int k = 0; k < clr_batch::WARM_NK; ++k) cands.K[k] = h->warm_cand[k];
-  clr::launch_warm_spans(h->t.p, h->t_stride, nb, h->wL, h->wnchunk, cands, h->scan.p, h->stream);
+  clr::launch_warm_spans(h->t.p, h->t_stride, nb, h->wL, h->wnchunk, cands, h->scan.p, h->stream.get());
   h->warm_span.assign(n, 0.0);
-  HIP_TRY(hipMemcpyAsync(h->warm_span.data(), h->scan.p, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipMemcpyAsync(h->warm_span.data(), h->scan.p, n * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
+  HIP_TRY(hipStreamSynchronize(h->stream.get()));
   return CLR_OK;
 }
 
@@ -309,7 +275,7 @@ int clr_batch_set_series(clr_batch* h, const double* t, long t_stride, const dou
   if ((st = h->t.reserve(count(t_stride))) != CLR_OK) return st;
   if ((st = h->diag.reserve(count(diag_stride))) != CLR_OK) return st;
   if ((st = h->y.reserve(count(y_stride))) != CLR_OK) return st;
-  HIP_TRY(hipStreamSynchronize(h->stream));  // (kernels of an earlier evaluation may still be reading the old series)
+  HIP_TRY(hipStreamSynchronize(h->stream.get()));  // (kernels of an earlier evaluation may still be reading the old series)
   // from here on the old series is being overwritten: the plan has NO series until every copy and scan below has
   // succeeded (a failed upload must not leave have_series set over half-written arrays), and nothing derived from
   // the old one -- interleaved copies, warm-up spans and their selection -- survives
@@ -332,14 +298,14 @@ int clr_batch_set_series(clr_batch* h, const double* t, long t_stride, const dou
       if (e != 0) return fail(CLR_HIP_ERROR, hipGetErrorString((hipError_t)e));
       staged = true;
     } else {
-      clr::staging_destroy(h->staging);
+      h->staging = clr::UploadStaging();
       (void)hipGetLastError();
     }
   }
   if (!staged) {
     for (const clr::CopyJob& j : jobs)
-      if (j.n) HIP_TRY(hipMemcpyAsync(j.dst, j.src, j.n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+      if (j.n) HIP_TRY(hipMemcpyAsync(j.dst, j.src, j.n * sizeof(double), hipMemcpyHostToDevice, h->stream.get()));
+    HIP_TRY(hipStreamSynchronize(h->stream.get()));
   }
   h->t_stride = t_stride;
   h->diag_stride = diag_stride;
@@ -349,10 +315,10 @@ int clr_batch_set_series(clr_batch* h, const double* t, long t_stride, const dou
   {
     const int nb = t_stride == 0 ? 1 : h->B;
     if ((st = h->scan.reserve((size_t)nb * std::max(4, (int)clr_batch::WARM_NK))) != CLR_OK) return st;
-    clr::launch_series_stats(h->t.p, t_stride, nb, (int)N, h->scan.p, h->stream);
+    clr::launch_series_stats(h->t.p, t_stride, nb, (int)N, h->scan.p, h->stream.get());
     std::vector<double> stats((size_t)nb * 4);
-    HIP_TRY(hipMemcpyAsync(stats.data(), h->scan.p, stats.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpyAsync(stats.data(), h->scan.p, stats.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
+    HIP_TRY(hipStreamSynchronize(h->stream.get()));
     double tm = 0.0, dm = 0.0, dmin = INFINITY;
     bool nan = false;
     for (int b = 0; b < nb; ++b) {
@@ -416,17 +382,10 @@ int clr_batch_set_selection_bounds(clr_batch* h, double tmax, double dxmax, doub
 }
 
 static int reserve_pinned(clr_batch* h, size_t doubles) {
-  if (doubles <= h->pin_cap && h->pin) return CLR_OK;
+  if (doubles <= h->pin.cap && h->pin.p) return CLR_OK;
   h->pin_results = false;
-  if (h->pin) {
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    (void)hipHostFree(h->pin);
-    h->pin = nullptr;
-    h->pin_cap = 0;
-  }
-  HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->pin), doubles * sizeof(double), hipHostMallocDefault));
-  h->pin_cap = doubles;
-  return CLR_OK;
+  if (h->pin.p) HIP_TRY(hipStreamSynchronize(h->stream.get()));
+  return h->pin.reserve(doubles);
 }
 
 int clr_batch_set_coefficients(clr_batch* h, const double* jitter, const double* a_real,
@@ -467,18 +426,18 @@ int clr_batch_set_coefficients(clr_batch* h, const double* jitter, const double*
   // one pinned staging buffer, one copy: a_real c_real a_comp b_comp c_comp d_comp | jitter
   const size_t total = 2 * nr + 4 * nc + B;
   if ((st = reserve_pinned(h, std::max(total, 3 * B + (B + 1) / 2) + (B + 1) / 2)) != CLR_OK) return st;
-  HIP_TRY(hipStreamSynchronize(h->stream));  // (a previous upload may still read the staging buffer)
-  double* w = h->pin;
+  HIP_TRY(hipStreamSynchronize(h->stream.get()));  // (a previous upload may still read the staging buffer)
+  double* w = h->pin.p;
   auto put = [&](const double* p, size_t n) { if (n) memcpy(w, p, n * sizeof(double)); w += n; };
   put(a_real, nr); put(c_real, nr); put(a_comp, nc); put(b_comp, nc); put(c_comp, nc); put(d_comp, nc);
   if (jitter) { put(jitter, B); h->host_jitter.assign(jitter, jitter + B); }
   else { memset(w, 0, B * sizeof(double)); w += B; h->host_jitter.assign(B, 0.0); }  // NULL: no jitter
   if ((st = h->coeffs.reserve(total)) != CLR_OK) return st;
-  HIP_TRY(hipMemcpyAsync(h->coeffs.p, h->pin, total * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipMemcpyAsync(h->coeffs.p, h->pin.p, total * sizeof(double), hipMemcpyHostToDevice, h->stream.get()));
   if (h->warm_active) {  // K per problem, behind the coefficients in the staging buffer
-    int* kk = reinterpret_cast<int*>(h->pin + std::max(total, 3 * B + (B + 1) / 2));
+    int* kk = reinterpret_cast<int*>(h->pin.p + std::max(total, 3 * B + (B + 1) / 2));
     memcpy(kk, h->warm_K.data(), B * sizeof(int));
-    HIP_TRY(hipMemcpyAsync(h->wints + (size_t)h->B * h->wnchunk + B, kk, B * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->wints.p + (size_t)h->B * h->wnchunk + B, kk, B * sizeof(int), hipMemcpyHostToDevice, h->stream.get()));
     h->warm_K_dirty = false;
   }
   h->have_coeffs = true;
@@ -501,9 +460,9 @@ int clr_batch_get_exact_count(clr_batch* h, int* count) {
   }
   std::vector<int> need((size_t)h->B);
   const size_t pc = (size_t)h->B * h->nchunk;
-  HIP_TRY(hipMemcpyAsync(need.data(), h->flags + 2 * pc, need.size() * sizeof(int),
-                         hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipMemcpyAsync(need.data(), h->flags.p + 2 * pc, need.size() * sizeof(int),
+                         hipMemcpyDeviceToHost, h->stream.get()));
+  HIP_TRY(hipStreamSynchronize(h->stream.get()));
   int n = 0;
   for (int v : need) n += v != 0;
   *count = n;
@@ -520,8 +479,8 @@ int clr_batch_get_exact_flags(clr_batch* h, int* flags) {
     return CLR_OK;
   }
   const size_t pc = (size_t)h->B * h->nchunk;
-  HIP_TRY(hipMemcpyAsync(flags, h->flags + 2 * pc, (size_t)h->B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipMemcpyAsync(flags, h->flags.p + 2 * pc, (size_t)h->B * sizeof(int), hipMemcpyDeviceToHost, h->stream.get()));
+  HIP_TRY(hipStreamSynchronize(h->stream.get()));
   if (h->force_exact)
     for (int b = 0; b < h->B; ++b) flags[b] = flags[b] < 1 ? 1 : flags[b];
   return CLR_OK;
@@ -539,8 +498,8 @@ int clr_batch_get_conditioning_chunkwise(clr_batch* h, double* ratio_max) {
   }
   const size_t pc = (size_t)h->B * h->nchunk;
   std::vector<double> c(pc * 3);
-  HIP_TRY(hipMemcpyAsync(c.data(), h->cond.p, c.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipMemcpyAsync(c.data(), h->cond.p, c.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
+  HIP_TRY(hipStreamSynchronize(h->stream.get()));
   for (int b = 0; b < h->B; ++b) {
     double r = 0.0;
     for (int k = 0; k < h->nchunk; ++k) {
@@ -567,19 +526,19 @@ int clr_batch_get_conditioning(clr_batch* h, double* gamma_max, double* mu_min, 
   }
   const size_t pc = (size_t)h->B * h->nchunk;
   std::vector<double> c(pc * 3);
-  HIP_TRY(hipMemcpyAsync(c.data(), h->cond.p, c.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipMemcpyAsync(c.data(), h->cond.p, c.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
+  HIP_TRY(hipStreamSynchronize(h->stream.get()));
   // problems the warm-started recurrence settled have no scan record: gamma 0, mu 1, and the largest boundary
   // mismatch of the warm path as the residual
   std::vector<int> scanned;
   std::vector<double> wres;
-  if (h->warm_active && h->wints && h->warm_settled > 0) {
+  if (h->warm_active && h->wints.p && h->warm_settled > 0) {
     scanned.resize((size_t)h->B);
     wres.resize((size_t)h->B);
-    HIP_TRY(hipMemcpyAsync(scanned.data(), h->wints + (size_t)h->B * h->wnchunk, scanned.size() * sizeof(int),
-                           hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(wres.data(), h->wresid.p, wres.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpyAsync(scanned.data(), h->wints.p + (size_t)h->B * h->wnchunk, scanned.size() * sizeof(int),
+                           hipMemcpyDeviceToHost, h->stream.get()));
+    HIP_TRY(hipMemcpyAsync(wres.data(), h->wresid.p, wres.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
+    HIP_TRY(hipStreamSynchronize(h->stream.get()));
   }
   for (int b = 0; b < h->B; ++b) {
     double g = 0.0, m = 1.0, r = 0.0;
@@ -608,8 +567,8 @@ int clr_batch_get_measured_error(clr_batch* h, double* eg_max) {
   const size_t pc = (size_t)h->B * h->nchunk;
   std::vector<double> c(pc);
   if (h->nchunk >= 2) {
-    HIP_TRY(hipMemcpyAsync(c.data(), h->cond.p + pc * 3, pc * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpyAsync(c.data(), h->cond.p + pc * 3, pc * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
+    HIP_TRY(hipStreamSynchronize(h->stream.get()));
   }
   for (int b = 0; b < h->B; ++b) {
     double e = 0.0;
@@ -666,8 +625,8 @@ int clr_batch_debug_get_starts(clr_batch* h, double* starts) {
   if (st != CLR_OK) return st;
   if (!h->launch || !starts) return fail(CLR_INVALID_ARGUMENT, "start states are kept for widths 1..8");
   const size_t n = (size_t)h->B * h->nchunk * h->launch->start_doubles;
-  HIP_TRY(hipMemcpyAsync(starts, h->starts.p, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipMemcpyAsync(starts, h->starts.p, n * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
+  HIP_TRY(hipStreamSynchronize(h->stream.get()));
   return CLR_OK;
 }
 
@@ -682,12 +641,12 @@ int clr_batch_debug_compose_check(clr_batch* h, int group, double* max_abs_diff,
   const size_t n = (size_t)h->B * np * E;
   DevBuf a, b;
   if ((st = a.reserve(n)) != CLR_OK || (st = b.reserve(n)) != CLR_OK) return st;
-  h->launch->compose_check(P, group, a.p, b.p, h->stream);
+  h->launch->compose_check(P, group, a.p, b.p, h->stream.get());
   HIP_TRY(hipGetLastError());
   std::vector<double> ha(n), hb(n);
-  HIP_TRY(hipMemcpyAsync(ha.data(), a.p, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipMemcpyAsync(hb.data(), b.p, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipMemcpyAsync(ha.data(), a.p, n * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
+  HIP_TRY(hipMemcpyAsync(hb.data(), b.p, n * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
+  HIP_TRY(hipStreamSynchronize(h->stream.get()));
   a.release();
   b.release();
   // per element (one composed group) and per block of it (A | b | C | eta | Jm): the largest difference against the
@@ -777,11 +736,10 @@ static int plan_general_chunks(clr_batch* h) {
     }
     if ((st = h->gen_part.reserve(pc * 4)) != CLR_OK) return st;
     if ((st = h->gen_cond.reserve(pc * 4)) != CLR_OK) return st;
-    if (h->gen_flags) (void)hipFree(h->gen_flags);
-    h->gen_flags = nullptr;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&h->gen_flags), (2 * pc + (size_t)h->B) * sizeof(int)));
-    HIP_TRY(hipMemsetAsync(h->gen_flags, 0, (2 * pc + (size_t)h->B) * sizeof(int), h->stream));
-    HIP_TRY(hipMemsetAsync(h->gen_cond.p, 0, pc * 4 * sizeof(double), h->stream));
+    h->gen_flags.release();
+    if ((st = h->gen_flags.reserve(2 * pc + (size_t)h->B)) != CLR_OK) return st;
+    HIP_TRY(hipMemsetAsync(h->gen_flags.p, 0, (2 * pc + (size_t)h->B) * sizeof(int), h->stream.get()));
+    HIP_TRY(hipMemsetAsync(h->gen_cond.p, 0, pc * 4 * sizeof(double), h->stream.get()));
     h->gen_nchunk = nchunk; h->gen_L = L; h->gen_L0 = L0;
   }
   return CLR_OK;
@@ -803,10 +761,10 @@ int clr_batch_set_general(clr_batch* h, int J_general, const double* A, long A_s
   if ((A_stride != 0 && A_stride != N) || (U_stride != 0 && U_stride != UV) || (V_stride != 0 && V_stride != UV))
     return fail(CLR_INVALID_ARGUMENT, "general-term strides must be 0 (shared) or the size of one problem's block");
   auto count = [&](long sd, long one) { return (size_t)(sd == 0 ? one : one * (long)h->B); };
-  if ((st = upload(h->gA, A, count(A_stride, N), h->stream)) != CLR_OK) return st;
-  if ((st = upload(h->gU, U, count(U_stride, UV), h->stream)) != CLR_OK) return st;
-  if ((st = upload(h->gV, V, count(V_stride, UV), h->stream)) != CLR_OK) return st;
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  if ((st = upload(h->gA, A, count(A_stride, N), h->stream.get())) != CLR_OK) return st;
+  if ((st = upload(h->gU, U, count(U_stride, UV), h->stream.get())) != CLR_OK) return st;
+  if ((st = upload(h->gV, V, count(V_stride, UV), h->stream.get())) != CLR_OK) return st;
+  HIP_TRY(hipStreamSynchronize(h->stream.get()));
   h->J_general = J_general;
   h->gA_stride = A_stride; h->gU_stride = U_stride; h->gV_stride = V_stride;
   if ((st = plan_general_chunks(h)) != CLR_OK) { h->J_general = 0; return st; }
@@ -904,14 +862,14 @@ int clr_batch_set_profiling(clr_batch* h, int on) {
 int clr_batch_get_profile(clr_batch* h, double* kernel_ms /* [6] */, int* steps) {
   int st = require_device(h->device);
   if (st != CLR_OK) return st;
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream.get()));
   double k[PROF_NK] = {0, 0, 0, 0, 0, 0};
   for (int i = 0; i < h->prof_steps; ++i)
     for (int j = 0; j < PROF_NK; ++j) {
       if (h->prof_on == 2 && j != 1) continue;  // (only events 1 and 2 were recorded)
       float ms = 0.f;
-      HIP_TRY(hipEventElapsedTime(&ms, h->prof_events[(size_t)i * (PROF_NK + 1) + j],
-                                  h->prof_events[(size_t)i * (PROF_NK + 1) + j + 1]));
+      HIP_TRY(hipEventElapsedTime(&ms, h->prof_events[(size_t)i * (PROF_NK + 1) + j].get(),
+                                  h->prof_events[(size_t)i * (PROF_NK + 1) + j + 1].get()));
       k[j] += ms;
     }
   if (kernel_ms)
@@ -924,7 +882,7 @@ int clr_batch_get_profile(clr_batch* h, double* kernel_ms /* [6] */, int* steps)
 // (small_batch_kernel, small_kernels.hip); problems it cannot certify stay pending for the scan pipeline
 static bool small_runs(const clr_batch* h, int materialize) {
   if (h->grad_scan_only || h->small_mode == 0) return false;
-  if (!h->launch || materialize || h->force_exact || !h->wints || h->J_general > 0) return false;
+  if (!h->launch || materialize || h->force_exact || !h->wints.p || h->J_general > 0) return false;
   if (!clr::small_batch_supported(h->J_real, h->J_comp, h->N)) return false;
   // (automatic: while a workgroup per problem still fits one round of the chip -- above that the scan pipeline's
   //  throughput wins, profiles/r04i_small_batch.txt)
@@ -957,7 +915,7 @@ static int small_params(clr_batch* h, clr::BatchParams& Sp) {
     struct { DevBuf* src; DevBuf* dst; long stride; int pad; } jobs[3] = {
         {&h->t, &h->sT, h->t_stride, 1}, {&h->diag, &h->sD, h->diag_stride, 2}, {&h->y, &h->sY, h->y_stride, 0}};
     for (auto& j : jobs)
-      clr::launch_relayout(j.src->p, j.stride, j.dst->p, j.stride ? cells : 0, j.stride ? h->B : 1, h->N, L, T, j.pad, h->stream);
+      clr::launch_relayout(j.src->p, j.stride, j.dst->p, j.stride ? cells : 0, j.stride ? h->B : 1, h->N, L, T, j.pad, h->stream.get());
     h->small_copy_pending = false;
   }
   Sp.t = h->sT.p; Sp.diag = h->sD.p; Sp.y = h->sY.p;
@@ -986,17 +944,17 @@ static int warm_copy(clr_batch* h) {
       {&h->t, &h->wT, h->t_stride, 1}, {&h->diag, &h->wD, h->diag_stride, 2}, {&h->y, &h->wY, h->y_stride, 0}};
   for (auto& j : jobs)
     clr::launch_relayout_warm(j.src->p, j.stride, j.dst->p, j.stride ? (long)cells : 0, j.stride ? h->B : 1, h->N,
-                              h->wL, h->wnchunk, h->wKpad, h->wrows, j.pad, h->stream);
+                              h->wL, h->wnchunk, h->wKpad, h->wrows, j.pad, h->stream.get());
   h->warm_copy_pending = false;
   return CLR_OK;
 }
 
 // K per problem on the device, when set_series re-selected it after the coefficients were uploaded
 static int warm_upload_K(clr_batch* h) {
-  if (!h->warm_K_dirty || !h->wints) return CLR_OK;
-  HIP_TRY(hipMemcpyAsync(h->wints + (size_t)h->B * h->wnchunk + h->B, h->warm_K.data(), (size_t)h->B * sizeof(int),
-                         hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));  // (pageable source)
+  if (!h->warm_K_dirty || !h->wints.p) return CLR_OK;
+  HIP_TRY(hipMemcpyAsync(h->wints.p + (size_t)h->B * h->wnchunk + h->B, h->warm_K.data(), (size_t)h->B * sizeof(int),
+                         hipMemcpyHostToDevice, h->stream.get()));
+  HIP_TRY(hipStreamSynchronize(h->stream.get()));  // (pageable source)
   h->warm_K_dirty = false;
   return CLR_OK;
 }
@@ -1008,12 +966,12 @@ static int warm_fallback(clr_batch* h) {
   int st = batch_params(h, 0, P);
   h->in_fallback = false;
   if (st != CLR_OK) return st;
-  h->launch->summarize(P, h->stream);
-  h->launch->prefix(P, h->stream);
-  h->launch->correct(P, h->stream);
-  h->launch->replay(P, 0, h->stream);
-  h->launch->sequential(P, 0, h->stream);
-  clr::launch_finalize(P, h->stream);
+  h->launch->summarize(P, h->stream.get());
+  h->launch->prefix(P, h->stream.get());
+  h->launch->correct(P, h->stream.get());
+  h->launch->replay(P, 0, h->stream.get());
+  h->launch->sequential(P, 0, h->stream.get());
+  clr::launch_finalize(P, h->stream.get());
   HIP_TRY(hipGetLastError());
   return CLR_OK;
 }
@@ -1028,12 +986,9 @@ static int warm_fallback(clr_batch* h) {
 // 160 KB of LDS), so without the masks concurrency only serialises whole kernels.  The prefix and the corrections of
 // a group (small, latency-bound) run on a third, unmasked stream between the two.
 static void mp_release(clr_batch* h) {
-  for (hipStream_t s : h->mp_s) if (s) (void)hipStreamDestroy(s);
   h->mp_s.clear();
-  if (h->mp_p) (void)hipStreamDestroy(h->mp_p);
-  if (h->mp_r) (void)hipStreamDestroy(h->mp_r);
-  h->mp_p = h->mp_r = nullptr;
-  for (hipEvent_t e : h->mp_ev) (void)hipEventDestroy(e);
+  h->mp_p.reset();
+  h->mp_r.reset();
   h->mp_ev.clear();
 }
 
@@ -1059,16 +1014,16 @@ static int mp_prepare(clr_batch* h) {
   std::vector<uint32_t> ms, mr;
   const bool masked = h->mp_cus >= 16 && h->mp_cus <= ncu - 16;
   if (masked) mp_masks(ncu, h->mp_cus, ms, mr);
-  h->mp_s.assign((size_t)h->mp_nstreams, nullptr);
-  for (hipStream_t& s : h->mp_s) {
-    if (masked) HIP_TRY(hipExtStreamCreateWithCUMask(&s, (uint32_t)ms.size(), ms.data()));
-    else HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+  h->mp_s.resize((size_t)h->mp_nstreams);
+  for (clr::Stream& s : h->mp_s) {
+    if (masked) HIP_TRY(clr::create_stream(s, (uint32_t)ms.size(), ms.data()));
+    else HIP_TRY(clr::create_stream(s));
   }
-  if (masked) HIP_TRY(hipExtStreamCreateWithCUMask(&h->mp_r, (uint32_t)mr.size(), mr.data()));
-  else HIP_TRY(hipStreamCreateWithFlags(&h->mp_r, hipStreamNonBlocking));
-  HIP_TRY(hipStreamCreateWithFlags(&h->mp_p, hipStreamNonBlocking));
-  h->mp_ev.assign((size_t)2 * G + 2, nullptr);
-  for (hipEvent_t& e : h->mp_ev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  if (masked) HIP_TRY(clr::create_stream(h->mp_r, (uint32_t)mr.size(), mr.data()));
+  else HIP_TRY(clr::create_stream(h->mp_r));
+  HIP_TRY(clr::create_stream(h->mp_p));
+  h->mp_ev.resize((size_t)2 * G + 2);
+  for (clr::Event& e : h->mp_ev) HIP_TRY(clr::create_event(e, hipEventDisableTiming));
   return CLR_OK;
 }
 
@@ -1123,33 +1078,33 @@ static int materialize_pipeline(clr_batch* h, const clr::BatchParams& P) {
   if (st != CLR_OK) return st;
   const int G = h->mp_groups;
   const clr::BatchParams R = replay_view(h, P, 1);
-  HIP_TRY(hipEventRecord(h->mp_ev[0], h->stream));  // (whatever the plan's stream holds -- uploads, the relayout -- comes first)
-  for (hipStream_t s : h->mp_s) HIP_TRY(hipStreamWaitEvent(s, h->mp_ev[0], 0));
-  HIP_TRY(hipStreamWaitEvent(h->mp_p, h->mp_ev[0], 0));
-  HIP_TRY(hipStreamWaitEvent(h->mp_r, h->mp_ev[0], 0));
+  HIP_TRY(hipEventRecord(h->mp_ev[0].get(), h->stream.get()));  // (whatever the plan's stream holds -- uploads, the relayout -- comes first)
+  for (const clr::Stream& s : h->mp_s) HIP_TRY(hipStreamWaitEvent(s.get(), h->mp_ev[0].get(), 0));
+  HIP_TRY(hipStreamWaitEvent(h->mp_p.get(), h->mp_ev[0].get(), 0));
+  HIP_TRY(hipStreamWaitEvent(h->mp_r.get(), h->mp_ev[0].get(), 0));
   for (int g = 0; g < G; ++g) {
     int lo = 0, hi = 0;
     clr_shard_bounds(h->B, G, g, &lo, &hi);
     const clr::BatchParams Pg = group_view(h, P, lo, hi - lo), Rg = group_view(h, R, lo, hi - lo);
-    hipStream_t ss = h->mp_s[(size_t)g % h->mp_s.size()];
+    hipStream_t ss = h->mp_s[(size_t)g % h->mp_s.size()].get();
     h->launch->summarize(Pg, ss);
-    HIP_TRY(hipEventRecord(h->mp_ev[1 + 2 * g], ss));
-    HIP_TRY(hipStreamWaitEvent(h->mp_p, h->mp_ev[1 + 2 * g], 0));
-    h->launch->prefix(Pg, h->mp_p);
-    h->launch->correct(Pg, h->mp_p);
-    HIP_TRY(hipEventRecord(h->mp_ev[2 + 2 * g], h->mp_p));
-    HIP_TRY(hipStreamWaitEvent(h->mp_r, h->mp_ev[2 + 2 * g], 0));
-    h->launch->replay(Rg, replay_mode(h, 1), h->mp_r);
-    if (Rg.ends) refine_chunk_heads(h, Rg, 1, h->mp_r);
-    h->launch->sequential(Pg, replay_mode(h, 1), h->mp_r);
+    HIP_TRY(hipEventRecord(h->mp_ev[1 + 2 * g].get(), ss));
+    HIP_TRY(hipStreamWaitEvent(h->mp_p.get(), h->mp_ev[1 + 2 * g].get(), 0));
+    h->launch->prefix(Pg, h->mp_p.get());
+    h->launch->correct(Pg, h->mp_p.get());
+    HIP_TRY(hipEventRecord(h->mp_ev[2 + 2 * g].get(), h->mp_p.get()));
+    HIP_TRY(hipStreamWaitEvent(h->mp_r.get(), h->mp_ev[2 + 2 * g].get(), 0));
+    h->launch->replay(Rg, replay_mode(h, 1), h->mp_r.get());
+    if (Rg.ends) refine_chunk_heads(h, Rg, 1, h->mp_r.get());
+    h->launch->sequential(Pg, replay_mode(h, 1), h->mp_r.get());
   }
-  HIP_TRY(hipEventRecord(h->mp_ev[2 * G + 1], h->mp_r));  // (the replay stream's last group closes every chain of events)
-  HIP_TRY(hipStreamWaitEvent(h->stream, h->mp_ev[2 * G + 1], 0));
+  HIP_TRY(hipEventRecord(h->mp_ev[2 * G + 1].get(), h->mp_r.get()));  // (the replay stream's last group closes every chain of events)
+  HIP_TRY(hipStreamWaitEvent(h->stream.get(), h->mp_ev[2 * G + 1].get(), 0));
   h->factor_is_lean = h->factor_layout == 1;
   h->factor_inputs_changed = false;
   h->factor_valid = true;
   h->bs_M_valid = false;
-  clr::launch_finalize(P, h->stream);
+  clr::launch_finalize(P, h->stream.get());
   HIP_TRY(hipGetLastError());
   return CLR_OK;
 }
@@ -1197,8 +1152,8 @@ int clr_batch_set_materialize_pipeline(clr_batch* h, int groups, int summarize_c
   if (groups < 0 || groups == 1 || groups > 64 || summarize_cus < 0 || summarize_streams < 1 || summarize_streams > 8)
     return fail(CLR_INVALID_ARGUMENT, "materialize pipeline: groups 0 (off) or 2..64, summarize_cus >= 0, 1..8 summarize streams");
   if (!h->launch && groups) return fail(CLR_UNSUPPORTED, "the materialising pipeline covers widths 1..8");
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  for (hipStream_t s : h->mp_s) if (s) HIP_TRY(hipStreamSynchronize(s));
+  HIP_TRY(hipStreamSynchronize(h->stream.get()));
+  for (const clr::Stream& s : h->mp_s) HIP_TRY(hipStreamSynchronize(s.get()));
   mp_release(h);
   h->mp_groups = groups;
   h->mp_cus = (summarize_cus / 16) * 16;
@@ -1210,20 +1165,19 @@ int clr_batch_debug_cu_census(clr_batch* h, int which, int* cus_per_xcc /* [8] *
   int st = require_device(h->device);
   if (st != CLR_OK) return st;
   if (!cus_per_xcc || which < 0 || which > 2) return fail(CLR_INVALID_ARGUMENT, "cu census: which = 0 (plan), 1 (summarize), 2 (replay)");
-  hipStream_t s = h->stream;
+  hipStream_t s = h->stream.get();
   if (which > 0) {
     if (h->mp_groups < 2) return fail(CLR_INVALID_ARGUMENT, "cu census: no materialising pipeline is set");
     if ((st = mp_prepare(h)) != CLR_OK) return st;
-    s = which == 1 ? h->mp_s[0] : h->mp_r;
+    s = which == 1 ? h->mp_s[0].get() : h->mp_r.get();
   }
-  int* seen = nullptr;
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&seen), 8 * 256 * sizeof(int)));
-  HIP_TRY(hipMemsetAsync(seen, 0, 8 * 256 * sizeof(int), s));
-  clr::launch_cu_census(seen, 8192, 20000, s);
+  DevArray<int> seen;
+  if ((st = seen.reserve(8 * 256)) != CLR_OK) return st;
+  HIP_TRY(hipMemsetAsync(seen.p, 0, 8 * 256 * sizeof(int), s));
+  clr::launch_cu_census(seen.p, 8192, 20000, s);
   std::vector<int> host(8 * 256);
-  HIP_TRY(hipMemcpyAsync(host.data(), seen, host.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(host.data(), seen.p, host.size() * sizeof(int), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
-  (void)hipFree(seen);
   for (int x = 0; x < 8; ++x) {
     int n = 0;
     for (int c = 0; c < 256; ++c) n += host[(size_t)x * 256 + c] > 0;
@@ -1238,13 +1192,13 @@ int clr_batch_enqueue(clr_batch* h, int materialize) {
   clr::BatchParams P;
   if ((st = batch_params(h, materialize, P)) != CLR_OK) return st;
   // profiling: one event per kernel boundary of this evaluation, on the plan's stream
-  hipEvent_t* ev = nullptr;
+  const clr::Event* ev = nullptr;
   if (h->prof_on && h->prof_steps < PROF_MAX_STEPS) {
     const size_t need = (size_t)(h->prof_steps + 1) * (PROF_NK + 1);
     while (h->prof_events.size() < need) {
-      hipEvent_t e;
-      HIP_TRY(hipEventCreate(&e));
-      h->prof_events.push_back(e);
+      clr::Event e;
+      HIP_TRY(clr::create_event(e));
+      h->prof_events.push_back(std::move(e));
     }
     ev = &h->prof_events[(size_t)h->prof_steps * (PROF_NK + 1)];
     ++h->prof_steps;
@@ -1252,7 +1206,7 @@ int clr_batch_enqueue(clr_batch* h, int materialize) {
   if (!P.defer_level1) h->rescue_last = 0;  // (nothing is re-planned behind this evaluation)
   h->pin_results = false;
   const bool all_marks = h->prof_on != 2;
-  auto mark = [&](int i) { if (ev && (all_marks || i == 1 || i == 2)) (void)hipEventRecord(ev[i], h->stream); };
+  auto mark = [&](int i) { if (ev && (all_marks || i == 1 || i == 2)) (void)hipEventRecord(ev[i].get(), h->stream.get()); };
   h->evaluated = true;
   if (h->J_general > 0 || h->J > clr::wide_max_width()) {
     // general terms -- and (round 5) celerite-only kernels of widths 65..128, which have no wave-per-problem kernel --: the
@@ -1265,7 +1219,7 @@ int clr_batch_enqueue(clr_batch* h, int materialize) {
       clr::BatchParams W;
       general_wide_params(h, P, W);
       mark(0);
-      if ((st = wide_flow(W, h->J_real, h->J_comp, h->stream, ev)) != CLR_OK) return st;
+      if ((st = wide_flow(W, h->J_real, h->J_comp, h->stream.get(), ev)) != CLR_OK) return st;
       HIP_TRY(hipGetLastError());
       return CLR_OK;
     }
@@ -1283,9 +1237,9 @@ int clr_batch_enqueue(clr_batch* h, int materialize) {
     // (round 6) total widths 33 .. 128: S in the registers of the problem's workgroup (rows_kernels.hip: 1.6 us per sample at
     // width 128 where the LDS-resident kernel takes 20)
     if (clr::factor_rows_batch_supported(h->J + h->J_general) && !clr::option("CLR_NO_ROWS_KERNEL"))
-      clr::launch_factor_rows_batch(G, P.fast_trig, h->stream);
+      clr::launch_factor_rows_batch(G, P.fast_trig, h->stream.get());
     else
-    clr::launch_generic_loglike_batch(G, h->stream);
+    clr::launch_generic_loglike_batch(G, h->stream.get());
     mark(2); mark(3); mark(4); mark(5); mark(6);
     HIP_TRY(hipGetLastError());
     return CLR_OK;
@@ -1306,7 +1260,7 @@ int clr_batch_enqueue(clr_batch* h, int materialize) {
     clr::BatchParams Sp;
     if ((st = small_params(h, Sp)) != CLR_OK) return st;
     mark(1);
-    clr::launch_small_batch(h->J_real, h->J_comp, Sp, 256, h->stream);
+    clr::launch_small_batch(h->J_real, h->J_comp, Sp, 256, h->stream.get());
     mark(2); mark(3); mark(4); mark(5); mark(6);
     h->small_inflight = true;  // (pending problems are settled like the warm path's: warm_resolve)
     HIP_TRY(hipGetLastError());
@@ -1323,7 +1277,7 @@ int clr_batch_enqueue(clr_batch* h, int materialize) {
     h->in_fallback = false;
     if (st != CLR_OK) return st;
     mark(1);
-    h->launch->warm(Wp, h->stream);
+    h->launch->warm(Wp, h->stream.get());
     mark(2); mark(3); mark(4); mark(5); mark(6);
     h->warm_inflight = true;
     HIP_TRY(hipGetLastError());
@@ -1337,18 +1291,18 @@ int clr_batch_enqueue(clr_batch* h, int materialize) {
     return CLR_OK;
   }
   mark(1);
-  h->launch->summarize(P, h->stream);
+  h->launch->summarize(P, h->stream.get());
   mark(2);
-  h->launch->prefix(P, h->stream);
+  h->launch->prefix(P, h->stream.get());
   mark(3);
-  h->launch->correct(P, h->stream);  // (also on forced-exact runs: flags + conditioning record)
+  h->launch->correct(P, h->stream.get());  // (also on forced-exact runs: flags + conditioning record)
   mark(4);
-  h->launch->replay(replay_view(h, P, materialize), replay_mode(h, materialize), h->stream);  // forced-exact / materialising runs only
-  if (P.ends) refine_chunk_heads(h, replay_view(h, P, materialize), materialize, h->stream);
-  h->launch->sequential(P, replay_mode(h, materialize), h->stream);  // flagged / ill-conditioned problems only
+  h->launch->replay(replay_view(h, P, materialize), replay_mode(h, materialize), h->stream.get());  // forced-exact / materialising runs only
+  if (P.ends) refine_chunk_heads(h, replay_view(h, P, materialize), materialize, h->stream.get());
+  h->launch->sequential(P, replay_mode(h, materialize), h->stream.get());  // flagged / ill-conditioned problems only
   if (materialize) { h->factor_is_lean = h->factor_layout == 1; h->factor_inputs_changed = false; h->factor_valid = true; h->bs_M_valid = false; }
   mark(5);
-  clr::launch_finalize(P, h->stream);
+  clr::launch_finalize(P, h->stream.get());
   mark(6);
   h->rescue_inflight = P.defer_level1 != 0;
   // (capturing these five launches in a hipGraph was measured: no gain -- the gaps between
@@ -1367,23 +1321,20 @@ int clr_batch_fp32_probe(clr_batch* h, double* logdet, double* quad, double* ms)
   const size_t B = (size_t)h->B;
   DevBuf tmp;
   if ((st = tmp.reserve(2 * B)) != CLR_OK) return st;
-  hipEvent_t e0, e1;
-  HIP_TRY(hipEventCreate(&e0));
-  HIP_TRY(hipEventCreate(&e1));
-  clr::launch_wide_f32_probe(P, h->J_real, h->J_comp, tmp.p, tmp.p + B, h->stream);  // warm-up
-  HIP_TRY(hipEventRecord(e0, h->stream));
-  clr::launch_wide_f32_probe(P, h->J_real, h->J_comp, tmp.p, tmp.p + B, h->stream);
-  HIP_TRY(hipEventRecord(e1, h->stream));
+  clr::Event e0, e1;
+  HIP_TRY(clr::create_event(e0));
+  HIP_TRY(clr::create_event(e1));
+  clr::launch_wide_f32_probe(P, h->J_real, h->J_comp, tmp.p, tmp.p + B, h->stream.get());  // warm-up
+  HIP_TRY(hipEventRecord(e0.get(), h->stream.get()));
+  clr::launch_wide_f32_probe(P, h->J_real, h->J_comp, tmp.p, tmp.p + B, h->stream.get());
+  HIP_TRY(hipEventRecord(e1.get(), h->stream.get()));
   HIP_TRY(hipGetLastError());
-  if (logdet) HIP_TRY(hipMemcpyAsync(logdet, tmp.p, B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (quad) HIP_TRY(hipMemcpyAsync(quad, tmp.p + B, B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  if (logdet) HIP_TRY(hipMemcpyAsync(logdet, tmp.p, B * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
+  if (quad) HIP_TRY(hipMemcpyAsync(quad, tmp.p + B, B * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
+  HIP_TRY(hipStreamSynchronize(h->stream.get()));
   float t = 0.f;
-  HIP_TRY(hipEventElapsedTime(&t, e0, e1));
+  HIP_TRY(hipEventElapsedTime(&t, e0.get(), e1.get()));
   if (ms) *ms = t;
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  tmp.release();
   return CLR_OK;
 }
 
@@ -1400,16 +1351,16 @@ static int rescue_inline(clr_batch* h) {
   if (st != CLR_OK) return st;
   P.defer_level1 = 0;
   if (!h->launch) {
-    clr::launch_wide_loglike(P, h->J_real, h->J_comp, h->stream);
-    clr::launch_wide_check_replay(P, h->stream);
-    clr::launch_finalize(P, h->stream);
+    clr::launch_wide_loglike(P, h->J_real, h->J_comp, h->stream.get());
+    clr::launch_wide_check_replay(P, h->stream.get());
+    clr::launch_finalize(P, h->stream.get());
     clr::BatchParams S = P;
     S.nchunk = 1; S.L = P.N; S.L0 = 0; S.seq_only = 1; S.force_exact = 1;
-    clr::launch_wide_loglike(S, h->J_real, h->J_comp, h->stream);
+    clr::launch_wide_loglike(S, h->J_real, h->J_comp, h->stream.get());
   } else {
-    h->launch->replay(replay_view(h, P, 0), 0, h->stream);
-    h->launch->sequential(P, 0, h->stream);
-    clr::launch_finalize(P, h->stream);
+    h->launch->replay(replay_view(h, P, 0), 0, h->stream.get());
+    h->launch->sequential(P, 0, h->stream.get());
+    clr::launch_finalize(P, h->stream.get());
   }
   HIP_TRY(hipGetLastError());
   return CLR_OK;
@@ -1428,11 +1379,11 @@ static int rescue_run(clr_batch* h, const std::vector<int>& idx, long n_total) {
   h->rescue_last = n;
   int st;
   if (!h->rescue || h->rescue->B != n || h->rescue_plan_key != n_total) {
-    if (h->rescue) clr_batch_destroy(h->rescue);
+    h->rescue.reset();
     h->rescue_plan_key = -1;
-    h->rescue = clr_batch_create(n, h->N, h->J_real, h->J_comp, h->device);
+    h->rescue.reset(clr_batch_create(n, h->N, h->J_real, h->J_comp, h->device));
     if (!h->rescue) return CLR_HIP_ERROR;
-    clr_batch* r = h->rescue;
+    clr_batch* r = h->rescue.get();
     r->is_rescue_plan = true;
     r->force_exact = 1;
     r->warm_mode = 0;
@@ -1447,36 +1398,30 @@ static int rescue_run(clr_batch* h, const std::vector<int>& idx, long n_total) {
         if (nchunk < 8) nchunk = 0;  // (short series: the plan's own choice)
       }  // (widths 33..64: the plan's own rule -- 1024 / n chunks, at most 16, chained by the walk)
       if (nchunk == 0) {  // the automatic rule, asked as the side plan of the whole batch would ask it
-        clr_batch* probe = (nt == n) ? nullptr : clr_batch_create(nt, h->N, h->J_real, h->J_comp, h->device);
-        if (probe) { nchunk = probe->nchunk; clr_batch_destroy(probe); }
+        const BatchPtr probe((nt == n) ? nullptr : clr_batch_create(nt, h->N, h->J_real, h->J_comp, h->device));
+        if (probe) nchunk = probe->nchunk;
       }
     } else {
       nchunk = auto_chunks(nt, h->N, h->J, true);
     }
     // (a failed set-up must not leave a half-initialised side plan behind: the next resolve would take it for ready)
     if ((st = clr_batch_set_chunks(r, nchunk)) != CLR_OK) {
-      clr_batch_destroy(h->rescue);
-      h->rescue = nullptr;
+      h->rescue.reset();
       return st;
     }
     h->rescue_plan_key = n_total;
   }
-  clr_batch* r = h->rescue;
+  clr_batch* r = h->rescue.get();
   // the parent's settings that decide routes and kernels
   r->cert_resid = h->cert_resid; r->cert_gamma = h->cert_gamma; r->cert_gamma_abs = h->cert_gamma_abs; r->cert_eg = h->cert_eg;
   r->force_library_trig = h->force_library_trig;
   r->floor_tmax = sel_max(h->tmax, h->floor_tmax); r->floor_dxmax = sel_max(h->dxmax, h->floor_dxmax);
   r->floor_dmax = sel_max(h->dmax, h->floor_dmax); r->floor_cmax = sel_max(h->cmax, h->floor_cmax);
   r->tmax = h->tmax; r->dxmax = h->dxmax; r->dmax = h->dmax; r->cmax = h->cmax; r->dtmin = h->dtmin;
-  if ((size_t)n > h->rescue_idx_cap) {
-    if (h->rescue_idx) (void)hipFree(h->rescue_idx);
-    h->rescue_idx = nullptr;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&h->rescue_idx), (size_t)n * sizeof(int)));
-    h->rescue_idx_cap = (size_t)n;
-  }
-  HIP_TRY(hipStreamSynchronize(r->stream));
-  HIP_TRY(hipMemcpyAsync(h->rescue_idx, idx.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, r->stream));
-  HIP_TRY(hipStreamSynchronize(r->stream));  // (pageable source)
+  if ((st = h->rescue_idx.reserve((size_t)n)) != CLR_OK) return st;
+  HIP_TRY(hipStreamSynchronize(r->stream.get()));
+  HIP_TRY(hipMemcpyAsync(h->rescue_idx.p, idx.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, r->stream.get()));
+  HIP_TRY(hipStreamSynchronize(r->stream.get()));  // (pageable source)
   // series and coefficients of the n problems, device to device (the parent's stream is idle: warm_resolve synchronised it)
   const size_t N = (size_t)h->N;
   struct { DevBuf* src; DevBuf* dst; long stride; long* sub_stride; } arrs[3] = {
@@ -1484,11 +1429,11 @@ static int rescue_run(clr_batch* h, const std::vector<int>& idx, long n_total) {
   for (auto& a : arrs) {
     if (a.stride == 0) {  // one series shared by all problems: shared by the side plan's too
       if ((st = a.dst->reserve(N)) != CLR_OK) return st;
-      HIP_TRY(hipMemcpyAsync(a.dst->p, a.src->p, N * sizeof(double), hipMemcpyDeviceToDevice, r->stream));
+      HIP_TRY(hipMemcpyAsync(a.dst->p, a.src->p, N * sizeof(double), hipMemcpyDeviceToDevice, r->stream.get()));
       *a.sub_stride = 0;
     } else {
       if ((st = a.dst->reserve((size_t)n * N)) != CLR_OK) return st;
-      clr::launch_gather_series(a.src->p, a.stride, a.dst->p, h->rescue_idx, n, h->N, r->stream);
+      clr::launch_gather_series(a.src->p, a.stride, a.dst->p, h->rescue_idx.p, n, h->N, r->stream.get());
       *a.sub_stride = (long)N;
     }
   }
@@ -1500,16 +1445,16 @@ static int rescue_run(clr_batch* h, const std::vector<int>& idx, long n_total) {
   r->factor_inputs_changed = true;
   const size_t total = (size_t)n * (2 * h->J_real + 4 * h->J_comp + 1);
   if ((st = r->coeffs.reserve(total)) != CLR_OK) return st;
-  clr::launch_gather_coeffs(h->coeffs.p, r->coeffs.p, h->rescue_idx, h->B, n, h->J_real, h->J_comp, r->stream);
+  clr::launch_gather_coeffs(h->coeffs.p, r->coeffs.p, h->rescue_idx.p, h->B, n, h->J_real, h->J_comp, r->stream.get());
   r->host_cmin.assign((size_t)n, 0.0);
   r->host_cmax.assign((size_t)n, h->cmax);
   r->host_jitter.assign((size_t)n, 0.0);
   r->have_coeffs = true;
   if ((st = clr_batch_enqueue(r, 0)) != CLR_OK) return st;
   const size_t pc = (size_t)n * r->nchunk, pcp = (size_t)h->B * h->nchunk;
-  clr::launch_scatter_results(r->out.p, r->flags + 2 * pc, n, h->out.p, h->flags + 2 * pcp, h->B, h->rescue_idx, r->stream);
+  clr::launch_scatter_results(r->out.p, r->flags.p + 2 * pc, n, h->out.p, h->flags.p + 2 * pcp, h->B, h->rescue_idx.p, r->stream.get());
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(r->stream));
+  HIP_TRY(hipStreamSynchronize(r->stream.get()));
   return CLR_OK;
 }
 
@@ -1541,9 +1486,9 @@ static int resolve_begin(clr_batch* h, long* pending_out, long* eligible_out) {
   const size_t B = (size_t)h->B, words = 3 * B + (B + 1) / 2;
   int st;
   if ((st = reserve_pinned(h, words)) != CLR_OK) return st;
-  HIP_TRY(hipMemcpyAsync(h->pin, h->out.p, words * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  const int* stw = reinterpret_cast<const int*>(h->pin + 3 * B);
+  HIP_TRY(hipMemcpyAsync(h->pin.p, h->out.p, words * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
+  HIP_TRY(hipStreamSynchronize(h->stream.get()));
+  const int* stw = reinterpret_cast<const int*>(h->pin.p + 3 * B);
   long pending = 0;
   for (size_t b = 0; b < B; ++b) pending += stw[b] == clr::CLR_PENDING_STATUS;
   if (h->res_was_warm) {
@@ -1565,7 +1510,7 @@ static int resolve_finish(clr_batch* h, long pending_total, long eligible_total)
   const size_t B = (size_t)h->B, words = 3 * B + (B + 1) / 2;
   const bool was_warm = h->res_was_warm, was_rescue = h->res_was_rescue;
   const long pending = h->res_pending;
-  const int* stw = reinterpret_cast<const int*>(h->pin + 3 * B);
+  const int* stw = reinterpret_cast<const int*>(h->pin.p + 3 * B);
   int st;
   if (was_rescue) {
     // the scan pipeline itself ran: what is pending are its level-1 problems, re-planned with short chunks
@@ -1575,8 +1520,8 @@ static int resolve_finish(clr_batch* h, long pending_total, long eligible_total)
       for (size_t b = 0; b < B; ++b) if (stw[b] == clr::CLR_PENDING_STATUS) idx.push_back((int)b);
       h->pin_results = false;
       if ((st = rescue_run(h, idx, pending_total)) != CLR_OK) return st;
-      HIP_TRY(hipMemcpyAsync(h->pin, h->out.p, words * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-      HIP_TRY(hipStreamSynchronize(h->stream));
+      HIP_TRY(hipMemcpyAsync(h->pin.p, h->out.p, words * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
+      HIP_TRY(hipStreamSynchronize(h->stream.get()));
       h->pin_results = true;
     }
     return CLR_OK;
@@ -1584,8 +1529,8 @@ static int resolve_finish(clr_batch* h, long pending_total, long eligible_total)
   if (pending) {
     h->pin_results = false;
     if ((st = warm_fallback(h)) != CLR_OK) return st;
-    HIP_TRY(hipMemcpyAsync(h->pin, h->out.p, words * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpyAsync(h->pin.p, h->out.p, words * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
+    HIP_TRY(hipStreamSynchronize(h->stream.get()));
     h->pin_results = true;
   }
   if (pending_total) {
@@ -1621,7 +1566,7 @@ int clr_batch_synchronize(clr_batch* h) {
   int st = require_device(h->device);
   if (st != CLR_OK) return st;
   if ((st = warm_resolve(h, nullptr)) != CLR_OK) return st;
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream.get()));
   return CLR_OK;
 }
 
@@ -1636,13 +1581,13 @@ int clr_batch_get_results(clr_batch* h, double* loglike, double* logdet, double*
   bool pin_current = false;
   if ((st = warm_resolve(h, &pin_current)) != CLR_OK) return st;
   if (!pin_current) {
-    HIP_TRY(hipMemcpyAsync(h->pin, h->out.p, words * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpyAsync(h->pin.p, h->out.p, words * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
+    HIP_TRY(hipStreamSynchronize(h->stream.get()));
   }
-  if (loglike) memcpy(loglike, h->pin, B * sizeof(double));
-  if (logdet) memcpy(logdet, h->pin + B, B * sizeof(double));
-  if (quad) memcpy(quad, h->pin + 2 * B, B * sizeof(double));
-  if (status) memcpy(status, h->pin + 3 * B, B * sizeof(int));
+  if (loglike) memcpy(loglike, h->pin.p, B * sizeof(double));
+  if (logdet) memcpy(logdet, h->pin.p + B, B * sizeof(double));
+  if (quad) memcpy(quad, h->pin.p + 2 * B, B * sizeof(double));
+  if (status) memcpy(status, h->pin.p + 3 * B, B * sizeof(int));
   return CLR_OK;
 }
 
@@ -1653,11 +1598,11 @@ int clr_batch_get_factor(clr_batch* h, int p, double* phi, double* u, double* W,
   if (p < 0 || p >= h->B) return fail(CLR_INVALID_ARGUMENT, "problem index out of range");
   const size_t N = (size_t)h->N, J = (size_t)h->J, Nm1 = N - 1, cells = (size_t)h->L * h->nchunk;
   if (!h->launch) {  // widths 9..64: already in the reference's storage, problem after problem
-    if (phi && J * Nm1) HIP_TRY(hipMemcpyAsync(phi, h->phi.p + p * J * Nm1, J * Nm1 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (u && J * Nm1) HIP_TRY(hipMemcpyAsync(u, h->u.p + p * J * Nm1, J * Nm1 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (W) HIP_TRY(hipMemcpyAsync(W, h->W.p + p * J * N, J * N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (D) HIP_TRY(hipMemcpyAsync(D, h->D.p + p * N, N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (phi && J * Nm1) HIP_TRY(hipMemcpyAsync(phi, h->phi.p + p * J * Nm1, J * Nm1 * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
+    if (u && J * Nm1) HIP_TRY(hipMemcpyAsync(u, h->u.p + p * J * Nm1, J * Nm1 * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
+    if (W) HIP_TRY(hipMemcpyAsync(W, h->W.p + p * J * N, J * N * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
+    if (D) HIP_TRY(hipMemcpyAsync(D, h->D.p + p * N, N * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
+    HIP_TRY(hipStreamSynchronize(h->stream.get()));
     return CLR_OK;
   }
   if ((st = h->fphi.reserve(J * Nm1)) != CLR_OK) return st;
@@ -1672,17 +1617,17 @@ int clr_batch_get_factor(clr_batch* h, int p, double* phi, double* u, double* W,
     // which must still be the ones of the materialising run (any change drops the factor: have_factor)
     clr::BatchParams P;
     if ((st = batch_params(h, 0, P)) != CLR_OK) return st;
-    h->launch->expand(P, p, h->t.p + (size_t)p * (size_t)h->t_stride, h->fphi.p, h->fu.p, h->fW.p, h->fD.p, h->stream);
+    h->launch->expand(P, p, h->t.p + (size_t)p * (size_t)h->t_stride, h->fphi.p, h->fu.p, h->fW.p, h->fD.p, h->stream.get());
   } else
   clr::launch_deinterleave_factor(h->phi.p + p * J * cells, h->u.p + p * J * cells,
                                   h->W.p + p * J * cells, h->D.p + p * cells, h->fphi.p, h->fu.p,
-                                  h->fW.p, h->fD.p, h->N, h->J, h->L, h->nchunk, h->stream);
+                                  h->fW.p, h->fD.p, h->N, h->J, h->L, h->nchunk, h->stream.get());
   HIP_TRY(hipGetLastError());
-  if (phi && J * Nm1) HIP_TRY(hipMemcpyAsync(phi, h->fphi.p, J * Nm1 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (u && J * Nm1) HIP_TRY(hipMemcpyAsync(u, h->fu.p, J * Nm1 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (W) HIP_TRY(hipMemcpyAsync(W, h->fW.p, J * N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (D) HIP_TRY(hipMemcpyAsync(D, h->fD.p, N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  if (phi && J * Nm1) HIP_TRY(hipMemcpyAsync(phi, h->fphi.p, J * Nm1 * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
+  if (u && J * Nm1) HIP_TRY(hipMemcpyAsync(u, h->fu.p, J * Nm1 * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
+  if (W) HIP_TRY(hipMemcpyAsync(W, h->fW.p, J * N * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
+  if (D) HIP_TRY(hipMemcpyAsync(D, h->fD.p, N * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
+  HIP_TRY(hipStreamSynchronize(h->stream.get()));
   return CLR_OK;
 }
 
@@ -1712,13 +1657,13 @@ static int wide_batch_solve(clr_batch* h, int nrhs, const double* b, double* x) 
   const double* src = h->y.p;
   long src_stride = h->y_stride;
   if (b) {
-    HIP_TRY(hipMemcpyAsync(h->bs_rm.p, b, B * R * N * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->bs_rm.p, b, B * R * N * sizeof(double), hipMemcpyHostToDevice, h->stream.get()));
     src = h->bs_rm.p;
     src_stride = (long)(R * N);
   }
-  for (hipEvent_t& e : h->bs_ev)
-    if (!e) HIP_TRY(hipEventCreate(&e));
-  HIP_TRY(hipEventRecord(h->bs_ev[0], h->stream));
+  for (clr::Event& e : h->bs_ev)
+    if (!e) HIP_TRY(clr::create_event(e));
+  HIP_TRY(hipEventRecord(h->bs_ev[0].get(), h->stream.get()));
   P.phi = h->phi.p; P.u = h->u.p; P.W = h->W.p; P.D = h->D.p;
   P.batch = h->B;
   P.stride_phi = (long)(J * (N - 1)); P.stride_W = (long)(J * N); P.stride_D = (long)N;
@@ -1726,17 +1671,17 @@ static int wide_batch_solve(clr_batch* h, int nrhs, const double* b, double* x) 
   P.in = src; P.stride_in = src_stride;
   P.out = h->bs_x.p; P.stride_out = (long)(R * N);
   P.backward = 0;
-  clr::launch_wsweep_scan(P, h->bs_M.p, h->stream);
+  clr::launch_wsweep_scan(P, h->bs_M.p, h->stream.get());
   P.in = h->bs_x.p; P.stride_in = (long)(R * N);
   P.out = h->bs_rm.p; P.stride_out = (long)(R * N);
   P.backward = 1;
-  clr::launch_wsweep_scan(P, h->bs_M.p, h->stream);
-  HIP_TRY(hipEventRecord(h->bs_ev[1], h->stream));
+  clr::launch_wsweep_scan(P, h->bs_M.p, h->stream.get());
+  HIP_TRY(hipEventRecord(h->bs_ev[1].get(), h->stream.get()));
   HIP_TRY(hipGetLastError());
-  if (x) HIP_TRY(hipMemcpyAsync(x, h->bs_rm.p, B * R * N * sizeof(double), hipMemcpyDeviceToHost, h->stream));  // (null: the result stays in bs_rm)
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  if (x) HIP_TRY(hipMemcpyAsync(x, h->bs_rm.p, B * R * N * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));  // (null: the result stays in bs_rm)
+  HIP_TRY(hipStreamSynchronize(h->stream.get()));
   float ms = 0.f;
-  HIP_TRY(hipEventElapsedTime(&ms, h->bs_ev[0], h->bs_ev[1]));
+  HIP_TRY(hipEventElapsedTime(&ms, h->bs_ev[0].get(), h->bs_ev[1].get()));
   h->solve_device_ms = ms;
   return CLR_OK;
 }
@@ -1768,15 +1713,15 @@ static int batch_solve_impl(clr_batch* h, int nrhs, const double* b, double* x) 
   const double* src = h->y.p;
   long src_stride = h->y_stride;
   if (b) {
-    HIP_TRY(hipMemcpyAsync(h->bs_rm.p, b, B * R * N * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->bs_rm.p, b, B * R * N * sizeof(double), hipMemcpyHostToDevice, h->stream.get()));
     src = h->bs_rm.p;
     src_stride = (long)N;
   }
-  for (hipEvent_t& e : h->bs_ev)
-    if (!e) HIP_TRY(hipEventCreate(&e));
-  hipEvent_t e0 = h->bs_ev[0], e1 = h->bs_ev[1];
-  HIP_TRY(hipEventRecord(e0, h->stream));
-  clr::launch_relayout(src, src_stride, h->bs_x.p, (long)cells, (int)(B * R), h->N, h->L, h->nchunk, 0, h->stream);
+  for (clr::Event& e : h->bs_ev)
+    if (!e) HIP_TRY(clr::create_event(e));
+  hipEvent_t e0 = h->bs_ev[0].get(), e1 = h->bs_ev[1].get();
+  HIP_TRY(hipEventRecord(e0, h->stream.get()));
+  clr::launch_relayout(src, src_stride, h->bs_x.p, (long)cells, (int)(B * R), h->N, h->L, h->nchunk, 0, h->stream.get());
   clr::BSolveParams S;
   S.nrhs = nrhs; S.r = 0; S.lean = h->factor_is_lean ? 1 : 0;
   // (the chunk maps depend on the factor only: formed by the first solve after a materialising run; they count as
@@ -1785,12 +1730,12 @@ static int batch_solve_impl(clr_batch* h, int nrhs, const double* b, double* x) 
   S.have_M = h->bs_M_valid ? 1 : 0;
   h->bs_M_valid = false;
   S.xT = h->bs_x.p; S.M = h->bs_M.p; S.off = h->bs_off.p; S.starts = h->bs_starts.p;
-  h->launch->bsolve(P, S, h->stream);
-  clr::launch_relayout_back(h->bs_x.p, (long)cells, h->bs_rm.p, (long)N, (int)(B * R), h->N, h->L, h->nchunk, h->stream);
-  HIP_TRY(hipEventRecord(e1, h->stream));
+  h->launch->bsolve(P, S, h->stream.get());
+  clr::launch_relayout_back(h->bs_x.p, (long)cells, h->bs_rm.p, (long)N, (int)(B * R), h->N, h->L, h->nchunk, h->stream.get());
+  HIP_TRY(hipEventRecord(e1, h->stream.get()));
   HIP_TRY(hipGetLastError());
-  if (x) HIP_TRY(hipMemcpyAsync(x, h->bs_rm.p, B * R * N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  if (x) HIP_TRY(hipMemcpyAsync(x, h->bs_rm.p, B * R * N * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
+  HIP_TRY(hipStreamSynchronize(h->stream.get()));
   h->bs_M_valid = true;
   float ms = 0.f;
   HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
@@ -1817,13 +1762,13 @@ int clr_batch_dot_L(clr_batch* h, int nrhs, const double* z, double* y) {
   if (h->J_general > 0 || h->J > clr::wide_max_width()) return fail(CLR_UNSUPPORTED, "clr_batch_dot_L covers celerite-only plans of widths 1..64");
   const size_t B = (size_t)h->B, N = (size_t)h->N, J = (size_t)h->J, R = (size_t)nrhs;
   if ((st = h->bs_rm.reserve(B * R * N)) != CLR_OK) return st;
-  for (hipEvent_t& e : h->bs_ev)
-    if (!e) HIP_TRY(hipEventCreate(&e));
-  HIP_TRY(hipMemcpyAsync(h->bs_rm.p, z, B * R * N * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  for (clr::Event& e : h->bs_ev)
+    if (!e) HIP_TRY(clr::create_event(e));
+  HIP_TRY(hipMemcpyAsync(h->bs_rm.p, z, B * R * N * sizeof(double), hipMemcpyHostToDevice, h->stream.get()));
   const double* result = nullptr;
   if (!h->launch) {  // wide plans
     if ((st = h->bs_x.reserve(B * R * N)) != CLR_OK) return st;
-    HIP_TRY(hipEventRecord(h->bs_ev[0], h->stream));
+    HIP_TRY(hipEventRecord(h->bs_ev[0].get(), h->stream.get()));
     if (clr::wdotl_scan_supported(h->N, h->J)) {
       clr::SweepParams P;
       memset(&P, 0, sizeof(P));
@@ -1841,13 +1786,13 @@ int clr_batch_dot_L(clr_batch* h, int nrhs, const double* z, double* y) {
       P.stride_ws = (long)ws;
       P.in = h->bs_rm.p; P.stride_in = (long)(R * N);
       P.out = h->bs_x.p; P.stride_out = (long)(R * N);
-      clr::launch_wdotl_scan(P, h->bs_off.p, h->stream);
+      clr::launch_wdotl_scan(P, h->bs_off.p, h->stream.get());
     } else {
       for (size_t p = 0; p < B; ++p)
         clr::launch_dot_L(h->N, h->J, nrhs, h->phi.p + p * J * (N - 1), h->u.p + p * J * (N - 1), h->W.p + p * J * N,
-                          h->D.p + p * N, h->bs_rm.p + p * R * N, h->bs_x.p + p * R * N, h->stream);
+                          h->D.p + p * N, h->bs_rm.p + p * R * N, h->bs_x.p + p * R * N, h->stream.get());
     }
-    HIP_TRY(hipEventRecord(h->bs_ev[1], h->stream));
+    HIP_TRY(hipEventRecord(h->bs_ev[1].get(), h->stream.get()));
     result = h->bs_x.p;
   } else {
     if (h->factor_is_lean && h->factor_inputs_changed)
@@ -1863,21 +1808,21 @@ int clr_batch_dot_L(clr_batch* h, int nrhs, const double* z, double* y) {
     if ((st = h->bs_decay.reserve(B * h->nchunk * J)) != CLR_OK) return st;
     if ((st = h->bs_off.reserve(B * R * h->nchunk * J)) != CLR_OK) return st;
     if ((st = h->bs_starts.reserve(B * R * h->nchunk * J)) != CLR_OK) return st;
-    HIP_TRY(hipEventRecord(h->bs_ev[0], h->stream));
-    clr::launch_relayout(h->bs_rm.p, (long)N, h->bs_x.p, (long)cells, (int)(B * R), h->N, h->L, h->nchunk, 0, h->stream);
+    HIP_TRY(hipEventRecord(h->bs_ev[0].get(), h->stream.get()));
+    clr::launch_relayout(h->bs_rm.p, (long)N, h->bs_x.p, (long)cells, (int)(B * R), h->N, h->L, h->nchunk, 0, h->stream.get());
     clr::BDotLParams S;
     S.nrhs = nrhs; S.lean = h->factor_is_lean ? 1 : 0;
     S.xT = h->bs_x.p; S.decay = h->bs_decay.p; S.off = h->bs_off.p; S.starts = h->bs_starts.p;
-    h->launch->bdotl(P, S, h->stream);
-    clr::launch_relayout_back(h->bs_x.p, (long)cells, h->bs_rm.p, (long)N, (int)(B * R), h->N, h->L, h->nchunk, h->stream);
-    HIP_TRY(hipEventRecord(h->bs_ev[1], h->stream));
+    h->launch->bdotl(P, S, h->stream.get());
+    clr::launch_relayout_back(h->bs_x.p, (long)cells, h->bs_rm.p, (long)N, (int)(B * R), h->N, h->L, h->nchunk, h->stream.get());
+    HIP_TRY(hipEventRecord(h->bs_ev[1].get(), h->stream.get()));
     result = h->bs_rm.p;
   }
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(y, result, B * R * N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipMemcpyAsync(y, result, B * R * N * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
+  HIP_TRY(hipStreamSynchronize(h->stream.get()));
   float ms = 0.f;
-  HIP_TRY(hipEventElapsedTime(&ms, h->bs_ev[0], h->bs_ev[1]));
+  HIP_TRY(hipEventElapsedTime(&ms, h->bs_ev[0].get(), h->bs_ev[1].get()));
   h->solve_device_ms = ms;
   return CLR_OK;
 }
@@ -1908,16 +1853,16 @@ int clr_batch_dot(clr_batch* h, int nrhs, const double* z, double* y) {
   if ((st = batch_params(h, 0, P)) != CLR_OK) return st;
   const size_t B = (size_t)h->B, N = (size_t)h->N, J = (size_t)h->J, R = (size_t)nrhs;
   if ((st = h->bs_rm.reserve(B * R * N)) != CLR_OK) return st;
-  for (hipEvent_t& e : h->bs_ev)
-    if (!e) HIP_TRY(hipEventCreate(&e));
-  HIP_TRY(hipMemcpyAsync(h->bs_rm.p, z, B * R * N * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  for (clr::Event& e : h->bs_ev)
+    if (!e) HIP_TRY(clr::create_event(e));
+  HIP_TRY(hipMemcpyAsync(h->bs_rm.p, z, B * R * N * sizeof(double), hipMemcpyHostToDevice, h->stream.get()));
   const double* result = nullptr;
   if (!h->launch) {  // wide plans: problem by problem
+    // (every return from here on waits for the stream first: its kernels read the local buffers)
     DevBuf feat, dgb, ws;
-    auto cleanup = [&](int code) { (void)hipStreamSynchronize(h->stream); feat.release(); dgb.release(); ws.release(); return code; };
-    if ((st = feat.reserve(3 * J * N)) != CLR_OK) return cleanup(st);
-    if ((st = dgb.reserve(N)) != CLR_OK) return cleanup(st);  // the problem's constant diagonal, refilled per problem (same stream)
-    if ((st = h->bs_x.reserve(B * R * N)) != CLR_OK) return cleanup(st);
+    if ((st = feat.reserve(3 * J * N)) != CLR_OK) return synced(h->stream.get(), st);
+    if ((st = dgb.reserve(N)) != CLR_OK) return synced(h->stream.get(), st);  // the problem's constant diagonal, refilled per problem (same stream)
+    if ((st = h->bs_x.reserve(B * R * N)) != CLR_OK) return synced(h->stream.get(), st);
     const bool scan = clr::wdotl_scan_supported(h->N, h->J);
     clr::SweepParams SP;
     memset(&SP, 0, sizeof(SP));
@@ -1926,9 +1871,9 @@ int clr_batch_dot(clr_batch* h, int nrhs, const double* z, double* y) {
       SP.nchunk = clr::wdotl_chunks(h->N);
       SP.L = (h->N - 1 + SP.nchunk - 1) / SP.nchunk;
       SP.nchunk = (h->N - 1 + SP.L - 1) / SP.L;
-      if ((st = ws.reserve(R * (size_t)SP.nchunk * 3 * J)) != CLR_OK) return cleanup(st);
+      if ((st = ws.reserve(R * (size_t)SP.nchunk * 3 * J)) != CLR_OK) return synced(h->stream.get(), st);
     }
-    (void)hipEventRecord(h->bs_ev[0], h->stream);
+    (void)hipEventRecord(h->bs_ev[0].get(), h->stream.get());
     for (size_t p = 0; p < B; ++p) {
       clr::GenericProblem g;
       g.N = h->N; g.J = h->J; g.J_real = h->J_real; g.J_comp = h->J_comp; g.J_general = 0;
@@ -1938,22 +1883,22 @@ int clr_batch_dot(clr_batch* h, int nrhs, const double* z, double* y) {
       g.U = nullptr; g.V = nullptr;
       g.t = h->t.p + p * (size_t)h->t_stride;
       double *phi = feat.p, *u = feat.p + J * N, *v = feat.p + 2 * J * N;
-      clr::launch_dot_setup(g, phi, u, v, h->stream);
-      hipLaunchKernelGGL(dot_diagonal_kernel, dim3((unsigned)std::min<size_t>((N + 255) / 256, 1024)), dim3(256), 0, h->stream,
+      clr::launch_dot_setup(g, phi, u, v, h->stream.get());
+      hipLaunchKernelGGL(dot_diagonal_kernel, dim3((unsigned)std::min<size_t>((N + 255) / 256, 1024)), dim3(256), 0, h->stream.get(),
                          g.a_real, g.a_comp, P.jitter + p, h->J_real, h->J_comp, dgb.p, h->N);
       if (scan) {
         SP.phi = phi; SP.u = u;
         SP.in = h->bs_rm.p + p * R * N; SP.out = h->bs_x.p + p * R * N;
-        clr::launch_wdot_scan(SP, v, dgb.p, ws.p, h->stream);
+        clr::launch_wdot_scan(SP, v, dgb.p, ws.p, h->stream.get());
       } else {
-        clr::launch_dot(h->N, h->J, nrhs, phi, u, v, dgb.p, h->bs_rm.p + p * R * N, h->bs_x.p + p * R * N, h->stream);
+        clr::launch_dot(h->N, h->J, nrhs, phi, u, v, dgb.p, h->bs_rm.p + p * R * N, h->bs_x.p + p * R * N, h->stream.get());
       }
     }
-    (void)hipEventRecord(h->bs_ev[1], h->stream);
+    (void)hipEventRecord(h->bs_ev[1].get(), h->stream.get());
     if (hipGetLastError() != hipSuccess ||
-        hipMemcpyAsync(y, h->bs_x.p, B * R * N * sizeof(double), hipMemcpyDeviceToHost, h->stream) != hipSuccess)
-      return cleanup(fail(CLR_HIP_ERROR, "clr_batch_dot: kernels or the download failed"));
-    if ((st = cleanup(CLR_OK)) != CLR_OK) return st;
+        hipMemcpyAsync(y, h->bs_x.p, B * R * N * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()) != hipSuccess)
+      return synced(h->stream.get(), fail(CLR_HIP_ERROR, "clr_batch_dot: kernels or the download failed"));
+    (void)hipStreamSynchronize(h->stream.get());
   } else {
     // the row-major times addressed directly (the chunk-interleaved copy of the role-split summarize is only made by an
     // evaluation: clr_batch_dot must not depend on one having run)
@@ -1964,20 +1909,20 @@ int clr_batch_dot(clr_batch* h, int nrhs, const double* z, double* y) {
     if ((st = h->bs_decay.reserve(B * h->nchunk * J)) != CLR_OK) return st;
     if ((st = h->bs_off.reserve(B * R * h->nchunk * J)) != CLR_OK) return st;
     if ((st = h->bs_starts.reserve(B * R * h->nchunk * J)) != CLR_OK) return st;
-    HIP_TRY(hipEventRecord(h->bs_ev[0], h->stream));
-    clr::launch_relayout(h->bs_rm.p, (long)N, h->bs_x.p, (long)cells, (int)(B * R), h->N, h->L, h->nchunk, 0, h->stream);
+    HIP_TRY(hipEventRecord(h->bs_ev[0].get(), h->stream.get()));
+    clr::launch_relayout(h->bs_rm.p, (long)N, h->bs_x.p, (long)cells, (int)(B * R), h->N, h->L, h->nchunk, 0, h->stream.get());
     clr::BDotParams S;
     S.nrhs = nrhs; S.zT = h->bs_x.p; S.yT = h->bs_y.p; S.decay = h->bs_decay.p; S.off = h->bs_off.p; S.starts = h->bs_starts.p;
-    h->launch->bdot(P, S, h->stream);
-    clr::launch_relayout_back(h->bs_y.p, (long)cells, h->bs_rm.p, (long)N, (int)(B * R), h->N, h->L, h->nchunk, h->stream);
-    HIP_TRY(hipEventRecord(h->bs_ev[1], h->stream));
+    h->launch->bdot(P, S, h->stream.get());
+    clr::launch_relayout_back(h->bs_y.p, (long)cells, h->bs_rm.p, (long)N, (int)(B * R), h->N, h->L, h->nchunk, h->stream.get());
+    HIP_TRY(hipEventRecord(h->bs_ev[1].get(), h->stream.get()));
     result = h->bs_rm.p;
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(y, result, B * R * N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpyAsync(y, result, B * R * N * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
+    HIP_TRY(hipStreamSynchronize(h->stream.get()));
   }
   float ms = 0.f;
-  HIP_TRY(hipEventElapsedTime(&ms, h->bs_ev[0], h->bs_ev[1]));
+  HIP_TRY(hipEventElapsedTime(&ms, h->bs_ev[0].get(), h->bs_ev[1].get()));
   h->solve_device_ms = ms;
   return CLR_OK;
 }
@@ -2000,20 +1945,19 @@ int clr_batch_predict(clr_batch* h, int M, const double* xs, long xs_stride, dou
   if ((st = batch_params(h, 0, P)) != CLR_OK) return st;
   const size_t B = (size_t)h->B, Mm = (size_t)M, nsrc = xs_stride == 0 ? 1 : B;
   DevBuf dxs, dpred, ws;
-  auto cleanup = [&](int code) { dxs.release(); dpred.release(); ws.release(); return code; };
-  if ((st = dxs.reserve(nsrc * Mm)) != CLR_OK) return cleanup(st);
-  if ((st = dpred.reserve(B * Mm)) != CLR_OK) return cleanup(st);
+  if ((st = dxs.reserve(nsrc * Mm)) != CLR_OK) return st;
+  if ((st = dpred.reserve(B * Mm)) != CLR_OK) return st;
   const bool scan_ok = clr::predict_scan_supported(h->N, h->J_real, h->J_comp);
   int pchunk = 0, pL = 0;
   if (scan_ok) {
     pchunk = std::max(1, std::min(h->N / 16, 8192));
     pL = (h->N + pchunk - 1) / pchunk;
     pchunk = (h->N + pL - 1) / pL;
-    if ((st = ws.reserve(clr::predict_workspace_doubles(pchunk, h->J))) != CLR_OK) return cleanup(st);
+    if ((st = ws.reserve(clr::predict_workspace_doubles(pchunk, h->J))) != CLR_OK) return st;
   }
-  if (hipMemcpyAsync(dxs.p, xs, nsrc * Mm * sizeof(double), hipMemcpyHostToDevice, h->stream) != hipSuccess ||
-      hipMemsetAsync(dpred.p, 0, B * Mm * sizeof(double), h->stream) != hipSuccess)
-    return cleanup(fail(CLR_HIP_ERROR, "clr_batch_predict: upload failed"));
+  if (hipMemcpyAsync(dxs.p, xs, nsrc * Mm * sizeof(double), hipMemcpyHostToDevice, h->stream.get()) != hipSuccess ||
+      hipMemsetAsync(dpred.p, 0, B * Mm * sizeof(double), h->stream.get()) != hipSuccess)
+    return fail(CLR_HIP_ERROR, "clr_batch_predict: upload failed");
   std::vector<char> sorted(nsrc, 1);
   for (size_t p = 0; p < nsrc; ++p)
     for (size_t m = 1; m < Mm && sorted[p]; ++m) sorted[p] = xs[p * Mm + m - 1] <= xs[p * Mm + m];
@@ -2027,14 +1971,14 @@ int clr_batch_predict(clr_batch* h, int M, const double* xs, long xs_stride, dou
     g.t = h->t.p + p * (size_t)h->t_stride;
     const double* alpha = h->bs_rm.p + p * (size_t)h->N;
     const double* xp = dxs.p + (xs_stride == 0 ? 0 : p * Mm);
-    if (scan_ok && sorted[xs_stride == 0 ? 0 : p]) clr::launch_predict_scan(g, alpha, M, xp, dpred.p + p * Mm, ws.p, pchunk, pL, h->stream);
-    else clr::launch_predict(g, alpha, M, xp, dpred.p + p * Mm, h->stream);
+    if (scan_ok && sorted[xs_stride == 0 ? 0 : p]) clr::launch_predict_scan(g, alpha, M, xp, dpred.p + p * Mm, ws.p, pchunk, pL, h->stream.get());
+    else clr::launch_predict(g, alpha, M, xp, dpred.p + p * Mm, h->stream.get());
   }
   if (hipGetLastError() != hipSuccess ||
-      hipMemcpyAsync(pred, dpred.p, B * Mm * sizeof(double), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
-      hipStreamSynchronize(h->stream) != hipSuccess)
-    return cleanup(fail(CLR_HIP_ERROR, "clr_batch_predict: kernels or the download failed"));
-  return cleanup(CLR_OK);
+      hipMemcpyAsync(pred, dpred.p, B * Mm * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()) != hipSuccess ||
+      hipStreamSynchronize(h->stream.get()) != hipSuccess)
+    return fail(CLR_HIP_ERROR, "clr_batch_predict: kernels or the download failed");
+  return CLR_OK;
 }
 
 int clr_batch_get_solve_ms(const clr_batch* h, double* device_ms) {
@@ -2053,18 +1997,16 @@ int clr_batch_run_timed(clr_batch* h, int materialize, int steps, int relayout_e
   h->pin_results = false;
   if (h->J_general > 0 || h->J > clr::wide_max_width()) {
     // (plans on the any-width sequential kernel or with general terms: the evaluation itself, `steps` times, as one "replay" slot)
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0));
-    HIP_TRY(hipEventCreate(&e1));
-    HIP_TRY(hipEventRecord(e0, h->stream));
+    clr::Event e0, e1;
+    HIP_TRY(clr::create_event(e0));
+    HIP_TRY(clr::create_event(e1));
+    HIP_TRY(hipEventRecord(e0.get(), h->stream.get()));
     for (int i = 0; i < steps; ++i)
       if ((st = clr_batch_enqueue(h, materialize)) != CLR_OK) return st;
-    HIP_TRY(hipEventRecord(e1, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipEventRecord(e1.get(), h->stream.get()));
+    HIP_TRY(hipStreamSynchronize(h->stream.get()));
     float tot = 0.f;
-    HIP_TRY(hipEventElapsedTime(&tot, e0, e1));
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
+    HIP_TRY(hipEventElapsedTime(&tot, e0.get(), e1.get()));
     if (total_ms) *total_ms = tot;
     if (kernel_ms) { for (int j = 0; j < 6; ++j) kernel_ms[j] = 0.0; kernel_ms[4] = tot; }
     return CLR_OK;
@@ -2072,17 +2014,17 @@ int clr_batch_run_timed(clr_batch* h, int materialize, int steps, int relayout_e
   if (!warm_runs(h, materialize) && h->relayout_pending && !relayout_each_step && batch_relayout(h)) h->relayout_pending = false;
   // one event per kernel boundary per step, all recorded on the handle's stream
   const int NK = 6;
-  std::vector<hipEvent_t> ev((size_t)steps * (NK + 1));
-  for (auto& e : ev) HIP_TRY(hipEventCreate(&e));
+  std::vector<clr::Event> ev((size_t)steps * (NK + 1));
+  for (clr::Event& e : ev) HIP_TRY(clr::create_event(e));
   for (int i = 0; i < steps; ++i) {
-    hipEvent_t* e = &ev[(size_t)i * (NK + 1)];
-    HIP_TRY(hipEventRecord(e[0], h->stream));
+    const clr::Event* e = &ev[(size_t)i * (NK + 1)];
+    HIP_TRY(hipEventRecord(e[0].get(), h->stream.get()));
     if (!h->launch) {  // wide path (one chunk: the whole sweep is reported in the "replay" slot)
       if ((st = wide_launch(h, P, e)) != CLR_OK) return st;
       if (materialize) { h->factor_is_lean = false; h->factor_inputs_changed = false; h->factor_valid = true; h->bs_M_valid = false; }
       // (a plan that re-planned level-1 problems at its last evaluation does so inside every timed step: the step's
       //  time then includes the side plan -- at the price of a host round trip per step)
-      if (P.defer_level1 && h->rescue_last != 0) { h->rescue_inflight = true; if ((st = warm_resolve(h, nullptr)) != CLR_OK) return st; HIP_TRY(hipEventRecord(e[6], h->stream)); }
+      if (P.defer_level1 && h->rescue_last != 0) { h->rescue_inflight = true; if ((st = warm_resolve(h, nullptr)) != CLR_OK) return st; HIP_TRY(hipEventRecord(e[6].get(), h->stream.get())); }
       else h->rescue_inflight = P.defer_level1 != 0;
       continue;
     }
@@ -2090,9 +2032,9 @@ int clr_batch_run_timed(clr_batch* h, int materialize, int steps, int relayout_e
       clr::BatchParams Sp;
       if (relayout_each_step) h->small_copy_pending = true;  // (new series every step: the copy is rebuilt inside it)
       if ((st = small_params(h, Sp)) != CLR_OK) return st;
-      HIP_TRY(hipEventRecord(e[1], h->stream));
-      clr::launch_small_batch(h->J_real, h->J_comp, Sp, 256, h->stream);
-      for (int j = 2; j <= 6; ++j) HIP_TRY(hipEventRecord(e[j], h->stream));
+      HIP_TRY(hipEventRecord(e[1].get(), h->stream.get()));
+      clr::launch_small_batch(h->J_real, h->J_comp, Sp, 256, h->stream.get());
+      for (int j = 2; j <= 6; ++j) HIP_TRY(hipEventRecord(e[j].get(), h->stream.get()));
       h->small_inflight = true;
       continue;
     }
@@ -2105,53 +2047,52 @@ int clr_batch_run_timed(clr_batch* h, int materialize, int steps, int relayout_e
       st = batch_params(h, 0, Wp);
       h->in_fallback = false;
       if (st != CLR_OK) return st;
-      HIP_TRY(hipEventRecord(e[1], h->stream));
-      h->launch->warm(Wp, h->stream);
-      for (int j = 2; j <= 6; ++j) HIP_TRY(hipEventRecord(e[j], h->stream));
+      HIP_TRY(hipEventRecord(e[1].get(), h->stream.get()));
+      h->launch->warm(Wp, h->stream.get());
+      for (int j = 2; j <= 6; ++j) HIP_TRY(hipEventRecord(e[j].get(), h->stream.get()));
       h->warm_inflight = true;
       continue;
     }
     if (relayout_each_step) batch_relayout(h);
     if (mp_runs(h, materialize)) {  // (the whole pipeline in the "replay" slot)
-      for (int j = 1; j <= 4; ++j) HIP_TRY(hipEventRecord(e[j], h->stream));
+      for (int j = 1; j <= 4; ++j) HIP_TRY(hipEventRecord(e[j].get(), h->stream.get()));
       if ((st = materialize_pipeline(h, P)) != CLR_OK) return st;
-      HIP_TRY(hipEventRecord(e[5], h->stream));
-      HIP_TRY(hipEventRecord(e[6], h->stream));
+      HIP_TRY(hipEventRecord(e[5].get(), h->stream.get()));
+      HIP_TRY(hipEventRecord(e[6].get(), h->stream.get()));
       continue;
     }
-    HIP_TRY(hipEventRecord(e[1], h->stream));
-    h->launch->summarize(P, h->stream);
-    HIP_TRY(hipEventRecord(e[2], h->stream));
-    h->launch->prefix(P, h->stream);
-    HIP_TRY(hipEventRecord(e[3], h->stream));
-    h->launch->correct(P, h->stream);
-    HIP_TRY(hipEventRecord(e[4], h->stream));
-    h->launch->replay(replay_view(h, P, materialize), replay_mode(h, materialize), h->stream);
-    if (P.ends) refine_chunk_heads(h, replay_view(h, P, materialize), materialize, h->stream);
-    h->launch->sequential(P, replay_mode(h, materialize), h->stream);
+    HIP_TRY(hipEventRecord(e[1].get(), h->stream.get()));
+    h->launch->summarize(P, h->stream.get());
+    HIP_TRY(hipEventRecord(e[2].get(), h->stream.get()));
+    h->launch->prefix(P, h->stream.get());
+    HIP_TRY(hipEventRecord(e[3].get(), h->stream.get()));
+    h->launch->correct(P, h->stream.get());
+    HIP_TRY(hipEventRecord(e[4].get(), h->stream.get()));
+    h->launch->replay(replay_view(h, P, materialize), replay_mode(h, materialize), h->stream.get());
+    if (P.ends) refine_chunk_heads(h, replay_view(h, P, materialize), materialize, h->stream.get());
+    h->launch->sequential(P, replay_mode(h, materialize), h->stream.get());
     if (materialize) { h->factor_is_lean = h->factor_layout == 1; h->factor_inputs_changed = false; h->factor_valid = true; h->bs_M_valid = false; }
-    HIP_TRY(hipEventRecord(e[5], h->stream));
-    clr::launch_finalize(P, h->stream);
+    HIP_TRY(hipEventRecord(e[5].get(), h->stream.get()));
+    clr::launch_finalize(P, h->stream.get());
     if (P.defer_level1 && h->rescue_last != 0) { h->rescue_inflight = true; if ((st = warm_resolve(h, nullptr)) != CLR_OK) return st; }
     else h->rescue_inflight = P.defer_level1 != 0;
-    HIP_TRY(hipEventRecord(e[6], h->stream));
+    HIP_TRY(hipEventRecord(e[6].get(), h->stream.get()));
   }
   if (relayout_each_step && !warm_runs(h, materialize) && (h->layout == 1 || split_active(h)) && h->nchunk > 1)
     h->relayout_pending = false;
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream.get()));
   double k[NK] = {0, 0, 0, 0, 0, 0};
   for (int i = 0; i < steps; ++i) {
-    hipEvent_t* e = &ev[(size_t)i * (NK + 1)];
+    const clr::Event* e = &ev[(size_t)i * (NK + 1)];
     for (int j = 0; j < NK; ++j) {
       float ms = 0.f;
-      HIP_TRY(hipEventElapsedTime(&ms, e[j], e[j + 1]));
+      HIP_TRY(hipEventElapsedTime(&ms, e[j].get(), e[j + 1].get()));
       k[j] += ms;
     }
   }
   float tot = 0.f;
-  HIP_TRY(hipEventElapsedTime(&tot, ev.front(), ev.back()));
-  for (auto& e : ev) (void)hipEventDestroy(e);
+  HIP_TRY(hipEventElapsedTime(&tot, ev.front().get(), ev.back().get()));
   if (total_ms) *total_ms = tot;
   if (kernel_ms)
     for (int j = 0; j < NK; ++j) kernel_ms[j] = k[j];

@@ -24,12 +24,12 @@ static int grad_chunk_spans(clr_batch* h) {
   DevBuf tmp;
   int st = tmp.reserve(n);
   if (st != CLR_OK) return st;
-  hipLaunchKernelGGL(chunk_span_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->t.p, h->t_stride,
+  hipLaunchKernelGGL(chunk_span_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream.get(), h->t.p, h->t_stride,
                      h->N, h->L, h->nchunk, nsrc, tmp.p);
   std::vector<double> spans(n);
   const bool ok = hipGetLastError() == hipSuccess &&
-                  hipMemcpyAsync(spans.data(), tmp.p, n * sizeof(double), hipMemcpyDeviceToHost, h->stream) == hipSuccess &&
-                  hipStreamSynchronize(h->stream) == hipSuccess;
+                  hipMemcpyAsync(spans.data(), tmp.p, n * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()) == hipSuccess &&
+                  hipStreamSynchronize(h->stream.get()) == hipSuccess;
   tmp.release();
   if (!ok) return fail(CLR_HIP_ERROR, "chunk span kernel failed");
   h->grad_span.assign(nsrc, 0.0);
@@ -116,15 +116,15 @@ static int wide_batch_grad(clr_batch* h, double* value, double* grad, int* statu
   G.out_value = d_value; G.out_grad = d_grad; G.out_status = d_status;
 
   if (!seq_all) {
-    if (clr::launch_wide_grad_riders(W, h->stream) != 0) return fail(CLR_HIP_ERROR, "the riders kernel could not be configured (LDS)");
-    clr::launch_grad_chunked(G, h->stream);
-    if (clr::launch_wide_grad_walk(W, h->stream) != 0) return fail(CLR_HIP_ERROR, "the walk kernel could not be configured (LDS)");
+    if (clr::launch_wide_grad_riders(W, h->stream.get()) != 0) return fail(CLR_HIP_ERROR, "the riders kernel could not be configured (LDS)");
+    clr::launch_grad_chunked(G, h->stream.get());
+    if (clr::launch_wide_grad_walk(W, h->stream.get()) != 0) return fail(CLR_HIP_ERROR, "the walk kernel could not be configured (LDS)");
   }
-  clr::launch_grad(G, h->stream);  // (sequential form: only the problems with level >= 2 -- or, widths 33..64, all)
+  clr::launch_grad(G, h->stream.get());  // (sequential form: only the problems with level >= 2 -- or, widths 33..64, all)
   HIP_TRY(hipGetLastError());
   std::vector<double> back(B * (NG + 2));
-  HIP_TRY(hipMemcpyAsync(back.data(), h->g_res.p, back.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipMemcpyAsync(back.data(), h->g_res.p, back.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
+  HIP_TRY(hipStreamSynchronize(h->stream.get()));
   const int* hst = reinterpret_cast<const int*>(back.data() + B + B * NG);
   int nfb = 0;
   std::vector<int> levels(B, 2);
@@ -232,20 +232,10 @@ int clr_batch_grad(clr_batch* h, double* value, double* grad, int* status) {
     P.g_rec_stride = Lg * (long)(J + 2) * P.g_nchunk;
     P.g_ck_stride = nalloc * (long)(SZ + J) * P.g_nchunk;
     const size_t nflag = B * (size_t)((P.g_nchunk + 63) / 64) * (size_t)Lg;
-    bool flags_fit = true;  // (a flag buffer that does not fit degrades to forward mode like the record buffers)
-    if (nflag > h->g_ckflag_cap) {
-      if (h->g_ckflag) (void)hipFree(h->g_ckflag);
-      h->g_ckflag = nullptr;
-      h->g_ckflag_cap = 0;
-      if (hipMalloc(reinterpret_cast<void**>(&h->g_ckflag), nflag) != hipSuccess) {
-        h->g_ckflag = nullptr;
-        flags_fit = false;
-      } else {
-        h->g_ckflag_cap = nflag;
-      }
-    }
-    if (flags_fit) HIP_TRY(hipMemsetAsync(h->g_ckflag, 0, nflag, h->stream));
-    P.g_ckflag = h->g_ckflag;
+    // (a flag buffer that does not fit degrades to forward mode like the record buffers)
+    const bool flags_fit = h->g_ckflag.reserve(nflag) == CLR_OK;
+    if (flags_fit) HIP_TRY(hipMemsetAsync(h->g_ckflag.p, 0, nflag, h->stream.get()));
+    P.g_ckflag = h->g_ckflag.p;
     // one long series: the adjoint walk over its thousands of gradient chunks in two levels (clr_grad_kernels.h) --
     // groups of sqrt(chunks / 2): compose + walk the groups + fan out = 2 seg + chunks / seg dependent steps
     P.g_seg = P.g_nchunk >= 256 ? std::max(16, (int)std::sqrt(0.5 * P.g_nchunk)) : 0;
@@ -271,7 +261,7 @@ int clr_batch_grad(clr_batch* h, double* value, double* grad, int* status) {
       P.g_grp_adj = ngr ? P.g_grp_riders + B * ngr * RID : nullptr;
       P.g_slab = P.g_drift_max + B + B * ngr * (RID + SZ + J);
       P.g_from_elems = (P.g_m == 1 && h->grad_riders_mode != 1) ? 1 : 0;
-      h->launch->grad_reverse(P, h->stream);
+      h->launch->grad_reverse(P, h->stream.get());
       HIP_TRY(hipGetLastError());
       h->grad_reverse_used = true;
     }
@@ -287,20 +277,20 @@ int clr_batch_grad(clr_batch* h, double* value, double* grad, int* status) {
   };
   if (scan_grad && !reverse) {
     if ((st = forward_buffers()) != CLR_OK) return st;
-    h->launch->grad(P, h->stream);
+    h->launch->grad(P, h->stream.get());
     HIP_TRY(hipGetLastError());
   }
   std::vector<double> ll(B), ld(B), qd(B), res(B * NG);
   std::vector<int> stt(B), lvl(B);
   if ((st = clr_batch_get_results(h, ll.data(), ld.data(), qd.data(), stt.data())) != CLR_OK) return st;
-  HIP_TRY(hipMemcpyAsync(res.data(), h->g_res.p, B * NG * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipMemcpyAsync(lvl.data(), P.need_exact, B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipMemcpyAsync(res.data(), h->g_res.p, B * NG * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
+  HIP_TRY(hipMemcpyAsync(lvl.data(), P.need_exact, B * sizeof(int), hipMemcpyDeviceToHost, h->stream.get()));
   std::vector<double> drift;
   if (reverse) {
     drift.resize(B);
-    HIP_TRY(hipMemcpyAsync(drift.data(), P.g_drift_max, B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(drift.data(), P.g_drift_max, B * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
   }
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream.get()));
   h->grad_drift_max = 0.0;
   h->grad_forward_reruns = 0;
   if (reverse) {
@@ -317,14 +307,14 @@ int clr_batch_grad(clr_batch* h, double* value, double* grad, int* status) {
     h->grad_forward_reruns = nre;
     if (nre) {
       int* dmask = reinterpret_cast<int*>(h->g_res.p + B * NG + B * (NG + 1));
-      HIP_TRY(hipMemcpyAsync(dmask, mask.data(), B * sizeof(int), hipMemcpyHostToDevice, h->stream));
+      HIP_TRY(hipMemcpyAsync(dmask, mask.data(), B * sizeof(int), hipMemcpyHostToDevice, h->stream.get()));
       if ((st = forward_buffers()) != CLR_OK) return st;
       P.g_mask = dmask;
       // (the forward-mode result lands in the same g_res rows, only for the masked problems)
-      h->launch->grad(P, h->stream);
+      h->launch->grad(P, h->stream.get());
       HIP_TRY(hipGetLastError());
-      HIP_TRY(hipMemcpyAsync(res.data(), h->g_res.p, B * NG * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-      HIP_TRY(hipStreamSynchronize(h->stream));
+      HIP_TRY(hipMemcpyAsync(res.data(), h->g_res.p, B * NG * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
+      HIP_TRY(hipStreamSynchronize(h->stream.get()));
       P.g_mask = nullptr;
     }
   }
@@ -346,11 +336,11 @@ int clr_batch_grad(clr_batch* h, double* value, double* grad, int* status) {
     G.only_level = scan_grad ? P.need_exact : nullptr;
     G.out_value = h->g_res.p + B * NG; G.out_grad = G.out_value + B;
     G.out_status = reinterpret_cast<int*>(G.out_grad + B * NG);
-    clr::launch_grad(G, h->stream);
+    clr::launch_grad(G, h->stream.get());
     HIP_TRY(hipGetLastError());
     fb.resize(B * NG);
-    HIP_TRY(hipMemcpyAsync(fb.data(), G.out_grad, B * NG * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpyAsync(fb.data(), G.out_grad, B * NG * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
+    HIP_TRY(hipStreamSynchronize(h->stream.get()));
   }
   const double cst = 3.14159265358979323846 * log((double)h->N);  // the reference's constant (solver.cpp:415)
   for (size_t b = 0; b < B; ++b) {
@@ -414,25 +404,21 @@ int clr_batch_grad_log_likelihood(int B, int N, int J_real, int J_comp, const do
   }
   const size_t Bn = (size_t)B, nr = Bn * J_real, nc = Bn * J_comp, NG = 1 + 2 * (size_t)J_real + 4 * (size_t)J_comp;
   auto count = [&](long sd) { return (size_t)(sd == 0 ? N : (long)N * B); };
-  hipStream_t stream;
-  HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+  // (declared before the buffers: destroyed after them; every return below waits for the stream first)
+  clr::Stream owned_stream;
+  HIP_TRY(clr::create_stream(owned_stream));
+  hipStream_t stream = owned_stream.get();
   DevBuf buf, out;
-  int* dstatus = nullptr;
-  auto done = [&](int code) {
-    buf.release(); out.release();
-    if (dstatus) (void)hipFree(dstatus);
-    (void)hipStreamDestroy(stream);
-    return code;
-  };
+  DevArray<int> dstatus;
   // one staging vector: coefficients | jitter | t | diag | y
   std::vector<double> host;
   auto put = [&](const double* p, size_t n) { const size_t at = host.size(); if (n) host.insert(host.end(), p, p + n); return at; };
   const size_t o_ar = put(a_real, nr), o_cr = put(c_real, nr), o_ac = put(a_comp, nc), o_bc = put(b_comp, nc),
                o_cc = put(c_comp, nc), o_dc = put(d_comp, nc), o_j = put(jitter, Bn);
   const size_t o_t = put(t, count(t_stride)), o_d = put(diag, count(diag_stride)), o_y = put(y, count(y_stride));
-  if ((st = upload(buf, host.data(), host.size(), stream)) != CLR_OK) return done(st);
-  if ((st = out.reserve(Bn * (NG + 1))) != CLR_OK) return done(st);
-  if (hipMalloc(reinterpret_cast<void**>(&dstatus), Bn * sizeof(int)) != hipSuccess) return done(fail(CLR_HIP_ERROR, "hipMalloc failed"));
+  if ((st = upload(buf, host.data(), host.size(), stream)) != CLR_OK) return synced(stream, st);
+  if ((st = out.reserve(Bn * (NG + 1))) != CLR_OK) return synced(stream, st);
+  if ((st = dstatus.reserve(Bn)) != CLR_OK) return synced(stream, st);
   clr::GradParams P;
   memset(&P, 0, sizeof(P));
   const double* base = buf.p;
@@ -448,15 +434,15 @@ int clr_batch_grad_log_likelihood(int B, int N, int J_real, int J_comp, const do
     for (size_t i = 0; i < nc; ++i) { const double m = fabs(d_comp[i]); if (!(m <= dmax)) dmax = m; }
     P.fast_trig = (dmax * max_abs(t, (long)count(t_stride)) < CLR_FAST_TRIG_LIMIT) ? 1 : 0;
   }
-  P.out_value = out.p; P.out_grad = out.p + Bn; P.out_status = dstatus;
+  P.out_value = out.p; P.out_grad = out.p + Bn; P.out_status = dstatus.p;
   clr::launch_grad(P, stream);
-  if (hipGetLastError() != hipSuccess) return done(fail(CLR_HIP_ERROR, "grad kernel launch failed"));
+  if (hipGetLastError() != hipSuccess) return synced(stream, fail(CLR_HIP_ERROR, "grad kernel launch failed"));
   std::vector<double> back(Bn * (NG + 1));
   std::vector<int> hst(Bn);
   if (hipMemcpyAsync(back.data(), out.p, back.size() * sizeof(double), hipMemcpyDeviceToHost, stream) != hipSuccess ||
-      hipMemcpyAsync(hst.data(), dstatus, Bn * sizeof(int), hipMemcpyDeviceToHost, stream) != hipSuccess ||
+      hipMemcpyAsync(hst.data(), dstatus.p, Bn * sizeof(int), hipMemcpyDeviceToHost, stream) != hipSuccess ||
       hipStreamSynchronize(stream) != hipSuccess)
-    return done(fail(CLR_HIP_ERROR, "copy back failed"));
+    return synced(stream, fail(CLR_HIP_ERROR, "copy back failed"));
   for (size_t b = 0; b < Bn; ++b) {
     const bool bad = hst[b] != CLR_OK;
     if (status) status[b] = hst[b];
@@ -465,7 +451,7 @@ int clr_batch_grad_log_likelihood(int B, int N, int J_real, int J_comp, const do
       for (size_t g = 0; g < NG; ++g) grad[b * NG + g] = bad ? 0.0 : back[Bn + b * NG + g];
     if (grad && !(jitter[b] > 2.220446049250313e-16)) grad[b * NG] = 0.0;  // solver.cpp:379-389,419-426
   }
-  return done(CLR_OK);
+  return CLR_OK;
 }
 
 }  // extern "C"

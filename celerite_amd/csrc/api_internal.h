@@ -4,7 +4,7 @@
 //   api_batch.hip   clr_batch_*: plans, HBM residency, path selection, evaluation, results
 //   api_grad.hip    clr_batch_grad*: the gradient entry points
 //   api_kernels.hip the small kernels the plans launch themselves (finalize, relayouts, factor de-interleave)
-// Here: error reporting, the device buffer, the two handle structs, and the functions that turn a plan's state into
+// Here: error reporting, the device buffer types, the two handle structs, and the functions that turn a plan's state into
 // kernel parameters (used by the evaluation and by the gradient).  Everything is internal to libcelerite_hip.so.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -27,6 +27,7 @@
 #include "clr_small.h"
 #include "clr_wide.h"
 #include "clr_options.h"
+#include "clr_handles.h"
 
 // the last error message of the calling thread (clr_last_error) and its current device: ONE object per thread for the
 // whole library (defined in api_misc.hip)
@@ -77,26 +78,16 @@ int require_device(int device) {
   return CLR_OK;
 }
 
-// Grow-only device buffer.
-struct DevBuf {
-  double* p = nullptr;
-  size_t cap = 0;  // doubles
-  int reserve(size_t n) {
-    if (n <= cap && p) return CLR_OK;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    const size_t want = std::max<size_t>(n, 1);
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&p), want * sizeof(double)));
-    cap = want;
-    return CLR_OK;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-};
+// Grow-only device arrays (clr_handles.h): freed with the plan, solver or scope that holds them.
+using DevBuf = clr::Buffer<double>;
+template <class T>
+using DevArray = clr::Buffer<T>;
+
+// returns `code` once `s` has drained (early returns of a function whose kernels may still use its local buffers)
+int synced(hipStream_t s, int code) {
+  (void)hipStreamSynchronize(s);
+  return code;
+}
 
 int upload(DevBuf& buf, const double* host, size_t n, hipStream_t s) {
   int st = buf.reserve(n);
@@ -151,13 +142,19 @@ int auto_chunks(int B, int N, int J, bool with_replay = false) {
 }  // namespace
 
 /* ======================================================================== */
+// a plan owned by another handle (a side plan, the solver's gradient plan)
+struct BatchDeleter { void operator()(clr_batch* b) const { clr_batch_destroy(b); } };
+using BatchPtr = std::unique_ptr<clr_batch, BatchDeleter>;
+
+// The handles own their device memory, pinned memory, streams and events (clr_handles.h): members are freed in reverse
+// order of declaration after the destructor's body, so each stream is declared before everything queued on it.
 struct clr_solver {
   int device = 0;
-  hipStream_t stream = nullptr;
+  clr::Stream stream;
   bool have_stream = false;
   // grad_log_likelihood parallel in n (widths 1..8, no general terms): a one-problem plan kept between calls, and
   // the series it holds (an optimiser calls with the same t, diag, y and new coefficients)
-  struct clr_batch* grad_plan = nullptr;
+  BatchPtr grad_plan;
   int grad_N = 0, grad_JR = -1, grad_JC = -1;
   bool grad_wide = false, grad_had_general = false;
   std::vector<double> grad_series;
@@ -199,18 +196,25 @@ struct clr_solver {
   bool rhs_hint = false, have_quad = false;
   bool coeffs_lazy = false;             // host_coeffs not yet on the device (the one-launch route passes them as arguments)
   double cached_quad = 0.0;
-  int* ws_flags = nullptr;
-  size_t ws_flags_cap = 0;
-  int* d_status = nullptr;
+  DevArray<int> ws_flags;
+  DevArray<int> d_status;
   // pinned staging of compute's inputs and results: copies from pageable memory cost ~15 us of host time each
   // (six of them per GP.log_likelihood on a short series: profiles/r02zzz_config0_hip_trace.txt)
-  double* pin = nullptr;
-  size_t pin_cap = 0, pin_off = 0;
+  clr::PinnedBuffer<double> pin;
+  size_t pin_off = 0;
+
+  ~clr_solver() {
+    grad_plan.reset();
+    if (have_stream) {
+      (void)hipSetDevice(device);
+      (void)hipStreamSynchronize(stream.get());
+    }
+  }
 };
 
 struct clr_batch {
   int device = 0;
-  hipStream_t stream = nullptr;
+  clr::Stream stream;
   int B = 0, N = 0, J_real = 0, J_comp = 0, J = 0;
   int nchunk = 1, L = 0;
   int L0 = 0;                      // wide plans: samples of the first chunk when it is longer than L (0: uniform)
@@ -220,14 +224,13 @@ struct clr_batch {
   int gen_nchunk = 0, gen_L = 0, gen_L0 = 0;
   DevBuf gen_elems, gen_starts, gen_part, gen_cond, gen_scan;
   size_t gen_scan_ws_doubles = 0, scan_ws_doubles = 0;  // workspace of the wide parallel prefix (0: sequential walk)
-  int* gen_flags = nullptr;
+  DevArray<int> gen_flags;
   bool pipeline_pinned = false;    // the caller tuned the scan pipeline (chunks, prefix, summarize kernel, layout, certificate): auto small mode stays out
   double wide_first_ratio64 = 1.45;  // ... at widths 33..64 (2.3 before the summarize split the features' work between a row's lanes: profiles/r05k_wide_feature_batch.txt)
   double wide_first_ratio = 1.25;  // wide plans: cost of a chunk with riders / cost of the riderless first chunk (1.1-1.25 within 2 %: profiles/r04c, r04p)
   const clr::BatchLaunchers* launch = nullptr;
   DevBuf coeffs, t, diag, y;          // coefficients (| jitter at the end); series in the API's row-major layout
-  double* pin = nullptr;              // pinned host staging: coefficient uploads, result downloads
-  size_t pin_cap = 0;
+  clr::PinnedBuffer<double> pin;      // pinned host staging: coefficient uploads, result downloads
   DevBuf tT, dT, yT;                  // chunk-interleaved copies the kernels read
   long t_stride = 0, diag_stride = 0, y_stride = 0;
   int layout = 2;                     // 0 row-major direct, 1 interleaved copy, 2 staged through LDS
@@ -248,8 +251,7 @@ struct clr_batch {
   DevBuf g_riders, g_out, g_res;      // chunk-parallel gradient (clr_grad_kernels.h): riders, records, result (+ fallback)
   int grad_rebuild_span = 4;          // reverse mode, adaptive rule: stored states at least this many steps apart (GradStore::span)
   DevBuf g_rec, g_ck;                 // reverse mode: w, D, x per sample; stored states (GradStore, clr_grad_core.h)
-  unsigned char* g_ckflag = nullptr;  // what the forward pass did before each step, per wave of 64 chunks
-  size_t g_ckflag_cap = 0;
+  DevArray<unsigned char> g_ckflag;   // what the forward pass did before each step, per wave of 64 chunks
   std::vector<double> host_cmax;      // per problem: largest decay rate (sizes the stored states)
   std::vector<double> grad_span;      // per problem (one entry when the series is shared): longest time a scan chunk spans
   bool grad_span_valid = false;
@@ -293,8 +295,7 @@ struct clr_batch {
   bool warm_copy_pending = true;
   DevBuf sT, sD, sY;                  // the one-launch path's chunk-interleaved copy of the series (small_params, api_batch.hip)
   bool small_copy_pending = true;
-  int* wints = nullptr;               // wflags [B * wnchunk] | need_scan [B] | K [B]
-  size_t wints_cap = 0;
+  DevArray<int> wints;                // wflags [B * wnchunk] | need_scan [B] | K [B]
   // general terms for the whole batch (clr_batch_set_general): the plan then evaluates through the any-width sequential
   // kernel, one workgroup per problem (generic_kernels.hip: generic_loglike_batch_kernel)
   int J_general = 0;
@@ -306,14 +307,14 @@ struct clr_batch {
   bool have_series = false, have_coeffs = false, have_factor = false;
   bool evaluated = false;             // an evaluation has been enqueued since the plan was (re)chunked
   DevBuf elems, starts, part, partx, cond, out;  // out: ll | logdet | quad | status (B ints)
-  int* flags = nullptr;                    // flags [B*nchunk] | flagsx [B*nchunk] | need_exact [B]
+  DevArray<int> flags;                     // flags [B*nchunk] | flagsx [B*nchunk] | need_exact [B]
   int force_exact = 0;
   bool factor_valid = false;  // a materialising run has written the factor under the chunking in force
   DevBuf bs_decay, bs_y;                        // clr_batch_dot_L / clr_batch_dot: the chunks' decay products; dot's output, chunk-interleaved
   DevBuf bs_rm, bs_x, bs_M, bs_off, bs_starts;  // clr_batch_solve: right-hand sides row-major / chunk-interleaved, chunk maps, offsets, start states
   bool bs_M_valid = false;                      // bs_M holds the chunk maps of the factor in HBM (they depend on the factor only)
   double solve_device_ms = 0.0;                 // device time of the last clr_batch_solve (HIP events around its kernels)
-  hipEvent_t bs_ev[2] = {nullptr, nullptr};     // ... its two timing events, created by the first solve, kept for the plan's life
+  clr::Event bs_ev[2];                          // ... its two timing events, created by the first solve, kept for the plan's life
   int factor_layout = 0;      // clr_batch_set_factor_layout: 0 the reference's four arrays, 1 lean (W, D; phi, u regenerated)
   bool factor_is_lean = false;  // what the factor in HBM holds (set by the materialising run that wrote it)
   bool factor_inputs_changed = false;  // series or coefficients replaced since that run (a lean factor can then no longer be expanded)
@@ -325,17 +326,16 @@ struct clr_batch {
   // materialising runs as a pipeline over groups of problems (clr_batch_set_materialize_pipeline): the summarize of
   // group g + 1 (fp64-VALU-bound) runs beside the replay of group g (HBM-bound) on streams that own disjoint sets of CUs
   int mp_groups = 0, mp_cus = 0, mp_nstreams = 1;
-  std::vector<hipStream_t> mp_s;        // summarize streams (CU-masked when mp_cus > 0)
-  hipStream_t mp_p = nullptr, mp_r = nullptr;  // prefix + corrections (any CU); replay (the other CUs)
-  std::vector<hipEvent_t> mp_ev;        // [0] start, [1 + 2 g] group g summarized, [2 + 2 g] its start states ready, [last] replay done
+  std::vector<clr::Stream> mp_s;        // summarize streams (CU-masked when mp_cus > 0)
+  clr::Stream mp_p, mp_r;               // prefix + corrections (any CU); replay (the other CUs)
+  std::vector<clr::Event> mp_ev;        // [0] start, [1 + 2 g] group g summarized, [2 + 2 g] its start states ready, [last] replay done
   // problems the conditioning record sends to the checked chunked replay (level 1), re-planned as a small plan of their
   // own with many short chunks instead of replaying long chunks sequentially beside an idle chip (clr_batch_set_rescue)
   int rescue_mode = -1;            // -1 auto (chunks of >= 1024 samples), 0 off: the inline chunked replay, 1 whenever possible
   bool rescue_inflight = false;    // the evaluation in flight deferred its level-1 problems (pending until resolved)
   bool is_rescue_plan = false;     // this plan IS such a side plan (never defers)
-  struct clr_batch* rescue = nullptr;
-  int* rescue_idx = nullptr;       // device: the re-planned problems' indices
-  size_t rescue_idx_cap = 0;
+  BatchPtr rescue;
+  DevArray<int> rescue_idx;        // device: the re-planned problems' indices
   int rescue_last = 0;             // problems of the last resolved evaluation that were re-planned (or replayed inline: negative)
   long rescue_total = 0;
   long rescue_plan_key = -1;       // the batch-wide count of pending problems the side plan in `rescue` was chunked for
@@ -352,7 +352,13 @@ struct clr_batch {
   bool pin_results = false;        // the pinned staging buffer holds the final results of the evaluation in force
   // optional per-kernel HIP events around the launches of clr_batch_enqueue (clr_batch_set_profiling)
   int prof_on = 0, prof_steps = 0;
-  std::vector<hipEvent_t> prof_events;  // 7 per recorded step
+  std::vector<clr::Event> prof_events;  // 7 per recorded step
+
+  ~clr_batch() {
+    (void)hipSetDevice(device);
+    if (stream) (void)hipStreamSynchronize(stream.get());
+    rescue.reset();  // (its own plan: gone before this plan's pipeline streams)
+  }
 };
 
 
@@ -480,7 +486,7 @@ int batch_params(clr_batch* h, int materialize, clr::BatchParams& P) {
     P.lane_is = 1; P.lane_cs = h->L;
     P.staged = ((h->layout == 2 || h->in_fallback) && h->nchunk > 1) ? 1 : 0;
   }
-  P.elems = h->elems.p; P.starts = h->starts.p; P.part = h->part.p; P.flags = h->flags;
+  P.elems = h->elems.p; P.starts = h->starts.p; P.part = h->part.p; P.flags = h->flags.p;
   P.cond = h->cond.p;
   P.cert_gamma = h->cert_gamma;
   P.cert_gamma_abs = h->cert_gamma_abs;
@@ -490,15 +496,15 @@ int batch_params(clr_batch* h, int materialize, clr::BatchParams& P) {
   P.head_cap = clr::output_check_cap(); P.head_tol = clr::output_check_tol();  // (materialising wide plans: BatchParams::head_check)
   {
     const size_t pc = B * (size_t)h->nchunk;
-    P.partx = h->partx.p; P.flagsx = h->flags + pc; P.need_exact = h->flags + 2 * pc;
+    P.partx = h->partx.p; P.flagsx = h->flags.p + pc; P.need_exact = h->flags.p + 2 * pc;
     // a single chunk starts from the zero state: its replay IS the whole recurrence
     P.force_exact = (materialize || h->force_exact || h->nchunk < 2) ? 1 : 0;
   }
   P.out_ll = h->out.p; P.out_logdet = h->out.p + B; P.out_quad = h->out.p + 2 * B;
   P.out_status = reinterpret_cast<int*>(h->out.p + 3 * B);
-  if (h->wints) {
+  if (h->wints.p) {
     const size_t wpc = B * (size_t)h->wnchunk;
-    P.wflags = h->wints; P.need_scan = h->wints + wpc; P.wK = h->wints + wpc + B;
+    P.wflags = h->wints.p; P.need_scan = h->wints.p + wpc; P.wK = h->wints.p + wpc + B;
     P.wL = h->wL; P.wnchunk = h->wnchunk;
     P.wstarts = h->wstarts.p; P.wends = h->wends.p; P.wpart = h->wpart.p; P.wresid = h->wresid.p;
     P.warm_resid = h->cert_resid;
@@ -556,15 +562,15 @@ bool batch_relayout(clr_batch* h) {
       {&h->t, &h->tT, h->t_stride, 1}, {&h->diag, &h->dT, h->diag_stride, 2}, {&h->y, &h->yT, h->y_stride, 0}};
   for (auto& j : jobs)
     clr::launch_relayout(j.src->p, j.stride, j.dst->p, j.stride ? cells : 0, j.stride ? h->B : 1,
-                         h->N, h->L, h->nchunk, j.pad, h->stream);
+                         h->N, h->L, h->nchunk, j.pad, h->stream.get());
   return true;
 }
 
 
 // CLR_OK, or CLR_HIP_ERROR when a kernel of the flow could not be configured (nothing after it is launched: the later
 // kernels would run on stale start states)
-int wide_flow(clr::BatchParams& P, int J_real, int J_comp, hipStream_t stream, hipEvent_t* ev) {
-  auto mark = [&](int i) { if (ev) (void)hipEventRecord(ev[i], stream); };
+int wide_flow(clr::BatchParams& P, int J_real, int J_comp, hipStream_t stream, const clr::Event* ev) {
+  auto mark = [&](int i) { if (ev) (void)hipEventRecord(ev[i].get(), stream); };
   const int JP = clr::wide_padded_width(J_real + 2 * J_comp + P.J_general);
   mark(1);
   if (P.nchunk > 1) clr::launch_wide_summarize(P, J_real, J_comp, stream);
@@ -620,8 +626,8 @@ int wide_flow(clr::BatchParams& P, int J_real, int J_comp, hipStream_t stream, h
   mark(6);
   return CLR_OK;
 }
-int wide_launch(clr_batch* h, clr::BatchParams& P, hipEvent_t* ev) {
-  return wide_flow(P, h->J_real, h->J_comp, h->stream, ev);
+int wide_launch(clr_batch* h, clr::BatchParams& P, const clr::Event* ev) {
+  return wide_flow(P, h->J_real, h->J_comp, h->stream.get(), ev);
 }
 
 const int PROF_NK = 6, PROF_MAX_STEPS = 4096;
@@ -644,7 +650,7 @@ void general_wide_params(const clr_batch* h, const clr::BatchParams& P, clr::Bat
   W.scan_ws = h->gen_scan_ws_doubles ? h->gen_scan.p : nullptr;
   W.part = h->gen_part.p; W.partx = h->gen_part.p + pc * 2;
   W.cond = h->gen_cond.p; W.egerr = h->gen_cond.p + pc * 3;
-  W.flags = h->gen_flags; W.flagsx = h->gen_flags + pc; W.need_exact = h->gen_flags + 2 * pc;
+  W.flags = h->gen_flags.p; W.flagsx = h->gen_flags.p + pc; W.need_exact = h->gen_flags.p + 2 * pc;
   W.force_exact = (h->force_exact || W.nchunk < 2) ? 1 : 0;
   W.wide_materialize = 0;
 }

@@ -145,22 +145,21 @@ int clr_device_measure_fp64(int waves_per_simd, int iters, double* tflops, doubl
   hipDeviceProp_t prop;
   HIP_TRY(hipGetDeviceProperties(&prop, g_device));
   const int waves = prop.multiProcessorCount * 4 * waves_per_simd;
-  double* out = nullptr;
-  unsigned long long* rec = nullptr;
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&out), (size_t)waves * 64 * sizeof(double)));
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&rec), (size_t)waves * 2 * sizeof(unsigned long long)));
-  hipEvent_t e0, e1;
-  HIP_TRY(hipEventCreate(&e0));
-  HIP_TRY(hipEventCreate(&e1));
-  hipLaunchKernelGGL(fp64_load_kernel, dim3(waves), dim3(64), 0, 0, out, rec, iters / 4, 1.0);  // (clocks settle)
-  HIP_TRY(hipEventRecord(e0, 0));
-  hipLaunchKernelGGL(fp64_load_kernel, dim3(waves), dim3(64), 0, 0, out, rec, iters, 1.0);
-  HIP_TRY(hipEventRecord(e1, 0));
+  DevBuf out;
+  DevArray<unsigned long long> rec;
+  if ((st = out.reserve((size_t)waves * 64)) != CLR_OK || (st = rec.reserve((size_t)waves * 2)) != CLR_OK) return st;
+  clr::Event e0, e1;
+  HIP_TRY(clr::create_event(e0));
+  HIP_TRY(clr::create_event(e1));
+  hipLaunchKernelGGL(fp64_load_kernel, dim3(waves), dim3(64), 0, 0, out.p, rec.p, iters / 4, 1.0);  // (clocks settle)
+  HIP_TRY(hipEventRecord(e0.get(), 0));
+  hipLaunchKernelGGL(fp64_load_kernel, dim3(waves), dim3(64), 0, 0, out.p, rec.p, iters, 1.0);
+  HIP_TRY(hipEventRecord(e1.get(), 0));
   HIP_TRY(hipDeviceSynchronize());
   float ms = 0.f;
-  HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
+  HIP_TRY(hipEventElapsedTime(&ms, e0.get(), e1.get()));
   std::vector<unsigned long long> h((size_t)waves * 2);
-  HIP_TRY(hipMemcpy(h.data(), rec, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(h.data(), rec.p, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
   std::vector<double> mhz((size_t)waves), cpi((size_t)waves);
   for (int w = 0; w < waves; ++w) {
     mhz[(size_t)w] = (double)h[2 * (size_t)w] / (double)h[2 * (size_t)w + 1] * 100.0;
@@ -172,10 +171,6 @@ int clr_device_measure_fp64(int waves_per_simd, int iters, double* tflops, doubl
   if (tflops) *tflops = 2.0 * 64.0 * 64.0 * iters * waves / (ms * 1e-3) / 1e12;
   if (clock_mhz) *clock_mhz = mhz[mhz.size() / 2];
   if (cycles_per_fma) *cycles_per_fma = cpi[cpi.size() / 2];
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  (void)hipFree(out);
-  (void)hipFree(rec);
   return CLR_OK;
 }
 
@@ -186,9 +181,13 @@ int clr_device_measure_fp64(int waves_per_simd, int iters, double* tflops, doubl
 struct clr_carma {
   clr::CarmaModel model;
   int device = 0;
-  hipStream_t stream = nullptr;
+  clr::Stream stream;
   DevBuf dmodel, dt, dy, dyerr, dout;  // dout: [ll | status as int bits]
   bool model_resident = false;
+
+  ~clr_carma() {
+    if (stream || dmodel.p) (void)hipSetDevice(device);
+  }
 };
 
 clr_carma* clr_carma_create(double log_sigma, int p, const double* arparams, int q, const double* maparams,
@@ -213,15 +212,7 @@ clr_carma* clr_carma_create(double log_sigma, int p, const double* arparams, int
   return h;
 }
 
-void clr_carma_destroy(clr_carma* h) {
-  if (!h) return;
-  if (h->stream || h->dmodel.p) {
-    (void)hipSetDevice(h->device);
-    for (DevBuf* b : {&h->dmodel, &h->dt, &h->dy, &h->dyerr, &h->dout}) b->release();
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-  }
-  delete h;
-}
+void clr_carma_destroy(clr_carma* h) { delete h; }
 
 int clr_carma_get_celerite_coeffs(const clr_carma* h, int* n_real, int* n_comp, double* a_real, double* c_real,
                                   double* a_comp, double* b_comp, double* c_comp, double* d_comp) {
@@ -240,7 +231,7 @@ int clr_carma_log_likelihood(clr_carma* h, int n_t, const double* t, int n_y, co
   if (n_y != n_t || n_yerr != n_t) return fail(CLR_DIMENSION_MISMATCH, "dimension mismatch");  // carma.h:223
   int st = require_device(h->device);
   if (st != CLR_OK) return st;
-  if (!h->stream) HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+  if (!h->stream) HIP_TRY(clr::create_stream(h->stream));
   const int p = h->model.p, n = n_t;
   if (n == 0 || p == 0) {
     // (an empty series: the filter loop does not run; p = 0 cannot happen, q < p)
@@ -253,20 +244,20 @@ int clr_carma_log_likelihood(clr_carma* h, int n_t, const double* t, int n_y, co
       for (const std::complex<double>& c : a) { pk.push_back(c.real()); pk.push_back(c.imag()); }
     };
     push(h->model.b); push(h->model.V); push(h->model.loglam);
-    if ((st = upload(h->dmodel, pk.data(), pk.size(), h->stream)) != CLR_OK) return st;
-    HIP_TRY(hipStreamSynchronize(h->stream));  // (pk is a local)
+    if ((st = upload(h->dmodel, pk.data(), pk.size(), h->stream.get())) != CLR_OK) return st;
+    HIP_TRY(hipStreamSynchronize(h->stream.get()));  // (pk is a local)
     h->model_resident = true;
   }
-  if ((st = upload(h->dt, t, (size_t)n, h->stream)) != CLR_OK) return st;
-  if ((st = upload(h->dy, y, (size_t)n, h->stream)) != CLR_OK) return st;
-  if ((st = upload(h->dyerr, yerr, (size_t)n, h->stream)) != CLR_OK) return st;
+  if ((st = upload(h->dt, t, (size_t)n, h->stream.get())) != CLR_OK) return st;
+  if ((st = upload(h->dy, y, (size_t)n, h->stream.get())) != CLR_OK) return st;
+  if ((st = upload(h->dyerr, yerr, (size_t)n, h->stream.get())) != CLR_OK) return st;
   if ((st = h->dout.reserve(2)) != CLR_OK) return st;
   clr::launch_carma_filter(n, p, h->dmodel.p, h->dt.p, h->dy.p, h->dyerr.p, h->dout.p,
-                           reinterpret_cast<int*>(h->dout.p + 1), h->stream);
+                           reinterpret_cast<int*>(h->dout.p + 1), h->stream.get());
   HIP_TRY(hipGetLastError());
   double host[2] = {0.0, 0.0};
-  HIP_TRY(hipMemcpyAsync(host, h->dout.p, sizeof(host), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipMemcpyAsync(host, h->dout.p, sizeof(host), hipMemcpyDeviceToHost, h->stream.get()));
+  HIP_TRY(hipStreamSynchronize(h->stream.get()));
   int bad = 0;
   memcpy(&bad, &host[1], sizeof(int));
   if (bad) return fail(CLR_CARMA_INSTABILITY, "CARMA model encountered an instability");  // exceptions.h:8-12

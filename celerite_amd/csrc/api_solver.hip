@@ -11,8 +11,8 @@ int ensure_stream(clr_solver* s) {
   int st = require_device(s->device);
   if (st != CLR_OK) return st;
   if (!s->have_stream) {
-    HIP_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&s->d_status), sizeof(int) * 4));
+    HIP_TRY(clr::create_stream(s->stream));
+    if ((st = s->d_status.reserve(4)) != CLR_OK) return st;
     s->have_stream = true;
   }
   return CLR_OK;
@@ -36,15 +36,6 @@ clr::GenericProblem generic_view(const clr_solver* s) {
   g.V = s->V.p;
   g.t = s->t.p;
   return g;
-}
-
-int reserve_flags(int*& p, size_t& cap, size_t n) {
-  if (n <= cap && p) return CLR_OK;
-  if (p) (void)hipFree(p);
-  p = nullptr;
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(n, 1) * sizeof(int)));
-  cap = std::max<size_t>(n, 1);
-  return CLR_OK;
 }
 
 int check_coeff_dims(int n_a_real, int n_c_real, int n_a_comp, int n_b_comp, int n_c_comp,
@@ -80,30 +71,19 @@ void arena_reset(clr_solver* s, size_t want_doubles) {
   s->pin_off = 0;
   const size_t LIMIT = (size_t)1 << 20;  // 8 MB of pinned memory per solver at most
   if (want_doubles > LIMIT) return;      // (long series: the copies are bandwidth-, not latency-bound)
-  if (want_doubles > s->pin_cap) {
-    if (s->pin) (void)hipHostFree(s->pin);
-    s->pin = nullptr;
-    s->pin_cap = 0;
-    void* p = nullptr;
-    if (hipHostMalloc(&p, want_doubles * sizeof(double), hipHostMallocDefault) == hipSuccess) {
-      s->pin = static_cast<double*>(p);
-      s->pin_cap = want_doubles;
-    } else {
-      (void)hipGetLastError();
-    }
-  }
+  if (want_doubles > s->pin.cap && s->pin.reserve(want_doubles) != CLR_OK) (void)hipGetLastError();
 }
 double* arena_take(clr_solver* s, size_t n) {
-  if (!s->pin || s->pin_off + n > s->pin_cap) return nullptr;
-  double* p = s->pin + s->pin_off;
+  if (!s->pin.p || s->pin_off + n > s->pin.cap) return nullptr;
+  double* p = s->pin.p + s->pin_off;
   s->pin_off += n;
   return p;
 }
 int stage_upload(clr_solver* s, DevBuf& buf, const double* host, size_t n) {
   double* p = arena_take(s, n);
-  if (!p) return upload(buf, host, n, s->stream);
+  if (!p) return upload(buf, host, n, s->stream.get());
   memcpy(p, host, n * sizeof(double));
-  return upload(buf, p, n, s->stream);
+  return upload(buf, p, n, s->stream.get());
 }
 
 }  // namespace
@@ -123,25 +103,7 @@ clr_solver* clr_solver_create(void) {
   return s;  // device resources are acquired lazily, so construction never fails
 }
 
-void clr_solver_destroy(clr_solver* s) {
-  if (!s) return;
-  if (s->grad_plan) clr_batch_destroy(s->grad_plan);
-  if (s->have_stream) {
-    (void)hipSetDevice(s->device);
-    (void)hipStreamSynchronize(s->stream);
-    for (DevBuf* b : {&s->phi, &s->u, &s->W, &s->D, &s->coeffs, &s->t, &s->U, &s->V,
-                      &s->scratch, &s->scratch2, &s->scalars, &s->keep_diag, &s->keep_jitter, &s->ws_ends, &s->ws_elems, &s->ws_starts,
-                      &s->ws_part, &s->ws_cond, &s->gradbuf, &s->gradws, &s->rhs, &s->ws_lvl_elems, &s->ws_lvl_starts})
-      b->release();
-    for (DevBuf& b : s->dot_buf) b.release();
-    for (DevBuf& b : s->pred_buf) b.release();
-    if (s->ws_flags) (void)hipFree(s->ws_flags);
-    if (s->d_status) (void)hipFree(s->d_status);
-    if (s->pin) (void)hipHostFree(s->pin);
-    (void)hipStreamDestroy(s->stream);
-  }
-  delete s;
-}
+void clr_solver_destroy(clr_solver* s) { delete s; }
 
 
 int clr_solver_compute(clr_solver* s, double jitter, int n_a_real, const double* a_real,
@@ -173,7 +135,7 @@ int clr_solver_compute(clr_solver* s, double jitter, int n_a_real, const double*
 
   st = ensure_stream(s);
   if (st != CLR_OK) return st;
-  hipStream_t stream = s->stream;
+  hipStream_t stream = s->stream.get();
 
   s->N = N;
   s->J = J;
@@ -296,7 +258,7 @@ int clr_solver_compute(clr_solver* s, double jitter, int n_a_real, const double*
     if ((st = s->ws_starts.reserve((size_t)P.nchunk * L->start_doubles)) != CLR_OK) return st;
     if ((st = s->ws_part.reserve((size_t)P.nchunk * 2)) != CLR_OK) return st;
     if ((st = s->ws_cond.reserve((size_t)P.nchunk * 4)) != CLR_OK) return st;
-    if ((st = reserve_flags(s->ws_flags, s->ws_flags_cap, (size_t)P.nchunk + 1)) != CLR_OK) return st;
+    if ((st = s->ws_flags.reserve((size_t)P.nchunk + 1)) != CLR_OK) return st;
     const clr::GenericProblem g = generic_view(s);
     P.jitter = s->keep_jitter.p;
     P.a_real = g.a_real; P.c_real = g.c_real;
@@ -311,9 +273,9 @@ int clr_solver_compute(clr_solver* s, double jitter, int n_a_real, const double*
     P.lane_is = 1; P.lane_cs = P.L;
     P.staged = P.nchunk > 1 ? 1 : 0;
     P.elems = s->ws_elems.p; P.starts = s->ws_starts.p; P.part = s->ws_part.p;
-    P.flags = s->ws_flags;
+    P.flags = s->ws_flags.p;
     // the factor is wanted: always the exact replay, which overwrites the zero-start sums
-    P.partx = P.part; P.flagsx = P.flags; P.need_exact = s->ws_flags + P.nchunk; P.force_exact = 1;
+    P.partx = P.part; P.flagsx = P.flags; P.need_exact = s->ws_flags.p + P.nchunk; P.force_exact = 1;
     P.out_ll = s->scalars.p; P.out_logdet = s->scalars.p + 1; P.out_quad = s->scalars.p + 2;
     P.out_status = reinterpret_cast<int*>(s->scalars.p + 3);
     P.phi = s->phi.p; P.u = s->u.p; P.W = s->W.p; P.D = s->D.p;
@@ -391,7 +353,7 @@ int clr_solver_compute(clr_solver* s, double jitter, int n_a_real, const double*
     P.scan_ws = scan_ws ? s->ws_lvl_elems.p : nullptr;
     if ((st = s->ws_part.reserve(pc * 4)) != CLR_OK) return st;
     if ((st = s->ws_cond.reserve(pc * 4)) != CLR_OK) return st;
-    if ((st = reserve_flags(s->ws_flags, s->ws_flags_cap, 2 * pc + 1)) != CLR_OK) return st;
+    if ((st = s->ws_flags.reserve(2 * pc + 1)) != CLR_OK) return st;
     const clr::GenericProblem g = generic_view(s);
     P.jitter = s->keep_jitter.p;
     P.a_real = g.a_real; P.c_real = g.c_real;
@@ -406,7 +368,7 @@ int clr_solver_compute(clr_solver* s, double jitter, int n_a_real, const double*
     P.lane_is = 1; P.lane_cs = P.L;
     P.elems = s->ws_elems.p; P.starts = s->ws_starts.p;
     P.part = s->ws_part.p; P.partx = s->ws_part.p + pc * 2;
-    P.flags = s->ws_flags; P.flagsx = s->ws_flags + pc; P.need_exact = s->ws_flags + 2 * pc;
+    P.flags = s->ws_flags.p; P.flagsx = s->ws_flags.p + pc; P.need_exact = s->ws_flags.p + 2 * pc;
     P.cond = s->ws_cond.p; P.cert_gamma = 1e7; P.cert_gamma_abs = 1e4; P.cert_eg = 3e-9; P.egerr = s->ws_cond.p + (size_t)P.nchunk * 3; P.cert_resid = solver_cert_resid(); P.logdet_only = use_rhs ? 0 : 1;
     P.force_exact = 1;       // the factor is wanted: every chunk is replayed (and checked against the scan)
     P.wide_materialize = 1;
@@ -474,16 +436,16 @@ int clr_solver_compute(clr_solver* s, double jitter, int n_a_real, const double*
       const int fast = (dmax * max_abs(x, N) < CLR_FAST_TRIG_LIMIT) ? 1 : 0;
       // (a hinted right-hand side: its quadratic form comes out of the same pass, as on the chunked routes)
       if (use_rhs && (st = stage_upload(s, s->rhs, s->host_rhs.data(), (size_t)N)) != CLR_OK) return st;
-      clr::launch_factor_rows(g, fast, use_rhs ? s->rhs.p : nullptr, s->ws_elems.p, s->phi.p, s->u.p, s->W.p, s->D.p, s->d_status, s->scalars.p, stream);
+      clr::launch_factor_rows(g, fast, use_rhs ? s->rhs.p : nullptr, s->ws_elems.p, s->phi.p, s->u.p, s->W.p, s->D.p, s->d_status.p, s->scalars.p, stream);
       rows_quad = use_rhs;
     } else if (J > CLR_MAX_WIDTH) {  // S (J^2 doubles) in HBM / L2 instead of LDS (huge_kernels.hip)
       if ((st = s->ws_elems.reserve(clr::factor_huge_workspace_doubles(J))) != CLR_OK) return st;
-      clr::launch_factor_huge(g, s->ws_elems.p, s->phi.p, s->u.p, s->W.p, s->D.p, s->d_status, s->scalars.p, stream);
+      clr::launch_factor_huge(g, s->ws_elems.p, s->phi.p, s->u.p, s->W.p, s->D.p, s->d_status.p, s->scalars.p, stream);
     } else
-    clr::launch_factor_generic(g, s->phi.p, s->u.p, s->W.p, s->D.p, s->d_status, s->scalars.p,
+    clr::launch_factor_generic(g, s->phi.p, s->u.p, s->W.p, s->D.p, s->d_status.p, s->scalars.p,
                                stream);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(&h_status, s->d_status, sizeof(int), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(&h_status, s->d_status.p, sizeof(int), hipMemcpyDeviceToHost, stream));
     double two[2] = {0.0, 0.0};
     HIP_TRY(hipMemcpyAsync(two, s->scalars.p, (rows_quad ? 2 : 1) * sizeof(double), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
@@ -521,7 +483,7 @@ int clr_solver_grad_log_likelihood(clr_solver* s, double jitter, int n_a_real, c
   const int G = 1 + 2 * JR + 4 * JC;
   if (n_grad != G || !value || !grad) return fail(CLR_INVALID_ARGUMENT, "grad must hold 1 + 2 J_real + 4 J_comp values");
   if ((st = ensure_stream(s)) != CLR_OK) return st;
-  hipStream_t stream = s->stream;
+  hipStream_t stream = s->stream.get();
 
   const int Wc = JR + 2 * JC, Wt = Wc + JG;
   const bool narrow_plan = !has_general && JG == 0 && Wc >= 1 && Wc <= 8 && N >= 1024;
@@ -532,8 +494,8 @@ int clr_solver_grad_log_likelihood(clr_solver* s, double jitter, int n_a_real, c
   if ((narrow_plan || wide_plan) && !clr::option("CLR_GRAD_SEQUENTIAL")) {
     // parallel in n: the scan + the chunk-wise tangents (clr_batch_grad) on a one-problem plan
     if (!s->grad_plan || s->grad_N != N || s->grad_JR != JR || s->grad_JC != JC || s->grad_wide != wide_plan) {
-      if (s->grad_plan) clr_batch_destroy(s->grad_plan);
-      s->grad_plan = clr_batch_create(1, N, JR, JC, s->device);
+      s->grad_plan.reset();
+      s->grad_plan.reset(clr_batch_create(1, N, JR, JC, s->device));
       s->grad_series.clear();
       s->grad_N = N; s->grad_JR = JR; s->grad_JC = JC; s->grad_wide = wide_plan;
       if (s->grad_plan && wide_plan) {
@@ -569,7 +531,7 @@ int clr_solver_grad_log_likelihood(clr_solver* s, double jitter, int n_a_real, c
           }
         }
         nc = std::max(4, std::min(nc, 128));
-        if ((st = clr_batch_set_chunks(s->grad_plan, nc)) != CLR_OK) return st;
+        if ((st = clr_batch_set_chunks(s->grad_plan.get(), nc)) != CLR_OK) return st;
       }
     }
     if (s->grad_plan) {
@@ -578,20 +540,20 @@ int clr_solver_grad_log_likelihood(clr_solver* s, double jitter, int n_a_real, c
                         !memcmp(s->grad_series.data() + n, diag, n * sizeof(double)) &&
                         !memcmp(s->grad_series.data() + 2 * n, y, n * sizeof(double));
       if (!same) {
-        if ((st = clr_batch_set_series(s->grad_plan, x, 0, diag, 0, y, 0)) != CLR_OK) return st;
+        if ((st = clr_batch_set_series(s->grad_plan.get(), x, 0, diag, 0, y, 0)) != CLR_OK) return st;
         s->grad_series.resize(3 * n);
         memcpy(s->grad_series.data(), x, n * sizeof(double));
         memcpy(s->grad_series.data() + n, diag, n * sizeof(double));
         memcpy(s->grad_series.data() + 2 * n, y, n * sizeof(double));
       }
       if (wide_plan && (JG > 0 || s->grad_had_general)) {  // (general terms are arguments of every call)
-        if ((st = clr_batch_set_general(s->grad_plan, JG, A, 0, U, 0, V, 0)) != CLR_OK) return st;
+        if ((st = clr_batch_set_general(s->grad_plan.get(), JG, A, 0, U, 0, V, 0)) != CLR_OK) return st;
         s->grad_had_general = JG > 0;
       }
-      if ((st = clr_batch_set_coefficients(s->grad_plan, &jitter, a_real, c_real, a_comp, b_comp, c_comp, d_comp)) != CLR_OK)
+      if ((st = clr_batch_set_coefficients(s->grad_plan.get(), &jitter, a_real, c_real, a_comp, b_comp, c_comp, d_comp)) != CLR_OK)
         return st;
       int pst = CLR_OK;
-      if ((st = clr_batch_grad(s->grad_plan, value, grad, &pst)) != CLR_OK) return st;
+      if ((st = clr_batch_grad(s->grad_plan.get(), value, grad, &pst)) != CLR_OK) return st;
       if (pst != CLR_OK) return fail(CLR_NOT_POSITIVE_DEFINITE, "failed to factorize or solve matrix");
       return CLR_OK;
     }
@@ -625,7 +587,7 @@ int clr_solver_grad_log_likelihood(clr_solver* s, double jitter, int n_a_real, c
   }
   P.out_value = s->gradbuf.p + o_out;
   P.out_grad = s->gradbuf.p + o_out + 1;
-  P.out_status = s->d_status;
+  P.out_status = s->d_status.p;
   if (Wt > 64 || clr::option("CLR_GRAD_ANY_WIDTH")) {
     // above width 64 (round 6): one workgroup per direction, S and dS in an HBM / L2 workspace (grad_any_kernels.hip)
     if ((st = s->gradws.reserve(clr::grad_any_workspace_doubles(Wt, G))) != CLR_OK) return st;
@@ -636,7 +598,7 @@ int clr_solver_grad_log_likelihood(clr_solver* s, double jitter, int n_a_real, c
   std::vector<double> out((size_t)G + 1);
   int h_status = 0;
   HIP_TRY(hipMemcpyAsync(out.data(), s->gradbuf.p + o_out, out.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipMemcpyAsync(&h_status, s->d_status, sizeof(int), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemcpyAsync(&h_status, s->d_status.p, sizeof(int), hipMemcpyDeviceToHost, stream));
   HIP_TRY(hipStreamSynchronize(stream));
   if (h_status != CLR_OK) return fail(CLR_NOT_POSITIVE_DEFINITE, "failed to factorize or solve matrix");
   *value = out[0];
@@ -674,7 +636,7 @@ static int big_sweep_scan(clr_solver* s, int nrhs, const double* in, double* out
   int st;
   if (!s->big_maps_valid[backward]) {
     if ((st = s->big_maps[backward].reserve(clr::bigsweep_maps_doubles(s->J, nchunk))) != CLR_OK) return st;
-    clr::launch_bigsweep_maps(s->N, s->J, nchunk, L, backward, s->phi.p, s->u.p, s->W.p, s->big_maps[backward].p, s->stream);
+    clr::launch_bigsweep_maps(s->N, s->J, nchunk, L, backward, s->phi.p, s->u.p, s->W.p, s->big_maps[backward].p, s->stream.get());
     s->big_maps_valid[backward] = true;
   }
   const int SLICE = 4096;
@@ -689,7 +651,7 @@ static int big_sweep_scan(clr_solver* s, int nrhs, const double* in, double* out
     P.quad = quad ? quad + r0 : nullptr;
     P.backward = backward;
     if ((st = s->ws_elems.reserve(clr::bigsweep_workspace_doubles(s->J, nchunk, nr))) != CLR_OK) return st;
-    clr::launch_bigsweep_scan(P, s->big_maps[backward].p, s->ws_elems.p, s->stream);
+    clr::launch_bigsweep_scan(P, s->big_maps[backward].p, s->ws_elems.p, s->stream.get());
   }
   return CLR_OK;
 }
@@ -713,8 +675,8 @@ static int sweep_scan(clr_solver* s, int nrhs, const double* in, double* out, do
     int st = s->ws_elems.reserve(wide ? clr::wsweep_workspace_doubles(s->J, P.nchunk, nr)
                                       : clr::sweep_workspace_doubles(s->J, P.nchunk, nr));
     if (st != CLR_OK) return st;
-    if (wide) clr::launch_wsweep_scan(P, s->ws_elems.p, s->stream);
-    else clr::launch_sweep_scan(P, s->ws_elems.p, s->stream);
+    if (wide) clr::launch_wsweep_scan(P, s->ws_elems.p, s->stream.get());
+    else clr::launch_sweep_scan(P, s->ws_elems.p, s->stream.get());
   }
   return CLR_OK;
 }
@@ -731,9 +693,9 @@ int clr_solver_debug_route(const clr_solver* cs, int* level, int* nchunk, double
   if (st != CLR_OK) return st;
   int lv = -1;
   std::vector<double> rec((size_t)s->route_nchunk * 3);
-  HIP_TRY(hipMemcpyAsync(&lv, s->route_level, sizeof(int), hipMemcpyDeviceToHost, s->stream));
-  if (s->route_cond) HIP_TRY(hipMemcpyAsync(rec.data(), s->route_cond, rec.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
+  HIP_TRY(hipMemcpyAsync(&lv, s->route_level, sizeof(int), hipMemcpyDeviceToHost, s->stream.get()));
+  if (s->route_cond) HIP_TRY(hipMemcpyAsync(rec.data(), s->route_cond, rec.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream.get()));
+  HIP_TRY(hipStreamSynchronize(s->stream.get()));
   double r = 0.0;
   for (int c = 0; c < s->route_nchunk; ++c) { const double v = rec[(size_t)c * 3 + 2]; r = (v != v) ? INFINITY : std::max(r, v); }
   if (level) *level = lv;
@@ -755,19 +717,19 @@ int clr_solver_dot_solve(const clr_solver* cs, int n_b, const double* b, double*
   int st = ensure_stream(s);
   if (st != CLR_OK) return st;
   if ((st = ensure_refined(s)) != CLR_OK) return st;
-  if ((st = upload(s->scratch, b, (size_t)s->N, s->stream)) != CLR_OK) return st;
+  if ((st = upload(s->scratch, b, (size_t)s->N, s->stream.get())) != CLR_OK) return st;
   if ((st = s->scalars.reserve(8)) != CLR_OK) return st;
   if (sweep_scan_ok(s)) {
     if ((st = sweep_scan(s, 1, s->scratch.p, nullptr, s->scalars.p, 0)) != CLR_OK) return st;
   } else if (s->J > CLR_MAX_WIDTH) {
-    clr::launch_dot_solve_huge(s->N, s->J, s->phi.p, s->u.p, s->W.p, s->D.p, s->scratch.p, s->scalars.p, s->stream);
+    clr::launch_dot_solve_huge(s->N, s->J, s->phi.p, s->u.p, s->W.p, s->D.p, s->scratch.p, s->scalars.p, s->stream.get());
   } else {
     clr::launch_dot_solve(s->N, s->J, s->phi.p, s->u.p, s->W.p, s->D.p, s->scratch.p,
-                          s->scalars.p, s->stream);
+                          s->scalars.p, s->stream.get());
   }
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(out, s->scalars.p, sizeof(double), hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
+  HIP_TRY(hipMemcpyAsync(out, s->scalars.p, sizeof(double), hipMemcpyDeviceToHost, s->stream.get()));
+  HIP_TRY(hipStreamSynchronize(s->stream.get()));
   return CLR_OK;
 }
 
@@ -779,9 +741,9 @@ static int ensure_refined(clr_solver* s) {
   F.fixup_steps = F.L + (F.L0 > F.L ? F.L0 - F.L : 0);
   if (s->refine_pending == 1) {
     const clr::BatchLaunchers* L = clr::find_batch_launchers(s->J_real, s->J_comp);
-    if (L) L->replay(F, 1, s->stream);
+    if (L) L->replay(F, 1, s->stream.get());
   } else {
-    clr::launch_wide_loglike(F, s->J_real, s->J_comp, s->stream);
+    clr::launch_wide_loglike(F, s->J_real, s->J_comp, s->stream.get());
   }
   s->refine_pending = 0;
   HIP_TRY(hipGetLastError());
@@ -795,7 +757,7 @@ static int sweep_common(clr_solver* s, int rows, int nrhs, const double* in) {
   if (st != CLR_OK) return st;
   if ((st = ensure_refined(s)) != CLR_OK) return st;
   const size_t n = (size_t)s->N * (size_t)std::max(nrhs, 0);
-  if ((st = upload(s->scratch, in, n, s->stream)) != CLR_OK) return st;
+  if ((st = upload(s->scratch, in, n, s->stream.get())) != CLR_OK) return st;
   return s->scratch2.reserve(n);
 }
 
@@ -813,15 +775,15 @@ int clr_solver_solve(const clr_solver* cs, int b_rows, int nrhs, const double* b
     if ((st = sweep_scan(s, nrhs, s->scratch.p, s->scratch2.p, nullptr, 0)) != CLR_OK) return st;   // :240-248
     if ((st = sweep_scan(s, nrhs, s->scratch2.p, s->scratch2.p, nullptr, 1)) != CLR_OK) return st;  // :249-259
   } else if (s->J > CLR_MAX_WIDTH) {
-    clr::launch_solve_huge(s->N, s->J, nrhs, s->phi.p, s->u.p, s->W.p, s->D.p, s->scratch.p, s->scratch2.p, s->stream);
+    clr::launch_solve_huge(s->N, s->J, nrhs, s->phi.p, s->u.p, s->W.p, s->D.p, s->scratch.p, s->scratch2.p, s->stream.get());
   } else {
     clr::launch_solve(s->N, s->J, nrhs, s->phi.p, s->u.p, s->W.p, s->D.p, s->scratch.p,
-                      s->scratch2.p, s->stream);
+                      s->scratch2.p, s->stream.get());
   }
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(x, result, sizeof(double) * (size_t)s->N * nrhs,
-                         hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
+                         hipMemcpyDeviceToHost, s->stream.get()));
+  HIP_TRY(hipStreamSynchronize(s->stream.get()));
   return CLR_OK;
 }
 
@@ -844,17 +806,17 @@ int clr_solver_dot_L(const clr_solver* cs, int z_rows, int nrhs, const double* z
       P.phi = s->phi.p; P.u = s->u.p; P.W = s->W.p; P.D = s->D.p;
       P.in = s->scratch.p + (size_t)r0 * s->N; P.out = s->scratch2.p + (size_t)r0 * s->N;
       if ((st = s->ws_elems.reserve((size_t)nr * P.nchunk * 3 * s->J)) != CLR_OK) return st;
-      if (wide) clr::launch_wdotl_scan(P, s->ws_elems.p, s->stream);
-      else clr::launch_dot_L_scan(P, s->ws_elems.p, s->stream);
+      if (wide) clr::launch_wdotl_scan(P, s->ws_elems.p, s->stream.get());
+      else clr::launch_dot_L_scan(P, s->ws_elems.p, s->stream.get());
     }
   } else {
     clr::launch_dot_L(s->N, s->J, nrhs, s->phi.p, s->u.p, s->W.p, s->D.p, s->scratch.p,
-                      s->scratch2.p, s->stream);
+                      s->scratch2.p, s->stream.get());
   }
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(y, s->scratch2.p, sizeof(double) * (size_t)s->N * nrhs,
-                         hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
+                         hipMemcpyDeviceToHost, s->stream.get()));
+  HIP_TRY(hipStreamSynchronize(s->stream.get()));
   return CLR_OK;
 }
 
@@ -877,7 +839,7 @@ int clr_solver_dot(clr_solver* s, double jitter, int n_a_real, const double* a_r
   if (N < 1 || nrhs < 1) return CLR_OK;
 
   if ((st = ensure_stream(s)) != CLR_OK) return st;
-  hipStream_t stream = s->stream;
+  hipStream_t stream = s->stream.get();
   const size_t total = (size_t)N * nrhs;
 
   if (J == 0) {  // cholesky.h:477-481: y = jitter * z (scaling done by the device copy engine
@@ -886,13 +848,12 @@ int clr_solver_dot(clr_solver* s, double jitter, int n_a_real, const double* a_r
     std::vector<double> dg((size_t)N, jitter);
     DevBuf tmp;
     if ((st = upload(tmp, dg.data(), (size_t)N, stream)) != CLR_OK) return st;
-    if ((st = s->scratch2.reserve(total)) != CLR_OK) { tmp.release(); return st; }
+    if ((st = s->scratch2.reserve(total)) != CLR_OK) return st;
     clr::launch_dot(N, 0, nrhs, nullptr, nullptr, nullptr, tmp.p, s->scratch.p, s->scratch2.p,
                     stream);
     hipError_t e = hipMemcpyAsync(y, s->scratch2.p, sizeof(double) * total,
                                   hipMemcpyDeviceToHost, stream);
     (void)hipStreamSynchronize(stream);
-    tmp.release();
     if (e != hipSuccess) return fail(CLR_HIP_ERROR, hipGetErrorString(e));
     return CLR_OK;
   }
@@ -902,7 +863,6 @@ int clr_solver_dot(clr_solver* s, double jitter, int n_a_real, const double* a_r
   DevBuf &coeffs = s->dot_buf[0], &tt = s->dot_buf[1], &dU = s->dot_buf[2], &dV = s->dot_buf[3], &phi = s->dot_buf[4],
          &u = s->dot_buf[5], &v = s->dot_buf[6], &dg = s->dot_buf[7], &zin = s->dot_buf[8], &yout = s->dot_buf[9],
          &ws = s->dot_buf[10];
-  auto cleanup = [&]() {};  // (released with the solver)
   std::vector<double> hc;
   double sum_ar = 0.0, sum_ac = 0.0;
   for (int j = 0; j < J_real; ++j) sum_ar += a_real[j];
@@ -915,7 +875,6 @@ int clr_solver_dot(clr_solver* s, double jitter, int n_a_real, const double* a_r
 #define DOT_TRY(e)                \
   if ((st = (e)) != CLR_OK) {     \
     (void)hipStreamSynchronize(stream); \
-    cleanup();                    \
     return st;                    \
   }
   DOT_TRY(upload_coeffs(coeffs, J_real, a_real, c_real, J_comp, a_comp, b_comp, c_comp, d_comp,
@@ -959,7 +918,6 @@ int clr_solver_dot(clr_solver* s, double jitter, int n_a_real, const double* a_r
   if (e == hipSuccess)
     e = hipMemcpyAsync(y, yout.p, sizeof(double) * total, hipMemcpyDeviceToHost, stream);
   hipError_t e2 = hipStreamSynchronize(stream);
-  cleanup();
 #undef DOT_TRY
   if (e != hipSuccess) return fail(CLR_HIP_ERROR, hipGetErrorString(e));
   if (e2 != hipSuccess) return fail(CLR_HIP_ERROR, hipGetErrorString(e2));
@@ -973,14 +931,14 @@ int clr_solver_predict(const clr_solver* cs, int n_y, const double* y, int M, co
   if (st != CLR_OK) return st;
   if (M <= 0) return CLR_OK;
   if (s->coeffs_lazy) {  // (the one-launch compute passed the coefficients as kernel arguments)
-    if ((st = upload(s->coeffs, s->host_coeffs.data(), s->host_coeffs.size(), s->stream)) != CLR_OK) return st;
+    if ((st = upload(s->coeffs, s->host_coeffs.data(), s->host_coeffs.size(), s->stream.get())) != CLR_OK) return st;
     s->coeffs_lazy = false;
   }
   if (s->t.cap < (size_t)s->N || s->coeffs.p == nullptr)
     return fail(CLR_UNSUPPORTED,
                 "predict needs the inputs of compute(); a solver restored from a pickled "
                 "state does not carry them (same as the reference, solver.cpp:36-42)");
-  hipStream_t stream = s->stream;
+  hipStream_t stream = s->stream.get();
   // alpha = K^-1 y  (:608)
   if (big_sweep(s)) {  // (not in place: y -> scratch2 -> scratch, then back to scratch2 where predict reads alpha)
     if ((st = sweep_scan(s, 1, s->scratch.p, s->scratch2.p, nullptr, 0)) != CLR_OK) return st;
@@ -1043,13 +1001,13 @@ int clr_solver_get_state(const clr_solver* cs, double* phi, double* u, double* W
   if ((st = ensure_refined(s)) != CLR_OK) return st;
   const size_t N = (size_t)s->N, J = (size_t)s->J, Nm1 = N - 1;
   if (J * Nm1) {
-    HIP_TRY(hipMemcpyAsync(phi, s->phi.p, sizeof(double) * J * Nm1, hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipMemcpyAsync(u, s->u.p, sizeof(double) * J * Nm1, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipMemcpyAsync(phi, s->phi.p, sizeof(double) * J * Nm1, hipMemcpyDeviceToHost, s->stream.get()));
+    HIP_TRY(hipMemcpyAsync(u, s->u.p, sizeof(double) * J * Nm1, hipMemcpyDeviceToHost, s->stream.get()));
   }
   if (J * N)
-    HIP_TRY(hipMemcpyAsync(W, s->W.p, sizeof(double) * J * N, hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipMemcpyAsync(D, s->D.p, sizeof(double) * N, hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
+    HIP_TRY(hipMemcpyAsync(W, s->W.p, sizeof(double) * J * N, hipMemcpyDeviceToHost, s->stream.get()));
+  HIP_TRY(hipMemcpyAsync(D, s->D.p, sizeof(double) * N, hipMemcpyDeviceToHost, s->stream.get()));
+  HIP_TRY(hipStreamSynchronize(s->stream.get()));
   return CLR_OK;
 }
 
@@ -1069,11 +1027,11 @@ int clr_solver_set_state(clr_solver* s, int computed, int N, int J, double log_d
   int st = ensure_stream(s);
   if (st != CLR_OK) return st;
   const size_t Nn = (size_t)N, Jn = (size_t)J, Nm1 = Nn - 1;
-  if ((st = upload(s->phi, phi, Jn * Nm1, s->stream)) != CLR_OK) return st;
-  if ((st = upload(s->u, u, Jn * Nm1, s->stream)) != CLR_OK) return st;
-  if ((st = upload(s->W, W, Jn * Nn, s->stream)) != CLR_OK) return st;
-  if ((st = upload(s->D, D, Nn, s->stream)) != CLR_OK) return st;
-  HIP_TRY(hipStreamSynchronize(s->stream));
+  if ((st = upload(s->phi, phi, Jn * Nm1, s->stream.get())) != CLR_OK) return st;
+  if ((st = upload(s->u, u, Jn * Nm1, s->stream.get())) != CLR_OK) return st;
+  if ((st = upload(s->W, W, Jn * Nn, s->stream.get())) != CLR_OK) return st;
+  if ((st = upload(s->D, D, Nn, s->stream.get())) != CLR_OK) return st;
+  HIP_TRY(hipStreamSynchronize(s->stream.get()));
   s->coeffs.release();  // marks "inputs unknown" for predict
   s->computed = 1;
   return CLR_OK;

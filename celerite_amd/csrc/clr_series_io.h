@@ -4,18 +4,21 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 
+#include "clr_handles.h"
+
 namespace clr {
 
 // Pinned staging for uploads from PAGEABLE host memory (what a NumPy array is): NT host threads, each with two pinned
 // buffers and its own stream.  A thread copies a piece into one buffer (a host memcpy, ~10 GB/s per thread), queues the
 // DMA of that buffer and meanwhile fills the other one; the threads' DMAs share the PCIe link.  One hipMemcpy from
 // pageable memory does the same staging on ONE thread: 10-12 GB/s (profiles/r03end_bench.json: 196 ms for 2.46 GB).
+// (the streams come first: members are freed in reverse order)
 struct UploadStaging {
   static constexpr int NT = 8;
   static constexpr size_t PIECE = (size_t)4 << 20;  // bytes per piece
-  double* pin[NT][2] = {};
-  hipStream_t stream[NT] = {};
-  hipEvent_t ev[NT][2] = {};
+  Stream stream[NT];
+  PinnedBuffer<double> pin[NT][2];
+  Event ev[NT][2];
   int device = -1;
   bool ready = false;
 };
@@ -25,7 +28,6 @@ struct CopyJob {
   size_t n;           // doubles
 };
 int staging_create(UploadStaging& s, int device);  // 0 on success, else a hipError_t
-void staging_destroy(UploadStaging& s);
 // copies all jobs, returns when every byte has arrived (0 on success, else a hipError_t)
 int upload_parallel(UploadStaging& s, const CopyJob* jobs, int njobs);
 

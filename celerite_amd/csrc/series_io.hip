@@ -17,34 +17,18 @@ namespace clr {
 
 int staging_create(UploadStaging& s, int device) {
   if (s.ready && s.device == device) return 0;
-  staging_destroy(s);
+  s = UploadStaging();
   hipError_t e;
   for (int i = 0; i < UploadStaging::NT; ++i) {
     for (int k = 0; k < 2; ++k) {
-      if ((e = hipHostMalloc(reinterpret_cast<void**>(&s.pin[i][k]), UploadStaging::PIECE, hipHostMallocDefault)) != hipSuccess)
-        return (int)e;
-      if ((e = hipEventCreateWithFlags(&s.ev[i][k], hipEventDisableTiming)) != hipSuccess) return (int)e;
+      if (s.pin[i][k].reserve(UploadStaging::PIECE / sizeof(double)) != CLR_OK) return (int)hipErrorOutOfMemory;
+      if ((e = create_event(s.ev[i][k], hipEventDisableTiming)) != hipSuccess) return (int)e;
     }
-    if ((e = hipStreamCreateWithFlags(&s.stream[i], hipStreamNonBlocking)) != hipSuccess) return (int)e;
+    if ((e = create_stream(s.stream[i])) != hipSuccess) return (int)e;
   }
   s.device = device;
   s.ready = true;
   return 0;
-}
-
-void staging_destroy(UploadStaging& s) {
-  for (int i = 0; i < UploadStaging::NT; ++i) {
-    for (int k = 0; k < 2; ++k) {
-      if (s.pin[i][k]) (void)hipHostFree(s.pin[i][k]);
-      if (s.ev[i][k]) (void)hipEventDestroy(s.ev[i][k]);
-      s.pin[i][k] = nullptr;
-      s.ev[i][k] = nullptr;
-    }
-    if (s.stream[i]) (void)hipStreamDestroy(s.stream[i]);
-    s.stream[i] = nullptr;
-  }
-  s.ready = false;
-  s.device = -1;
 }
 
 int upload_parallel(UploadStaging& s, const CopyJob* jobs, int njobs) {
@@ -69,16 +53,16 @@ int upload_parallel(UploadStaging& s, const CopyJob* jobs, int njobs) {
       if (p >= pieces.size() || err.load()) break;
       const int slot = used & 1;
       hipError_t e = hipSuccess;
-      if (used >= 2) e = hipEventSynchronize(s.ev[i][slot]);  // the DMA that last read this buffer is done
+      if (used >= 2) e = hipEventSynchronize(s.ev[i][slot].get());  // the DMA that last read this buffer is done
       if (e == hipSuccess) {
-        memcpy(s.pin[i][slot], pieces[p].src, pieces[p].bytes);
-        e = hipMemcpyAsync(pieces[p].dst, s.pin[i][slot], pieces[p].bytes, hipMemcpyHostToDevice, s.stream[i]);
+        memcpy(s.pin[i][slot].p, pieces[p].src, pieces[p].bytes);
+        e = hipMemcpyAsync(pieces[p].dst, s.pin[i][slot].p, pieces[p].bytes, hipMemcpyHostToDevice, s.stream[i].get());
       }
-      if (e == hipSuccess) e = hipEventRecord(s.ev[i][slot], s.stream[i]);
+      if (e == hipSuccess) e = hipEventRecord(s.ev[i][slot].get(), s.stream[i].get());
       if (e != hipSuccess) { err = (int)e; break; }
       ++used;
     }
-    const hipError_t e = hipStreamSynchronize(s.stream[i]);
+    const hipError_t e = hipStreamSynchronize(s.stream[i].get());
     if (e != hipSuccess && !err.load()) err = (int)e;
   };
   std::vector<std::thread> th;

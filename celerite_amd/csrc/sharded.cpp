@@ -28,6 +28,7 @@
 // bit-identical results).
 #include <condition_variable>
 #include <functional>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -91,6 +92,7 @@ struct Worker {
     cv.notify_all();
     if (th.joinable()) th.join();
   }
+  ~Worker() { stop(); }
 };
 
 thread_local std::string g_sharded_error;
@@ -101,7 +103,7 @@ struct clr_sharded {
   int B = 0, N = 0, J_real = 0, J_comp = 0;
   std::vector<int> device, lo, hi;
   std::vector<clr_batch*> plan;
-  std::vector<Worker*> worker;
+  std::vector<std::unique_ptr<Worker>> worker;
 
   // run f(shard) on every shard's worker; first non-OK status wins
   int all(const std::function<int(int)>& f) {
@@ -179,10 +181,8 @@ void clr_sharded_destroy(clr_sharded* h) {
       h->worker[s]->post([p] { clr_batch_destroy(p); return (int)CLR_OK; });
       h->worker[s]->wait();
     }
-    h->worker[s]->stop();
-    delete h->worker[s];
   }
-  delete h;
+  delete h;  // (stops and joins the worker threads)
 }
 
 clr_sharded* clr_sharded_create(int B, int N, int J_real, int J_comp, const int* devices, int nshards) {
@@ -212,9 +212,9 @@ clr_sharded* clr_sharded_create(int B, int N, int J_real, int J_comp, const int*
     h->device.push_back(devices[s]);
     h->lo.push_back(lo);
     h->hi.push_back(hi);
-    Worker* w = new Worker();
+    h->worker.push_back(std::make_unique<Worker>());
+    Worker* w = h->worker.back().get();
     w->th = std::thread([w] { w->loop(); });
-    h->worker.push_back(w);
   }
   const int st = h->all([h, N, J_real, J_comp](int s) {
     h->plan[s] = clr_batch_create(h->hi[s] - h->lo[s], N, J_real, J_comp, h->device[s]);

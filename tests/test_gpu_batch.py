@@ -2888,6 +2888,36 @@ def test_device_memory_and_plan_lifecycle():
     assert used_b - used_a < 64 * 2**20                 # (allocator granularity, not a per-cycle leak)
 
 
+def test_wide_solver_lifecycle_frees_the_chunk_maps():
+    """No leak over create / compute / solve / destroy cycles of a solver above width 64: its solve runs the affine scans
+    of bigsweep_kernels.hip, whose chunk maps (one set per direction) the solver keeps.  64 complex terms (width 128),
+    N = 16384: bigsweep_chunks = 161, so the maps hold 2 x 161 x 128^2 x 8 B = 42 MB per solver -- six cycles that
+    leaked them would grow by 253 MB."""
+    import celerite_amd
+    total = batch.device_memory()[1]
+    rng = np.random.RandomState(3)
+    N, JC = 16384, 64
+    t = np.sort(rng.rand(N)) * 100.0
+    diag = rng.uniform(0.01, 0.04, N)
+    y = np.sin(t)
+    a, c, d = np.exp(rng.randn(JC) - 2.0), np.exp(rng.randn(JC)), np.exp(1.0 + rng.randn(JC))
+    def cycle():
+        s = celerite_amd.CholeskySolver()
+        s.compute(0.0, np.empty(0), np.empty(0), a, np.zeros(JC), c, d, np.empty(0), np.empty((0, 0)), np.empty((0, 0)), t, diag)
+        x = s.solve(y)
+        assert np.all(np.isfinite(x))
+        del s
+    for _ in range(2):
+        cycle()
+    batch.device_synchronize()
+    used_a = total - batch.device_memory()[0]
+    for _ in range(6):
+        cycle()
+    batch.device_synchronize()
+    used_b = total - batch.device_memory()[0]
+    assert used_b - used_a < 64 * 2**20                 # (allocator granularity, not a per-cycle leak)
+
+
 @pytest.mark.parametrize("N,nchunk", [(1025, 64), (8193, 64), (5000, 128), (2049, 2)])
 def test_role_split_tail_padding_and_shared_series(N, nchunk):
     """The lazy role-split kernels read the chunk-interleaved copy unguarded: its tail past N is padded by the

@@ -406,3 +406,19 @@ def test_options_table_and_the_split_of_the_headers():
             text = open(os.path.join(dirpath, f)).read()
             if f != "api_misc.hip":
                 assert "getenv(" not in text.replace("own getenv", ""), f
+
+
+def test_hip_resources_are_released_only_by_their_owning_types():
+    """Device and pinned memory, streams and events are owned by the types of clr_handles.h: members of the handles
+    and locals free them in their destructors, so no release list can drift from the struct it releases."""
+    import re
+    calls = re.compile(r"\b(hipFree|hipHostFree|hipStreamDestroy|hipEventDestroy)\s*\(")
+    csrc = os.path.join(ROOT, "celerite_amd", "csrc")
+    seen = {}
+    for f in sorted(os.listdir(csrc)):
+        if not f.endswith((".hip", ".cpp", ".h")):
+            continue
+        for m in calls.finditer(open(os.path.join(csrc, f)).read()):
+            seen.setdefault(f, []).append(m.group(1))
+    assert sorted(seen) == ["clr_handles.h"], seen
+    assert sorted(seen["clr_handles.h"]) == ["hipEventDestroy", "hipFree", "hipHostFree", "hipStreamDestroy"]
