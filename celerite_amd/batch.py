@@ -53,14 +53,12 @@ def _load():
     lib.clr_batch_get_factor.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp]
     lib.clr_batch_run_timed.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, _dp, _dp]
     lib.clr_batch_set_layout.argtypes = [C.c_void_p, C.c_int]
-    lib.clr_batch_set_library_trig.argtypes = [C.c_void_p, C.c_int]
     lib.clr_batch_set_summarize_mode.argtypes = [C.c_void_p, C.c_int]
     lib.clr_batch_get_summarize_kernel.argtypes = [C.c_void_p, _ip]
     lib.clr_batch_fp32_probe.argtypes = [C.c_void_p, _dp, _dp, _dp]
     lib.clr_batch_set_profiling.argtypes = [C.c_void_p, C.c_int]
     lib.clr_batch_get_profile.argtypes = [C.c_void_p, _dp, _ip]
     lib.clr_batch_set_prefix_mode.argtypes = [C.c_void_p, C.c_int]
-    lib.clr_batch_set_replay_source.argtypes = [C.c_void_p, C.c_int]
     lib.clr_batch_set_general.argtypes = [C.c_void_p, C.c_int, _dp, C.c_long, _dp, C.c_long, _dp, C.c_long]
     lib.clr_batch_set_warm_start.argtypes = [C.c_void_p, C.c_int, C.c_int]
     lib.clr_batch_get_warm_start.argtypes = [C.c_void_p] + [_ip] * 7
@@ -562,11 +560,6 @@ class BatchedGP(object):
         _check(_load().clr_batch_get_grad_fallbacks(self._h, C.byref(n)))
         return n.value
 
-    def set_replay_source(self, source=-1):
-        """Series view of the replay pass behind the role-split summarize: 0 the chunk-interleaved copy,
-        1 the row-major arrays staged through LDS, -1 auto (``clr_batch_set_replay_source``)."""
-        _check(_load().clr_batch_set_replay_source(self._h, int(source)))
-
     def set_rescue(self, mode=-1):
         """Route-1 problems (ill-conditioned, checked chunked replay) re-planned as a small plan of their own with many
         short chunks (``clr_batch_set_rescue``): -1 automatic (chunks of >= 1024 samples), 0 the inline replay, 1 always."""
@@ -607,23 +600,6 @@ class BatchedGP(object):
         lib.clr_batch_get_factor_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_size_t)]
         _check(lib.clr_batch_get_factor_bytes(self._h, C.byref(n)))
         return int(n.value)
-
-    def set_materialize_pipeline(self, groups=0, summarize_cus=0, summarize_streams=1):
-        """Materialising runs as a pipeline over ``groups`` groups of problems (``clr_batch_set_materialize_pipeline``):
-        the summarize of one group beside the replay of the previous one, on streams owning ``summarize_cus`` /
-        the remaining compute units.  ``groups=0`` switches it off."""
-        lib = _load()
-        lib.clr_batch_set_materialize_pipeline.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
-        _check(lib.clr_batch_set_materialize_pipeline(self._h, int(groups), int(summarize_cus), int(summarize_streams)))
-
-    def cu_census(self, which=0):
-        """Distinct compute units per XCD a grid reaches on the plan's stream (0), the pipeline's summarize stream (1)
-        or its replay stream (2) (``clr_batch_debug_cu_census``)."""
-        lib = _load()
-        out = (C.c_int * 8)()
-        lib.clr_batch_debug_cu_census.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
-        _check(lib.clr_batch_debug_cu_census(self._h, int(which), out))
-        return list(out)
 
     def set_exact(self, force=True):
         """Replay every problem step by step (the reference's recurrence) instead
@@ -695,11 +671,6 @@ class BatchedGP(object):
         ms = C.c_double()
         _check(_load().clr_batch_fp32_probe(self._h, _ptr(ld), _ptr(q), C.byref(ms)))
         return ld, q, ms.value
-
-    def set_library_trig(self, force=True):
-        """Use the library (ocml) sincos instead of the FMA Cody-Waite routine
-        (which is picked automatically when max|d| * max|t| < 1e9)."""
-        _check(_load().clr_batch_set_library_trig(self._h, int(bool(force))))
 
     def set_profiling(self, on=True):
         """Bracket the kernels of every following :meth:`enqueue` with HIP events; ``on=2`` brackets the

@@ -101,8 +101,6 @@ int clr_batch_set_chunks(clr_batch* h, int nchunk) {
   if (nchunk > 1 && h->L > 8) h->L = (h->L + 7) & ~7;  // 64-B aligned chunk rows for the tile loads
   h->nchunk = (h->N + h->L - 1) / h->L;
   h->L0 = 0;
-  if (const char* e = clr::option("CLR_WIDE_FIRST_RATIO")) h->wide_first_ratio = atof(e);  // (tuning runs only)
-  if (const char* e = clr::option("CLR_WIDE_FIRST_RATIO64")) h->wide_first_ratio64 = atof(e);
   const double first_ratio = h->J > 32 ? h->wide_first_ratio64 : h->wide_first_ratio;
   if (!h->launch && h->nchunk > 1 && first_ratio > 1.0) {
     // wide scan: the first chunk's summarize carries no riders (wide_scan_body, RIDERS == false) and costs
@@ -825,18 +823,6 @@ int clr_batch_get_warm_start(const clr_batch* h, int* active, int* nchunk, int* 
   return CLR_OK;
 }
 
-int clr_batch_set_replay_source(clr_batch* h, int source) {
-  if (source < -1 || source > 1) return fail(CLR_INVALID_ARGUMENT, "replay source must be -1, 0 or 1");
-  h->replay_source = source;
-  h->pipeline_pinned = true;
-  return CLR_OK;
-}
-
-int clr_batch_set_library_trig(clr_batch* h, int force) {
-  h->force_library_trig = force ? 1 : 0;
-  return CLR_OK;
-}
-
 int clr_batch_set_layout(clr_batch* h, int layout) {
   if (layout < 0 || layout > 2) return fail(CLR_INVALID_ARGUMENT, "layout must be 0, 1 or 2");
   h->layout = layout;
@@ -977,86 +963,6 @@ static int warm_fallback(clr_batch* h) {
 }
 
 
-// ---- materialising runs as a pipeline over groups of problems ---------------------------------------------------
-// The materialising step is a fp64-VALU-bound pass (summarize: the chunk elements) followed by an HBM-bound one
-// (replay: 8 N (3 J + 1) bytes of factor per problem).  Back to back on one stream they add up -- 2.2 + 3.8 ms at the
-// headline shape, 48 % of the HBM roofline for the whole step.  Here the batch is cut into G contiguous groups of
-// problems; the summarize of group g + 1 runs while group g is replayed, on streams that own DISJOINT sets of compute
-// units (hipExtStreamCreateWithCUMask): the role-split summarize fills a CU completely (2 x 256 registers per SIMD,
-// 160 KB of LDS), so without the masks concurrency only serialises whole kernels.  The prefix and the corrections of
-// a group (small, latency-bound) run on a third, unmasked stream between the two.
-static void mp_release(clr_batch* h) {
-  h->mp_s.clear();
-  h->mp_p.reset();
-  h->mp_r.reset();
-  h->mp_ev.clear();
-}
-
-// CU `i` of the mask belongs to the summarize set iff ((i / 8) + (i % 8)) % 16 < k: whichever way the runtime numbers
-// the mask bits over the 8 XCDs (round-robin or XCD-major) both sets are spread over every XCD -- each XCD's L2 and
-// fabric port then carry their share of the replay's stores.
-static void mp_masks(int total_cus, int summarize_cus, std::vector<uint32_t>& ms, std::vector<uint32_t>& mr) {
-  const int words = (total_cus + 31) / 32, k = summarize_cus / 16;
-  ms.assign(words, 0u);
-  mr.assign(words, 0u);
-  for (int i = 0; i < total_cus; ++i) {
-    const bool sset = ((i / 8) + (i % 8)) % 16 < k;
-    (sset ? ms : mr)[i / 32] |= 1u << (i % 32);
-  }
-}
-
-static int mp_prepare(clr_batch* h) {
-  const int G = h->mp_groups;
-  if (!h->mp_s.empty() && (int)h->mp_ev.size() == 2 * G + 2) return CLR_OK;
-  mp_release(h);
-  int ncu = 0;
-  HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, h->device));
-  std::vector<uint32_t> ms, mr;
-  const bool masked = h->mp_cus >= 16 && h->mp_cus <= ncu - 16;
-  if (masked) mp_masks(ncu, h->mp_cus, ms, mr);
-  h->mp_s.resize((size_t)h->mp_nstreams);
-  for (clr::Stream& s : h->mp_s) {
-    if (masked) HIP_TRY(clr::create_stream(s, (uint32_t)ms.size(), ms.data()));
-    else HIP_TRY(clr::create_stream(s));
-  }
-  if (masked) HIP_TRY(clr::create_stream(h->mp_r, (uint32_t)mr.size(), mr.data()));
-  else HIP_TRY(clr::create_stream(h->mp_r));
-  HIP_TRY(clr::create_stream(h->mp_p));
-  h->mp_ev.resize((size_t)2 * G + 2);
-  for (clr::Event& e : h->mp_ev) HIP_TRY(clr::create_event(e, hipEventDisableTiming));
-  return CLR_OK;
-}
-
-// the kernels' view of problems [b0, b0 + Bg) of the plan: every per-problem pointer advanced, B = Bg (the levels of the
-// multi-level prefix are laid out per view: [Bg][n_l] blocks back to back inside the group's own region)
-static clr::BatchParams group_view(const clr_batch* h, const clr::BatchParams& P, int b0, int Bg) {
-  clr::BatchParams G = P;
-  const size_t o = (size_t)b0, JR = (size_t)h->J_real, JC = (size_t)h->J_comp, J = (size_t)h->J, nc = (size_t)P.nchunk;
-  const size_t E = (size_t)h->launch->elem_doubles, S = (size_t)h->launch->start_doubles, cells = (size_t)P.L * nc;
-  G.B = Bg;
-  G.jitter += o; G.a_real += o * JR; G.c_real += o * JR;
-  G.a_comp += o * JC; G.b_comp += o * JC; G.c_comp += o * JC; G.d_comp += o * JC;
-  G.t += (long)o * P.t_stride; G.diag += (long)o * P.diag_stride; G.y += (long)o * P.y_stride;
-  G.elems += o * nc * E; G.starts += o * nc * S;
-  G.part += o * nc * 2; G.partx += o * nc * 2;
-  if (G.cond) G.cond += o * nc * 3;
-  if (G.egerr) G.egerr += o * nc;
-  G.flags += o * nc; G.flagsx += o * nc; G.need_exact += o;
-  size_t le = 0, ls = 0;
-  clr::multilevel_workspace(P.plan, (int)J, &le, &ls);
-  if (G.lvl_elems) G.lvl_elems += o * le;
-  if (G.lvl_starts) G.lvl_starts += o * ls;
-  // (the lean factor layout stores W and D only: phi / u are never reserved there)
-  if (G.phi) G.phi += o * J * cells;
-  if (G.u) G.u += o * J * cells;
-  if (G.W) G.W += o * J * cells;
-  if (G.D) G.D += o * cells;
-  if (G.ends) G.ends += o * nc * S;
-  G.out_ll += o; G.out_logdet += o; G.out_quad += o; G.out_status += o;
-  G.only_pending = 0;
-  return G;
-}
-
 // replay mode of a materialising run: 2 the four arrays chunk-interleaved, 3 the lean layout (W, D only)
 static int replay_mode(const clr_batch* h, int materialize) {
   return materialize ? (h->factor_layout == 1 ? 3 : 2) : 0;
@@ -1067,46 +973,6 @@ static int replay_mode(const clr_batch* h, int materialize) {
 static void refine_chunk_heads(const clr_batch* h, clr::BatchParams R, int materialize, hipStream_t s) {
   R.fixup_steps = R.refine_samples;
   h->launch->replay(R, replay_mode(h, materialize), s);
-}
-
-static bool mp_runs(const clr_batch* h, int materialize) {
-  return materialize && h->launch && h->mp_groups >= 2 && h->nchunk > 1 && h->B >= h->mp_groups && h->J_general == 0;
-}
-
-static int materialize_pipeline(clr_batch* h, const clr::BatchParams& P) {
-  int st = mp_prepare(h);
-  if (st != CLR_OK) return st;
-  const int G = h->mp_groups;
-  const clr::BatchParams R = replay_view(h, P, 1);
-  HIP_TRY(hipEventRecord(h->mp_ev[0].get(), h->stream.get()));  // (whatever the plan's stream holds -- uploads, the relayout -- comes first)
-  for (const clr::Stream& s : h->mp_s) HIP_TRY(hipStreamWaitEvent(s.get(), h->mp_ev[0].get(), 0));
-  HIP_TRY(hipStreamWaitEvent(h->mp_p.get(), h->mp_ev[0].get(), 0));
-  HIP_TRY(hipStreamWaitEvent(h->mp_r.get(), h->mp_ev[0].get(), 0));
-  for (int g = 0; g < G; ++g) {
-    int lo = 0, hi = 0;
-    clr_shard_bounds(h->B, G, g, &lo, &hi);
-    const clr::BatchParams Pg = group_view(h, P, lo, hi - lo), Rg = group_view(h, R, lo, hi - lo);
-    hipStream_t ss = h->mp_s[(size_t)g % h->mp_s.size()].get();
-    h->launch->summarize(Pg, ss);
-    HIP_TRY(hipEventRecord(h->mp_ev[1 + 2 * g].get(), ss));
-    HIP_TRY(hipStreamWaitEvent(h->mp_p.get(), h->mp_ev[1 + 2 * g].get(), 0));
-    h->launch->prefix(Pg, h->mp_p.get());
-    h->launch->correct(Pg, h->mp_p.get());
-    HIP_TRY(hipEventRecord(h->mp_ev[2 + 2 * g].get(), h->mp_p.get()));
-    HIP_TRY(hipStreamWaitEvent(h->mp_r.get(), h->mp_ev[2 + 2 * g].get(), 0));
-    h->launch->replay(Rg, replay_mode(h, 1), h->mp_r.get());
-    if (Rg.ends) refine_chunk_heads(h, Rg, 1, h->mp_r.get());
-    h->launch->sequential(Pg, replay_mode(h, 1), h->mp_r.get());
-  }
-  HIP_TRY(hipEventRecord(h->mp_ev[2 * G + 1].get(), h->mp_r.get()));  // (the replay stream's last group closes every chain of events)
-  HIP_TRY(hipStreamWaitEvent(h->stream.get(), h->mp_ev[2 * G + 1].get(), 0));
-  h->factor_is_lean = h->factor_layout == 1;
-  h->factor_inputs_changed = false;
-  h->factor_valid = true;
-  h->bs_M_valid = false;
-  clr::launch_finalize(P, h->stream.get());
-  HIP_TRY(hipGetLastError());
-  return CLR_OK;
 }
 
 int clr_batch_set_rescue(clr_batch* h, int mode) {
@@ -1143,46 +1009,6 @@ int clr_batch_get_factor_bytes(const clr_batch* h, size_t* bytes_per_problem) {
   if (!bytes_per_problem) return fail(CLR_INVALID_ARGUMENT, "bytes_per_problem is null");
   const size_t cells = h->launch ? (size_t)h->L * h->nchunk : (size_t)h->N, J = (size_t)h->J;
   *bytes_per_problem = 8 * cells * ((h->launch && h->factor_layout == 1) ? (J + 1) : (3 * J + 1));
-  return CLR_OK;
-}
-
-int clr_batch_set_materialize_pipeline(clr_batch* h, int groups, int summarize_cus, int summarize_streams) {
-  int st = require_device(h->device);
-  if (st != CLR_OK) return st;
-  if (groups < 0 || groups == 1 || groups > 64 || summarize_cus < 0 || summarize_streams < 1 || summarize_streams > 8)
-    return fail(CLR_INVALID_ARGUMENT, "materialize pipeline: groups 0 (off) or 2..64, summarize_cus >= 0, 1..8 summarize streams");
-  if (!h->launch && groups) return fail(CLR_UNSUPPORTED, "the materialising pipeline covers widths 1..8");
-  HIP_TRY(hipStreamSynchronize(h->stream.get()));
-  for (const clr::Stream& s : h->mp_s) HIP_TRY(hipStreamSynchronize(s.get()));
-  mp_release(h);
-  h->mp_groups = groups;
-  h->mp_cus = (summarize_cus / 16) * 16;
-  h->mp_nstreams = summarize_streams;
-  return CLR_OK;
-}
-
-int clr_batch_debug_cu_census(clr_batch* h, int which, int* cus_per_xcc /* [8] */) {
-  int st = require_device(h->device);
-  if (st != CLR_OK) return st;
-  if (!cus_per_xcc || which < 0 || which > 2) return fail(CLR_INVALID_ARGUMENT, "cu census: which = 0 (plan), 1 (summarize), 2 (replay)");
-  hipStream_t s = h->stream.get();
-  if (which > 0) {
-    if (h->mp_groups < 2) return fail(CLR_INVALID_ARGUMENT, "cu census: no materialising pipeline is set");
-    if ((st = mp_prepare(h)) != CLR_OK) return st;
-    s = which == 1 ? h->mp_s[0].get() : h->mp_r.get();
-  }
-  DevArray<int> seen;
-  if ((st = seen.reserve(8 * 256)) != CLR_OK) return st;
-  HIP_TRY(hipMemsetAsync(seen.p, 0, 8 * 256 * sizeof(int), s));
-  clr::launch_cu_census(seen.p, 8192, 20000, s);
-  std::vector<int> host(8 * 256);
-  HIP_TRY(hipMemcpyAsync(host.data(), seen.p, host.size() * sizeof(int), hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  for (int x = 0; x < 8; ++x) {
-    int n = 0;
-    for (int c = 0; c < 256; ++c) n += host[(size_t)x * 256 + c] > 0;
-    cus_per_xcc[x] = n;
-  }
   return CLR_OK;
 }
 
@@ -1284,12 +1110,6 @@ int clr_batch_enqueue(clr_batch* h, int materialize) {
     return CLR_OK;
   }
   if (h->relayout_pending && batch_relayout(h)) h->relayout_pending = false;
-  if (mp_runs(h, materialize)) {  // groups of problems: summarize of one beside the replay of the previous (above)
-    mark(1); mark(2); mark(3); mark(4);
-    if ((st = materialize_pipeline(h, P)) != CLR_OK) return st;
-    mark(5); mark(6);
-    return CLR_OK;
-  }
   mark(1);
   h->launch->summarize(P, h->stream.get());
   mark(2);
@@ -1297,8 +1117,11 @@ int clr_batch_enqueue(clr_batch* h, int materialize) {
   mark(3);
   h->launch->correct(P, h->stream.get());  // (also on forced-exact runs: flags + conditioning record)
   mark(4);
-  h->launch->replay(replay_view(h, P, materialize), replay_mode(h, materialize), h->stream.get());  // forced-exact / materialising runs only
-  if (P.ends) refine_chunk_heads(h, replay_view(h, P, materialize), materialize, h->stream.get());
+  // forced-exact / materialising runs only.  The replay reads the series where the summarize did: from the role split's
+  // chunk-interleaved copy 4.41 ms = 65 % of HBM for the materialising replay at B = 1024, N = 1e5, width 8, against
+  // 4.77 ms from the row-major arrays through LDS-staged tiles (profiles/r03a_prefix_ab.txt)
+  h->launch->replay(P, replay_mode(h, materialize), h->stream.get());
+  if (P.ends) refine_chunk_heads(h, P, materialize, h->stream.get());
   h->launch->sequential(P, replay_mode(h, materialize), h->stream.get());  // flagged / ill-conditioned problems only
   if (materialize) { h->factor_is_lean = h->factor_layout == 1; h->factor_inputs_changed = false; h->factor_valid = true; h->bs_M_valid = false; }
   mark(5);
@@ -1358,7 +1181,7 @@ static int rescue_inline(clr_batch* h) {
     S.nchunk = 1; S.L = P.N; S.L0 = 0; S.seq_only = 1; S.force_exact = 1;
     clr::launch_wide_loglike(S, h->J_real, h->J_comp, h->stream.get());
   } else {
-    h->launch->replay(replay_view(h, P, 0), 0, h->stream.get());
+    h->launch->replay(P, 0, h->stream.get());
     h->launch->sequential(P, 0, h->stream.get());
     clr::launch_finalize(P, h->stream.get());
   }
@@ -1414,7 +1237,6 @@ static int rescue_run(clr_batch* h, const std::vector<int>& idx, long n_total) {
   clr_batch* r = h->rescue.get();
   // the parent's settings that decide routes and kernels
   r->cert_resid = h->cert_resid; r->cert_gamma = h->cert_gamma; r->cert_gamma_abs = h->cert_gamma_abs; r->cert_eg = h->cert_eg;
-  r->force_library_trig = h->force_library_trig;
   r->floor_tmax = sel_max(h->tmax, h->floor_tmax); r->floor_dxmax = sel_max(h->dxmax, h->floor_dxmax);
   r->floor_dmax = sel_max(h->dmax, h->floor_dmax); r->floor_cmax = sel_max(h->cmax, h->floor_cmax);
   r->tmax = h->tmax; r->dxmax = h->dxmax; r->dmax = h->dmax; r->cmax = h->cmax; r->dtmin = h->dtmin;
@@ -2054,13 +1876,6 @@ int clr_batch_run_timed(clr_batch* h, int materialize, int steps, int relayout_e
       continue;
     }
     if (relayout_each_step) batch_relayout(h);
-    if (mp_runs(h, materialize)) {  // (the whole pipeline in the "replay" slot)
-      for (int j = 1; j <= 4; ++j) HIP_TRY(hipEventRecord(e[j].get(), h->stream.get()));
-      if ((st = materialize_pipeline(h, P)) != CLR_OK) return st;
-      HIP_TRY(hipEventRecord(e[5].get(), h->stream.get()));
-      HIP_TRY(hipEventRecord(e[6].get(), h->stream.get()));
-      continue;
-    }
     HIP_TRY(hipEventRecord(e[1].get(), h->stream.get()));
     h->launch->summarize(P, h->stream.get());
     HIP_TRY(hipEventRecord(e[2].get(), h->stream.get()));
@@ -2068,8 +1883,8 @@ int clr_batch_run_timed(clr_batch* h, int materialize, int steps, int relayout_e
     HIP_TRY(hipEventRecord(e[3].get(), h->stream.get()));
     h->launch->correct(P, h->stream.get());
     HIP_TRY(hipEventRecord(e[4].get(), h->stream.get()));
-    h->launch->replay(replay_view(h, P, materialize), replay_mode(h, materialize), h->stream.get());
-    if (P.ends) refine_chunk_heads(h, replay_view(h, P, materialize), materialize, h->stream.get());
+    h->launch->replay(P, replay_mode(h, materialize), h->stream.get());
+    if (P.ends) refine_chunk_heads(h, P, materialize, h->stream.get());
     h->launch->sequential(P, replay_mode(h, materialize), h->stream.get());
     if (materialize) { h->factor_is_lean = h->factor_layout == 1; h->factor_inputs_changed = false; h->factor_valid = true; h->bs_M_valid = false; }
     HIP_TRY(hipEventRecord(e[5].get(), h->stream.get()));

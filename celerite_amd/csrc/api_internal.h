@@ -243,7 +243,6 @@ struct clr_batch {
   double dtmin = 0.0;                 // smallest step of t over the plan's series (negative: not sorted; NaN: a NaN time)
   clr::UploadStaging staging;         // pinned staging + copy streams of clr_batch_set_series (large series only)
   DevBuf scan;                        // results of the device-side scans of t
-  int force_library_trig = 0;
   int coop_prefix = 2;                // 0 single lane, 1 16 lanes walking the chunks, 2 multi-level (clr_prefix_kernels.h)
   int plan_levels = -1, plan_g = 0;   // clr_batch_set_prefix_plan: < 0 = chosen by clr::plan_prefix
   clr::PrefixPlan plan;
@@ -301,8 +300,6 @@ struct clr_batch {
   int J_general = 0;
   DevBuf gA, gU, gV;
   long gA_stride = 0, gU_stride = 0, gV_stride = 0;
-  int replay_source = -1;             // where the replay reads the series when summarize reads the chunk-interleaved
-                                      // copy: 0 the same copy, 1 the row-major arrays staged through LDS, -1 auto
   bool relayout_pending = true;
   bool have_series = false, have_coeffs = false, have_factor = false;
   bool evaluated = false;             // an evaluation has been enqueued since the plan was (re)chunked
@@ -323,12 +320,6 @@ struct clr_batch {
   int factor_refine = 64;     // samples per chunk head (0: off -- round 5's factor)
   DevBuf ends;                // [B][nchunk][START] states at the chunks' ends, written by the materialising replay
   DevBuf fphi, fu, fW, fD;    // one problem in the reference's storage (get_factor)
-  // materialising runs as a pipeline over groups of problems (clr_batch_set_materialize_pipeline): the summarize of
-  // group g + 1 (fp64-VALU-bound) runs beside the replay of group g (HBM-bound) on streams that own disjoint sets of CUs
-  int mp_groups = 0, mp_cus = 0, mp_nstreams = 1;
-  std::vector<clr::Stream> mp_s;        // summarize streams (CU-masked when mp_cus > 0)
-  clr::Stream mp_p, mp_r;               // prefix + corrections (any CU); replay (the other CUs)
-  std::vector<clr::Event> mp_ev;        // [0] start, [1 + 2 g] group g summarized, [2 + 2 g] its start states ready, [last] replay done
   // problems the conditioning record sends to the checked chunked replay (level 1), re-planned as a small plan of their
   // own with many short chunks instead of replaying long chunks sequentially beside an idle chip (clr_batch_set_rescue)
   int rescue_mode = -1;            // -1 auto (chunks of >= 1024 samples), 0 off: the inline chunked replay, 1 whenever possible
@@ -357,7 +348,7 @@ struct clr_batch {
   ~clr_batch() {
     (void)hipSetDevice(device);
     if (stream) (void)hipStreamSynchronize(stream.get());
-    rescue.reset();  // (its own plan: gone before this plan's pipeline streams)
+    rescue.reset();  // (its own plan: gone before this plan's members)
   }
 };
 
@@ -384,17 +375,13 @@ bool lazy_eligible(const clr_batch* h) {
 // Wide plans (wave per (problem, chunk), widths 9..64): the lazy flavour of the summarize takes any series since round 5 --
 // a lane whose own interval is too long for the Taylor steps sends its wave through the full sincos / exp for that batch
 // (wide_scan_body, feature_batch) -- as long as the decay accumulated between two renormalisations (64 steps) stays far
-// from the exponent range: Psi^-2 < e^(2 x 64 x 2) = e^256.  (The one-wave kernels of CLR_WIDE64_ONE_WAVE keep the strict rule.)
+// from the exponent range: Psi^-2 < e^(2 x 64 x 2) = e^256.
 bool lazy_eligible_wide(const clr_batch* h) {
-  // (read per call, like the launcher's own getenv: a process may toggle them between plans)
-  if (clr::option("CLR_WIDE64_ONE_WAVE") && h->J > 32) return lazy_eligible(h);
-  const char* env = clr::option("CLR_WIDE_LAZY_BOUND");  // (tuning runs: 0 = the strict rule of the narrow kernels)
-  const double bound = env ? atof(env) : 2.0;
   // widths 9..16 (four lanes per row): the two flavours cost the same there -- 6.5 against 6.7 ms on a dense series, 7.4
   // against 7.0 on one where EVERY batch takes the slow path (profiles/r05m_wide_lazy_gaps.txt) -- so they keep the strict rule
-  if (!(bound > 0.0) || h->J + h->J_general <= 16) return lazy_eligible(h);
+  if (h->J + h->J_general <= 16) return lazy_eligible(h);
   const double cmax = sel_max(h->cmax, h->floor_cmax), dxmax = sel_max(h->dxmax, h->floor_dxmax);
-  return h->have_series && h->have_coeffs && cmax * dxmax < bound;
+  return h->have_series && h->have_coeffs && cmax * dxmax < 2.0;
 }
 
 bool split_active(const clr_batch* h) {
@@ -444,8 +431,7 @@ int batch_params(clr_batch* h, int materialize, clr::BatchParams& P) {
   memset(&P, 0, sizeof(P));
   const size_t B = (size_t)h->B, nr = B * h->J_real, nc = B * h->J_comp;
   P.B = h->B; P.N = h->N; P.nchunk = h->nchunk; P.L = h->L; P.L0 = h->L0;
-  P.fast_trig = (!h->force_library_trig &&
-                 sel_max(h->dmax, h->floor_dmax) * sel_max(h->tmax, h->floor_tmax) < CLR_FAST_TRIG_LIMIT) ? 1 : 0;
+  P.fast_trig = (sel_max(h->dmax, h->floor_dmax) * sel_max(h->tmax, h->floor_tmax) < CLR_FAST_TRIG_LIMIT) ? 1 : 0;
   P.coop_prefix = h->coop_prefix;
   P.plan = h->plan;
   P.lvl_elems = h->lvl_elems.p;
@@ -537,21 +523,6 @@ int batch_params(clr_batch* h, int materialize, clr::BatchParams& P) {
   return CLR_OK;
 }
 
-// The replay's view of the series.  The role-split summarize reads the chunk-interleaved copy; the replay is free to
-// read either that copy (one 512-B line per array and step per wave, but a second 2.4 GB stream competing with the
-// factor's stores) or the row-major arrays through the LDS-staged tiles (round 1's path).
-clr::BatchParams replay_view(const clr_batch* h, const clr::BatchParams& P, int materialize) {
-  clr::BatchParams R = P;
-  const int src = h->replay_source < 0 ? 0 : h->replay_source;  // (measured: profiles/r03a_prefix_ab.txt)
-  if (src == 1 && !P.staged && P.lane_cs == 1 && h->nchunk > 1 && h->layout == 2) {
-    R.t = h->t.p; R.diag = h->diag.p; R.y = h->y.p;
-    R.t_stride = h->t_stride; R.diag_stride = h->diag_stride; R.y_stride = h->y_stride;
-    R.lane_is = 1; R.lane_cs = h->L;
-    R.staged = 1;
-  }
-  return R;
-}
-
 // Row-major API layout -> chunk-interleaved layout (3 tiled transposes).  Returns whether the copy
 // was (re)built: `relayout_pending` may only be cleared then -- the need for the copy can appear later
 // (a new coefficient draw can switch the summarize kernel) with the series unchanged.
@@ -598,8 +569,8 @@ int wide_flow(clr::BatchParams& P, int J_real, int J_comp, hipStream_t stream, c
       // end states off the scanned start states, but not by much (level 3): the chunks again, each from the previous
       // chunk's replayed end state, until what two consecutive replays wrote agrees (BatchParams::head_check); an even
       // number of attempts, so that P.ends holds the last (or last but one: equal to head_tol) end states for the fix-up
-      int attempts = 4;
-      if (const char* e = clr::option("CLR_OUTPUT_CHECK_ATTEMPTS")) attempts = std::max(1, std::min(atoi(e), 16));  // (tools/gpu_reference_family_factor.py)
+      // (the mismatch reaches its floor at the second or third: profiles/r06q_output_check_convergence.txt)
+      const int attempts = 4;
       for (int k = 0; k < attempts; ++k) {
         clr::BatchParams F = P;
         F.fixup_steps = P.L + (P.L0 > P.L ? P.L0 - P.L : 0);

@@ -248,18 +248,4 @@ void launch_scatter_results(const double* sub_out, const int* sub_level, int n, 
   hipLaunchKernelGGL(scatter_results_kernel, dim3((n + 63) / 64), dim3(64), 0, s, sub_out, sub_level, n, out, level, B, idx);
 }
 
-// Which compute units a stream's workgroups land on (diagnostic for CU-masked streams): every workgroup marks the
-// (XCC, HW_ID cu / sh / se) it ran on; `spin` iterations of dependent arithmetic keep it resident long enough for the
-// dispatcher to spread a grid over every unit the stream may use.
-__global__ void __launch_bounds__(64) cu_census_kernel(int* seen, int spin) {
-  const unsigned xcc = __builtin_amdgcn_s_getreg((31 << 11) | 20) & 7;    // HW_REG_XCC_ID
-  const unsigned hw = __builtin_amdgcn_s_getreg((31 << 11) | 4);          // HW_REG_HW_ID: cu_id [11:8], sh_id [12], se_id [15:13]
-  double x = 1.0 + threadIdx.x * 1e-9;
-  for (int i = 0; i < spin; ++i) x = fma(x, 1.0000001, 1e-9);
-  if (threadIdx.x == 0) atomicAdd(seen + xcc * 256 + ((hw >> 8) & 0xff), x > 0.0 ? 1 : 0);
-}
-void launch_cu_census(int* seen, int blocks, int spin, hipStream_t s) {
-  hipLaunchKernelGGL(cu_census_kernel, dim3(blocks), dim3(64), 0, s, seen, spin);
-}
-
 }  // namespace clr

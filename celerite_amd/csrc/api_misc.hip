@@ -9,6 +9,16 @@ thread_local int clr_api_device = 0;
 
 // ---- the option table (clr_options.h) ---------------------------------------------------------------------------
 namespace {
+// every key the library reads (include/celerite_hip.h describes them); clr_set_option refuses any other
+const char* const k_option_keys[] = {
+    "CLR_GRAD_SEQUENTIAL", "CLR_GRAD_ANY_WIDTH", "CLR_GRAD_REBUILD_SPAN", "CLR_WIDE_WALK", "CLR_WIDE_NO_PAIRED",
+    "CLR_NO_ROWS_KERNEL", "CLR_NO_BIG_SWEEP", "CLR_OUTPUT_CHECK_CAP", "CLR_OUTPUT_CHECK_TOL",
+};
+bool known_option(const char* key) {
+  for (const char* k : k_option_keys)
+    if (strcmp(key, k) == 0) return true;
+  return false;
+}
 std::mutex g_option_mutex;
 std::map<std::string, std::string>& option_table() {
   static std::map<std::string, std::string> table;
@@ -31,7 +41,7 @@ const char* option(const char* key) {
       return value.c_str();
     }
   }
-  return env_allowed() ? getenv(key) : nullptr;
+  return env_allowed() && known_option(key) ? getenv(key) : nullptr;
 }
 double output_check_cap() {
   if (const char* e = option("CLR_OUTPUT_CHECK_CAP")) return atof(e);
@@ -88,7 +98,7 @@ const char* clr_status_string(int status) {
 }
 
 int clr_set_option(const char* key, const char* value) {
-  if (!key || strncmp(key, "CLR_", 4) != 0) return fail(CLR_INVALID_ARGUMENT, "clr_set_option: keys start with CLR_");
+  if (!key || !known_option(key)) return fail(CLR_INVALID_ARGUMENT, std::string("clr_set_option: unknown key ") + (key ? key : "(null)"));
   std::lock_guard<std::mutex> lock(g_option_mutex);
   if (value) option_table()[key] = value;
   else option_table().erase(key);

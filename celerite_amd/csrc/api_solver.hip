@@ -88,12 +88,6 @@ int stage_upload(clr_solver* s, DevBuf& buf, const double* host, size_t n) {
 
 }  // namespace
 
-// the end-state mismatch of the chunked replay that still counts as consistent (tuning: CLR_SOLVER_CERT_RESID)
-static double solver_cert_resid() {
-  if (const char* e = clr::option("CLR_SOLVER_CERT_RESID")) return atof(e);
-  return 1e-11;
-}
-
 extern "C" {
 
 /* ---- single-problem solver --------------------------------------------------- */
@@ -166,7 +160,7 @@ int clr_solver_compute(clr_solver* s, double jitter, int n_a_real, const double*
   // One short series of a narrow kernel: the whole factorisation in ONE launch and one upload (small_kernels.hip);
   // it settles the problem itself when every chunk boundary is consistent and no pivot is flagged, and hands it to
   // the general route below otherwise.
-  if (!has_general && clr::small_compute_supported(J_real, J_comp, N) && !clr::option("CLR_NO_SMALL_SOLVER")) {
+  if (!has_general && clr::small_compute_supported(J_real, J_comp, N)) {
     const size_t ELEM = (size_t)J * J + 2 * J + (size_t)J * (J + 1);
     int threads = 64;
     while (threads < 256 && threads * 8 < N && (size_t)threads * 2 * ELEM * sizeof(double) <= 60000) threads *= 2;
@@ -279,7 +273,7 @@ int clr_solver_compute(clr_solver* s, double jitter, int n_a_real, const double*
     P.out_ll = s->scalars.p; P.out_logdet = s->scalars.p + 1; P.out_quad = s->scalars.p + 2;
     P.out_status = reinterpret_cast<int*>(s->scalars.p + 3);
     P.phi = s->phi.p; P.u = s->u.p; P.W = s->W.p; P.D = s->D.p;
-    P.cond = s->ws_cond.p; P.cert_gamma = 1e7; P.cert_gamma_abs = 1e4; P.cert_eg = 3e-9; P.egerr = s->ws_cond.p + (size_t)P.nchunk * 3; P.cert_resid = solver_cert_resid(); P.logdet_only = use_rhs ? 0 : 1;
+    P.cond = s->ws_cond.p; P.cert_gamma = 1e7; P.cert_gamma_abs = 1e4; P.cert_eg = 3e-9; P.egerr = s->ws_cond.p + (size_t)P.nchunk * 3; P.cert_resid = 1e-11; P.logdet_only = use_rhs ? 0 : 1;
     if (P.nchunk < 2) HIP_TRY(hipMemsetAsync(P.need_exact, 0, sizeof(int), stream));  // (no prefix kernel clears it)
     L->summarize(P, stream);
     L->prefix(P, stream);
@@ -335,20 +329,19 @@ int clr_solver_compute(clr_solver* s, double jitter, int n_a_real, const double*
       // nchunk steps of 14 / 50 us), so the chunks only have to amortise their own set-up -- 48 samples up to width 16, 96
       // above, at most 1024 / 512 chunks, at least 8 (profiles/r04v_single_wide_chunks.txt, r04z_single_wide_short.txt:
       // N = 1e5 width 16 3.0 -> 0.79 ms, width 32 6.9 -> 1.56 ms; N = 1000 0.74 -> 0.24 / 0.87 -> 0.58 ms)
-      if (!clr::option("CLR_WIDE_PREFIX_WALK") && J <= 32) {
+      if (J <= 32) {
         const int cap = clr::wide_prefix_scan_max_chunks(J <= 16 ? 16 : 32), Lmin = J <= 16 ? 48 : 96;
         int nk = std::min(N / Lmin, cap);
         if (nk < 8 && N >= 8 * (J <= 16 ? 32 : 64)) nk = 8;
         if (nk >= 8) nchunk = nk;
       }
-      if (const char* e = clr::option("CLR_SOLVER_WIDE_CHUNKS")) nchunk = std::max(1, std::min(atoi(e), N / 32));  // (tools/gpu_single_wide_chunks*.py)
     }
     P.L = (N + nchunk - 1) / nchunk;
     P.nchunk = (N + P.L - 1) / P.L;
     const size_t pc = (size_t)P.nchunk, JP = (size_t)clr::wide_padded_width(J), SZP = JP * (JP + 1) / 2;
     if ((st = s->ws_elems.reserve(pc * (JP * JP + JP + SZP + JP + SZP))) != CLR_OK) return st;
     if ((st = s->ws_starts.reserve(pc * (SZP + JP))) != CLR_OK) return st;
-    const size_t scan_ws = clr::option("CLR_WIDE_PREFIX_WALK") ? 0 : clr::wide_prefix_scan_workspace(1, P.nchunk, (int)JP);  // the prefix as a parallel scan
+    const size_t scan_ws = clr::wide_prefix_scan_workspace(1, P.nchunk, (int)JP);  // the prefix as a parallel scan
     if (scan_ws && (st = s->ws_lvl_elems.reserve(scan_ws)) != CLR_OK) return st;
     P.scan_ws = scan_ws ? s->ws_lvl_elems.p : nullptr;
     if ((st = s->ws_part.reserve(pc * 4)) != CLR_OK) return st;
@@ -369,7 +362,7 @@ int clr_solver_compute(clr_solver* s, double jitter, int n_a_real, const double*
     P.elems = s->ws_elems.p; P.starts = s->ws_starts.p;
     P.part = s->ws_part.p; P.partx = s->ws_part.p + pc * 2;
     P.flags = s->ws_flags.p; P.flagsx = s->ws_flags.p + pc; P.need_exact = s->ws_flags.p + 2 * pc;
-    P.cond = s->ws_cond.p; P.cert_gamma = 1e7; P.cert_gamma_abs = 1e4; P.cert_eg = 3e-9; P.egerr = s->ws_cond.p + (size_t)P.nchunk * 3; P.cert_resid = solver_cert_resid(); P.logdet_only = use_rhs ? 0 : 1;
+    P.cond = s->ws_cond.p; P.cert_gamma = 1e7; P.cert_gamma_abs = 1e4; P.cert_eg = 3e-9; P.egerr = s->ws_cond.p + (size_t)P.nchunk * 3; P.cert_resid = 1e-11; P.logdet_only = use_rhs ? 0 : 1;
     P.force_exact = 1;       // the factor is wanted: every chunk is replayed (and checked against the scan)
     P.wide_materialize = 1;
     P.head_cap = clr::output_check_cap(); P.head_tol = clr::output_check_tol();  // (a state mismatch no output sees: BatchParams::head_check)
@@ -424,10 +417,8 @@ int clr_solver_compute(clr_solver* s, double jitter, int n_a_real, const double*
     static std::mutex rows_many_mutex;
     std::unique_lock<std::mutex> rows_lock(rows_many_mutex, std::defer_lock);
     // (general terms at ANY total width: even at width 5 the padded width-128 step of the rows kernel, 1.6 us, is shorter
-    //  than the LDS-resident kernel's five barriers, 1.9 .. 5.6 us at widths 5 .. 40 -- tools/gpu_rows_min_width.py)
-    int rows_min = 1;
-    if (const char* e = clr::option("CLR_ROWS_MIN_WIDTH")) rows_min = std::max(1, atoi(e));
-    if (J >= rows_min && clr::factor_rows_supported(J) && !clr::option("CLR_NO_ROWS_KERNEL")) {
+    //  than the LDS-resident kernel's five barriers, 1.9 .. 5.6 us at widths 5 .. 40)
+    if (clr::factor_rows_supported(J) && !clr::option("CLR_NO_ROWS_KERNEL")) {
       if (J > 128) rows_lock.lock();
       // S in the registers of 1 .. 64 workgroups (rows_kernels.hip; round 6: width 128 20.5 -> ~1 us per step)
       if ((st = s->ws_elems.reserve(clr::factor_rows_workspace_doubles(J))) != CLR_OK) return st;
@@ -964,7 +955,6 @@ int clr_solver_predict(const clr_solver* cs, int n_y, const double* y, int M, co
     // prediction points and the chunk summaries walk <= one chunk each (profiles/r04z_predict_chunks.txt: N = 1e5, M = 2e4,
     // width 8 2.1 -> 0.84 ms, width 32 4.9 -> 1.5 ms; rounds 2-3: 1.8 sqrt(N) chunks, their prefix one thread's walk)
     pchunk = std::max(1, std::min(s->N / 16, 8192));
-    if (const char* e = clr::option("CLR_PREDICT_CHUNKS")) pchunk = std::max(1, std::min(atoi(e), s->N / 8));  // (tools/gpu_predict_chunks.py)
     pL = (s->N + pchunk - 1) / pchunk;
     pchunk = (s->N + pL - 1) / pL;
     if ((st = s->ws_elems.reserve(clr::predict_workspace_doubles(pchunk, s->J_real + 2 * s->J_comp))) != CLR_OK) return st;

@@ -1243,8 +1243,6 @@ void launch_gather_series(const double* src, long src_stride, double* dst, const
 void launch_gather_coeffs(const double* src, double* dst, const int* idx, int B, int n, int JR, int JC, hipStream_t s);
 void launch_scatter_results(const double* sub_out, const int* sub_level, int n, double* out, int* level, int B, const int* idx,
                             hipStream_t s);
-// diagnostic: the compute units a stream's workgroups run on, seen[xcc * 256 + HW_ID bits 15:8] (api_kernels.hip)
-void launch_cu_census(int* seen, int blocks, int spin, hipStream_t s);
 // Filled by the per-width translation units (batch_w*.hip).
 const BatchLaunchers* find_batch_launchers(int JR, int JC);
 // prefix phase at the padded widths of the wide scan (16: 2 problems per wave, 32: one)

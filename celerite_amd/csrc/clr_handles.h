@@ -81,12 +81,6 @@ inline hipError_t create_stream(Stream& s) {
   if (e == hipSuccess) s.reset(r);
   return e;
 }
-inline hipError_t create_stream(Stream& s, uint32_t cu_mask_words, const uint32_t* cu_mask) {
-  hipStream_t r = nullptr;
-  const hipError_t e = hipExtStreamCreateWithCUMask(&r, cu_mask_words, cu_mask);
-  if (e == hipSuccess) s.reset(r);
-  return e;
-}
 inline hipError_t create_event(Event& ev, unsigned flags = hipEventDefault) {
   hipEvent_t r = nullptr;
   const hipError_t e = hipEventCreateWithFlags(&r, flags);

@@ -2,6 +2,8 @@
 // ONE table per process; `clr::option(key)` is what every translation unit asks instead of getenv: the value set through
 // clr_set_option, else -- only when the process was started with CLR_ALLOW_ENV=1 -- the environment variable of the same
 // name, else null.  (Round 5 read 19 environment variables directly: a stray variable silently changed kernel selection.)
+// The keys are listed once, in api_misc.hip (k_option_keys): clr_set_option refuses any other key, so a misspelt or
+// retired one fails loudly instead of being ignored.
 #pragma once
 
 namespace clr {

@@ -30,7 +30,6 @@
 
 #include "../../include/celerite_hip.h"
 #include "clr_generic_kernels.h"
-#include "clr_options.h"
 #include "clr_wide.h"
 
 namespace clr {
@@ -461,9 +460,8 @@ void launch_factor_rows(const GenericProblem& g, int fast_trig, const double* y,
     if (fast_trig) hipLaunchKernelGGL((factor_rows_kernel<T, true>), dim3(G), dim3(ROWS_THREADS), 0, s, g, X, y, phi, u, W, D, status, log_det); \
     else hipLaunchKernelGGL((factor_rows_kernel<T, false>), dim3(G), dim3(ROWS_THREADS), 0, s, g, X, y, phi, u, W, D, status, log_det);          \
   } while (0)
-  if (tpr == 4) {  // (one workgroup: the 4 x 8 register blocks; CLR_ROWS_NO_BLOCKS=1 keeps the row-per-lane-group layout for A/B)
-    if (clr::option("CLR_ROWS_NO_BLOCKS")) CLR_ROWS_LAUNCH(4);
-    else if (fast_trig) hipLaunchKernelGGL((factor_rows_kernel<4, true, true>), dim3(G), dim3(ROWS_THREADS), 0, s, g, X, y, phi, u, W, D, status, log_det);
+  if (tpr == 4) {  // (one workgroup: the 4 x 8 register blocks)
+    if (fast_trig) hipLaunchKernelGGL((factor_rows_kernel<4, true, true>), dim3(G), dim3(ROWS_THREADS), 0, s, g, X, y, phi, u, W, D, status, log_det);
     else hipLaunchKernelGGL((factor_rows_kernel<4, false, true>), dim3(G), dim3(ROWS_THREADS), 0, s, g, X, y, phi, u, W, D, status, log_det);
   }
   else if (tpr == 8) CLR_ROWS_LAUNCH(8);

@@ -7,7 +7,7 @@
 // distributed over the 64 lanes in registers:
 //     WMAX = 16: 4 lanes per row, 4 columns each      (LPR = 4, COLS = 4)
 //     WMAX = 32: 2 lanes per row, 16 columns each     (LPR = 2, COLS = 16)
-//     WMAX = 64: 1 lane  per row, 64 columns          (LPR = 1, COLS = 64)
+//     WMAX = 64: 2 lanes per row, 32 columns each, over TWO waves (NW = 2; LPR = 2, COLS = 32)
 // S is kept in FULL (not packed-symmetric) storage: every lane updates its own row
 // segment, no lane idles on a triangle.
 //
@@ -251,7 +251,7 @@ __device__ __forceinline__ L& wide_lds() {
 template <int WMAX, bool FAST, int MODE, bool LAZY, bool RIDERS, bool GEN, int NW = 1, bool PAIRED = false, bool GAPS = false>
 __device__ __forceinline__ void wide_scan_body(const BatchParams& P, int JR, int JC) {
   static_assert(!LAZY || MODE == 1, "the lazy decay is a summarize flavour");
-  static_assert(NW == 1 || (NW == 2 && WMAX == 64), "two waves per (problem, chunk): the padded width 64");
+  static_assert((NW == 1 && WMAX <= 32) || (NW == 2 && WMAX == 64), "one wave per (problem, chunk) up to the padded width 32, two at 64");
   constexpr bool RID = MODE == 1 && RIDERS;
   constexpr int LPR = 64 * NW / WMAX, COLS = WMAX / LPR;
   constexpr int J = WMAX, SZ = J * (J + 1) / 2;
@@ -265,7 +265,7 @@ __device__ __forceinline__ void wide_scan_body(const BatchParams& P, int JR, int
   constexpr bool JMM = RID && LAZY && (WMAX == 32 || WMAX == 64) && CLR_WIDE_JM_MFMA;
   constexpr int NTL = WMAX / 16, NTILE = NTL * (NTL + 1) / 2;  // (JMM) 16 x 16 tiles per side / of the upper triangle of Jm
   constexpr int NTW = NTILE / NW;                              // ... tiles per wave (NW = 2: every other tile)
-  constexpr bool PACKED = LPR >= 2 && CLR_WIDE_PACKED_SUMS;
+  constexpr bool PACKED = CLR_WIDE_PACKED_SUMS;
   constexpr bool LPWIN = LAZY && CLR_WIDE_LOGPROD_WINDOW;
 #ifndef CLR_WIDE_RENORM_STEPS
 #define CLR_WIDE_RENORM_STEPS 64
@@ -285,7 +285,7 @@ __device__ __forceinline__ void wide_scan_body(const BatchParams& P, int JR, int
   // sample's features are a full sincos of the absolute phase and an exp of the step (cholesky.h:130,137,140), ~100 of
   // the step's vector instructions, and nothing is carried from sample to sample: u, v, phi go to the slots as they are.
   // General rows ride along: their "features" are the row's U, V samples (no arithmetic), fetched a batch ahead.
-  constexpr bool FBA = LPR >= 2 && CLR_WIDE_FEATURE_BATCH;
+  constexpr bool FBA = CLR_WIDE_FEATURE_BATCH;
   constexpr bool FB = FBA && LAZY, FBN = FBA && !LAZY;
   // PAIRED (host: no real terms, two lanes per row): the cos and the sin row of a complex term share c and d, hence the
   // (cos, sin) pair and Psi -- the term's FOUR lanes split the next four samples, and each publishes BOTH rows' entries
@@ -682,7 +682,7 @@ __device__ __forceinline__ void wide_scan_body(const BatchParams& P, int JR, int
           }
         }
       }
-      if (LPR >= 2) { q = dpp_add<DPP_QUAD_XOR1>(q); if (RID) r = dpp_add<DPP_QUAD_XOR1>(r); }
+      q = dpp_add<DPP_QUAD_XOR1>(q); if (RID) r = dpp_add<DPP_QUAD_XOR1>(r);
       if (LPR >= 4) { q = dpp_add<DPP_QUAD_XOR2>(q); if (RID) r = dpp_add<DPP_QUAD_XOR2>(r); }
       double s, ub;
 #ifndef CLR_WIDE_PERMLANE_SUMS
@@ -690,7 +690,7 @@ __device__ __forceinline__ void wide_scan_body(const BatchParams& P, int JR, int
 #endif
       if constexpr (PACKED && CLR_WIDE_PERMLANE_SUMS) row_sum2_all<LPR>(ueff * (seg == 0 ? q : f), seg, &s, &ub);
       else if constexpr (PACKED) row_sum2<LPR>(ueff * (seg == 0 ? q : f), seg, &s, &ub);
-      else { s = row_sum_all<LPR>(ueff * q); ub = row_sum_all<LPR>(ueff * f); }  // (one lane per row: width 64)
+      else { s = row_sum_all<LPR>(ueff * q); ub = row_sum_all<LPR>(ueff * f); }
       if (NW == 2) {  // the other wave's rows: partial sums through LDS, added in the same order by both waves
         if (lane == 0) { xbuf[2 * wvi] = s; xbuf[2 * wvi + 1] = ub; }
         xsync();
@@ -718,14 +718,9 @@ __device__ __forceinline__ void wide_scan_body(const BatchParams& P, int JR, int
         wbuf[row] = LAZY ? w : phi * w;
         if (RID && !JMM) rbuf[row] = r;
       }
-      if (JMM) {  // this step's r (first lane of the row) and -r / D (second lane), for the block's rank-16 update
-        if (LPR >= 2) {  // r (first lane) | -r / D (second lane) = r * (ra + rb / D) with per-lane constants: no selects
-          rdst[((n - n_lo) & 15) * WMAX] = r * fma(invD, rsel_b, rsel_a);
-        } else {  // (width 64: one lane per row writes both)
-          rblk[((n - n_lo) & 15) * WMAX + row] = r;
-          rsblk[((n - n_lo) & 15) * WMAX + row] = -(r * invD);
-        }
-      }
+      // JMM: this step's r (first lane of the row) and -r / D (second lane), for the block's rank-16 update -- as
+      // r * (ra + rb / D) with per-lane constants: no selects
+      if (JMM) rdst[((n - n_lo) & 15) * WMAX] = r * fma(invD, rsel_b, rsel_a);
       xsync();  // (NW = 2: the step's w -- and r -- of BOTH waves' rows, before the rank-1 updates read them)
       // (one wave: program order is enough for the hardware; this pins it for the compiler too -- the rank-1 updates
       //  below read wbuf / rbuf entries other lanes wrote inside the `writer` arm above)
@@ -986,16 +981,10 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) wi
   if (MODE == 1 && blockIdx.x == 0) wide_scan_body<WMAX, FAST, MODE, LAZY, false, GEN, 1, PAIRED, GAPS>(P, JR, JC);
   else wide_scan_body<WMAX, FAST, MODE, LAZY, true, GEN, 1, PAIRED, GAPS>(P, JR, JC);
 }
-// Round 5: the summarize flavour at widths 33..64 (one lane per row, 64 columns each).  S and A^T alone are 2 x 64 doubles
-// = 256 registers per lane, Jm sits in the matrix cores' accumulators (10 tiles x 4 doubles: the lazy flavour) or in 64
-// more doubles: ONE wave per SIMD (512 registers), where the narrower kernels run two.
-template <bool FAST, bool LAZY, bool GEN>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) wide_summarize64_kernel(const BatchParams P, int JR, int JC) {
-  if (blockIdx.x == 0) wide_scan_body<64, FAST, 1, LAZY, false, GEN>(P, JR, JC);
-  else wide_scan_body<64, FAST, 1, LAZY, true, GEN>(P, JR, JC);
-}
-// ... and TWO waves per (problem, chunk): two lanes per row, 32 columns per lane (wide_scan_body, NW = 2) -- the state fits
-// the architectural registers, two waves per SIMD, both the summarize (MODE 1) and the replay / sequential sweep (MODE 0).
+// Widths 33..64: TWO waves per (problem, chunk), two lanes per row, 32 columns per lane (wide_scan_body, NW = 2) -- the
+// state fits the architectural registers, two waves per SIMD, both the summarize (MODE 1) and the replay / sequential sweep
+// (MODE 0).  (One wave per (problem, chunk), S and A^T in 256 registers per lane at one wave per SIMD, measured slower:
+// profiles/r05e_wide64_two_waves.txt.)
 template <bool FAST, int MODE, bool LAZY, bool GEN, bool PAIRED = false, bool GAPS = false>
 __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) wide_scan64x2_kernel(const BatchParams P, int JR, int JC) {
   if (MODE == 1 && blockIdx.x == 0) wide_scan_body<64, FAST, MODE, LAZY, false, GEN, 2, PAIRED, GAPS>(P, JR, JC);
@@ -1428,20 +1417,13 @@ void launch_wide_scan32_lazy(const BatchParams& P, int JR, int JC, bool paired, 
 int wide_max_width() { return 64; }
 int wide_scan_max_width() { return 64; }  // the chunk algebra: prefix_coop_kernel<16>, wide_prefix32_kernel, wide_walk64_kernel (wide64_kernels.hip)
 
-// widths 33..64: two waves per (problem, chunk) (wide_scan64x2_kernel); CLR_WIDE64_ONE_WAVE=1 keeps the one-wave kernels (A/B)
-static bool wide64_one_wave() { return clr::option("CLR_WIDE64_ONE_WAVE") != nullptr; }
 static bool wide_paired(int JR) { return JR == 0 && clr::option("CLR_WIDE_NO_PAIRED") == nullptr; }  // complex terms only: a term's four lanes share its features
 template <bool GEN>
 static void launch_wide64(const BatchParams& P, int JR, int JC, hipStream_t s) {
   const dim3 grid(P.nchunk, P.B);
-  if (!GEN && !wide64_one_wave() && wide_paired(JR)) {
+  if (!GEN && wide_paired(JR)) {
     if (P.fast_trig) hipLaunchKernelGGL((wide_scan64x2_kernel<true, 0, false, false, true>), grid, dim3(128), 0, s, P, JR, JC);
     else hipLaunchKernelGGL((wide_scan64x2_kernel<false, 0, false, false, true>), grid, dim3(128), 0, s, P, JR, JC);
-    return;
-  }
-  if (wide64_one_wave()) {
-    if (P.fast_trig) hipLaunchKernelGGL((wide_scan_kernel<64, true, 0, false, GEN>), grid, dim3(64), 0, s, P, JR, JC);
-    else hipLaunchKernelGGL((wide_scan_kernel<64, false, 0, false, GEN>), grid, dim3(64), 0, s, P, JR, JC);
     return;
   }
   if (P.fast_trig) hipLaunchKernelGGL((wide_scan64x2_kernel<true, 0, false, GEN>), grid, dim3(128), 0, s, P, JR, JC);
@@ -1464,7 +1446,7 @@ static void launch_wide_g(const BatchParams& P, int JR, int JC, hipStream_t s) {
     if (W <= 16) CLR_GOL(16);
     else if (W <= 32 && !GEN && (paired || gaps)) launch_wide_scan32_lazy(P, JR, JC, paired, gaps, s);  // (wide_scan32.hip: its own scheduling strategy)
     else if (W <= 32) CLR_GOL(32);
-    else if (!wide64_one_wave() && !GEN && (paired || gaps)) {
+    else if (!GEN && (paired || gaps)) {
       if (P.fast_trig) {
         if (paired && gaps) hipLaunchKernelGGL((wide_scan64x2_kernel<true, 1, true, false, true, true>), grid, dim3(128), 0, s, P, JR, JC);
         else if (paired) hipLaunchKernelGGL((wide_scan64x2_kernel<true, 1, true, false, true, false>), grid, dim3(128), 0, s, P, JR, JC);
@@ -1474,24 +1456,18 @@ static void launch_wide_g(const BatchParams& P, int JR, int JC, hipStream_t s) {
         else if (paired) hipLaunchKernelGGL((wide_scan64x2_kernel<false, 1, true, false, true, false>), grid, dim3(128), 0, s, P, JR, JC);
         else hipLaunchKernelGGL((wide_scan64x2_kernel<false, 1, true, false, false, true>), grid, dim3(128), 0, s, P, JR, JC);
       }
-    } else if (wide64_one_wave()) {
-      if (P.fast_trig) hipLaunchKernelGGL((wide_summarize64_kernel<true, true, GEN>), grid, dim3(64), 0, s, P, JR, JC);
-      else hipLaunchKernelGGL((wide_summarize64_kernel<false, true, GEN>), grid, dim3(64), 0, s, P, JR, JC);
     } else if (P.fast_trig) hipLaunchKernelGGL((wide_scan64x2_kernel<true, 1, true, GEN>), grid, dim3(128), 0, s, P, JR, JC);
     else hipLaunchKernelGGL((wide_scan64x2_kernel<false, 1, true, GEN>), grid, dim3(128), 0, s, P, JR, JC);
 #undef CLR_GOL
     return;
   }
   if (MODE == 1 && W > 32) {  // widths 33..64 on a series that is not densely sampled
-    if (!GEN && !wide64_one_wave() && wide_paired(JR)) {
+    if (!GEN && wide_paired(JR)) {
       if (P.fast_trig) hipLaunchKernelGGL((wide_scan64x2_kernel<true, 1, false, false, true>), grid, dim3(128), 0, s, P, JR, JC);
       else hipLaunchKernelGGL((wide_scan64x2_kernel<false, 1, false, false, true>), grid, dim3(128), 0, s, P, JR, JC);
       return;
     }
-    if (wide64_one_wave()) {
-      if (P.fast_trig) hipLaunchKernelGGL((wide_summarize64_kernel<true, false, GEN>), grid, dim3(64), 0, s, P, JR, JC);
-      else hipLaunchKernelGGL((wide_summarize64_kernel<false, false, GEN>), grid, dim3(64), 0, s, P, JR, JC);
-    } else if (P.fast_trig) hipLaunchKernelGGL((wide_scan64x2_kernel<true, 1, false, GEN>), grid, dim3(128), 0, s, P, JR, JC);
+    if (P.fast_trig) hipLaunchKernelGGL((wide_scan64x2_kernel<true, 1, false, GEN>), grid, dim3(128), 0, s, P, JR, JC);
     else hipLaunchKernelGGL((wide_scan64x2_kernel<false, 1, false, GEN>), grid, dim3(128), 0, s, P, JR, JC);
     return;
   }

@@ -86,19 +86,16 @@ int clr_device_memory(size_t* free_bytes, size_t* total_bytes);
  *   CLR_GRAD_SEQUENTIAL      the sequential tangent kernel for every gradient (cross-checks); with CLR_GRAD_ANY_WIDTH the
  *                            workgroup-per-partial kernel of the widths above 64 at every width
  *   CLR_GRAD_REBUILD_SPAN    reverse-mode gradient: distance of the stored states
- *   CLR_NO_SMALL_SOLVER      CholeskySolver: never the one-workgroup kernel of short narrow problems
  *   CLR_WIDE_WALK            widths 17..32: prefix + corrections as one walk per problem (cross-check of the two-kernel path)
- *   CLR_WIDE_PREFIX_WALK     CholeskySolver at widths 9..32: the sequential walk instead of the parallel prefix
+ *   CLR_WIDE_NO_PAIRED       widths 17..64, complex terms only: the kernels without the term-paired features (cross-check)
  *   CLR_OUTPUT_CHECK_CAP, CLR_OUTPUT_CHECK_TOL   materialising replays at widths 9..64 whose end states miss the scanned start
  *                            states by more than the certificate's bound but less than CAP (default 1e-6; 0: off) are
  *                            settled by comparing what a second replay writes (within TOL, default 2e-11) instead of
- *                            going to the sequential recurrence; CLR_SOLVER_CERT_RESID: that bound for CholeskySolver (1e-11);
- *                            CLR_OUTPUT_CHECK_ATTEMPTS: replays before giving up (4)
+ *                            going to the sequential recurrence
  *   CLR_NO_ROWS_KERNEL       CholeskySolver above width 64 / general terms above 32: the one-workgroup kernels (S in LDS / L2)
- *                            instead of the row-distributed one (cross-checks); CLR_ROWS_NO_BLOCKS: its row-per-lane-group layout
+ *                            instead of the row-distributed one (cross-checks)
  *   CLR_NO_BIG_SWEEP         dot_solve / solve above width 64: the sequential sweeps instead of the chunked affine scans
- *   CLR_WIDE_NO_PAIRED, CLR_WIDE64_ONE_WAVE, CLR_WIDE_LAZY_BOUND, CLR_WIDE_FIRST_RATIO, CLR_WIDE_FIRST_RATIO64,
- *   CLR_WIDE_SCAN_CAP, CLR_SOLVER_WIDE_CHUNKS, CLR_PREDICT_CHUNKS, CLR_WSWEEP_RUN, CLR_WSWEEP_CHUNKS   (tuning runs, tools/)
+ * Any other key is refused with CLR_INVALID_ARGUMENT.
  * clr_get_option: the value in force (NULL: not set); the pointer is valid until the calling thread's next call. */
 int clr_set_option(const char* key, const char* value);
 const char* clr_get_option(const char* key);
@@ -296,11 +293,9 @@ int clr_batch_set_general_route(clr_batch* h, int route);
  *       times, but costs a 0.87 ms pass (B=1024, N=1e5) whenever they change.
  *   0 row-major direct: every lane streams its own run (slow; kept for A/B). */
 int clr_batch_set_layout(clr_batch* h, int layout);
-/* The kernels evaluate sin/cos(d_comp * t) with a 25-instruction FMA Cody-Waite
+/* (The kernels evaluate sin/cos(d_comp * t) with a 25-instruction FMA Cody-Waite
  * routine (abs. error < 1 ulp(1)) when the host-side check max|d_comp| * max|t| <
- * 1e9 holds, and with the library (ocml) sincos otherwise.  force != 0 selects the
- * library routine unconditionally (for A/B measurements). */
-int clr_batch_set_library_trig(clr_batch* h, int force);
+ * 1e9 holds, and with the library (ocml) sincos otherwise.) */
 /* summarize kernel of widths 7 and 8 (csrc/clr_split_kernels.h):
  *   0  the single-wave kernel (one wave per SIMD, part of the state in AGPRs);
  *   1  two roles on two waves per SIMD: a "trajectory" wave (C, b) and a "riders" wave (A, eta in
@@ -332,11 +327,6 @@ int clr_batch_set_warm_start(clr_batch* h, int mode, int forced_warmup);
  * clr_batch_get_results).  Any pointer may be NULL. */
 int clr_batch_get_warm_start(const clr_batch* h, int* active, int* nchunk, int* chunk_len, int* warmup_min,
                              int* warmup_max, int* settled, int* fallbacks);
-/* Where the replay pass (materialising / forced-exact runs) reads the series when the summarize kernel reads the
- * chunk-interleaved copy: 0 that copy (default, also -1: 4.41 ms = 65 % of HBM for the materialising replay at
- * B = 1024, N = 1e5, width 8), 1 the row-major arrays through LDS-staged tiles (4.77 ms = 60 %;
- * profiles/r03a_prefix_ab.txt). */
-int clr_batch_set_replay_source(clr_batch* h, int source);
 /* Which one the next evaluation will run (0, 1 or 2 as above), given the series and coefficients set. */
 int clr_batch_get_summarize_kernel(const clr_batch* h, int* kind);
 /* Prefix phase of the scan (widths 1..8): how the chunk elements are turned into chunk start states.
@@ -448,14 +438,6 @@ int clr_batch_set_factor_layout(clr_batch* h, int layout);
 int clr_batch_set_factor_refine(clr_batch* h, int samples);
 /* Bytes of factor one problem occupies in HBM under the layout and chunking in force. */
 int clr_batch_get_factor_bytes(const clr_batch* h, size_t* bytes_per_problem);
-
-/* Materialising runs (widths 1..8) as a PIPELINE over `groups` contiguous groups of problems: the summarize pass of
- * group g + 1 (fp64-VALU-bound) runs while group g is replayed (HBM-bound: the factor's stores), on streams that own
- * disjoint sets of compute units -- `summarize_cus` of the device's CUs (a multiple of 16; 0: no CU masks, the
- * dispatcher decides) for `summarize_streams` summarize streams, the others for the replay stream; the prefix and the
- * corrections of a group run on a third stream in between.  Results and the factor are those of the plain sequence
- * of kernels, bit for bit (the same kernels on the same data, group by group).  groups = 0: off (default). */
-int clr_batch_set_materialize_pipeline(clr_batch* h, int groups, int summarize_cus, int summarize_streams);
 
 
 /* Enqueue one evaluation of all B problems on the handle's stream (inputs

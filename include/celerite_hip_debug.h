@@ -2,8 +2,7 @@
  * include/celerite_hip_debug.h -- diagnostics, probes and test hooks of libcelerite_hip.so.  NOT part of the drop-in
  * boundary (include/celerite_hip.h): nothing a caller of the reference's CholeskySolver / GP path needs, no stability
  * promise.  Used by tests/, tools/ and bench.py (the measured fp64 rate of the box, the fp32-state probe of BASELINE
- * configs[4]'s "fp32 vs fp64 tolerance", the scanned start states, the element-composition check, the CU census of
- * the materialising pipeline's streams).
+ * configs[4]'s "fp32 vs fp64 tolerance", the scanned start states, the element-composition check).
  */
 #ifndef CELERITE_HIP_DEBUG_H
 #define CELERITE_HIP_DEBUG_H
@@ -36,10 +35,6 @@ int clr_batch_debug_get_starts(clr_batch* h, double* starts);
  * chunk elements in groups of `group`: the largest difference relative to the largest entry of the same block
  * (A, b, C, eta, Jm) of the same composed element, and the largest magnitude seen. */
 int clr_batch_debug_compose_check(clr_batch* h, int group, double* max_rel_diff, double* max_abs_value);
-
-/* Diagnostic: on how many distinct compute units of each of the 8 XCDs a grid launched on the plan's stream (which =
- * 0), on the pipeline's first summarize stream (1) or on its replay stream (2) runs. */
-int clr_batch_debug_cu_census(clr_batch* h, int which, int* cus_per_xcc /* [8] */);
 
 /* A measurement, not a product path (BASELINE config 5 asks for the fp32-vs-fp64 tolerance of the wide
  * recurrence): the sequential sweep of a width 9..32 plan with the state and every per-step operation in

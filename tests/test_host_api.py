@@ -377,9 +377,10 @@ def test_import_celerite_resolves_to_this_build():
     assert celerite.GP(k).kernel is k
 
 
-def test_options_table_and_the_split_of_the_headers():
+def test_closed_options_table_and_the_split_of_the_headers():
     """``clr_set_option`` replaces round 5's 19 direct ``getenv`` reads: one table per process, environment variables
-    honoured only under CLR_ALLOW_ENV=1; the diagnostics live in include/celerite_hip_debug.h, not in the boundary."""
+    honoured only under CLR_ALLOW_ENV=1, and only the keys the library reads are accepted (a retired or misspelt key is
+    refused); the diagnostics live in include/celerite_hip_debug.h, not in the boundary."""
     assert os.environ.get("CLR_ALLOW_ENV") != "1"
     os.environ["CLR_GRAD_SEQUENTIAL"] = "1"            # a stray variable must NOT reach the library
     try:
@@ -393,14 +394,32 @@ def test_options_table_and_the_split_of_the_headers():
         assert batch.get_option("CLR_GRAD_SEQUENTIAL") is None
         with pytest.raises(RuntimeError):
             batch.set_option("PATH", "x")
+        with pytest.raises(RuntimeError):                # a retired key fails loudly instead of being ignored
+            batch.set_option("CLR_WIDE64_ONE_WAVE", "1")
+        assert batch.get_option("CLR_WIDE64_ONE_WAVE") is None
+        batch.set_option("CLR_WIDE_WALK", "1")            # ... a kept one is still accepted
+        assert batch.get_option("CLR_WIDE_WALK") == "1"
+        batch.set_option("CLR_WIDE_WALK", None)
     finally:
         del os.environ["CLR_GRAD_SEQUENTIAL"]
         batch.set_option("CLR_GRAD_SEQUENTIAL", None)
     boundary = open(os.path.join(ROOT, "include", "celerite_hip.h")).read()
     debug = open(os.path.join(ROOT, "include", "celerite_hip_debug.h")).read()
-    for name in ("clr_batch_debug_get_starts", "clr_batch_debug_compose_check", "clr_batch_debug_cu_census",
-                 "clr_batch_fp32_probe", "clr_device_measure_fp64"):
+    for name in ("clr_batch_debug_get_starts", "clr_batch_debug_compose_check", "clr_batch_fp32_probe",
+                 "clr_device_measure_fp64"):
         assert name + "(" in debug and name + "(" not in boundary, name
+    # one list of keys: the ones the library reads are the ones clr_set_option accepts and the header describes
+    import re
+    csrc = os.path.join(ROOT, "celerite_amd", "csrc")
+    misc = open(os.path.join(csrc, "api_misc.hip")).read()
+    table = misc[misc.index("k_option_keys[]"):]
+    listed = set(re.findall(r'"(CLR_[A-Z0-9_]+)"', table[:table.index("};")]))
+    read = set()
+    for f in os.listdir(csrc):
+        read.update(re.findall(r'option\("(CLR_[A-Z0-9_]+)"\)', open(os.path.join(csrc, f)).read()))
+    assert read == listed
+    for key in listed:
+        assert key in boundary, key
     for dirpath, _, files in os.walk(os.path.join(ROOT, "celerite_amd", "csrc")):
         for f in files:
             text = open(os.path.join(dirpath, f)).read()
