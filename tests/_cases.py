@@ -99,6 +99,10 @@ def coeffs_of(case, p=None):
 
 ALL_WIDTH_SHAPES = [(jr, jc) for jc in range(5) for jr in range(9) if 1 <= jr + 2 * jc <= 8]
 
+# one wide shape per summarize / prefix instantiation bucket of launch_wsweep_scan (csrc/wsweep_kernels.hip): the batched
+# consumers of a wide plan at widths 12, 21, 31, 33, 45, 50, 61, 63, 64 (test_host_api.py keeps the list complete)
+CONSUMER_WIDE_SHAPES = [(4, 4), (1, 10), (1, 15), (33, 0), (1, 22), (0, 25), (1, 30), (1, 31), (0, 32)]
+
 
 def adversarial(B, N, J_real, J_comp, seed=0):
     """Near-singular and outright indefinite problems: white noise from exactly zero

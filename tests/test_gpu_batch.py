@@ -1908,7 +1908,7 @@ def test_an_unsorted_series_is_rejected_whatever_else_the_batch_holds():
             plan.close()
 
 
-@pytest.mark.parametrize("JR,JC,N", [(2, 3, 6000), (4, 6, 5000)])
+@pytest.mark.parametrize("JR,JC,N", [(2, 3, 6000), (4, 6, 5000), (1, 22, 3000)])
 def test_sharded_factor_consumers(JR, JC, N):
     """``clr_sharded_materialize`` + ``clr_sharded_solve`` / ``_dot_L`` / ``_predict``: the consumers of the factor
     (``GP.apply_inverse`` / ``.sample`` / ``.predict``, celerite.py:307-451) on a batch sharded over 1 / 2 / 3 / 7 plans --

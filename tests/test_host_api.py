@@ -441,3 +441,24 @@ def test_hip_resources_are_released_only_by_their_owning_types():
             seen.setdefault(f, []).append(m.group(1))
     assert sorted(seen) == ["clr_handles.h"], seen
     assert sorted(seen["clr_handles.h"]) == ["hipEventDestroy", "hipFree", "hipHostFree", "hipStreamDestroy"]
+
+
+def test_wide_consumer_shapes_cover_every_sweep_instantiation():
+    """The batched consumers of a wide plan (``clr_batch_solve`` / ``_dot_L`` / ``_predict``) run the chunked affine
+    scans of ``launch_wsweep_scan``, compiled once per width bucket of its summarize (``P.J <= K``) and prefix
+    (``Q.J <= K``) kernels.  ``CONSUMER_WIDE_SHAPES`` (tests/_cases.py, the shapes of tests/test_gpu_batch_consumers.py)
+    must hold a width in every bucket above width 8 (narrow plans never reach these sweeps), so a new instantiation
+    cannot ship untested."""
+    import re
+    from _cases import CONSUMER_WIDE_SHAPES
+    src = open(os.path.join(ROOT, "celerite_amd", "csrc", "wsweep_kernels.hip")).read()
+    body = src[src.index("void launch_wsweep_scan("):]
+    body = body[:body.index("\n}\n")]
+    widths = sorted({jr + 2 * jc for jr, jc in CONSUMER_WIDE_SHAPES})
+    assert widths[0] > 8 and widths[-1] <= 64
+    for var in ("P", "Q"):
+        limits = sorted({int(k) for k in re.findall(r"\b%s\.J <= (\d+)\)" % var, body)})
+        assert len(limits) >= 6 and limits[0] == 8 and limits[-1] < 64, (var, limits)
+        edges = limits + [64]                  # (the last branch: everything above the largest threshold)
+        for lo, hi in zip(edges[:-1], edges[1:]):
+            assert any(lo < w <= hi for w in widths), ("%s.J bucket %d..%d has no consumer test shape" % (var, lo + 1, hi), widths)
