@@ -4,6 +4,8 @@
 #include "clr_options.h"
 #include "clr_group_hooks.h"
 
+#include <functional>
+
 extern "C" {
 
 /* ---- batched log-likelihood ---------------------------------------------------- */
@@ -1012,6 +1014,11 @@ int clr_batch_get_factor_bytes(const clr_batch* h, size_t* bytes_per_problem) {
   return CLR_OK;
 }
 
+// a materialising run has queued the writes of the factor, in the lean layout or the reference's
+static void factor_written(clr_batch* h, bool lean) {
+  h->factor_is_lean = lean; h->factor_inputs_changed = false; h->factor_valid = true; h->bs_M_valid = false;
+}
+
 int clr_batch_enqueue(clr_batch* h, int materialize) {
   int st = require_device(h->device);
   if (st != CLR_OK) return st;
@@ -1073,7 +1080,7 @@ int clr_batch_enqueue(clr_batch* h, int materialize) {
   if (!h->launch) {
     mark(0);
     if ((st = wide_launch(h, P, ev)) != CLR_OK) return st;
-    if (materialize) { h->factor_is_lean = false; h->factor_inputs_changed = false; h->factor_valid = true; h->bs_M_valid = false; }
+    if (materialize) factor_written(h, false);
     h->rescue_inflight = P.defer_level1 != 0;
     HIP_TRY(hipGetLastError());
     return CLR_OK;
@@ -1123,7 +1130,7 @@ int clr_batch_enqueue(clr_batch* h, int materialize) {
   h->launch->replay(P, replay_mode(h, materialize), h->stream.get());
   if (P.ends) refine_chunk_heads(h, P, materialize, h->stream.get());
   h->launch->sequential(P, replay_mode(h, materialize), h->stream.get());  // flagged / ill-conditioned problems only
-  if (materialize) { h->factor_is_lean = h->factor_layout == 1; h->factor_inputs_changed = false; h->factor_valid = true; h->bs_M_valid = false; }
+  if (materialize) factor_written(h, h->factor_layout == 1);
   mark(5);
   clr::launch_finalize(P, h->stream.get());
   mark(6);
@@ -1413,44 +1420,136 @@ int clr_batch_get_results(clr_batch* h, double* loglike, double* logdet, double*
   return CLR_OK;
 }
 
-int clr_batch_get_factor(clr_batch* h, int p, double* phi, double* u, double* W, double* D) {
-  int st = require_device(h->device);
-  if (st != CLR_OK) return st;
-  if (!h->have_factor) return fail(CLR_NOT_COMPUTED, "no materialising run has been made");
-  if (p < 0 || p >= h->B) return fail(CLR_INVALID_ARGUMENT, "problem index out of range");
-  const size_t N = (size_t)h->N, J = (size_t)h->J, Nm1 = N - 1, cells = (size_t)h->L * h->nchunk;
-  if (!h->launch) {  // widths 9..64: already in the reference's storage, problem after problem
-    if (phi && J * Nm1) HIP_TRY(hipMemcpyAsync(phi, h->phi.p + p * J * Nm1, J * Nm1 * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
-    if (u && J * Nm1) HIP_TRY(hipMemcpyAsync(u, h->u.p + p * J * Nm1, J * Nm1 * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
-    if (W) HIP_TRY(hipMemcpyAsync(W, h->W.p + p * J * N, J * N * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
-    if (D) HIP_TRY(hipMemcpyAsync(D, h->D.p + p * N, N * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
-    HIP_TRY(hipStreamSynchronize(h->stream.get()));
-    return CLR_OK;
-  }
-  if ((st = h->fphi.reserve(J * Nm1)) != CLR_OK) return st;
-  if ((st = h->fu.reserve(J * Nm1)) != CLR_OK) return st;
-  if ((st = h->fW.reserve(J * N)) != CLR_OK) return st;
-  if ((st = h->fD.reserve(N)) != CLR_OK) return st;
+// ---- the batched consumers of a plan's factor and coefficients: clr_batch_get_factor, _solve, _dot_L, _dot, _predict
+
+// the factor of the last materialising run, still usable (a lean one is not once its series or coefficients changed);
+// `settle`: settle an evaluation in flight first and require a completed run -- all but clr_batch_get_factor
+static int require_factor(clr_batch* h, bool settle) {
+  int st;
+  if (settle && (st = warm_resolve(h, nullptr)) != CLR_OK) return st;
+  if (!h->have_factor || (settle && !h->factor_valid))
+    return fail(CLR_NOT_COMPUTED, settle ? "no materialising run has been made (clr_batch_enqueue(h, 1))"
+                                         : "no materialising run has been made");
   if (h->factor_is_lean && h->factor_inputs_changed)
     return fail(CLR_NOT_COMPUTED, "the lean factor's phi and u are regenerated from the plan's series and coefficients, "
                                   "which were replaced after the materialising run: materialise again");
-  if (h->factor_is_lean) {
-    // the lean layout holds W and D; phi and u are regenerated from the plan's times and the coefficients in force --
-    // which must still be the ones of the materialising run (any change drops the factor: have_factor)
-    clr::BatchParams P;
-    if ((st = batch_params(h, 0, P)) != CLR_OK) return st;
-    h->launch->expand(P, p, h->t.p + (size_t)p * (size_t)h->t_stride, h->fphi.p, h->fu.p, h->fW.p, h->fD.p, h->stream.get());
-  } else
-  clr::launch_deinterleave_factor(h->phi.p + p * J * cells, h->u.p + p * J * cells,
-                                  h->W.p + p * J * cells, h->D.p + p * cells, h->fphi.p, h->fu.p,
-                                  h->fW.p, h->fD.p, h->N, h->J, h->L, h->nchunk, h->stream.get());
-  HIP_TRY(hipGetLastError());
-  if (phi && J * Nm1) HIP_TRY(hipMemcpyAsync(phi, h->fphi.p, J * Nm1 * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
-  if (u && J * Nm1) HIP_TRY(hipMemcpyAsync(u, h->fu.p, J * Nm1 * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
-  if (W) HIP_TRY(hipMemcpyAsync(W, h->fW.p, J * N * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
-  if (D) HIP_TRY(hipMemcpyAsync(D, h->fD.p, N * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
-  HIP_TRY(hipStreamSynchronize(h->stream.get()));
   return CLR_OK;
+}
+
+// the consumers cover celerite terms up to width 64 (`entry`: the refused call)
+static int require_celerite_width(const clr_batch* h, const char* entry) {
+  if (h->J_general > 0 || h->J > clr::wide_max_width())
+    return fail(CLR_UNSUPPORTED, std::string(entry) + " covers celerite-only plans of widths 1..64");
+  return CLR_OK;
+}
+
+// a narrow consumer's parameters, the times read from the row-major series (lean: one time per step and lane) where the
+// evaluation stages them through LDS (solve, dot_L), or always (`row_major`, clr_batch_dot: it must not depend on an
+// evaluation having made the role-split summarize's chunk-interleaved copy)
+static int consumer_params(clr_batch* h, bool row_major, clr::BatchParams& P) {
+  const int st = batch_params(h, 0, P);
+  if (st != CLR_OK) return st;
+  if (row_major || P.staged) { P.t = h->t.p; P.t_stride = h->t_stride; P.lane_is = 1; P.lane_cs = h->L; P.staged = 0; }
+  return CLR_OK;
+}
+
+// One consumer call's device work, made before it queues anything: every return waits for the stream, so no kernel or
+// copy outlives the local buffers (declared before the frame) and host arrays it reads.  start() / stop() time the
+// kernels, never the copies, into solve_device_ms; finish() downloads n doubles of `result` into `out` and drains.
+struct ConsumerFrame {
+  clr_batch* h;
+  bool timed = false, drained = false;
+  ~ConsumerFrame() { if (!drained) (void)hipStreamSynchronize(h->stream.get()); }
+  hipError_t start() {
+    hipError_t r;
+    for (clr::Event& e : h->bs_ev)
+      if (!e && (r = clr::create_event(e)) != hipSuccess) return r;
+    timed = true;
+    return hipEventRecord(h->bs_ev[0].get(), h->stream.get());
+  }
+  hipError_t stop() { return hipEventRecord(h->bs_ev[1].get(), h->stream.get()); }
+  int finish(double* out = nullptr, const double* result = nullptr, size_t n = 0) {
+    HIP_TRY(hipGetLastError());
+    if (out) HIP_TRY(hipMemcpyAsync(out, result, n * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
+    drained = true;
+    HIP_TRY(hipStreamSynchronize(h->stream.get()));
+    float ms = 0.f;
+    if (timed) HIP_TRY(hipEventElapsedTime(&ms, h->bs_ev[0].get(), h->bs_ev[1].get()));
+    if (timed) h->solve_device_ms = ms;
+    return CLR_OK;
+  }
+};
+
+// a narrow consumer's kernels on the chunk-interleaved right-hand sides: the B * nrhs rows of `in` laid out into xT,
+// kernels(), and the result they leave in outT back row-major into bs_rm
+static void narrow_kernels(clr_batch* h, int nrhs, const double* in, long stride, double* xT, const double* outT,
+                           const std::function<void()>& kernels) {
+  const long cells = (long)h->L * h->nchunk;
+  const int rows = h->B * nrhs;
+  clr::launch_relayout(in, stride, xT, cells, rows, h->N, h->L, h->nchunk, 0, h->stream.get());
+  kernels();
+  clr::launch_relayout_back(outT, cells, h->bs_rm.p, (long)h->N, rows, h->N, h->L, h->nchunk, h->stream.get());
+}
+
+// problem p of the plan for the object API's kernels (the batched counterpart of generic_view)
+static clr::GenericProblem problem_view(const clr_batch* h, const clr::BatchParams& P, size_t p) {
+  clr::GenericProblem g;
+  g.N = h->N; g.J = h->J; g.J_real = h->J_real; g.J_comp = h->J_comp; g.J_general = 0;
+  g.a_real = P.a_real + p * h->J_real; g.c_real = P.c_real + p * h->J_real;
+  g.a_comp = P.a_comp + p * h->J_comp; g.b_comp = P.b_comp + p * h->J_comp;
+  g.c_comp = P.c_comp + p * h->J_comp; g.d_comp = P.d_comp + p * h->J_comp;
+  g.U = nullptr; g.V = nullptr;
+  g.t = h->t.p + p * (size_t)h->t_stride;
+  return g;
+}
+
+int clr_batch_get_factor(clr_batch* h, int p, double* phi, double* u, double* W, double* D) {
+  int st = require_device(h->device);
+  if (st != CLR_OK) return st;
+  if ((st = require_factor(h, false)) != CLR_OK) return st;
+  if (p < 0 || p >= h->B) return fail(CLR_INVALID_ARGUMENT, "problem index out of range");
+  const size_t N = (size_t)h->N, J = (size_t)h->J, Nm1 = N - 1, cells = (size_t)h->L * h->nchunk;
+  ConsumerFrame frame{h};
+  const double *fphi, *fu, *fW, *fD;
+  if (!h->launch) {  // widths 9..64: already in the reference's storage, problem after problem
+    fphi = h->phi.p + p * J * Nm1; fu = h->u.p + p * J * Nm1; fW = h->W.p + p * J * N; fD = h->D.p + p * N;
+  } else {
+    if ((st = h->fphi.reserve(J * Nm1)) != CLR_OK) return st;
+    if ((st = h->fu.reserve(J * Nm1)) != CLR_OK) return st;
+    if ((st = h->fW.reserve(J * N)) != CLR_OK) return st;
+    if ((st = h->fD.reserve(N)) != CLR_OK) return st;
+    if (h->factor_is_lean) {
+      // the lean layout holds W and D; phi and u are regenerated from the plan's times and the coefficients in force --
+      // which must still be the ones of the materialising run (require_factor)
+      clr::BatchParams P;
+      if ((st = batch_params(h, 0, P)) != CLR_OK) return st;
+      h->launch->expand(P, p, h->t.p + (size_t)p * (size_t)h->t_stride, h->fphi.p, h->fu.p, h->fW.p, h->fD.p, h->stream.get());
+    } else {
+      clr::launch_deinterleave_factor(h->phi.p + p * J * cells, h->u.p + p * J * cells,
+                                      h->W.p + p * J * cells, h->D.p + p * cells, h->fphi.p, h->fu.p,
+                                      h->fW.p, h->fD.p, h->N, h->J, h->L, h->nchunk, h->stream.get());
+    }
+    HIP_TRY(hipGetLastError());
+    fphi = h->fphi.p; fu = h->fu.p; fW = h->fW.p; fD = h->fD.p;
+  }
+  if (phi && J * Nm1) HIP_TRY(hipMemcpyAsync(phi, fphi, J * Nm1 * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
+  if (u && J * Nm1) HIP_TRY(hipMemcpyAsync(u, fu, J * Nm1 * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
+  if (W) HIP_TRY(hipMemcpyAsync(W, fW, J * N * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
+  if (D) HIP_TRY(hipMemcpyAsync(D, fD, N * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
+  return frame.finish();
+}
+
+// one launch over every problem of a wide plan (grid.z = problem) on its factor, about `want` chunks per problem
+static clr::SweepParams wide_sweep_params(const clr_batch* h, int nrhs, int want) {
+  clr::SweepParams P;
+  memset(&P, 0, sizeof(P));
+  const long N = h->N, J = h->J;
+  P.N = h->N; P.J = h->J; P.nrhs = nrhs; P.batch = h->B;
+  clr::chunking(h->N - 1, want, &P.L, &P.nchunk);
+  P.phi = h->phi.p; P.u = h->u.p; P.W = h->W.p; P.D = h->D.p;
+  P.stride_phi = J * (N - 1); P.stride_W = J * N; P.stride_D = N;
+  P.stride_in = P.stride_out = nrhs * N;
+  return P;
 }
 
 // clr_batch_solve on a wide plan (widths 9..64): the factor lies in the reference's storage, problem after problem
@@ -1460,52 +1559,30 @@ int clr_batch_get_factor(clr_batch* h, int p, double* phi, double* u, double* W,
 // (2048 / B, at most the single solver's 1024, at least 2).
 static int wide_batch_solve(clr_batch* h, int nrhs, const double* b, double* x) {
   int st;
-  if ((st = warm_resolve(h, nullptr)) != CLR_OK) return st;
-  if (!h->have_factor || !h->factor_valid) return fail(CLR_NOT_COMPUTED, "no materialising run has been made (clr_batch_enqueue(h, 1))");
-  if (h->J_general > 0 || h->J > clr::wide_max_width()) return fail(CLR_UNSUPPORTED, "clr_batch_solve covers celerite-only plans of widths 1..64");
+  if ((st = require_celerite_width(h, "clr_batch_solve")) != CLR_OK) return st;
   if (!clr::wsweep_scan_supported(h->N, h->J)) return fail(CLR_UNSUPPORTED, "clr_batch_solve on a wide plan needs N >= 512 (shorter series: CholeskySolver.solve)");
-  const size_t B = (size_t)h->B, N = (size_t)h->N, J = (size_t)h->J, R = (size_t)nrhs;
-  clr::SweepParams P;
-  memset(&P, 0, sizeof(P));
-  P.N = h->N; P.J = h->J; P.nrhs = nrhs;
-  int nchunk = std::min(clr::wsweep_chunks(h->N, h->J), std::max(2, (int)(2048 / B)));
-  if (nchunk > (h->N - 1) / 64) nchunk = std::max(1, (h->N - 1) / 64);
-  P.L = (h->N - 1 + nchunk - 1) / nchunk;
-  P.nchunk = (h->N - 1 + P.L - 1) / P.L;
+  const size_t B = (size_t)h->B, N = (size_t)h->N, R = (size_t)nrhs;
+  int want = std::min(clr::wsweep_chunks(h->N, h->J), std::max(2, (int)(2048 / B)));
+  if (want > (h->N - 1) / 64) want = std::max(1, (h->N - 1) / 64);
+  clr::SweepParams P = wide_sweep_params(h, nrhs, want);
   const size_t ws = clr::wsweep_workspace_doubles(h->J, P.nchunk, nrhs);
   if ((st = h->bs_M.reserve(B * ws)) != CLR_OK) return st;
   if ((st = h->bs_x.reserve(B * R * N)) != CLR_OK) return st;   // the forward sweep's output (undivided)
   if ((st = h->bs_rm.reserve(B * R * N)) != CLR_OK) return st;  // right-hand sides in, results out
-  const double* src = h->y.p;
-  long src_stride = h->y_stride;
-  if (b) {
-    HIP_TRY(hipMemcpyAsync(h->bs_rm.p, b, B * R * N * sizeof(double), hipMemcpyHostToDevice, h->stream.get()));
-    src = h->bs_rm.p;
-    src_stride = (long)(R * N);
-  }
-  for (clr::Event& e : h->bs_ev)
-    if (!e) HIP_TRY(clr::create_event(e));
-  HIP_TRY(hipEventRecord(h->bs_ev[0].get(), h->stream.get()));
-  P.phi = h->phi.p; P.u = h->u.p; P.W = h->W.p; P.D = h->D.p;
-  P.batch = h->B;
-  P.stride_phi = (long)(J * (N - 1)); P.stride_W = (long)(J * N); P.stride_D = (long)N;
+  ConsumerFrame frame{h};
+  if (b) HIP_TRY(hipMemcpyAsync(h->bs_rm.p, b, B * R * N * sizeof(double), hipMemcpyHostToDevice, h->stream.get()));
+  HIP_TRY(frame.start());
   P.stride_ws = (long)ws;
-  P.in = src; P.stride_in = src_stride;
-  P.out = h->bs_x.p; P.stride_out = (long)(R * N);
+  P.in = b ? h->bs_rm.p : h->y.p; P.stride_in = b ? (long)(R * N) : h->y_stride;
+  P.out = h->bs_x.p;
   P.backward = 0;
   clr::launch_wsweep_scan(P, h->bs_M.p, h->stream.get());
   P.in = h->bs_x.p; P.stride_in = (long)(R * N);
-  P.out = h->bs_rm.p; P.stride_out = (long)(R * N);
+  P.out = h->bs_rm.p;
   P.backward = 1;
   clr::launch_wsweep_scan(P, h->bs_M.p, h->stream.get());
-  HIP_TRY(hipEventRecord(h->bs_ev[1].get(), h->stream.get()));
-  HIP_TRY(hipGetLastError());
-  if (x) HIP_TRY(hipMemcpyAsync(x, h->bs_rm.p, B * R * N * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));  // (null: the result stays in bs_rm)
-  HIP_TRY(hipStreamSynchronize(h->stream.get()));
-  float ms = 0.f;
-  HIP_TRY(hipEventElapsedTime(&ms, h->bs_ev[0].get(), h->bs_ev[1].get()));
-  h->solve_device_ms = ms;
-  return CLR_OK;
+  HIP_TRY(frame.stop());
+  return frame.finish(x, h->bs_rm.p, B * R * N);  // (x null: the result stays in bs_rm)
 }
 
 // x == null: the result stays on the device, row-major [B][nrhs][N] in bs_rm (clr_batch_predict)
@@ -1514,36 +1591,20 @@ static int batch_solve_impl(clr_batch* h, int nrhs, const double* b, double* x) 
   if (st != CLR_OK) return st;
   if (nrhs < 1) return fail(CLR_INVALID_ARGUMENT, "clr_batch_solve: nrhs >= 1");
   if (!b && nrhs != 1) return fail(CLR_INVALID_ARGUMENT, "clr_batch_solve: b == NULL means the plan's own y (one right-hand side)");
+  if ((st = require_factor(h, true)) != CLR_OK) return st;
   if (!h->launch) return wide_batch_solve(h, nrhs, b, x);
-  if ((st = warm_resolve(h, nullptr)) != CLR_OK) return st;
-  if (!h->have_factor || !h->factor_valid) return fail(CLR_NOT_COMPUTED, "no materialising run has been made (clr_batch_enqueue(h, 1))");
-  if (h->factor_is_lean && h->factor_inputs_changed)
-    return fail(CLR_NOT_COMPUTED, "the lean factor's phi and u are regenerated from the plan's series and coefficients, "
-                                  "which were replaced after the materialising run: materialise again");
   if (h->nchunk < 2) return fail(CLR_UNSUPPORTED, "clr_batch_solve needs a chunked plan (N >= 128)");
   clr::BatchParams P;
-  if ((st = batch_params(h, 0, P)) != CLR_OK) return st;
-  if (P.staged) {  // the row-major times addressed directly (lean: one time per step and lane)
-    P.t = h->t.p; P.t_stride = h->t_stride; P.lane_is = 1; P.lane_cs = h->L; P.staged = 0;
-  }
+  if ((st = consumer_params(h, false, P)) != CLR_OK) return st;
   const size_t B = (size_t)h->B, N = (size_t)h->N, J = (size_t)h->J, R = (size_t)nrhs, cells = (size_t)h->L * h->nchunk;
   if ((st = h->bs_x.reserve(B * R * cells)) != CLR_OK) return st;
   if ((st = h->bs_rm.reserve(B * R * N)) != CLR_OK) return st;
   if ((st = h->bs_M.reserve(B * h->nchunk * J * J)) != CLR_OK) return st;
   if ((st = h->bs_off.reserve(B * R * h->nchunk * J)) != CLR_OK) return st;
   if ((st = h->bs_starts.reserve(B * R * h->nchunk * J)) != CLR_OK) return st;
-  const double* src = h->y.p;
-  long src_stride = h->y_stride;
-  if (b) {
-    HIP_TRY(hipMemcpyAsync(h->bs_rm.p, b, B * R * N * sizeof(double), hipMemcpyHostToDevice, h->stream.get()));
-    src = h->bs_rm.p;
-    src_stride = (long)N;
-  }
-  for (clr::Event& e : h->bs_ev)
-    if (!e) HIP_TRY(clr::create_event(e));
-  hipEvent_t e0 = h->bs_ev[0].get(), e1 = h->bs_ev[1].get();
-  HIP_TRY(hipEventRecord(e0, h->stream.get()));
-  clr::launch_relayout(src, src_stride, h->bs_x.p, (long)cells, (int)(B * R), h->N, h->L, h->nchunk, 0, h->stream.get());
+  ConsumerFrame frame{h};
+  if (b) HIP_TRY(hipMemcpyAsync(h->bs_rm.p, b, B * R * N * sizeof(double), hipMemcpyHostToDevice, h->stream.get()));
+  HIP_TRY(frame.start());
   clr::BSolveParams S;
   S.nrhs = nrhs; S.r = 0; S.lean = h->factor_is_lean ? 1 : 0;
   // (the chunk maps depend on the factor only: formed by the first solve after a materialising run; they count as
@@ -1552,16 +1613,11 @@ static int batch_solve_impl(clr_batch* h, int nrhs, const double* b, double* x) 
   S.have_M = h->bs_M_valid ? 1 : 0;
   h->bs_M_valid = false;
   S.xT = h->bs_x.p; S.M = h->bs_M.p; S.off = h->bs_off.p; S.starts = h->bs_starts.p;
-  h->launch->bsolve(P, S, h->stream.get());
-  clr::launch_relayout_back(h->bs_x.p, (long)cells, h->bs_rm.p, (long)N, (int)(B * R), h->N, h->L, h->nchunk, h->stream.get());
-  HIP_TRY(hipEventRecord(e1, h->stream.get()));
-  HIP_TRY(hipGetLastError());
-  if (x) HIP_TRY(hipMemcpyAsync(x, h->bs_rm.p, B * R * N * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
-  HIP_TRY(hipStreamSynchronize(h->stream.get()));
+  narrow_kernels(h, nrhs, b ? h->bs_rm.p : h->y.p, b ? (long)N : h->y_stride, h->bs_x.p, h->bs_x.p,
+                 [&] { h->launch->bsolve(P, S, h->stream.get()); });
+  HIP_TRY(frame.stop());
+  if ((st = frame.finish(x, h->bs_rm.p, B * R * N)) != CLR_OK) return st;
   h->bs_M_valid = true;
-  float ms = 0.f;
-  HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-  h->solve_device_ms = ms;
   return CLR_OK;
 }
 
@@ -1579,74 +1635,46 @@ int clr_batch_dot_L(clr_batch* h, int nrhs, const double* z, double* y) {
   int st = require_device(h->device);
   if (st != CLR_OK) return st;
   if (nrhs < 1 || nrhs > 65535 || !z || !y) return fail(CLR_INVALID_ARGUMENT, "clr_batch_dot_L: 1 <= nrhs <= 65535 (grid.z), z and an output array");
-  if ((st = warm_resolve(h, nullptr)) != CLR_OK) return st;
-  if (!h->have_factor || !h->factor_valid) return fail(CLR_NOT_COMPUTED, "no materialising run has been made (clr_batch_enqueue(h, 1))");
-  if (h->J_general > 0 || h->J > clr::wide_max_width()) return fail(CLR_UNSUPPORTED, "clr_batch_dot_L covers celerite-only plans of widths 1..64");
+  if ((st = require_factor(h, true)) != CLR_OK) return st;
+  if ((st = require_celerite_width(h, "clr_batch_dot_L")) != CLR_OK) return st;
   const size_t B = (size_t)h->B, N = (size_t)h->N, J = (size_t)h->J, R = (size_t)nrhs;
   if ((st = h->bs_rm.reserve(B * R * N)) != CLR_OK) return st;
-  for (clr::Event& e : h->bs_ev)
-    if (!e) HIP_TRY(clr::create_event(e));
+  ConsumerFrame frame{h};
   HIP_TRY(hipMemcpyAsync(h->bs_rm.p, z, B * R * N * sizeof(double), hipMemcpyHostToDevice, h->stream.get()));
-  const double* result = nullptr;
   if (!h->launch) {  // wide plans
     if ((st = h->bs_x.reserve(B * R * N)) != CLR_OK) return st;
-    HIP_TRY(hipEventRecord(h->bs_ev[0].get(), h->stream.get()));
+    HIP_TRY(frame.start());
     if (clr::wdotl_scan_supported(h->N, h->J)) {
-      clr::SweepParams P;
-      memset(&P, 0, sizeof(P));
-      P.N = h->N; P.J = h->J; P.nrhs = nrhs;
       // chunks per problem: about two rounds of the chip's SIMDs over the batch (not a function of nrhs: a right-hand
       // side's result does not depend on how many others ride along)
-      int nchunk = std::min(clr::wdotl_chunks(h->N), std::max(2, (int)(2048 / B)));
-      P.L = (h->N - 1 + nchunk - 1) / nchunk;
-      P.nchunk = (h->N - 1 + P.L - 1) / P.L;
+      clr::SweepParams P = wide_sweep_params(h, nrhs, std::min(clr::wdotl_chunks(h->N), std::max(2, (int)(2048 / B))));
       const size_t ws = R * (size_t)P.nchunk * 3 * J;
       if ((st = h->bs_off.reserve(B * ws)) != CLR_OK) return st;
-      P.phi = h->phi.p; P.u = h->u.p; P.W = h->W.p; P.D = h->D.p;
-      P.batch = h->B;
-      P.stride_phi = (long)(J * (N - 1)); P.stride_W = (long)(J * N); P.stride_D = (long)N;
       P.stride_ws = (long)ws;
-      P.in = h->bs_rm.p; P.stride_in = (long)(R * N);
-      P.out = h->bs_x.p; P.stride_out = (long)(R * N);
+      P.in = h->bs_rm.p; P.out = h->bs_x.p;
       clr::launch_wdotl_scan(P, h->bs_off.p, h->stream.get());
     } else {
       for (size_t p = 0; p < B; ++p)
         clr::launch_dot_L(h->N, h->J, nrhs, h->phi.p + p * J * (N - 1), h->u.p + p * J * (N - 1), h->W.p + p * J * N,
                           h->D.p + p * N, h->bs_rm.p + p * R * N, h->bs_x.p + p * R * N, h->stream.get());
     }
-    HIP_TRY(hipEventRecord(h->bs_ev[1].get(), h->stream.get()));
-    result = h->bs_x.p;
+    HIP_TRY(frame.stop());
   } else {
-    if (h->factor_is_lean && h->factor_inputs_changed)
-      return fail(CLR_NOT_COMPUTED, "the lean factor's phi and u are regenerated from the plan's series and coefficients, "
-                                    "which were replaced after the materialising run: materialise again");
     clr::BatchParams P;
-    if ((st = batch_params(h, 0, P)) != CLR_OK) return st;
-    if (P.staged) {  // the row-major times addressed directly (lean: one time per step and lane)
-      P.t = h->t.p; P.t_stride = h->t_stride; P.lane_is = 1; P.lane_cs = h->L; P.staged = 0;
-    }
+    if ((st = consumer_params(h, false, P)) != CLR_OK) return st;
     const size_t cells = (size_t)h->L * h->nchunk;
     if ((st = h->bs_x.reserve(B * R * cells)) != CLR_OK) return st;
     if ((st = h->bs_decay.reserve(B * h->nchunk * J)) != CLR_OK) return st;
     if ((st = h->bs_off.reserve(B * R * h->nchunk * J)) != CLR_OK) return st;
     if ((st = h->bs_starts.reserve(B * R * h->nchunk * J)) != CLR_OK) return st;
-    HIP_TRY(hipEventRecord(h->bs_ev[0].get(), h->stream.get()));
-    clr::launch_relayout(h->bs_rm.p, (long)N, h->bs_x.p, (long)cells, (int)(B * R), h->N, h->L, h->nchunk, 0, h->stream.get());
+    HIP_TRY(frame.start());
     clr::BDotLParams S;
     S.nrhs = nrhs; S.lean = h->factor_is_lean ? 1 : 0;
     S.xT = h->bs_x.p; S.decay = h->bs_decay.p; S.off = h->bs_off.p; S.starts = h->bs_starts.p;
-    h->launch->bdotl(P, S, h->stream.get());
-    clr::launch_relayout_back(h->bs_x.p, (long)cells, h->bs_rm.p, (long)N, (int)(B * R), h->N, h->L, h->nchunk, h->stream.get());
-    HIP_TRY(hipEventRecord(h->bs_ev[1].get(), h->stream.get()));
-    result = h->bs_rm.p;
+    narrow_kernels(h, nrhs, h->bs_rm.p, (long)N, h->bs_x.p, h->bs_x.p, [&] { h->launch->bdotl(P, S, h->stream.get()); });
+    HIP_TRY(frame.stop());
   }
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(y, result, B * R * N * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
-  HIP_TRY(hipStreamSynchronize(h->stream.get()));
-  float ms = 0.f;
-  HIP_TRY(hipEventElapsedTime(&ms, h->bs_ev[0].get(), h->bs_ev[1].get()));
-  h->solve_device_ms = ms;
-  return CLR_OK;
+  return frame.finish(y, h->launch ? h->bs_rm.p : h->bs_x.p, B * R * N);  // (bs_x as reserved above)
 }
 
 // the constant diagonal of one problem's K for dot: sum a_real + sum a_comp + jitter (cholesky.h:483-485), N copies
@@ -1670,40 +1698,29 @@ int clr_batch_dot(clr_batch* h, int nrhs, const double* z, double* y) {
   if (st != CLR_OK) return st;
   if (nrhs < 1 || nrhs > 65535 || !z || !y) return fail(CLR_INVALID_ARGUMENT, "clr_batch_dot: 1 <= nrhs <= 65535 (grid.z), z and an output array");
   if ((st = warm_resolve(h, nullptr)) != CLR_OK) return st;
-  if (h->J_general > 0 || h->J > clr::wide_max_width()) return fail(CLR_UNSUPPORTED, "clr_batch_dot covers celerite-only plans of widths 1..64");
-  clr::BatchParams P;
-  if ((st = batch_params(h, 0, P)) != CLR_OK) return st;
+  if ((st = require_celerite_width(h, "clr_batch_dot")) != CLR_OK) return st;
+  clr::BatchParams P;  // (wide plans read its coefficients only)
+  if ((st = consumer_params(h, true, P)) != CLR_OK) return st;
   const size_t B = (size_t)h->B, N = (size_t)h->N, J = (size_t)h->J, R = (size_t)nrhs;
   if ((st = h->bs_rm.reserve(B * R * N)) != CLR_OK) return st;
-  for (clr::Event& e : h->bs_ev)
-    if (!e) HIP_TRY(clr::create_event(e));
+  DevBuf feat, dgb, ws;  // (wide plans: one problem's features, its constant diagonal and the scan's workspace)
+  ConsumerFrame frame{h};
   HIP_TRY(hipMemcpyAsync(h->bs_rm.p, z, B * R * N * sizeof(double), hipMemcpyHostToDevice, h->stream.get()));
-  const double* result = nullptr;
   if (!h->launch) {  // wide plans: problem by problem
-    // (every return from here on waits for the stream first: its kernels read the local buffers)
-    DevBuf feat, dgb, ws;
-    if ((st = feat.reserve(3 * J * N)) != CLR_OK) return synced(h->stream.get(), st);
-    if ((st = dgb.reserve(N)) != CLR_OK) return synced(h->stream.get(), st);  // the problem's constant diagonal, refilled per problem (same stream)
-    if ((st = h->bs_x.reserve(B * R * N)) != CLR_OK) return synced(h->stream.get(), st);
+    if ((st = feat.reserve(3 * J * N)) != CLR_OK) return st;
+    if ((st = dgb.reserve(N)) != CLR_OK) return st;  // (refilled per problem, same stream)
+    if ((st = h->bs_x.reserve(B * R * N)) != CLR_OK) return st;
     const bool scan = clr::wdotl_scan_supported(h->N, h->J);
     clr::SweepParams SP;
     memset(&SP, 0, sizeof(SP));
     if (scan) {
       SP.N = h->N; SP.J = h->J; SP.nrhs = nrhs;
-      SP.nchunk = clr::wdotl_chunks(h->N);
-      SP.L = (h->N - 1 + SP.nchunk - 1) / SP.nchunk;
-      SP.nchunk = (h->N - 1 + SP.L - 1) / SP.L;
-      if ((st = ws.reserve(R * (size_t)SP.nchunk * 3 * J)) != CLR_OK) return synced(h->stream.get(), st);
+      clr::chunking(h->N - 1, clr::wdotl_chunks(h->N), &SP.L, &SP.nchunk);
+      if ((st = ws.reserve(R * (size_t)SP.nchunk * 3 * J)) != CLR_OK) return st;
     }
-    (void)hipEventRecord(h->bs_ev[0].get(), h->stream.get());
+    HIP_TRY(frame.start());
     for (size_t p = 0; p < B; ++p) {
-      clr::GenericProblem g;
-      g.N = h->N; g.J = h->J; g.J_real = h->J_real; g.J_comp = h->J_comp; g.J_general = 0;
-      g.a_real = P.a_real + p * h->J_real; g.c_real = P.c_real + p * h->J_real;
-      g.a_comp = P.a_comp + p * h->J_comp; g.b_comp = P.b_comp + p * h->J_comp;
-      g.c_comp = P.c_comp + p * h->J_comp; g.d_comp = P.d_comp + p * h->J_comp;
-      g.U = nullptr; g.V = nullptr;
-      g.t = h->t.p + p * (size_t)h->t_stride;
+      const clr::GenericProblem g = problem_view(h, P, p);
       double *phi = feat.p, *u = feat.p + J * N, *v = feat.p + 2 * J * N;
       clr::launch_dot_setup(g, phi, u, v, h->stream.get());
       hipLaunchKernelGGL(dot_diagonal_kernel, dim3((unsigned)std::min<size_t>((N + 255) / 256, 1024)), dim3(256), 0, h->stream.get(),
@@ -1716,37 +1733,21 @@ int clr_batch_dot(clr_batch* h, int nrhs, const double* z, double* y) {
         clr::launch_dot(h->N, h->J, nrhs, phi, u, v, dgb.p, h->bs_rm.p + p * R * N, h->bs_x.p + p * R * N, h->stream.get());
       }
     }
-    (void)hipEventRecord(h->bs_ev[1].get(), h->stream.get());
-    if (hipGetLastError() != hipSuccess ||
-        hipMemcpyAsync(y, h->bs_x.p, B * R * N * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()) != hipSuccess)
-      return synced(h->stream.get(), fail(CLR_HIP_ERROR, "clr_batch_dot: kernels or the download failed"));
-    (void)hipStreamSynchronize(h->stream.get());
+    HIP_TRY(frame.stop());
   } else {
-    // the row-major times addressed directly (the chunk-interleaved copy of the role-split summarize is only made by an
-    // evaluation: clr_batch_dot must not depend on one having run)
-    P.t = h->t.p; P.t_stride = h->t_stride; P.lane_is = 1; P.lane_cs = h->L; P.staged = 0;
     const size_t cells = (size_t)h->L * h->nchunk;
     if ((st = h->bs_x.reserve(B * R * cells)) != CLR_OK) return st;
     if ((st = h->bs_y.reserve(B * R * cells)) != CLR_OK) return st;
     if ((st = h->bs_decay.reserve(B * h->nchunk * J)) != CLR_OK) return st;
     if ((st = h->bs_off.reserve(B * R * h->nchunk * J)) != CLR_OK) return st;
     if ((st = h->bs_starts.reserve(B * R * h->nchunk * J)) != CLR_OK) return st;
-    HIP_TRY(hipEventRecord(h->bs_ev[0].get(), h->stream.get()));
-    clr::launch_relayout(h->bs_rm.p, (long)N, h->bs_x.p, (long)cells, (int)(B * R), h->N, h->L, h->nchunk, 0, h->stream.get());
+    HIP_TRY(frame.start());
     clr::BDotParams S;
     S.nrhs = nrhs; S.zT = h->bs_x.p; S.yT = h->bs_y.p; S.decay = h->bs_decay.p; S.off = h->bs_off.p; S.starts = h->bs_starts.p;
-    h->launch->bdot(P, S, h->stream.get());
-    clr::launch_relayout_back(h->bs_y.p, (long)cells, h->bs_rm.p, (long)N, (int)(B * R), h->N, h->L, h->nchunk, h->stream.get());
-    HIP_TRY(hipEventRecord(h->bs_ev[1].get(), h->stream.get()));
-    result = h->bs_rm.p;
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(y, result, B * R * N * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
-    HIP_TRY(hipStreamSynchronize(h->stream.get()));
+    narrow_kernels(h, nrhs, h->bs_rm.p, (long)N, h->bs_x.p, h->bs_y.p, [&] { h->launch->bdot(P, S, h->stream.get()); });
+    HIP_TRY(frame.stop());
   }
-  float ms = 0.f;
-  HIP_TRY(hipEventElapsedTime(&ms, h->bs_ev[0].get(), h->bs_ev[1].get()));
-  h->solve_device_ms = ms;
-  return CLR_OK;
+  return frame.finish(y, h->launch ? h->bs_rm.p : h->bs_x.p, B * R * N);  // (bs_x as reserved above)
 }
 
 // CholeskySolver::predict (cholesky.h:599-698; GP.predict's conditional mean, celerite.py:330-420) for every problem of
@@ -1760,7 +1761,7 @@ int clr_batch_predict(clr_batch* h, int M, const double* xs, long xs_stride, dou
   if (st != CLR_OK) return st;
   if (M < 0 || (M > 0 && (!xs || !pred))) return fail(CLR_INVALID_ARGUMENT, "clr_batch_predict: M >= 0, the points and an output array");
   if (xs_stride != 0 && xs_stride != M) return fail(CLR_INVALID_ARGUMENT, "clr_batch_predict: the points' stride is 0 (shared by all problems) or M");
-  if (h->J_general > 0 || h->J > clr::wide_max_width()) return fail(CLR_UNSUPPORTED, "clr_batch_predict covers celerite-only plans of widths 1..64");
+  if ((st = require_celerite_width(h, "clr_batch_predict")) != CLR_OK) return st;
   if (M == 0) return CLR_OK;
   if ((st = batch_solve_impl(h, 1, nullptr, nullptr)) != CLR_OK) return st;  // alpha = K^-1 y -> bs_rm [B][N]
   clr::BatchParams P;
@@ -1772,11 +1773,10 @@ int clr_batch_predict(clr_batch* h, int M, const double* xs, long xs_stride, dou
   const bool scan_ok = clr::predict_scan_supported(h->N, h->J_real, h->J_comp);
   int pchunk = 0, pL = 0;
   if (scan_ok) {
-    pchunk = std::max(1, std::min(h->N / 16, 8192));
-    pL = (h->N + pchunk - 1) / pchunk;
-    pchunk = (h->N + pL - 1) / pL;
+    clr::chunking(h->N, std::max(1, std::min(h->N / 16, 8192)), &pL, &pchunk);
     if ((st = ws.reserve(clr::predict_workspace_doubles(pchunk, h->J))) != CLR_OK) return st;
   }
+  ConsumerFrame frame{h};  // (untimed: solve_device_ms is the solve's)
   if (hipMemcpyAsync(dxs.p, xs, nsrc * Mm * sizeof(double), hipMemcpyHostToDevice, h->stream.get()) != hipSuccess ||
       hipMemsetAsync(dpred.p, 0, B * Mm * sizeof(double), h->stream.get()) != hipSuccess)
     return fail(CLR_HIP_ERROR, "clr_batch_predict: upload failed");
@@ -1784,21 +1784,13 @@ int clr_batch_predict(clr_batch* h, int M, const double* xs, long xs_stride, dou
   for (size_t p = 0; p < nsrc; ++p)
     for (size_t m = 1; m < Mm && sorted[p]; ++m) sorted[p] = xs[p * Mm + m - 1] <= xs[p * Mm + m];
   for (size_t p = 0; p < B; ++p) {
-    clr::GenericProblem g;
-    g.N = h->N; g.J = h->J; g.J_real = h->J_real; g.J_comp = h->J_comp; g.J_general = 0;
-    g.a_real = P.a_real + p * h->J_real; g.c_real = P.c_real + p * h->J_real;
-    g.a_comp = P.a_comp + p * h->J_comp; g.b_comp = P.b_comp + p * h->J_comp;
-    g.c_comp = P.c_comp + p * h->J_comp; g.d_comp = P.d_comp + p * h->J_comp;
-    g.U = nullptr; g.V = nullptr;
-    g.t = h->t.p + p * (size_t)h->t_stride;
+    const clr::GenericProblem g = problem_view(h, P, p);
     const double* alpha = h->bs_rm.p + p * (size_t)h->N;
     const double* xp = dxs.p + (xs_stride == 0 ? 0 : p * Mm);
     if (scan_ok && sorted[xs_stride == 0 ? 0 : p]) clr::launch_predict_scan(g, alpha, M, xp, dpred.p + p * Mm, ws.p, pchunk, pL, h->stream.get());
     else clr::launch_predict(g, alpha, M, xp, dpred.p + p * Mm, h->stream.get());
   }
-  if (hipGetLastError() != hipSuccess ||
-      hipMemcpyAsync(pred, dpred.p, B * Mm * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()) != hipSuccess ||
-      hipStreamSynchronize(h->stream.get()) != hipSuccess)
+  if (frame.finish(pred, dpred.p, B * Mm) != CLR_OK)
     return fail(CLR_HIP_ERROR, "clr_batch_predict: kernels or the download failed");
   return CLR_OK;
 }
@@ -1843,7 +1835,7 @@ int clr_batch_run_timed(clr_batch* h, int materialize, int steps, int relayout_e
     HIP_TRY(hipEventRecord(e[0].get(), h->stream.get()));
     if (!h->launch) {  // wide path (one chunk: the whole sweep is reported in the "replay" slot)
       if ((st = wide_launch(h, P, e)) != CLR_OK) return st;
-      if (materialize) { h->factor_is_lean = false; h->factor_inputs_changed = false; h->factor_valid = true; h->bs_M_valid = false; }
+      if (materialize) factor_written(h, false);
       // (a plan that re-planned level-1 problems at its last evaluation does so inside every timed step: the step's
       //  time then includes the side plan -- at the price of a host round trip per step)
       if (P.defer_level1 && h->rescue_last != 0) { h->rescue_inflight = true; if ((st = warm_resolve(h, nullptr)) != CLR_OK) return st; HIP_TRY(hipEventRecord(e[6].get(), h->stream.get())); }
@@ -1886,7 +1878,7 @@ int clr_batch_run_timed(clr_batch* h, int materialize, int steps, int relayout_e
     h->launch->replay(P, replay_mode(h, materialize), h->stream.get());
     if (P.ends) refine_chunk_heads(h, P, materialize, h->stream.get());
     h->launch->sequential(P, replay_mode(h, materialize), h->stream.get());
-    if (materialize) { h->factor_is_lean = h->factor_layout == 1; h->factor_inputs_changed = false; h->factor_valid = true; h->bs_M_valid = false; }
+    if (materialize) factor_written(h, h->factor_layout == 1);
     HIP_TRY(hipEventRecord(e[5].get(), h->stream.get()));
     clr::launch_finalize(P, h->stream.get());
     if (P.defer_level1 && h->rescue_last != 0) { h->rescue_inflight = true; if ((st = warm_resolve(h, nullptr)) != CLR_OK) return st; }

@@ -336,8 +336,7 @@ int clr_solver_compute(clr_solver* s, double jitter, int n_a_real, const double*
         if (nk >= 8) nchunk = nk;
       }
     }
-    P.L = (N + nchunk - 1) / nchunk;
-    P.nchunk = (N + P.L - 1) / P.L;
+    clr::chunking(N, nchunk, &P.L, &P.nchunk);
     const size_t pc = (size_t)P.nchunk, JP = (size_t)clr::wide_padded_width(J), SZP = JP * (JP + 1) / 2;
     if ((st = s->ws_elems.reserve(pc * (JP * JP + JP + SZP + JP + SZP))) != CLR_OK) return st;
     if ((st = s->ws_starts.reserve(pc * (SZP + JP))) != CLR_OK) return st;
@@ -622,8 +621,8 @@ static bool sweep_scan_ok(const clr_solver* s) {
 }
 // widths above 64: the affine scans of bigsweep_kernels.hip (`in` and `out` must be different arrays)
 static int big_sweep_scan(clr_solver* s, int nrhs, const double* in, double* out, double* quad, int backward) {
-  const int nc0 = clr::bigsweep_chunks(s->N, s->J);
-  const int L = (s->N - 1 + nc0 - 1) / nc0, nchunk = (s->N - 1 + L - 1) / L;
+  int L, nchunk;
+  clr::chunking(s->N - 1, clr::bigsweep_chunks(s->N, s->J), &L, &nchunk);
   int st;
   if (!s->big_maps_valid[backward]) {
     if ((st = s->big_maps[backward].reserve(clr::bigsweep_maps_doubles(s->J, nchunk))) != CLR_OK) return st;
@@ -655,9 +654,7 @@ static int sweep_scan(clr_solver* s, int nrhs, const double* in, double* out, do
     clr::SweepParams P;
     memset(&P, 0, sizeof(P));
     P.N = s->N; P.J = s->J; P.nrhs = nr;
-    P.nchunk = wide ? clr::wsweep_chunks(s->N, s->J) : clr::sweep_chunks(s->N);
-    P.L = (s->N - 1 + P.nchunk - 1) / P.nchunk;
-    P.nchunk = (s->N - 1 + P.L - 1) / P.L;
+    clr::chunking(s->N - 1, wide ? clr::wsweep_chunks(s->N, s->J) : clr::sweep_chunks(s->N), &P.L, &P.nchunk);
     P.phi = s->phi.p; P.u = s->u.p; P.W = s->W.p; P.D = s->D.p;
     P.in = in + (size_t)r0 * s->N;
     P.out = out ? out + (size_t)r0 * s->N : nullptr;
@@ -791,9 +788,7 @@ int clr_solver_dot_L(const clr_solver* cs, int z_rows, int nrhs, const double* z
       clr::SweepParams P;
       memset(&P, 0, sizeof(P));
       P.N = s->N; P.J = s->J; P.nrhs = nr;
-      P.nchunk = wide ? clr::wdotl_chunks(s->N) : clr::sweep_chunks(s->N);
-      P.L = (s->N - 1 + P.nchunk - 1) / P.nchunk;
-      P.nchunk = (s->N - 1 + P.L - 1) / P.L;
+      clr::chunking(s->N - 1, wide ? clr::wdotl_chunks(s->N) : clr::sweep_chunks(s->N), &P.L, &P.nchunk);
       P.phi = s->phi.p; P.u = s->u.p; P.W = s->W.p; P.D = s->D.p;
       P.in = s->scratch.p + (size_t)r0 * s->N; P.out = s->scratch2.p + (size_t)r0 * s->N;
       if ((st = s->ws_elems.reserve((size_t)nr * P.nchunk * 3 * s->J)) != CLR_OK) return st;
@@ -894,9 +889,7 @@ int clr_solver_dot(clr_solver* s, double jitter, int n_a_real, const double* a_r
       clr::SweepParams SP;
       memset(&SP, 0, sizeof(SP));
       SP.N = N; SP.J = J; SP.nrhs = nr;
-      SP.nchunk = clr::wdotl_chunks(N);
-      SP.L = (N - 1 + SP.nchunk - 1) / SP.nchunk;
-      SP.nchunk = (N - 1 + SP.L - 1) / SP.L;
+      clr::chunking(N - 1, clr::wdotl_chunks(N), &SP.L, &SP.nchunk);
       SP.phi = phi.p; SP.u = u.p;
       SP.in = zin.p + (size_t)r0 * N; SP.out = yout.p + (size_t)r0 * N;
       DOT_TRY(ws.reserve((size_t)nr * SP.nchunk * 3 * J));
@@ -954,9 +947,7 @@ int clr_solver_predict(const clr_solver* cs, int n_y, const double* y, int M, co
     // chunks of 16 samples (at most 8192): the prefix over the chunks is a parallel scan (predict_prefix_kernel), the
     // prediction points and the chunk summaries walk <= one chunk each (profiles/r04z_predict_chunks.txt: N = 1e5, M = 2e4,
     // width 8 2.1 -> 0.84 ms, width 32 4.9 -> 1.5 ms; rounds 2-3: 1.8 sqrt(N) chunks, their prefix one thread's walk)
-    pchunk = std::max(1, std::min(s->N / 16, 8192));
-    pL = (s->N + pchunk - 1) / pchunk;
-    pchunk = (s->N + pL - 1) / pL;
+    clr::chunking(s->N, std::max(1, std::min(s->N / 16, 8192)), &pL, &pchunk);
     if ((st = s->ws_elems.reserve(clr::predict_workspace_doubles(pchunk, s->J_real + 2 * s->J_comp))) != CLR_OK) return st;
   }
   DevBuf &dxs = s->pred_buf[0], &dpred = s->pred_buf[1];  // (kept between calls)

@@ -59,6 +59,12 @@ struct SweepParams {
   long stride_in, stride_out;           // ... right-hand sides and results (nrhs * N each)
   long stride_ws;                       // ... workspaces (wsweep_workspace_doubles)
 };
+// `span` steps in about `want` chunks: L = ceil(span / want) steps per chunk, then nchunk = ceil(span / L) (no empty
+// trailing chunk)
+inline void chunking(int span, int want, int* L, int* nchunk) {
+  *L = (span + want - 1) / want;
+  *nchunk = (span + *L - 1) / *L;
+}
 bool sweep_scan_supported(int N, int J);
 int sweep_chunks(int N);
 size_t sweep_workspace_doubles(int J, int nchunk, int nrhs);

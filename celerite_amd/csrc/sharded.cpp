@@ -158,6 +158,15 @@ int resolve_all(clr_sharded* h) {
   return resolve_finish_all(h, pend, elig, nullptr);
 }
 
+// the batched consumers on every shard concurrently, each on its slice of the host arrays (`f(plan, lo)`, lo = the
+// shard's first problem): arguments that are not `valid` are refused before any shard runs
+int on_slices(clr_sharded* h, bool valid, const std::function<int(clr_batch*, long)>& f) {
+  if (!valid) return CLR_INVALID_ARGUMENT;
+  const int st = resolve_all(h);
+  if (st != CLR_OK) return st;
+  return h->all([=](int s) { return f(h->plan[s], h->lo[s]); });
+}
+
 }  // namespace
 
 extern "C" {
@@ -493,47 +502,30 @@ int clr_sharded_materialize(clr_sharded* h, double* loglike, double* logdet, dou
   return resolve_finish_all(h, pend, elig, results);
 }
 
-// clr_batch_solve / clr_batch_dot_L / clr_batch_predict on every shard concurrently, each on its slice of the host arrays
 int clr_sharded_solve(clr_sharded* h, int nrhs, const double* b, double* x) {
-  if (nrhs < 1 || !x) return CLR_INVALID_ARGUMENT;
-  const int st0 = resolve_all(h);
-  if (st0 != CLR_OK) return st0;
   const long per = (long)nrhs * h->N;
-  return h->all([=](int s) {
-    const long lo = h->lo[s];
-    return clr_batch_solve(h->plan[s], nrhs, b ? b + lo * per : nullptr, x + lo * per);
+  return on_slices(h, nrhs >= 1 && x, [=](clr_batch* p, long lo) {
+    return clr_batch_solve(p, nrhs, b ? b + lo * per : nullptr, x + lo * per);
   });
 }
 
 int clr_sharded_dot_L(clr_sharded* h, int nrhs, const double* z, double* y) {
-  if (nrhs < 1 || !z || !y) return CLR_INVALID_ARGUMENT;
-  const int st0 = resolve_all(h);
-  if (st0 != CLR_OK) return st0;
   const long per = (long)nrhs * h->N;
-  return h->all([=](int s) {
-    const long lo = h->lo[s];
-    return clr_batch_dot_L(h->plan[s], nrhs, z + lo * per, y + lo * per);
+  return on_slices(h, nrhs >= 1 && z && y, [=](clr_batch* p, long lo) {
+    return clr_batch_dot_L(p, nrhs, z + lo * per, y + lo * per);
   });
 }
 
 int clr_sharded_dot(clr_sharded* h, int nrhs, const double* z, double* y) {
-  if (nrhs < 1 || !z || !y) return CLR_INVALID_ARGUMENT;
-  const int st0 = resolve_all(h);
-  if (st0 != CLR_OK) return st0;
   const long per = (long)nrhs * h->N;
-  return h->all([=](int s) {
-    const long lo = h->lo[s];
-    return clr_batch_dot(h->plan[s], nrhs, z + lo * per, y + lo * per);
+  return on_slices(h, nrhs >= 1 && z && y, [=](clr_batch* p, long lo) {
+    return clr_batch_dot(p, nrhs, z + lo * per, y + lo * per);
   });
 }
 
 int clr_sharded_predict(clr_sharded* h, int M, const double* xs, long xs_stride, double* pred) {
-  if (M < 0 || (M > 0 && (!xs || !pred)) || (xs_stride != 0 && xs_stride != M)) return CLR_INVALID_ARGUMENT;
-  const int st0 = resolve_all(h);
-  if (st0 != CLR_OK) return st0;
-  return h->all([=](int s) {
-    const long lo = h->lo[s];
-    return clr_batch_predict(h->plan[s], M, xs + lo * xs_stride, xs_stride, pred + lo * (long)M);
+  return on_slices(h, M >= 0 && (M == 0 || (xs && pred)) && (xs_stride == 0 || xs_stride == M), [=](clr_batch* p, long lo) {
+    return clr_batch_predict(p, M, xs + lo * xs_stride, xs_stride, pred + lo * (long)M);
   });
 }
 

@@ -475,9 +475,12 @@ def test_batched_dot_on_plans(JR, JC, N, chunks, family):
 
 def test_batched_dot_L_argument_and_state_errors():
     """``clr_batch_dot_L`` before a materialising run is CLR_NOT_COMPUTED (the reference's ``compute_exception``,
-    cholesky.h:411), a wrong shape a dimension mismatch (:410), and a lean factor whose inputs were replaced is refused."""
+    cholesky.h:411), a wrong shape a dimension mismatch (:410), and a lean factor whose inputs were replaced is refused.
+    The other consumers share those refusals: solve, predict and ``factor(p)`` need a materialising run and refuse a
+    stale lean factor; dot needs no factor at all."""
     B, N, JR, JC = 3, 2000, 2, 3
     case = synthetic(B, N, JR, JC, "bench", seed=5)
+    xs = np.linspace(case["t"].min(), case["t"].max(), 7)
     plan = batch.BatchedGP(B, N, JR, JC)
     try:
         plan.set_factor_layout("lean")
@@ -485,13 +488,52 @@ def test_batched_dot_L_argument_and_state_errors():
         plan.set_coefficients(*coeffs_of(case))
         with pytest.raises(RuntimeError):
             plan.dot_L(np.zeros((B, N)))
+        for consumer in (plan.solve, lambda: plan.solve(np.zeros((B, N))), lambda: plan.predict(xs), lambda: plan.factor(0)):
+            with pytest.raises(RuntimeError):
+                consumer()
+        plan.dot(np.zeros((B, N)))
         plan.log_likelihood(materialize=True)
         with pytest.raises(ValueError):
             plan.dot_L(np.zeros((B, N + 1)))
+        for consumer in (plan.solve, plan.dot):
+            with pytest.raises(ValueError):
+                consumer(np.zeros((B, N + 1)))
+        with pytest.raises(ValueError):
+            plan.predict(np.zeros((B + 1, 7)))
         plan.dot_L(np.zeros((B, N)))
+        plan.solve()
+        plan.predict(xs)
+        plan.factor(0)
         plan.set_coefficients(*coeffs_of(case))
         with pytest.raises(RuntimeError):
             plan.dot_L(np.zeros((B, N)))
+        for consumer in (plan.solve, lambda: plan.predict(xs), lambda: plan.factor(0)):
+            with pytest.raises(RuntimeError):
+                consumer()
+        plan.dot(np.zeros((B, N)))
+    finally:
+        plan.close()
+
+
+def test_batched_consumers_state_errors_on_a_wide_plan():
+    """The wide route (width 12) refuses solve, dot_L, predict and ``factor(p)`` before a materialising run, and serves
+    dot without one."""
+    B, N, JR, JC = 3, 2000, 2, 5
+    case = synthetic(B, N, JR, JC, "bench", seed=5)
+    xs = np.linspace(case["t"].min(), case["t"].max(), 7)
+    plan = batch.BatchedGP(B, N, JR, JC)
+    try:
+        plan.set_series(case["t"], case["diag"], case["y"])
+        plan.set_coefficients(*coeffs_of(case))
+        for consumer in (plan.solve, lambda: plan.dot_L(np.zeros((B, N))), lambda: plan.predict(xs), lambda: plan.factor(0)):
+            with pytest.raises(RuntimeError):
+                consumer()
+        plan.dot(np.zeros((B, N)))
+        plan.log_likelihood(materialize=True)
+        plan.solve()
+        plan.dot_L(np.zeros((B, N)))
+        plan.predict(xs)
+        plan.factor(0)
     finally:
         plan.close()
 
