@@ -157,6 +157,7 @@ struct clr_solver {
   BatchPtr grad_plan;
   int grad_N = 0, grad_JR = -1, grad_JC = -1;
   bool grad_wide = false, grad_had_general = false;
+  int grad_route = -1;                  // the last grad_log_likelihood's route (clr_solver_debug_grad_route)
   std::vector<double> grad_series;
   int computed = 0, N = 0, J = 0;
   double log_det = 0.0;
@@ -364,12 +365,21 @@ double sel_max(double own, double floor) {  // (NaN on either side wins: the con
 }
 // the batch size the selection rules look at: the whole batch's when the plan is a slice of one (clr_batch::group_B)
 int sel_B(const clr_batch* h) { return h->group_B > 0 ? h->group_B : h->B; }
+// The lazy flavours advance every row's (cos, sin) pair by a rotation through d (t_n+1 - t_n) between anchors, where the
+// reference (cholesky.h:137) and every other kernel take sincos of fl(d t_n) at each sample.  The two phases differ by the
+// rounding of d t, up to |d t| 2^-53 rad: at max |d| max |t| ~ 1.6e9 the wide summaries then settle values 5e-10 and
+// gradient riders ~3e-4 away from the reference's recurrence (tests/test_gpu_grad_truth.py, library trig at t ~ 3e8).
+// Below 2^20 the difference stays under 1.2e-10 rad.
+constexpr double CLR_LAZY_PHASE_LIMIT = 1048576.0;
+bool lazy_phases_ok(const clr_batch* h) {
+  return sel_max(h->dmax, h->floor_dmax) * sel_max(h->tmax, h->floor_tmax) < CLR_LAZY_PHASE_LIMIT;
+}
 bool lazy_eligible(const clr_batch* h) {
   // |c dx| < 2^-7 at every step: Psi stays within [0.88, 1] over the 16 steps between renormalisations;
   // |d dx| < 2^-5: the per-step rotation of the (cos, sin) pairs uses a short Taylor series
   const double cmax = sel_max(h->cmax, h->floor_cmax), dmax = sel_max(h->dmax, h->floor_dmax),
                dxmax = sel_max(h->dxmax, h->floor_dxmax);
-  return h->have_series && h->have_coeffs && cmax * dxmax < 0.0078125 && dmax * dxmax < 0.03125;
+  return h->have_series && h->have_coeffs && cmax * dxmax < 0.0078125 && dmax * dxmax < 0.03125 && lazy_phases_ok(h);
 }
 
 // Wide plans (wave per (problem, chunk), widths 9..64): the lazy flavour of the summarize takes any series since round 5 --
@@ -381,7 +391,7 @@ bool lazy_eligible_wide(const clr_batch* h) {
   // against 7.0 on one where EVERY batch takes the slow path (profiles/r05m_wide_lazy_gaps.txt) -- so they keep the strict rule
   if (h->J + h->J_general <= 16) return lazy_eligible(h);
   const double cmax = sel_max(h->cmax, h->floor_cmax), dxmax = sel_max(h->dxmax, h->floor_dxmax);
-  return h->have_series && h->have_coeffs && cmax * dxmax < 2.0;
+  return h->have_series && h->have_coeffs && cmax * dxmax < 2.0 && lazy_phases_ok(h);
 }
 
 bool split_active(const clr_batch* h) {
@@ -505,9 +515,9 @@ int batch_params(clr_batch* h, int materialize, clr::BatchParams& P) {
   P.ends = nullptr; P.ends_alt = nullptr; P.ends_in = nullptr;
   P.fixup_steps = 0;
   P.refine_samples = 0;
-  {  // (the rotation of the phases needs |d dx| < 2^-5 at every step; the decay is not involved)
+  {  // (the rotation of the phases needs |d dx| < 2^-5 at every step and phases below CLR_LAZY_PHASE_LIMIT; the decay is not involved)
     const double dmax = sel_max(h->dmax, h->floor_dmax), dxmax = sel_max(h->dxmax, h->floor_dxmax);
-    P.dense = (h->have_series && h->have_coeffs && dmax * dxmax < 0.03125) ? 1 : 0;
+    P.dense = (h->have_series && h->have_coeffs && dmax * dxmax < 0.03125 && lazy_phases_ok(h)) ? 1 : 0;
   }
   if (materialize && h->nchunk > 1 && h->factor_refine > 0 && h->J_general == 0 && h->J <= clr::wide_max_width()) {
     size_t START = 0;

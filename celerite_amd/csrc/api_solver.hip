@@ -474,6 +474,7 @@ int clr_solver_grad_log_likelihood(clr_solver* s, double jitter, int n_a_real, c
   if (n_grad != G || !value || !grad) return fail(CLR_INVALID_ARGUMENT, "grad must hold 1 + 2 J_real + 4 J_comp values");
   if ((st = ensure_stream(s)) != CLR_OK) return st;
   hipStream_t stream = s->stream.get();
+  s->grad_route = -1;
 
   const int Wc = JR + 2 * JC, Wt = Wc + JG;
   const bool narrow_plan = !has_general && JG == 0 && Wc >= 1 && Wc <= 8 && N >= 1024;
@@ -545,6 +546,7 @@ int clr_solver_grad_log_likelihood(clr_solver* s, double jitter, int n_a_real, c
       int pst = CLR_OK;
       if ((st = clr_batch_grad(s->grad_plan.get(), value, grad, &pst)) != CLR_OK) return st;
       if (pst != CLR_OK) return fail(CLR_NOT_POSITIVE_DEFINITE, "failed to factorize or solve matrix");
+      s->grad_route = wide_plan ? 2 : 1;
       return CLR_OK;
     }
   }
@@ -578,7 +580,8 @@ int clr_solver_grad_log_likelihood(clr_solver* s, double jitter, int n_a_real, c
   P.out_value = s->gradbuf.p + o_out;
   P.out_grad = s->gradbuf.p + o_out + 1;
   P.out_status = s->d_status.p;
-  if (Wt > 64 || clr::option("CLR_GRAD_ANY_WIDTH")) {
+  const bool any_width = Wt > 64 || clr::option("CLR_GRAD_ANY_WIDTH");
+  if (any_width) {
     // above width 64 (round 6): one workgroup per direction, S and dS in an HBM / L2 workspace (grad_any_kernels.hip)
     if ((st = s->gradws.reserve(clr::grad_any_workspace_doubles(Wt, G))) != CLR_OK) return st;
     if (clr::launch_grad_any(P, s->gradws.p, stream) != 0) return fail(CLR_HIP_ERROR, "grad_log_likelihood: the any-width kernel could not be configured");
@@ -594,6 +597,13 @@ int clr_solver_grad_log_likelihood(clr_solver* s, double jitter, int n_a_real, c
   *value = out[0];
   for (int i = 0; i < G; ++i) grad[i] = out[(size_t)i + 1];
   if (!(jitter > 2.220446049250313e-16)) grad[0] = 0.0;  // solver.cpp:379-389,419-426
+  s->grad_route = any_width ? 3 : 0;
+  return CLR_OK;
+}
+
+int clr_solver_debug_grad_route(const clr_solver* s, int* route) {
+  if (!s || !route) return fail(CLR_INVALID_ARGUMENT, "null argument");
+  *route = s->grad_route;
   return CLR_OK;
 }
 

@@ -299,6 +299,15 @@ PYBIND11_MODULE(solver, m) {
           "not in the reference: (level, chunks, residual) of the last compute's chunked flow (clr_solver_debug_route, "
           "include/celerite_hip_debug.h); level -1: the flow was not taken");
 
+  cls.def("_grad_route",
+          [](Solver& s) {
+            int route = -1;
+            check(clr_solver_debug_grad_route(s.h(), &route));
+            return route;
+          },
+          "not in the reference: the route of the last grad_log_likelihood (clr_solver_debug_grad_route, "
+          "include/celerite_hip_debug.h): 0 sequential tangent kernel, 1 narrow plan, 2 wide plan, 3 any-width kernel, -1 none");
+
   cls.def("dot_L",
           [](Solver& s, const darray& z) {
             Rhs rhs(z);

@@ -27,6 +27,11 @@ int clr_device_measure_fp64(int waves_per_simd, int iters, double* tflops, doubl
  * bound) the largest mismatch of what the two replays wrote. */
 int clr_solver_debug_route(const clr_solver* s, int* level, int* nchunk, double* residual);
 
+/* The route the last successful clr_solver_grad_log_likelihood took: 0 the sequential tangent kernel (grad_kernels.hip),
+ * 1 the narrow plan (widths 1..8, clr_batch_grad), 2 the wide plan (wide_batch_grad), 3 the any-width kernel
+ * (grad_any_kernels.hip); -1 before any, or after a call that failed. */
+int clr_solver_debug_grad_route(const clr_solver* s, int* route);
+
 /* Diagnostics (tests): the chunk start states of the last evaluation, [B][nchunk][J(J+1)/2 + J] (packed upper
  * triangle of P, then f) ... */
 int clr_batch_debug_get_starts(clr_batch* h, double* starts);

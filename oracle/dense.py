@@ -117,3 +117,74 @@ def mp_exact_logdet_quad(a_real, c_real, a_comp, b_comp, c_comp, d_comp, t, diag
     z = mp.lu_solve(K, yv)
     quad = sum(yv[i] * z[i] for i in range(n))
     return float(logdet), float(quad)
+
+
+def mp_grad_log_likelihood(jitter, a_real, c_real, a_comp, b_comp, c_comp, d_comp, A, U, V, t, y, diag, dps=40):
+    """The log-likelihood and its gradient from the DENSE matrix in ``dps``-digit arithmetic, analytically:
+    d/dp log L = 1/2 alpha^T K' alpha - 1/2 tr(K^-1 K'), alpha = K^-1 y, with K built from the fp64 inputs (kernel of
+    utils.h:106-132, general terms as in ``dense_matrix``) and K' = dK/dp from the kernel's closed form.  Conventions of
+    oracle/grad.py (solver.cpp:347-463): the value carries the double-precision constant pi log N, the jitter partial
+    comes first and is 0 when the jitter is <= DBL_EPSILON, then a_real, c_real, a_comp, b_comp, c_comp, d_comp.
+    Independent of the recurrence the other oracles restate.  O(N^3) in Python: N <~ 80."""
+    import math
+
+    import mpmath as mp
+
+    mp.mp.dps = dps
+    f = lambda v: [mp.mpf(float(x)) for x in np.atleast_1d(np.asarray(v, dtype=np.float64))]
+    ar, cr, ac, bc, cc, dc = (f(v) for v in (a_real, c_real, a_comp, b_comp, c_comp, d_comp))
+    n = len(t)
+    tm = f(t)
+    A = np.asarray(A, dtype=np.float64).reshape(-1)
+    tau = [[abs(tm[i] - tm[j]) for j in range(n)] for i in range(n)]
+    # per term, the kernel's pieces at every tau: exp(-c tau), cos(d tau), sin(d tau)
+    er = [[[mp.exp(-c * tau[i][j]) for j in range(n)] for i in range(n)] for c in cr]
+    ec = [[[mp.exp(-c * tau[i][j]) for j in range(n)] for i in range(n)] for c in cc]
+    co = [[[mp.cos(d * tau[i][j]) for j in range(n)] for i in range(n)] for d in dc]
+    si = [[[mp.sin(d * tau[i][j]) for j in range(n)] for i in range(n)] for d in dc]
+    K = mp.matrix(n, n)
+    for i in range(n):
+        for j in range(n):
+            s = mp.mpf(0)
+            for q, a in enumerate(ar):
+                s += a * er[q][i][j]
+            for q in range(len(ac)):
+                s += ec[q][i][j] * (ac[q] * co[q][i][j] + bc[q] * si[q][i][j])
+            K[i, j] = s
+        K[i, i] += mp.mpf(float(diag[i])) + mp.mpf(float(jitter))
+    if A.size:
+        Um = np.asarray(U, dtype=np.float64).reshape(-1, n)
+        Vm = np.asarray(V, dtype=np.float64).reshape(-1, n)
+        Uq = [f(r) for r in Um]
+        Vq = [f(r) for r in Vm]
+        for i in range(n):
+            K[i, i] += mp.mpf(float(A[i]))
+            for j in range(i):
+                s = mp.fsum(Uq[g][i] * Vq[g][j] for g in range(len(Uq)))   # tril(U^T V), triu(V^T U)
+                K[i, j] += s
+                K[j, i] += s
+    Kinv = mp.inverse(K)
+    yv = mp.matrix(f(y))
+    alpha = Kinv * yv
+    logdet = mp.log(mp.det(K))
+    quad = mp.fsum(yv[i] * alpha[i] for i in range(n))
+    value = -0.5 * (quad + logdet + mp.mpf(math.pi * math.log(n)))
+
+    def partial(dK):
+        # 1/2 alpha^T K' alpha - 1/2 tr(K^-1 K')  (K' symmetric)
+        s = mp.mpf(0)
+        for i in range(n):
+            for j in range(n):
+                s += dK(i, j) * (alpha[i] * alpha[j] - Kinv[i, j])
+        return s / 2
+
+    g = [partial(lambda i, j: mp.mpf(1) if i == j else mp.mpf(0)) if jitter > 2.220446049250313e-16 else mp.mpf(0)]
+    g += [partial(lambda i, j, q=q: er[q][i][j]) for q in range(len(ar))]
+    g += [partial(lambda i, j, q=q: -ar[q] * tau[i][j] * er[q][i][j]) for q in range(len(ar))]
+    g += [partial(lambda i, j, q=q: ec[q][i][j] * co[q][i][j]) for q in range(len(ac))]
+    g += [partial(lambda i, j, q=q: ec[q][i][j] * si[q][i][j]) for q in range(len(ac))]
+    g += [partial(lambda i, j, q=q: -tau[i][j] * ec[q][i][j] * (ac[q] * co[q][i][j] + bc[q] * si[q][i][j]))
+          for q in range(len(ac))]
+    g += [partial(lambda i, j, q=q: tau[i][j] * ec[q][i][j] * (bc[q] * co[q][i][j] - ac[q] * si[q][i][j]))
+          for q in range(len(ac))]
+    return float(value), np.array([float(v) for v in g])

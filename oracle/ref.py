@@ -16,7 +16,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.path.join(_HERE, "libcelerite_ref.so")
 
-REF_OK, REF_DIMENSION_MISMATCH, REF_LINALG, REF_NOT_COMPUTED = 0, 1, 2, 3
+REF_OK, REF_DIMENSION_MISMATCH, REF_LINALG, REF_NOT_COMPUTED, REF_NO_MEMORY = 0, 1, 2, 3, 4
 
 
 class RefLinAlgError(Exception):
@@ -34,11 +34,11 @@ def _load():
     build()
     try:
         lib = C.CDLL(_LIB_PATH)
-        if hasattr(lib, "refq_factor_solve"):
+        if hasattr(lib, "refq_factor_solve") and hasattr(lib, "ref_grad_q"):
             return lib
     except OSError:
         pass
-    build(force=True)      # (a library from before celerite_ref_quad.c, or built for another machine)
+    build(force=True)      # (a library from before celerite_ref_quad.c / celerite_ref_grad.c, or built for another machine)
     return C.CDLL(_LIB_PATH)
 
 
@@ -84,6 +84,8 @@ def _raise(status):
         raise RefLinAlgError("failed to factorize or solve matrix")
     if status == REF_NOT_COMPUTED:
         raise RuntimeError("you must call 'compute' first")
+    if status == REF_NO_MEMORY:
+        raise MemoryError("the oracle could not allocate its workspace")
     raise RuntimeError("oracle error %d" % status)
 
 
@@ -287,3 +289,84 @@ def quad_factor_solve(jitter, a_real, c_real, a_comp, b_comp, c_comp, d_comp, t,
     if st != REF_OK:
         raise ValueError("dimension mismatch")
     return (W.reshape(N, J).T.copy() if want_factor else None), D, x, ld.value, q.value
+
+
+def default_threads():
+    """Worker threads for the gradient oracle: at most 16, at most the CPUs this process may run on, at most
+    $OMP_NUM_THREADS when that is set (the machine's total CPU count says nothing about what a job may use)."""
+    n = min(16, len(os.sched_getaffinity(0)))
+    try:
+        n = min(n, int(os.environ.get("OMP_NUM_THREADS", "")))
+    except ValueError:
+        pass
+    return max(1, n)
+
+
+_GRAD_ARGS = [C.c_double, C.c_int, _dp, _dp, C.c_int, _dp, _dp, _dp, _dp, C.c_int, _dp, _dp, _dp,
+              C.c_int, _dp, _dp, _dp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp]
+for _f in (_lib.ref_grad_d, _lib.ref_grad_q):
+    _f.restype = C.c_int
+    _f.argtypes = _GRAD_ARGS
+
+
+def _grad(fn, jitter, a_real, c_real, a_comp, b_comp, c_comp, d_comp, A, U, V, t, y, diag, directions, nthreads,
+          phase_in_double):
+    ar, pa, JR = _vec(a_real)
+    cr, pc, _ = _vec(c_real)
+    ac, pac, JC = _vec(a_comp)
+    bc, pbc, _ = _vec(b_comp)
+    cc, pcc, _ = _vec(c_comp)
+    dc, pdc, _ = _vec(d_comp)
+    tt, pt, N = _vec(t)
+    yy, py, _ = _vec(y)
+    dd, pd, _ = _vec(diag)
+    if len(cr) != JR or len(bc) != JC or len(cc) != JC or len(dc) != JC or len(yy) != N or len(dd) != N:
+        raise ValueError("dimension mismatch")
+    G = 1 + 2 * JR + 4 * JC
+    A = np.asarray(A, dtype=np.float64).reshape(-1)
+    if A.size:
+        Ua = np.ascontiguousarray(np.asarray(U, dtype=np.float64).reshape(-1, N))
+        Va = np.ascontiguousarray(np.asarray(V, dtype=np.float64).reshape(-1, N))
+        Aa = np.ascontiguousarray(A)
+        JG = Ua.shape[0]
+        if Va.shape != Ua.shape or Aa.shape != (N,):
+            raise ValueError("dimension mismatch")
+        pA, pU, pV = Aa.ctypes.data_as(_dp), Ua.ctypes.data_as(_dp), Va.ctypes.data_as(_dp)
+    else:
+        JG, pA, pU, pV = 0, None, None, None
+    full = directions is None
+    dirs = np.eye(G) if full else np.ascontiguousarray(np.atleast_2d(np.asarray(directions, dtype=np.float64)))
+    if dirs.shape[1] != G:
+        raise ValueError("directions must have %d columns" % G)
+    dirs = np.ascontiguousarray(dirs)
+    out = np.zeros(dirs.shape[0])
+    value = C.c_double()
+    st = fn(float(jitter), JR, pa, pc, JC, pac, pbc, pcc, pdc, JG, pA, pU, pV, N, pt, pd, py,
+            int(dirs.shape[0]), dirs.ctypes.data_as(_dp), int(nthreads or default_threads()), int(bool(phase_in_double)),
+            C.byref(value), out.ctypes.data_as(_dp))
+    _raise(st)
+    return value.value, out
+
+
+def quad_grad(jitter, a_real, c_real, a_comp, b_comp, c_comp, d_comp, A, U, V, t, y, diag,
+              directions=None, nthreads=None, phase_in_double=False):
+    """The log-likelihood's value and gradient as celerite/solver.cpp:347-463 returns them (oracle/grad.py's
+    arguments and conventions: the value carries pi log N; the jitter partial first, 0 when jitter <= DBL_EPSILON; then
+    a_real, c_real, a_comp, b_comp, c_comp, d_comp), forward mode carried in IEEE binary128 from the double inputs
+    (oracle/celerite_ref_grad.inc) -- "the truth" the GPU gradient is measured against.
+
+    ``directions``: an ``ndir x G`` matrix; then the second result is the ``ndir`` directional derivatives instead of
+    the G partials (the identity gives the gradient).  ``nthreads``: workers the directions are split over (default
+    ``default_threads()``; the result does not depend on it).  ``phase_in_double``: take the phase's value as
+    fl(d t) in double, as the reference and the device form it, then carry it on in binary128.  Raises
+    ``RefLinAlgError`` where the reference throws (cholesky.h:176)."""
+    return _grad(_lib.ref_grad_q, jitter, a_real, c_real, a_comp, b_comp, c_comp, d_comp, A, U, V, t, y, diag,
+                 directions, nthreads, phase_in_double)
+
+
+def double_grad(jitter, a_real, c_real, a_comp, b_comp, c_comp, d_comp, A, U, V, t, y, diag,
+                directions=None, nthreads=None, phase_in_double=False):
+    """``quad_grad`` carried in double: oracle/grad.py's operations at C speed (its twin; ``phase_in_double`` changes
+    nothing here).  Its distance from ``quad_grad`` is what plain double precision costs on a problem."""
+    return _grad(_lib.ref_grad_d, jitter, a_real, c_real, a_comp, b_comp, c_comp, d_comp, A, U, V, t, y, diag,
+                 directions, nthreads, phase_in_double)

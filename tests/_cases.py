@@ -301,3 +301,84 @@ def output_check_truth(name):
         c = output_check_case(name)
         _TRUTH[name] = ref.quad_factor_solve(0.0, *coeffs_of(c), c["t"], c["diag"], c["y"])
     return _TRUTH[name]
+
+
+# ---- adversarial families of the reverse-mode gradient (csrc/clr_grad_core.h: states rebuilt backwards between stored
+# ones, certified by their drift) -- ONE problem each, widths 1..8 (the narrow plan), dict as above.  Every one stays on
+# the fast-trig path (max d x max t < 1e9), so that the chunked gradient routes, not the sequential fallback, take it.
+GRAD_FAMILY_SHAPE = (2, 3)
+
+
+def _grad_family(a_real, c_real, a_comp, b_comp, c_comp, d_comp, t, rng, y=None):
+    out = _family(a_real, c_real, a_comp, b_comp, c_comp, d_comp, t, rng)
+    if y is not None:
+        out["y"] = y
+    return out
+
+
+def grad_family_fast_decay(N, J_real=2, J_comp=3, seed=0):
+    """G1: one real term with c dt up to ~5 per sample (it forgets between samples: the backward rebuild of its state
+    amplifies rounding by exp(c dt) per step) beside slow real and complex terms (c dt ~ 1e-3) at unit mean cadence."""
+    rng = np.random.RandomState(seed)
+    t = np.cumsum(rng.uniform(0.05, 1.95, N))
+    c_real = np.full(J_real, 1e-3)
+    c_real[0] = 2.6
+    return _grad_family(np.full(J_real, 1.0), c_real, np.full(J_comp, 0.3), np.zeros(J_comp), np.full(J_comp, 2e-3),
+                        0.7 + 0.1 * np.arange(J_comp), t, rng, y=rng.randn(N))
+
+
+def grad_family_long_gap(N, J_real=2, J_comp=3, seed=0, gap_cadences=1000.0, at=0.37):
+    """G2: the benchmark's cadence with ONE gap of ``gap_cadences`` mean spacings at ``at`` of the series -- inside a
+    chunk for any chunk count that does not put a boundary exactly there.  Decay rates chosen so that the gap takes the
+    state down by exp(-2) .. exp(-20), not to nothing (over one cadence, by 2 % at most)."""
+    rng = np.random.RandomState(seed)
+    dt = rng.uniform(0.5, 1.5, N) / N
+    k = int(at * N)
+    dt[k] = gap_cadences / N
+    t = np.cumsum(dt)
+    c = np.geomspace(2.0, 20.0, J_real + J_comp) / dt[k]
+    return _grad_family(np.full(J_real, 1.0), c[:J_real], np.full(J_comp, 0.2), np.zeros(J_comp), c[J_real:],
+                        1.6 + np.arange(J_comp), t, rng)
+
+
+def grad_family_bursts(N, J_real=2, J_comp=3, seed=0, burst=64, spacing=1e-3, gap=5.0):
+    """G3: bursts of ``burst`` samples ``spacing`` apart, ``gap`` between bursts: within a burst nothing decays, across
+    a gap the fast terms forget (c gap ~ 10) and the slow ones do not (c gap ~ 0.05)."""
+    rng = np.random.RandomState(seed)
+    nb = (N + burst - 1) // burst
+    starts = np.cumsum(np.full(nb, gap))
+    t = (starts[:, None] + spacing * np.cumsum(rng.uniform(0.5, 1.5, (nb, burst)), axis=1)).reshape(-1)[:N]
+    c_real = np.full(J_real, 0.01)
+    c_real[0] = 2.0
+    c_comp = np.full(J_comp, 0.01)
+    c_comp[0] = 2.0
+    return _grad_family(np.full(J_real, 1.0), c_real, np.full(J_comp, 0.3), np.zeros(J_comp), c_comp,
+                        0.5 + np.arange(J_comp), t, rng)
+
+
+def grad_family_tiny_term(N, J_real=2, J_comp=3, seed=0, tiny=1e-8):
+    """G4: the last complex term at amplitude ``tiny`` of the largest: its c and d partials scale with its amplitude,
+    ~1e-8 of the largest partial -- a bar relative to the largest partial cannot see them."""
+    rng = np.random.RandomState(seed)
+    a = np.full(J_comp, 0.5)
+    a[-1] = tiny * 1.0
+    b = np.zeros(J_comp)
+    b[-1] = 0.5 * tiny
+    t = np.sort(rng.uniform(0, 0.8 * N, N))
+    return _grad_family(np.full(J_real, 1.0), np.full(J_real, 0.05), a, b, np.full(J_comp, 0.3),
+                        0.9 + 0.2 * np.arange(J_comp), t, rng, y=rng.randn(N))
+
+
+def grad_family_large_phase(N, J_real=2, J_comp=3, seed=0, phase=1e6):
+    """G5: d t up to ``phase`` (~1e6: the tangent of every phase carries a factor t, d' t ~ t) while max d x max t stays
+    far below the fast-trig limit 1e9."""
+    rng = np.random.RandomState(seed)
+    t = np.sort(rng.uniform(0, 0.8 * N, N))
+    d = (phase / t[-1]) * (1.0 - 0.1 * np.arange(J_comp))
+    return _grad_family(np.full(J_real, 1.0), np.full(J_real, 0.1), np.full(J_comp, 0.5), np.zeros(J_comp),
+                        np.full(J_comp, 0.5), d, t, rng, y=rng.randn(N))
+
+
+GRAD_FAMILIES = {"G1 fast decay": grad_family_fast_decay, "G2 long gap": grad_family_long_gap,
+                 "G3 bursts": grad_family_bursts, "G4 tiny term": grad_family_tiny_term,
+                 "G5 large phase": grad_family_large_phase}

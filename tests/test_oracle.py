@@ -372,3 +372,162 @@ def test_carma_oracle_errors():
     cs = carma.CARMASolver(-0.5, [0.1, 0.05], [0.2])
     with pytest.raises(RuntimeError, match="dimension mismatch"):      # carma.h:223
         cs.log_likelihood(np.zeros(3), np.zeros(2), np.ones(3))
+
+
+# ---- gradient oracle in binary128 and its double twin (oracle/celerite_ref_grad.inc) ---------------------------------
+def _grad_reference_case(with_general, N=100):
+    """The problem of the reference's gradient test (tests/test_celerite.py:427-430) as
+    test_grad_oracle_value_and_finite_differences sets it up."""
+    np.random.seed(42)
+    x = np.sort(np.random.rand(N))
+    yerr = np.random.uniform(0.1, 0.5, len(x))
+    y = np.sin(x)
+    gen = general_terms(x, np.random.rand) if with_general else NO_GENERAL
+    co = [np.array([1.5, 0.3]), np.array([0.7, 2.0]), np.array([1.0, 0.4]), np.array([0.1, 0.3]),
+          np.array([1.2, 0.5]), np.array([3.0, 1.5])]
+    return co, gen, x, y, yerr ** 2
+
+
+@pytest.mark.parametrize("with_general", [False, True])
+@pytest.mark.parametrize("jitter", [0.0, 0.05])
+def test_double_grad_twin_equals_the_dual_number_oracle(with_general, jitter):
+    """ref.double_grad performs oracle/grad.py's operations in the same order: the same value and partials, per partial
+    at rounding level (measured: 1.5e-14 of a partial at most)."""
+    from oracle import grad as ograd
+
+    co, gen, x, y, diag = _grad_reference_case(with_general)
+    v0, g0 = ograd.grad_log_likelihood(jitter, *co, *gen, x, y, diag)
+    v1, g1 = ref.double_grad(jitter, *co, *gen, x, y, diag)
+    assert g1.shape == g0.shape == (13,)
+    assert abs(v1 - v0) <= 1e-15 * abs(v0)
+    nz = g0 != 0
+    assert np.all(np.abs(g1[nz] - g0[nz]) <= 1e-13 * np.abs(g0[nz])), np.abs(g1 - g0)
+    assert (g1[0] == 0.0) == (jitter == 0.0) and (g0[0] == 0.0) == (jitter == 0.0)
+
+
+def test_double_grad_twin_equals_the_dual_number_oracle_at_n2000():
+    from oracle import grad as ograd
+
+    case = synthetic(1, 2000, 2, 1, "accuracy", seed=3)
+    co = coeffs_of(case, 0)
+    v0, g0 = ograd.grad_log_likelihood(0.02, *co, *NO_GENERAL, case["t"][0], case["y"][0], case["diag"][0])
+    v1, g1 = ref.double_grad(0.02, *co, *NO_GENERAL, case["t"][0], case["y"][0], case["diag"][0])
+    assert abs(v1 - v0) <= 1e-15 * abs(v0)
+    assert np.all(np.abs(g1 - g0) <= 1e-13 * np.abs(g0)), np.abs(g1 - g0) / np.abs(g0)
+
+
+@pytest.mark.parametrize("with_general", [False, True])
+@pytest.mark.parametrize("jitter", [0.0, 0.05])
+def test_binary128_grad_equals_the_dense_analytic_gradient(with_general, jitter):
+    """ref.quad_grad (the recurrence's tangents in binary128) against 1/2 alpha^T K' alpha - 1/2 tr(K^-1 K') of the dense
+    matrix in 40 digits (oracle/dense.py), which shares nothing with the recurrence: every partial to double rounding
+    (measured: 0 -- both round the same 1e-30-accurate number), while the double twin sits ~1e-13 away."""
+    co, gen, x, y, diag = _grad_reference_case(with_general, N=50)
+    vm, gm = dense.mp_grad_log_likelihood(jitter, *co, *gen, x, y, diag, dps=40)
+    vq, gq = ref.quad_grad(jitter, *co, *gen, x, y, diag)
+    assert abs(vq - vm) <= 4e-16 * abs(vm)
+    nz = gm != 0
+    assert np.all(np.abs(gq[nz] - gm[nz]) <= 4e-16 * np.abs(gm[nz])), np.abs(gq - gm)
+    assert gq[0] == 0.0 if jitter == 0.0 else gq[0] != 0.0
+    vd, gd = ref.double_grad(jitter, *co, *gen, x, y, diag)
+    assert np.max(np.abs(gd[nz] - gm[nz]) / np.abs(gm[nz])) <= 1e-11
+
+
+def test_binary128_grad_directions_are_linear_and_thread_independent():
+    """The directional derivative along v is v . (full gradient) (to binary128 rounding, read in double), the result is
+    bitwise the same on 1 and 4 threads, the jitter component of a direction counts only above DBL_EPSILON, and the
+    phase flag changes the tangents at t ~ 3e8 (the rounding of fl(d t) there) but not at t ~ 1."""
+    co, gen, x, y, diag = _grad_reference_case(True)
+    v, g = ref.quad_grad(0.05, *co, *gen, x, y, diag, nthreads=1)
+    rng = np.random.RandomState(0)
+    dirs = rng.randn(5, 13)
+    v1, d1 = ref.quad_grad(0.05, *co, *gen, x, y, diag, directions=dirs, nthreads=1)
+    v4, d4 = ref.quad_grad(0.05, *co, *gen, x, y, diag, directions=dirs, nthreads=4)
+    assert v1 == v4 == v and np.array_equal(d1, d4)
+    ref_d = dirs @ g
+    assert np.all(np.abs(d1 - ref_d) <= 4e-16 * (np.abs(dirs) @ np.abs(g))), (d1 - ref_d)
+    _, g4 = ref.quad_grad(0.05, *co, *gen, x, y, diag, nthreads=4)
+    assert np.array_equal(g4, g)
+    _, dz = ref.quad_grad(0.0, *co, *gen, x, y, diag, directions=np.eye(13)[:1])
+    assert dz[0] == 0.0                                   # solver.cpp:379-389
+    _, gp = ref.quad_grad(0.05, *co, *gen, x, y, diag, phase_in_double=True)
+    assert np.max(np.abs(gp - g) / np.abs(g)) <= 1e-15
+    xs = x + 3e8
+    _, gs = ref.quad_grad(0.05, *co, *NO_GENERAL, xs, y, diag)
+    _, gsp = ref.quad_grad(0.05, *co, *NO_GENERAL, xs, y, diag, phase_in_double=True)
+    assert np.max(np.abs(gsp - gs) / np.abs(gs)) > 1e-9
+    with pytest.raises(ValueError):
+        ref.quad_grad(0.05, *co, *gen, x, y, diag, directions=np.ones((2, 12)))
+
+
+def test_binary128_grad_raises_like_the_reference():
+    x = np.linspace(0, 1, 20)
+    for fn in (ref.quad_grad, ref.double_grad):
+        with pytest.raises(ref.RefLinAlgError):
+            fn(0.0, [-3.0], [0.5], [], [], [], [], *NO_GENERAL, x, np.sin(x), np.zeros(20))
+    # (a positive-definite one still goes through, on every thread count)
+    v, g = ref.quad_grad(0.0, [3.0], [0.5], [], [], [], [], *NO_GENERAL, x, np.sin(x), np.full(20, 0.1), nthreads=3)
+    assert np.isfinite(v) and np.all(np.isfinite(g)) and g.shape == (3,)
+
+
+def test_grad_fixture_at_1e5_against_binary128():
+    """tests/golden/grad_n1e5_w8.json (oracle/grad.py in double at the headline shape, N = 1e5, width 8) against the
+    binary128 tangents, per partial: measured 5e-12 (the d partials; 1e-14 elsewhere) -- the fixture the plan gradient
+    is held to at 1e-10 is itself within 1e-11 of the truth.  The double twin is measured beside it."""
+    import bench
+
+    with open(os.path.join(GOLDEN, "grad_n1e5_w8.json")) as f:
+        gold = json.load(f)
+    coeffs, t, diag, y = bench.make_inputs(2, gold["N"], gold["J_real"], gold["J_comp"], 42)
+    co = [c[0] for c in coeffs]
+    vq, gq = ref.quad_grad(gold["jitter"], *co, *NO_GENERAL, t[0], y[0], diag[0])
+    g0 = np.array(gold["grad"])
+    from _cases import within
+    within("oracle: N = 1e5 grad fixture vs binary128, value (relative)", abs(gold["value"] - vq) / abs(vq), 1e-13)
+    within("oracle: N = 1e5 grad fixture vs binary128, worst partial (relative to that partial)",
+           np.max(np.abs(g0 - gq) / np.abs(gq)), 1e-11)
+    vd, gd = ref.double_grad(gold["jitter"], *co, *NO_GENERAL, t[0], y[0], diag[0])
+    within("oracle: N = 1e5 double twin vs binary128, worst partial (relative to that partial)",
+           np.max(np.abs(gd - gq) / np.abs(gq)), 1e-11)
+
+
+# ---- adversarial families of the reverse-mode gradient (tests/_cases.py GRAD_FAMILIES; on the device:
+# tests/test_gpu_grad_truth.py) -------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", sorted(__import__("_cases").GRAD_FAMILIES))
+def test_grad_family_has_its_adversarial_property(name):
+    from _cases import GRAD_FAMILIES, GRAD_FAMILY_SHAPE, within
+
+    JR, JC = GRAD_FAMILY_SHAPE
+    N = 20000
+    c = GRAD_FAMILIES[name](N, JR, JC)
+    t = c["t"]
+    dt = np.diff(t)
+    assert len(t) == N and np.all(dt > 0)
+    assert np.max(np.abs(c["d_comp"])) * np.max(np.abs(t)) < 1e8          # far inside the fast-trig path (1e9)
+    r = ref.RefSolver()
+    r.compute(0.0, *coeffs_of(c), *NO_GENERAL, t, c["diag"])               # positive definite (raises otherwise)
+    if name.startswith("G1"):
+        assert 4.5 < np.max(c["c_real"]) * np.max(dt) < 6.0                # the fast term forgets between samples
+        assert np.max(c["c_comp"]) * np.max(dt) < 1e-2                      # the complex terms do not
+    elif name.startswith("G2"):
+        k = np.argmax(dt)
+        assert dt[k] > 500 * np.median(dt) and 0.3 * N < k < 0.45 * N
+        assert np.all(np.delete(dt, k) < 5 * np.median(dt))
+        decay = np.exp(-np.concatenate([c["c_real"], c["c_comp"]]) * dt[k])
+        assert np.all(decay > 1e-9) and np.all(decay < 0.2)                # the gap takes the state down, not out
+    elif name.startswith("G3"):
+        big = dt > 1.0
+        assert 200 < big.sum() < N / 32                                     # hundreds of bursts
+        assert np.max(dt[~big]) < 2e-3 and np.min(dt[big]) > 4.0
+        assert np.max(c["c_real"]) * np.min(dt[big]) > 8 and np.min(c["c_real"]) * np.max(dt[big]) < 0.06
+    elif name.startswith("G4"):
+        a = np.concatenate([c["a_real"], c["a_comp"]])
+        assert abs(c["a_comp"][-1]) <= 1e-8 * np.max(np.abs(a))
+        _, g = ref.double_grad(0.0, *coeffs_of(c), *NO_GENERAL, t, c["y"], c["diag"])
+        JRC = 1 + 2 * JR
+        small = np.abs(g[[JRC + 3 * JC - 1, JRC + 4 * JC - 1]])              # d / d c, d / d d of the tiny term
+        within("gradient families: G4 tiny term's c / d partials of the largest partial", np.max(small) / np.max(np.abs(g)), 1e-6)
+        assert np.min(small) > 0
+    else:
+        assert name.startswith("G5")
+        assert np.max(c["d_comp"]) * t[-1] > 5e5 and np.min(c["d_comp"]) * t[-1] > 5e5
