@@ -1,7 +1,7 @@
 # -*- coding: utf-8 -*-
 """Headline benchmark: GP log-likelihoods / second on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 Workload (BASELINE.json configs[2] per GPU; configs[3] = the same on 8 GPUs):
     B = 1024 independent (series x hyper-parameter draw) problems per GPU,
@@ -16,8 +16,15 @@ problem): a FRESH draw of hyper-parameters for all B problems goes host -> HBM
 replay -> finalize, csrc/), and the B log-likelihoods come back to the host
 (`results`, which synchronises).  The series are resident in HBM (uploaded
 before the timed region, in the public API's row-major layout).  `value` is
-that loop's rate; `device_only` is the same kernels launched back to back
-without the per-step transfers (what round 1 reported as `value`).
+that loop's rate; `device_only` (--full) is the same kernels launched back to
+back without the per-step transfers (what round 1 reported as `value`).
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and
+prints its line: the contract's keys and `config`.  Everything else -- per-kernel
+times, roofline, device-only and steady-state rates, the other layouts, shapes
+and configurations, the gradient, sharding, CPU baseline and oracle parity --
+runs after the timed steps only with `--full` (the --no-* switches and
+--sharded choose among those legs).  Both runs time the same K steps.
 
 Per-kernel times come from HIP events recorded on the plan's stream around
 every kernel INSIDE the timed loop (`clr_batch_set_profiling`).
@@ -32,9 +39,10 @@ single-process alternative is the product's `ShardedBatchedGP` /
 `clr_sharded_*`: one host thread per GPU.)
 
 Rank 0 prints ONE JSON line on stdout, the LAST thing written there and below 6 KB (the driver keeps the
-last 8 KB of stdout): the contract's keys, `config`, `roofline` (the dominant kernel + the promoted numbers of
-the side legs) and `cpu_baseline` -- `headline_line()`, held to that size by tests/test_host_api.py.  The
-COMPLETE record goes to `gpurun_out/bench_full.json` (or $CLR_BENCH_FULL) and to stderr: `configs` in it
+last 8 KB of stdout): the contract's keys, `config` and, with --full, `roofline` (the dominant kernel + the
+promoted numbers of the side legs) and `cpu_baseline` -- `headline_line()`, held to that size by
+tests/test_host_api.py.  With --full the COMPLETE record goes to stderr and to a side file ($CLR_BENCH_FULL, by
+default bench_full.json in the output folder next to this script; its path is the line's `full_record`): `configs` in it
 carries BASELINE configs 0, 1 and 4 (object API at N = 1e3; B = 256 x N = 1e4 width 4; B = 256 x N = 1e5
 width 32), each with its own time, rate, roofline and parity on a sample (and, for the batch configs, the
 histogram of problems by route and the conditioning record).  `accuracy_family` is SURVEY.md 8(d)'s second
@@ -63,6 +71,8 @@ import numpy as np
 ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
+
+METRIC = "GP log-likelihoods/sec, N=1e5 J=8 batch=1024; log_det rel-err vs CPU ref"
 
 # MI355X datasheet: 256 CU x 4 SIMD x 16 FMA lanes x 2 flop x 2.4 GHz (matrix = vector rate for fp64)
 PEAK_FP64_TFLOPS = 78.6
@@ -687,6 +697,10 @@ def main(argv=None):
     ap.add_argument("--steady-seconds", type=float, default=2.5)
     ap.add_argument("--settle-seconds", type=float, default=0.5, help="untimed extra warm-up before the K timed steps")
     ap.add_argument("--dump-outputs", metavar="DIR", help="write the results of the last timed step to DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every side leg (per-kernel times, roofline, the other layouts, "
+                         "sizes and configurations, CPU baseline and oracle parity) and write the complete record; "
+                         "the --no-* switches and --sharded pick among them")
     args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1 (it is the number of timed steps)")
@@ -724,22 +738,24 @@ def main(argv=None):
     W = JR + 2 * JC
     K, Wm = args.steps, max(args.warmup, 0)
 
-    try:  # the fp64 rate / clock of this box (rank 0's device stands for all; a few ms, outside every timed region)
-        tf, mhz, cyc = batch.measure_fp64(2, 20000, device=dist.local_rank % ndev)   # (every rank on its own GPU)
-        FP64_LIVE.update({"tflops": tf, "clock_mhz": mhz, "cycles_per_fma": cyc})
-    except Exception:
-        pass
+    if args.full:  # the fp64 rate / clock of this box for the roofline (rank 0's device stands for all; a few ms)
+        try:
+            tf, mhz, cyc = batch.measure_fp64(2, 20000, device=dist.local_rank % ndev)   # (every rank on its own GPU)
+            FP64_LIVE.update({"tflops": tf, "clock_mhz": mhz, "cycles_per_fma": cyc})
+        except Exception:
+            pass
     coeffs, t, diag, y = make_inputs(B, N, JR, JC, seed=42 + dist.rank)
     draws = [coeffs] + fresh_draws(coeffs, 7, seed=1042 + dist.rank)
     plan = batch.BatchedGP(B, N, JR, JC, device=dist.local_rank % ndev)
     if args.chunks:
         plan.set_chunks(args.chunks)
     plan.set_series(t, diag, y)          # host -> HBM, outside the timed region
-    set_series_first_ms = plan.selection_bounds()["set_series_host_ms"]   # (device buffers + pinned staging allocated)
-    plan.set_series(t, diag, y)          # ... and again: what every later batch of series costs
+    if args.full:
+        set_series_first_ms = plan.selection_bounds()["set_series_host_ms"]   # (device buffers + pinned staging allocated)
+        plan.set_series(t, diag, y)      # ... and again: what every later batch of series costs
     real_loop(plan, draws, Wm)
     # untimed settling beyond the W warm-up steps: a few steps are not enough for the clocks of an idle
-    # device (and the host's pinned-copy path) to reach their steady state; reported as settle_steps
+    # device (and the host's pinned-copy path) to reach their steady state; reported as settle_steps (--full)
     settle, t_s = 0, time.perf_counter()
     while time.perf_counter() - t_s < args.settle_seconds:
         real_loop(plan, draws, 5, offset=settle)
@@ -760,6 +776,8 @@ def main(argv=None):
     dt = dist.max(time.perf_counter() - t0)
     if args.dump_outputs:
         dump_outputs(args.dump_outputs, last_step, dist.rank, dist.world)
+    if not args.full:
+        return plain_finish(dist, plan, B, N, JR, JC, K, Wm, dt, last_step, json_fd)
     dominant_ms, nrec_dom = plan.profile()
     plan.set_profiling(True)
     real_loop(plan, draws, K, offset=1)
@@ -890,7 +908,7 @@ def main(argv=None):
 
         value = dist.world * B * K / dt
         out = {
-            "metric": "GP log-likelihoods/sec, N=1e5 J=8 batch=1024; log_det rel-err vs CPU ref",
+            "metric": METRIC,
             "value": value, "unit": "log-likelihoods/s", "n_gpus": dist.world, "steps": K, "warmup": Wm, "settle_steps": settle,
             "ms_per_step": dt / K * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "f64", "data": "synthetic",
@@ -1075,14 +1093,50 @@ def main(argv=None):
     if out is not None:
         full_path = write_full_record(out)
         line = headline_line(out, full_path)
-        sys.stderr.flush()
-        if json_fd is None:
-            sys.stdout.write(line + "\n")
-            sys.stdout.flush()
-        else:
-            sys.stdout.flush()
-            os.write(json_fd, (line + "\n").encode())
+        print_line(line, json_fd)
     return out
+
+
+def plain_finish(dist, plan, B, N, JR, JC, K, Wm, dt, last_step, json_fd):
+    """The end of a run without --full: the headline of the K timed steps and nothing that needs a run of its own."""
+    W = JR + 2 * JC
+    bad = dist.max(int((np.asarray(last_step[3]) != 0).sum()))     # (the last timed step, worst rank)
+    out = None
+    if dist.rank == 0:
+        out = {
+            "metric": METRIC,
+            "value": dist.world * B * K / dt, "unit": "log-likelihoods/s", "n_gpus": dist.world, "steps": K, "warmup": Wm,
+            "ms_per_step": dt / K * 1e3, "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "config": {
+                "workload": "BASELINE configs[2]: batch=%d problems/GPU x N=%d samples, width J=%d (%d real + %d "
+                            "complex terms), fp64, fused log-likelihood; per step: fresh hyper-parameter draw host->HBM, "
+                            "the kernels, results HBM->host (side legs: bench.py --full)" % (B, N, W, JR, JC),
+                "batch_per_gpu": B, "N": N, "width": W, "J_real": JR, "J_comp": JC,
+                "scan_chunks": plan.chunks[0], "chunk_len": plan.chunks[1],
+                "parallelism": "batch-sharded x%d, no collective" % dist.world,
+                "summarize_kernel": plan.summarize_kernel(),
+            },
+            "timed_region_s": dt,
+            "status_not_ok": int(bad),
+        }
+    plan.close()
+    dist.barrier()
+    dist.close()
+    if out is not None:
+        print_line(headline_line(out), json_fd)
+    return out
+
+
+def print_line(line, json_fd):
+    """The result line on stdout (with several ranks: on the descriptor main() saved before gloo could write there)."""
+    sys.stderr.flush()
+    if json_fd is None:
+        sys.stdout.write(line + "\n")
+        sys.stdout.flush()
+    else:
+        sys.stdout.flush()
+        os.write(json_fd, (line + "\n").encode())
 
 
 HEADLINE_MAX_BYTES = 6000     # the driver keeps the last 8 KB of stdout: the line it parses must fit with room to spare
@@ -1124,7 +1178,8 @@ def headline_record(out, full_path=None):
     `cpu_baseline`.  Everything else of `out` is named in `extra_keys` and kept in the full record."""
     rec = {k: out.get(k) for k in HEADLINE_KEYS}
     rec["config"] = {k: v for k, v in (out.get("config") or {}).items() if k in CONFIG_CORE}
-    rec["roofline"] = dict(out.get("roofline") or {})
+    if out.get("roofline") is not None:           # (a run without --full measures no roofline)
+        rec["roofline"] = dict(out["roofline"])
     cb = out.get("cpu_baseline")
     if cb is not None:
         rec["cpu_baseline"] = cb
@@ -1140,7 +1195,7 @@ def headline_line(out, full_path=None, max_bytes=HEADLINE_MAX_BYTES):
     """One strict-JSON line of at most `max_bytes` bytes (tests/test_host_api.py holds it to that)."""
     rec = headline_record(out, full_path)
     line = json.dumps(rec, allow_nan=False, separators=(",", ":"))
-    droppable = [k for k in rec["roofline"] if k not in ROOFLINE_CORE]
+    droppable = [k for k in rec.get("roofline", {}) if k not in ROOFLINE_CORE]
     while len(line.encode()) > max_bytes and droppable:
         rec["roofline"].pop(droppable.pop())
         line = json.dumps(rec, allow_nan=False, separators=(",", ":"))

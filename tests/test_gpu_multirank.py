@@ -4,8 +4,8 @@ one process -- or one host thread -- per GPU, no collective on the data path).
 
   * ``bench.py --gpus 2`` exactly as the driver launches it for N > 1 (``python -m torch.distributed.run ...``), here
     with both ranks on the visible GPU(s) (``CLR_BENCH_SHARE_GPU=1`` on a one-GPU box): ONE JSON line on stdout,
-    ``n_gpus == 2``, whole-job value = problems of both ranks over the max-over-ranks time, every rank's slice held
-    against the CPU oracle;
+    ``n_gpus == 2``, whole-job value = problems of both ranks over the max-over-ranks time; with ``--full`` every
+    rank's slice held against the CPU oracle;
   * the product's sharded plan over EVERY visible device (``range(device_count())``: one shard on a one-GPU box, the
     real thing on the 8-GPU node): bit-identical to the unsharded plan, oracle parity at 1e-10.
 """
@@ -14,6 +14,7 @@ import os
 import socket
 import subprocess
 import sys
+import time
 
 import numpy as np
 import pytest
@@ -45,7 +46,7 @@ def test_bench_two_ranks_as_the_driver_launches_it():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
            "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "64", "--nsamples", "10000",
-           "--steady-seconds", "0.2", "--settle-seconds", "0.1", "--no-configs", "--no-shared-series"]
+           "--steady-seconds", "0.2", "--settle-seconds", "0.1", "--no-configs", "--no-shared-series", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=840)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     lines = [ln for ln in r.stdout.decode().splitlines() if ln.strip().startswith("{")]
@@ -66,16 +67,43 @@ def test_bench_two_ranks_as_the_driver_launches_it():
 
 
 @pytest.mark.timeout(900)
+def test_bench_two_ranks_plain_run():
+    """The same launch without ``--full``: ONE JSON line with the whole-job headline of the timed steps, no side legs."""
+    ndev = batch.device_count()
+    env = dict(os.environ)
+    env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
+    if ndev < 2:
+        env["CLR_BENCH_SHARE_GPU"] = "1"
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
+           "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
+           "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "64", "--nsamples", "10000", "--settle-seconds", "0.1"]
+    r = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=840)
+    assert r.returncode == 0, r.stderr.decode()[-3000:]
+    lines = [ln for ln in r.stdout.decode().splitlines() if ln.strip().startswith("{")]
+    assert len(lines) == 1, r.stdout.decode()[-2000:]
+    out = json.loads(lines[0])
+    assert out["n_gpus"] == 2 and out["steps"] == 3 and out["warmup"] == 1 and out["scaling"] == "weak"
+    assert out["unit"] == "log-likelihoods/s" and out["dtype"] == "f64" and out["higher_is_better"] is True
+    assert out["config"]["batch_per_gpu"] == 64 and "x2" in out["config"]["parallelism"]
+    assert abs(out["value"] - 2 * 64 * 3 / out["timed_region_s"]) <= 1e-4 * out["value"]
+    assert abs(out["ms_per_step"] - out["timed_region_s"] / 3 * 1e3) <= 1e-4 * out["ms_per_step"]
+    assert out["status_not_ok"] == 0
+    for key in ("roofline", "cpu_baseline", "multi_rank_parity"):
+        assert key not in out, key
+    assert out["full_record"] is None
+
+
+@pytest.mark.timeout(900)
 def test_bench_one_gpu_line_as_the_driver_parses_it():
-    """``python bench.py --gpus 1 --steps 20 --warmup 5`` -- the driver's round-end command.  The driver keeps the last
-    8 KB of stdout and parses the LAST line: that line must be strict JSON, well under 8 KB, and carry the headline,
-    ``config.workload``, ``roofline`` and ``cpu_baseline`` (round 5's 26.5 KB line came back ``parsed: null``).  The
-    complete record goes to a side file."""
+    """``python bench.py --gpus 1 --steps 20 --warmup 5 --full`` -- the driver's command with every side leg.  The driver
+    keeps the last 8 KB of stdout and parses the LAST line: that line must be strict JSON, well under 8 KB, and carry the
+    headline, ``config.workload``, ``roofline`` and ``cpu_baseline`` (round 5's 26.5 KB line came back ``parsed:
+    null``).  The complete record goes to a side file."""
     env = dict(os.environ)
     full = os.path.join(ROOT, "gpurun_out", "bench_full_test.json")
     env["CLR_BENCH_FULL"] = full
     os.makedirs(os.path.dirname(full), exist_ok=True)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=840)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     stdout = r.stdout.decode()
@@ -103,6 +131,41 @@ def test_bench_one_gpu_line_as_the_driver_parses_it():
     assert out["status_not_ok"] == 0
     whole = json.load(open(full))
     assert whole["value"] == pytest.approx(out["value"], rel=1e-5) and "configs" in whole and "materialize" in whole
+
+
+@pytest.mark.timeout(900)
+def test_bench_plain_run_is_lean(tmp_path):
+    """``python bench.py --gpus 1 --steps 20 --warmup 5`` -- the driver's command, run for every change: one strict-JSON
+    line with the headline of the timed steps and ``config``, no side legs and no side file, and at most 30 s of the
+    whole process's wall clock (start to exit) outside the warm-up and timed steps."""
+    env = dict(os.environ)
+    full = str(tmp_path / "bench_full.json")
+    env["CLR_BENCH_FULL"] = full
+    K, Wm = 20, 5
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(K), "--warmup", str(Wm)]
+    t0 = time.perf_counter()
+    r = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=840)
+    wall = time.perf_counter() - t0
+    assert r.returncode == 0, r.stderr.decode()[-3000:]
+    stdout = r.stdout.decode()
+    assert len(stdout.encode()) < 8000, len(stdout)
+
+    def no_constants(name):
+        raise ValueError("not strict JSON: %s" % name)
+
+    out = json.loads(stdout.strip().splitlines()[-1], parse_constant=no_constants)
+    assert out["n_gpus"] == 1 and out["steps"] == K and out["warmup"] == Wm
+    assert out["metric"].startswith("GP log-likelihoods/sec") and out["unit"] == "log-likelihoods/s"
+    assert out["higher_is_better"] is True and out["dtype"] == "f64" and out["vs_baseline"] is None
+    assert abs(out["value"] - 1024 * K / out["timed_region_s"]) <= 1e-4 * out["value"]
+    assert abs(out["ms_per_step"] - out["timed_region_s"] / K * 1e3) <= 1e-4 * out["ms_per_step"]
+    assert "configs[2]" in out["config"]["workload"] and out["config"]["batch_per_gpu"] == 1024
+    assert out["status_not_ok"] == 0
+    for key in ("roofline", "cpu_baseline", "multi_rank_parity"):
+        assert key not in out, key
+    assert out["full_record"] is None and not os.path.exists(full)
+    outside = wall - (K + Wm) * out["ms_per_step"] * 1e-3
+    assert outside <= 30.0, "%.1f s outside the warm-up and timed steps" % outside
 
 
 @pytest.mark.timeout(900)

@@ -323,6 +323,49 @@ def test_bench_headline_line_is_small_strict_json():
     check(lean)
 
 
+def test_bench_plain_run_prints_the_headline_of_the_timed_steps_only(capsys):
+    """Without ``--full`` the run ends in ``plain_finish``: ONE strict-JSON line with the contract's keys and ``config``
+    from the timed region's own numbers, no roofline, CPU baseline or side file, and the plan is released."""
+    import json
+
+    import bench
+
+    class Plan(object):
+        chunks = (96, 1042)
+        closed = False
+
+        def summarize_kernel(self):
+            return "role split, lazy decay"
+
+        def close(self):
+            self.closed = True
+
+    plan = Plan()
+    status = np.zeros(1024, dtype=np.int32)
+    status[5] = 2
+    step = (np.zeros(1024), np.zeros(1024), np.zeros(1024), status)
+    K, dt = 20, 0.25
+    out = bench.plain_finish(bench.Dist(), plan, 1024, 100000, 2, 3, K, 5, dt, step, None)
+    assert plan.closed
+    lines = capsys.readouterr().out.strip().splitlines()
+    assert len(lines) == 1
+
+    def no_constants(name):
+        raise ValueError("not strict JSON: %s" % name)
+
+    line = json.loads(lines[0], parse_constant=no_constants)
+    for key in bench.HEADLINE_KEYS:
+        assert key in line, key
+    assert line["metric"] == bench.METRIC and line["unit"] == "log-likelihoods/s" and line["dtype"] == "f64"
+    assert line["higher_is_better"] is True and line["steps"] == K and line["warmup"] == 5 and line["n_gpus"] == 1
+    assert line["value"] == pytest.approx(1024 * K / dt, rel=1e-5) and line["ms_per_step"] == pytest.approx(dt / K * 1e3, rel=1e-5)
+    assert line["config"]["workload"].startswith("BASELINE configs[2]") and line["config"]["scan_chunks"] == 96
+    assert line["status_not_ok"] == 1 and line["full_record"] is None and line["extra_keys"] == []
+    for key in ("roofline", "cpu_baseline", "multi_rank_parity"):
+        assert key not in line, key
+    assert out["value"] == pytest.approx(line["value"], rel=1e-5)
+
+
 def test_bench_dump_outputs_writes_float64_arrays_within_the_size_cap(tmp_path, monkeypatch):
     """``bench.py --dump-outputs DIR``: one float64 .npy per result array of the step (the int32 status codes included);
     above the size cap a fixed, seeded sample of the problems with its indices, the same sample on every run; several
