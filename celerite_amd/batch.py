@@ -98,6 +98,12 @@ def _load():
     lib.clr_sharded_get_results.argtypes = [C.c_void_p, _dp, _dp, _dp, _ip]
     lib.clr_sharded_evaluate.argtypes = [C.c_void_p] + [_dp] * 7 + [_dp, _dp, _dp, _ip]
     lib.clr_sharded_run_timed.argtypes = [C.c_void_p, C.c_int, _dp]
+    lib.clr_batch_set_mean.argtypes = [C.c_void_p, _dp, C.c_long]
+    lib.clr_batch_evaluate_mean.argtypes = [C.c_void_p, C.c_void_p, C.c_long] + [C.c_void_p] * 11
+    lib.clr_batch_grad_mean.argtypes = [C.c_void_p, _dp, _dp, _dp, _ip]
+    lib.clr_sharded_set_mean.argtypes = [C.c_void_p, _dp, C.c_long]
+    lib.clr_sharded_evaluate_mean.argtypes = [C.c_void_p, _dp, C.c_long] + [_dp] * 10 + [_ip]
+    lib.clr_sharded_grad_mean.argtypes = [C.c_void_p, _dp, _dp, _dp, _ip]
     lib.clr_device_info.argtypes = [C.c_char_p, C.c_size_t, _ip, C.POINTER(C.c_size_t)]
     lib.clr_set_device.argtypes = [C.c_int]
     _lib = lib
@@ -193,6 +199,19 @@ def _ptr(a):
     return a.ctypes.data_as(_dp)
 
 
+def _mean_arg(mu, B):
+    """``(array, stride)`` of a constant mean for ``clr_*_set_mean``: a scalar (stride 0), ``(B,)`` (stride 1) or
+    ``None`` (no mean)."""
+    if mu is None:
+        return None, 0
+    m = np.asarray(mu, dtype=np.float64)
+    if m.ndim == 0:
+        return np.ascontiguousarray(m.reshape(1)), 0
+    if m.shape != (B,):
+        raise ValueError("dimension mismatch")
+    return np.ascontiguousarray(m), 1
+
+
 class BatchedGP(object):
     """Device-resident plan for B problems of N samples and a fixed kernel shape.
 
@@ -227,10 +246,11 @@ class BatchedGP(object):
 
     # -- inputs -------------------------------------------------------------
     def set_series(self, t, diag, y):
-        """``t``, ``diag`` (= yerr**2), ``y`` (mean already subtracted): each
-        ``(B, N)`` or ``(N,)`` for one series shared by all problems.  ``t``
-        must be sorted along the last axis (checked: GP.compute does the same,
-        celerite.py:126-129)."""
+        """``t``, ``diag`` (= yerr**2), ``y``: each ``(B, N)`` or ``(N,)`` for one
+        series shared by all problems.  ``t`` must be sorted along the last axis
+        (checked: GP.compute does the same, celerite.py:126-129).  A mean set by
+        :meth:`set_mean` stays in force and is subtracted from the new ``y`` on
+        the device; without one ``y`` is taken as it is (mean zero)."""
         arrs, strides = [], []
         for a in (t, diag, y):
             a = _f64(a)
@@ -253,6 +273,13 @@ class BatchedGP(object):
             lib.clr_batch_clear_series.argtypes = [C.c_void_p]
             _check(lib.clr_batch_clear_series(self._h))
             raise ValueError("the input coordinates must be sorted")
+
+    def set_mean(self, mu):
+        """A constant mean per problem (``clr_batch_set_mean``): a scalar for all problems, ``(B,)``, or ``None`` to
+        remove it.  Every route that reads ``y`` -- the evaluation, :meth:`solve` of ``None``, :meth:`predict`, the
+        gradient -- then sees the residual ``y - mu_b``, formed on the device from the uploaded ``y``."""
+        m, stride = _mean_arg(mu, self.B)
+        _check(_load().clr_batch_set_mean(self._h, None if m is None else _ptr(m), stride))
 
     def set_coefficients(self, a_real, c_real, a_comp, b_comp, c_comp, d_comp, jitter=0.0):
         """Coefficient tables ``(B, J_real)`` / ``(B, J_comp)``; ``jitter`` scalar or ``(B,)``."""
@@ -319,11 +346,12 @@ class BatchedGP(object):
                                              st.ctypes.data_as(_ip)))
         return ll, ld, q, st
 
-    def evaluate(self, a_real, c_real, a_comp, b_comp, c_comp, d_comp, jitter=0.0):
+    def evaluate(self, a_real, c_real, a_comp, b_comp, c_comp, d_comp, jitter=0.0, mean=None):
         """One optimiser / MCMC evaluation in ONE library call (``clr_batch_evaluate``): new coefficient tables in,
         ``(loglike, logdet, quad, status)`` of all B problems out -- ``set_coefficients`` + ``enqueue`` + ``results``
         without two of the three trips through ctypes.  Arrays that already are C-contiguous float64 of the right shape
-        are passed as they are."""
+        are passed as they are.  ``mean`` (a scalar or ``(B,)``): :meth:`set_mean` in the same call
+        (``clr_batch_evaluate_mean``); ``None`` leaves the mean in force as it is."""
         B, JR, JC = self.B, self.J_real, self.J_comp
         tabs = []
         for a, w in ((a_real, JR), (c_real, JR), (a_comp, JC), (b_comp, JC), (c_comp, JC), (d_comp, JC)):
@@ -335,6 +363,12 @@ class BatchedGP(object):
             tabs.append(a)
         jit = np.ascontiguousarray(np.broadcast_to(np.asarray(jitter, dtype=np.float64), (B,)))
         ll, ld, q, st = np.empty(B), np.empty(B), np.empty(B), np.empty(B, dtype=np.int32)
+        if mean is not None:
+            m, stride = _mean_arg(mean, B)
+            _check(_load().clr_batch_evaluate_mean(self._h, m.ctypes.data, stride, jit.ctypes.data,
+                                                   *([a.ctypes.data for a in tabs] + [ll.ctypes.data, ld.ctypes.data,
+                                                                                     q.ctypes.data, st.ctypes.data])))
+            return ll, ld, q, st
         fn = self._evaluate_fn
         if fn is None:
             fn = _load().clr_batch_evaluate
@@ -362,7 +396,8 @@ class BatchedGP(object):
     def solve(self, b=None):
         """``K_p^-1 b_p`` for every problem from the factor of the last materialising run (``clr_batch_solve``;
         ``CholeskySolver.solve``, cholesky.h:218-318, for B problems at once).  ``b``: ``(B, N)`` or ``(B, nrhs, N)``;
-        ``None``: the plan's own ``y`` (no upload).  Returns an array of the same shape."""
+        ``None``: the plan's own ``y`` less the mean of :meth:`set_mean` (no upload).  Returns an array of the same
+        shape."""
         lib = _load()
         lib.clr_batch_solve.argtypes = [C.c_void_p, C.c_int, _dp, _dp]
         if b is None:
@@ -378,7 +413,8 @@ class BatchedGP(object):
         return x
 
     def predict(self, xs):
-        """The conditional mean ``K_p(x*, t_p) K_p^-1 y_p`` of every problem at the prediction points ``xs`` --
+        """The conditional mean ``mu_p + K_p(x*, t_p) K_p^-1 (y_p - mu_p)`` of every problem (``mu_p`` the mean of
+        :meth:`set_mean`, zero without one; ``GP.predict``, celerite.py:279) at the prediction points ``xs`` --
         ``(M,)`` shared by all problems or ``(B, M)`` -- from the factor of the last materialising run
         (``clr_batch_predict``; ``CholeskySolver.predict``, cholesky.h:599-698, for B problems).  Returns ``(B, M)``."""
         lib = _load()
@@ -532,12 +568,17 @@ class BatchedGP(object):
         return dict(zip(("active", "chunks", "chunk_len", "warmup_min", "warmup_max", "settled", "fallbacks"),
                         [x.value for x in v]))
 
-    def grad_log_likelihood(self):
+    def grad_log_likelihood(self, mean_partial=False):
         """``(value[B], grad[B, 1 + 2 J_real + 4 J_comp], status[B])`` at the coefficients in force, parallel in n
         (``clr_batch_grad``; the reference's conventions per problem, ``CholeskySolver.grad_log_likelihood``,
-        solver.cpp:347-463)."""
+        solver.cpp:347-463).  ``mean_partial=True``: ``(value, grad, dmean[B], status)`` with ``dmean = d loglike /
+        d mu = 1^T K^-1 (y - mu)`` (``clr_batch_grad_mean``; the last column of :func:`chain_gradient`)."""
         NG = 1 + 2 * self.J_real + 4 * self.J_comp
         value, grad, st = np.empty(self.B), np.empty((self.B, NG)), np.empty(self.B, dtype=np.int32)
+        if mean_partial:
+            dmean = np.empty(self.B)
+            _check(_load().clr_batch_grad_mean(self._h, _ptr(value), _ptr(grad), _ptr(dmean), st.ctypes.data_as(_ip)))
+            return value, grad, dmean, st
         _check(_load().clr_batch_grad(self._h, _ptr(value), _ptr(grad), st.ctypes.data_as(_ip)))
         return value, grad, st
 
@@ -836,12 +877,23 @@ class ShardedBatchedGP(object):
         jit, blocks = self._coeff_blocks(a_real, c_real, a_comp, b_comp, c_comp, d_comp, jitter)
         self._ok(_load().clr_sharded_set_coefficients(self._h, _ptr(jit), *[_ptr(b) for b in blocks]))
 
-    def grad_log_likelihood(self):
+    def set_mean(self, mu):
+        """A constant mean (a scalar, ``(B,)`` or ``None``), as :meth:`BatchedGP.set_mean`; every shard takes its
+        slice (``clr_sharded_set_mean``)."""
+        m, stride = _mean_arg(mu, self.B)
+        self._ok(_load().clr_sharded_set_mean(self._h, None if m is None else _ptr(m), stride))
+
+    def grad_log_likelihood(self, mean_partial=False):
         """``(value[B], grad[B, 1 + 2 J_real + 4 J_comp], status[B])`` at the coefficients in force: every shard's
-        plan gradient concurrently (``clr_sharded_grad``)."""
+        plan gradient concurrently (``clr_sharded_grad``).  ``mean_partial=True``: ``(value, grad, dmean, status)``
+        as :meth:`BatchedGP.grad_log_likelihood` (``clr_sharded_grad_mean``)."""
         NG = 1 + 2 * self.J_real + 4 * self.J_comp
         value, grad, st = np.empty(self.B), np.empty((self.B, NG)), np.empty(self.B, dtype=np.int32)
         lib = _load()
+        if mean_partial:
+            dmean = np.empty(self.B)
+            self._ok(lib.clr_sharded_grad_mean(self._h, _ptr(value), _ptr(grad), _ptr(dmean), st.ctypes.data_as(_ip)))
+            return value, grad, dmean, st
         lib.clr_sharded_grad.argtypes = [C.c_void_p, _dp, _dp, _ip]
         self._ok(lib.clr_sharded_grad(self._h, _ptr(value), _ptr(grad), st.ctypes.data_as(_ip)))
         return value, grad, st
@@ -866,11 +918,17 @@ class ShardedBatchedGP(object):
         self.enqueue()
         return self.results()
 
-    def evaluate(self, a_real, c_real, a_comp, b_comp, c_comp, d_comp, jitter=0.0):
+    def evaluate(self, a_real, c_real, a_comp, b_comp, c_comp, d_comp, jitter=0.0, mean=None):
         """One optimiser / MCMC evaluation: new coefficients in, ``(loglike, logdet,
-        quad, status)`` of all B problems out."""
+        quad, status)`` of all B problems out.  ``mean``: as :meth:`BatchedGP.evaluate`
+        (``clr_sharded_evaluate_mean``)."""
         jit, blocks = self._coeff_blocks(a_real, c_real, a_comp, b_comp, c_comp, d_comp, jitter)
         ll, ld, q, st = self._out()
+        if mean is not None:
+            m, stride = _mean_arg(mean, self.B)
+            self._ok(_load().clr_sharded_evaluate_mean(self._h, _ptr(m), stride, _ptr(jit), *(
+                [_ptr(b) for b in blocks] + [_ptr(ll), _ptr(ld), _ptr(q), st.ctypes.data_as(_ip)])))
+            return ll, ld, q, st
         self._ok(_load().clr_sharded_evaluate(self._h, _ptr(jit), *([_ptr(b) for b in blocks] +
                                               [_ptr(ll), _ptr(ld), _ptr(q), st.ctypes.data_as(_ip)])))
         return ll, ld, q, st
@@ -1045,10 +1103,18 @@ def kernel_coefficient_jacobian_table(kernel, parameter_vectors):
     return np.array(jac), np.array(jit)
 
 
-def chain_gradient(grad, jac, jitter_jac):
+def chain_gradient(grad, jac, jitter_jac, dmean=None):
     """``d loglike / d parameters`` of every draw, ``[B, P]``, from the batched coefficient gradient ``grad``
     (``[B, 1 + 2 J_real + 4 J_comp]``: column 0 the jitter partial, as ``BatchedGP.grad_log_likelihood`` returns
     it) and the tables of :func:`kernel_coefficient_jacobian_table` (what ``GP.grad_log_likelihood`` does for one
-    problem, celerite.py:286-305)."""
+    problem, celerite.py:286-305).  ``dmean`` (``[B]``, ``grad_log_likelihood(mean_partial=True)``): appended as the
+    last column, the reference's order -- the kernel's parameters, then the constant mean's (celerite.py:224-227);
+    ``[B, P + 1]``."""
     grad = np.asarray(grad, dtype=np.float64)
-    return np.einsum("bpc,bc->bp", jac, grad[:, 1:]) + jitter_jac * grad[:, :1]
+    full = np.einsum("bpc,bc->bp", jac, grad[:, 1:]) + jitter_jac * grad[:, :1]
+    if dmean is None:
+        return full
+    dmean = np.asarray(dmean, dtype=np.float64).reshape(-1, 1)
+    if dmean.shape[0] != full.shape[0]:
+        raise ValueError("dimension mismatch")
+    return np.concatenate([full, dmean], axis=1)

@@ -261,6 +261,85 @@ static void warm_select(clr_batch* h) {
   h->warm_K_dirty = h->warm_active;  // (uploaded behind the next coefficients, or by the next enqueue)
 }
 
+// The residual y - mu of clr_batch_set_mean from the caller's series in `y_src`: one elementwise pass into `y`, where
+// every route reads its series; the copies derived from `y` are then stale (a shared series with a per-problem mean
+// becomes a per-problem residual: the copies are re-sized by the launches that rebuild them).
+static int apply_mean(clr_batch* h) {
+  const long N = h->N;
+  const bool per_problem = h->y_src_stride != 0 || h->mean_stride != 0;
+  const int nout = per_problem ? h->B : 1;
+  int st;
+  if ((st = h->y.reserve((size_t)nout * N)) != CLR_OK) return st;
+  const size_t nm = h->host_mean.size();
+  if ((st = h->mean_dev.reserve(nm)) != CLR_OK) return st;
+  // through pinned staging: the copy is asynchronous, and only the previous upload -- not the stream -- is waited for
+  // before the staging is rewritten
+  if (h->mean_ev) HIP_TRY(hipEventSynchronize(h->mean_ev.get()));
+  else HIP_TRY(clr::create_event(h->mean_ev, hipEventDisableTiming));
+  if ((st = h->mean_pin.reserve(nm)) != CLR_OK) return st;
+  std::copy(h->host_mean.begin(), h->host_mean.end(), h->mean_pin.p);
+  HIP_TRY(hipMemcpyAsync(h->mean_dev.p, h->mean_pin.p, nm * sizeof(double), hipMemcpyHostToDevice, h->stream.get()));
+  HIP_TRY(hipEventRecord(h->mean_ev.get(), h->stream.get()));
+  clr::launch_residual(h->y_src.p, h->y_src_stride, h->mean_dev.p, h->mean_stride, nout, (int)N, h->y.p, h->stream.get());
+  HIP_TRY(hipGetLastError());
+  const long stride = per_problem ? N : 0;
+  if (stride != h->y_stride) h->relayout_pending = true;
+  h->y_stride = stride;
+  h->relayout_y_pending = true;
+  h->small_copy_pending = true;
+  h->warm_copy_pending = true;
+  return CLR_OK;
+}
+
+// the chunk-interleaved copy of `y` alone (a new mean on an unchanged series): batch_relayout's y job
+static bool relayout_residual(clr_batch* h) {
+  if (!((h->layout == 1 || split_active(h)) && h->nchunk > 1)) return false;
+  const long cells = (long)h->nchunk * h->L;
+  clr::launch_relayout(h->y.p, h->y_stride, h->yT.p, h->y_stride ? cells : 0, h->y_stride ? h->B : 1, h->N, h->L,
+                       h->nchunk, 0, h->stream.get());
+  return true;
+}
+
+int clr_batch_set_mean(clr_batch* h, const double* mu, long mu_stride) {
+  int st = require_device(h->device);
+  if (st != CLR_OK) return st;
+  if (mu && mu_stride != 0 && mu_stride != 1) return fail(CLR_INVALID_ARGUMENT, "clr_batch_set_mean: mu_stride is 1 (mu[B]) or 0 (one value)");
+  const size_t n = mu ? (mu_stride ? (size_t)h->B : 1) : 0;
+  for (size_t i = 0; i < n; ++i)
+    if (!std::isfinite(mu[i])) return fail(CLR_INVALID_ARGUMENT, "clr_batch_set_mean: a non-finite mean");
+  if (mu && h->have_mean && h->have_series && h->mean_stride == mu_stride && h->host_mean.size() == n &&
+      memcmp(h->host_mean.data(), mu, n * sizeof(double)) == 0)
+    return CLR_OK;  // (the residual in HBM is this mean's)
+  if (!mu && !h->have_mean) return CLR_OK;
+  if ((st = warm_resolve(h, nullptr)) != CLR_OK) return st;  // (an evaluation in flight is settled on ITS residual)
+  if (!mu) {
+    h->have_mean = false;
+    h->host_mean.clear();
+    if (h->have_series) {  // the caller's series is the pipeline's again
+      std::swap(h->y, h->y_src);
+      if (h->y_src_stride != h->y_stride) h->relayout_pending = true;
+      h->y_stride = h->y_src_stride;
+      h->relayout_y_pending = true;
+      h->small_copy_pending = true;
+      h->warm_copy_pending = true;
+    }
+    return CLR_OK;
+  }
+  if (!h->have_mean && h->have_series) {  // the caller's series moves aside, `y` will hold the residual
+    std::swap(h->y, h->y_src);
+    h->y_src_stride = h->y_stride;
+  }
+  h->host_mean.assign(mu, mu + n);
+  h->mean_stride = mu_stride;
+  h->have_mean = true;
+  if (!h->have_series) return CLR_OK;  // (clr_batch_set_series applies it)
+  if ((st = apply_mean(h)) != CLR_OK) {
+    h->have_series = false;  // (no half-formed residual is ever evaluated: set the series again)
+    return st;
+  }
+  return CLR_OK;
+}
+
 int clr_batch_set_series(clr_batch* h, const double* t, long t_stride, const double* diag,
                          long diag_stride, const double* y, long y_stride) {
   int st = require_device(h->device);
@@ -335,6 +414,11 @@ int clr_batch_set_series(clr_batch* h, const double* t, long t_stride, const dou
     h->dtmin = (finite_min < 0.0) ? finite_min : (nan ? NAN : finite_min);
   }
   h->have_series = true;
+  if (h->have_mean) {  // (the upload went to `y`: it becomes the caller's series, `y` the residual)
+    std::swap(h->y, h->y_src);
+    h->y_src_stride = y_stride;
+    if ((st = apply_mean(h)) != CLR_OK) { h->have_series = false; return st; }
+  }
   if ((st = warm_scan_spans(h)) != CLR_OK) { h->have_series = false; return st; }
   h->set_series_host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - host_t0).count();
   h->grad_span_valid = false;
@@ -1116,7 +1200,8 @@ int clr_batch_enqueue(clr_batch* h, int materialize) {
     HIP_TRY(hipGetLastError());
     return CLR_OK;
   }
-  if (h->relayout_pending && batch_relayout(h)) h->relayout_pending = false;
+  if (h->relayout_pending && batch_relayout(h)) h->relayout_pending = h->relayout_y_pending = false;
+  else if (h->relayout_y_pending && relayout_residual(h)) h->relayout_y_pending = false;
   mark(1);
   h->launch->summarize(P, h->stream.get());
   mark(2);
@@ -1792,6 +1877,11 @@ int clr_batch_predict(clr_batch* h, int M, const double* xs, long xs_stride, dou
   }
   if (frame.finish(pred, dpred.p, B * Mm) != CLR_OK)
     return fail(CLR_HIP_ERROR, "clr_batch_predict: kernels or the download failed");
+  if (h->have_mean)  // the mean plus the conditional mean of the residual (celerite.py:279)
+    for (size_t p = 0; p < B; ++p) {
+      const double m = h->host_mean[h->mean_stride ? p : 0];
+      for (size_t k = 0; k < Mm; ++k) pred[p * Mm + k] = m + pred[p * Mm + k];
+    }
   return CLR_OK;
 }
 
@@ -1825,7 +1915,10 @@ int clr_batch_run_timed(clr_batch* h, int materialize, int steps, int relayout_e
     if (kernel_ms) { for (int j = 0; j < 6; ++j) kernel_ms[j] = 0.0; kernel_ms[4] = tot; }
     return CLR_OK;
   }
-  if (!warm_runs(h, materialize) && h->relayout_pending && !relayout_each_step && batch_relayout(h)) h->relayout_pending = false;
+  if (!warm_runs(h, materialize) && h->relayout_pending && !relayout_each_step && batch_relayout(h))
+    h->relayout_pending = h->relayout_y_pending = false;
+  else if (!warm_runs(h, materialize) && h->relayout_y_pending && !relayout_each_step && relayout_residual(h))
+    h->relayout_y_pending = false;
   // one event per kernel boundary per step, all recorded on the handle's stream
   const int NK = 6;
   std::vector<clr::Event> ev((size_t)steps * (NK + 1));
@@ -1886,7 +1979,7 @@ int clr_batch_run_timed(clr_batch* h, int materialize, int steps, int relayout_e
     HIP_TRY(hipEventRecord(e[6].get(), h->stream.get()));
   }
   if (relayout_each_step && !warm_runs(h, materialize) && (h->layout == 1 || split_active(h)) && h->nchunk > 1)
-    h->relayout_pending = false;
+    h->relayout_pending = h->relayout_y_pending = false;
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(h->stream.get()));
   double k[NK] = {0, 0, 0, 0, 0, 0};
@@ -1915,6 +2008,15 @@ int clr_batch_evaluate(clr_batch* h, const double* jitter, const double* a_real,
   if (st == CLR_OK) st = clr_batch_enqueue(h, 0);
   if (st == CLR_OK) st = clr_batch_get_results(h, loglike, logdet, quad, status);
   return st;
+}
+
+int clr_batch_evaluate_mean(clr_batch* h, const double* mean, long mean_stride, const double* jitter,
+                            const double* a_real, const double* c_real, const double* a_comp, const double* b_comp,
+                            const double* c_comp, const double* d_comp, double* loglike, double* logdet, double* quad,
+                            int* status) {
+  const int st = clr_batch_set_mean(h, mean, mean_stride);
+  if (st != CLR_OK) return st;
+  return clr_batch_evaluate(h, jitter, a_real, c_real, a_comp, b_comp, c_comp, d_comp, loglike, logdet, quad, status);
 }
 
 int clr_batch_log_likelihood(int B, int N, int J_real, int J_comp, const double* jitter,

@@ -241,7 +241,7 @@ int clr_batch_grad(clr_batch* h, double* value, double* grad, int* status) {
     P.g_seg = P.g_nchunk >= 256 ? std::max(16, (int)std::sqrt(0.5 * P.g_nchunk)) : 0;
     const size_t ngr = P.g_seg ? (size_t)((P.g_nchunk + P.g_seg - 1) / P.g_seg) : 0;
     const size_t nslab = (size_t)((P.g_nchunk + 255) / 256);
-    const size_t small = pc * (RID + 3 * (SZ + J) + NG + 2) + B + B * ngr * (RID + SZ + J) + B * nslab * 33;
+    const size_t small = pc * (RID + 3 * (SZ + J) + NG + 2) + B + B * ngr * (RID + SZ + J) + B * nslab * 33 + pc;
     if (!flags_fit || h->g_rec.reserve(B * (size_t)P.g_rec_stride) != CLR_OK ||
         h->g_ck.reserve(B * (size_t)P.g_ck_stride) != CLR_OK || h->g_riders.reserve(small) != CLR_OK) {
       h->g_rec.release(); h->g_ck.release();
@@ -260,8 +260,12 @@ int clr_batch_grad(clr_batch* h, double* value, double* grad, int* status) {
       P.g_grp_riders = ngr ? P.g_drift_max + B : nullptr;
       P.g_grp_adj = ngr ? P.g_grp_riders + B * ngr * RID : nullptr;
       P.g_slab = P.g_drift_max + B + B * ngr * (RID + SZ + J);
+      // clr_batch_grad_mean: the sweep also sums the adjoint of y per chunk, and d loglike / d mu = 1/2 of their sum
+      P.g_ysum = h->grad_want_mean ? P.g_slab + B * nslab * 33 : nullptr;
       P.g_from_elems = (P.g_m == 1 && h->grad_riders_mode != 1) ? 1 : 0;
       h->launch->grad_reverse(P, h->stream.get());
+      if (P.g_ysum) clr::launch_mean_reduce(P.g_ysum, h->B, P.g_nchunk, P.need_exact, h->mean_out.p, h->stream.get());
+      P.g_ysum = nullptr;
       HIP_TRY(hipGetLastError());
       h->grad_reverse_used = true;
     }
@@ -305,6 +309,8 @@ int clr_batch_grad(clr_batch* h, double* value, double* grad, int* status) {
       if (!(drift[b] <= h->grad_drift_tol)) { mask[b] = 1; ++nre; }
     }
     h->grad_forward_reruns = nre;
+    if (h->grad_want_mean)  // (the mean's partial of a problem redone forwards is not certified either)
+      for (size_t b = 0; b < B; ++b) h->grad_mean_done[b] = stt[b] == CLR_OK && lvl[b] < 2 && !mask[b];
     if (nre) {
       int* dmask = reinterpret_cast<int*>(h->g_res.p + B * NG + B * (NG + 1));
       HIP_TRY(hipMemcpyAsync(dmask, mask.data(), B * sizeof(int), hipMemcpyHostToDevice, h->stream.get()));
@@ -451,6 +457,52 @@ int clr_batch_grad_log_likelihood(int B, int N, int J_real, int J_comp, const do
       for (size_t g = 0; g < NG; ++g) grad[b * NG + g] = bad ? 0.0 : back[Bn + b * NG + g];
     if (grad && !(jitter[b] > 2.220446049250313e-16)) grad[b * NG] = 0.0;  // solver.cpp:379-389,419-426
   }
+  return CLR_OK;
+}
+
+int clr_batch_grad_mean(clr_batch* h, double* value, double* grad, double* dmean, int* status) {
+  int st = require_device(h->device);
+  if (st != CLR_OK) return st;
+  const size_t B = (size_t)h->B;
+  std::vector<int> stat(B);
+  // [B] partials | [B] ints: the problems left to the recurrence below
+  if (dmean && (st = h->mean_out.reserve(B + (B + 1) / 2)) != CLR_OK) return st;
+  h->grad_want_mean = dmean != nullptr;
+  h->grad_mean_done.assign(B, 0);
+  st = clr_batch_grad(h, value, grad, stat.data());
+  h->grad_want_mean = false;
+  if (st != CLR_OK) return st;
+  if (status) std::copy(stat.begin(), stat.end(), status);
+  if (!dmean) return CLR_OK;
+  // The narrow reverse route has settled its certified problems already (1/2 the sum of the sweep's adjoint of y).  The
+  // rest -- the other routes, the problems the evaluation settled sequentially or the sweep handed to forward mode --
+  // run the reference recurrence once more with the substitutions of r and of the ones (mean_partial_batch).
+  std::vector<int> rest;
+  for (size_t b = 0; b < B; ++b)
+    if (stat[b] == CLR_OK && !h->grad_mean_done[b]) rest.push_back((int)b);
+  clr::BatchParams P;
+  h->in_fallback = true;  // (the row-major arrays)
+  st = batch_params(h, 0, P);
+  h->in_fallback = false;
+  if (st != CLR_OK) return st;
+  int* didx = reinterpret_cast<int*>(h->mean_out.p + B);
+  if (!rest.empty())
+    HIP_TRY(hipMemcpyAsync(didx, rest.data(), rest.size() * sizeof(int), hipMemcpyHostToDevice, h->stream.get()));
+  clr::GenericBatch G;
+  memset(&G, 0, sizeof(G));
+  G.B = h->B; G.N = h->N; G.J_real = h->J_real; G.J_comp = h->J_comp; G.J_general = h->J_general;
+  G.a_real = P.a_real; G.c_real = P.c_real; G.a_comp = P.a_comp; G.b_comp = P.b_comp; G.c_comp = P.c_comp;
+  G.d_comp = P.d_comp; G.jitter = P.jitter;
+  G.t = h->t.p; G.diag = h->diag.p; G.y = h->y.p;
+  G.t_stride = h->t_stride; G.diag_stride = h->diag_stride; G.y_stride = h->y_stride;
+  G.A = h->gA.p; G.U = h->gU.p; G.V = h->gV.p;
+  G.A_stride = h->gA_stride; G.U_stride = h->gU_stride; G.V_stride = h->gV_stride;
+  clr::launch_mean_partial_batch(G, didx, (int)rest.size(), h->mean_out.p, h->stream.get());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(dmean, h->mean_out.p, B * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
+  HIP_TRY(hipStreamSynchronize(h->stream.get()));
+  for (size_t b = 0; b < B; ++b)
+    if (stat[b] != CLR_OK) dmean[b] = 0.0;  // (the gradient's quiet semantics: a zero gradient)
   return CLR_OK;
 }
 

@@ -234,7 +234,21 @@ struct clr_batch {
   clr::PinnedBuffer<double> pin;      // pinned host staging: coefficient uploads, result downloads
   DevBuf tT, dT, yT;                  // chunk-interleaved copies the kernels read
   long t_stride = 0, diag_stride = 0, y_stride = 0;
-  int layout = 2;                     // 0 row-major direct, 1 interleaved copy, 2 staged through LDS
+  // clr_batch_set_mean: with a mean in force `y` holds the residual y - mu that every route reads, and `y_src` the
+  // caller's series as uploaded (y_src_stride: its stride)
+  bool have_mean = false;
+  long mean_stride = 0;               // 1: one value per problem, 0: one value for all
+  std::vector<double> host_mean;      // [B] or [1]
+  DevBuf mean_dev, y_src, mean_out;   // the mean on the device; the caller's y; clr_batch_grad_mean's partials [B]
+  long y_src_stride = 0;
+  bool relayout_y_pending = false;    // only the residual changed: the interleaved copy of y alone is rebuilt
+  clr::PinnedBuffer<double> mean_pin; // pinned staging of the mean's upload ...
+  clr::Event mean_ev;                 // ... recorded behind it: the staging is rewritten only once the copy has run
+  // clr_batch_grad_mean: the narrow reverse sweep sums the adjoint of y per chunk (BatchParams::g_ysum) and reduces it
+  // into mean_out; grad_mean_done[b] says which problems it settled (the rest take mean_partial_batch)
+  bool grad_want_mean = false;
+  std::vector<char> grad_mean_done;
+  int layout = 2;                    // 0 row-major direct, 1 interleaved copy, 2 staged through LDS
   double tmax = 0.0, dmax = 0.0;      // max |t|, max |d_comp| (host side, O(B))
   double dxmax = 0.0, cmax = 0.0;     // max |t[n+1] - t[n]|, max decay rate: the lazy-decay kernels need cmax * dxmax < 2^-7
   // floors for the four maxima above (clr_batch_set_selection_bounds): a sharded plan hands every shard the maxima

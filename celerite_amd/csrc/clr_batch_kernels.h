@@ -122,6 +122,7 @@ struct BatchParams {
   // reverse mode: per-sample record w, D, x [B][step][J + 2][chunk], stored states every g_K steps
   // [B][checkpoint][SZ + J][chunk], state after / adjoint at the end of every chunk, per-chunk partials and drift
   double *g_rec, *g_ck, *g_ends, *g_adj, *g_adj0, *g_part, *g_drift, *g_drift_max;
+  double* g_ysum;                    // [B][gradient chunks] or null: each chunk's sum of the adjoint of y (clr_batch_grad_mean)
   double* g_slab;                    // [B][slabs of 256 gradient chunks][33]: partial sums of the partials | the slab's certificate
   double *g_grp_riders, *g_grp_adj;  // two-level adjoint walk: composed riders / end adjoints of groups of g_seg gradient chunks
   int g_seg;                         // 0: one walk over all gradient chunks

@@ -39,6 +39,16 @@ struct GenericBatch {
   int* out_status;
 };
 void launch_generic_loglike_batch(const GenericBatch& G, hipStream_t s);
+// d loglike / d mu = 1^T K^-1 r for the problems idx[0..count) of G (idx == nullptr: problems 0..count; G.y: the
+// residual r): the recurrence of generic_loglike_batch_kernel carrying the forward substitution of a vector of ones
+// beside that of r, dmean[b] = sum_n x1_n x_n / D_n; 0 where a pivot fails.  One workgroup per problem, any width.
+void launch_mean_partial_batch(const GenericBatch& G, const int* idx, int count, double* dmean, hipStream_t s);
+// dmean[b] = 1/2 sum_c ysum[b][c] (c < nchunk, in order) for the problems with level[b] < 2 (clr_batch_grad_mean on
+// the narrow reverse route: the sweep's per-chunk sums of the adjoint of y; level: BatchParams::need_exact)
+void launch_mean_reduce(const double* ysum, int B, int nchunk, const int* level, double* dmean, hipStream_t s);
+// r[p][n] = y[p * y_stride + n] - mu[p * mu_stride] for p < nout (clr_batch_set_mean; strides 0 = shared)
+void launch_residual(const double* y, long y_stride, const double* mu, long mu_stride, int nout, int N, double* r,
+                     hipStream_t s);
 
 // dot_solve / solve on a stored factor as chunked scans over n (sweep_kernels.hip).
 struct SweepParams {

@@ -749,7 +749,9 @@ CLR_HD void grad_adjoint_walk(int nchunk, const double* riders, double* adj) {
 //     -dt (2 sum_k Sbar'_jk S'_jk + fbar'_j f'_j) summed over the term's rows j.
 // out[NG]: this chunk's share of dL / d(coefficient) (the caller sums the chunks and applies -1/2); adj0_out
 // (may be null): the adjoint at the chunk's first sample, equal to what grad_adjoint_walk found for the end of the
-// previous chunk -- the built-in consistency check of the tests.
+// previous chunk -- the built-in consistency check of the tests.  ysum_out (may be null): the sum over the chunk's
+// samples of xbar = d F / d y_n (F = log det + quad), whose half is this chunk's share of d loglike / d mu for a
+// constant mean mu (r = y - mu: d loglike / d mu = 1/2 sum_n xbar_n = 1^T K^-1 r; clr_batch_grad_mean).
 // The reconstruction inverts a contraction: its rounding errors grow like exp(2 c T) over a time span T (measured on
 // the host instantiation: exact to 1e-13 over c T = 8, lost over c T = 40).  So the forward pass stores states
 // (GradStore: wherever the accumulated decay since the last stored one reaches the growth budget), the sweep continues
@@ -761,7 +763,8 @@ template <int JR, int JC, bool FAST, class Src>
 CLR_HD void grad_backward_chunk(const Problem<JR, JC>& p, Src& src, int L, int N, int n0, const double* end_state,
                                 const double* end_adj, const double* rec, long rstride, double* out,
                                 double* adj0_out = nullptr, GradStore store = GradStore(),
-                                double* mismatch_out = nullptr, const double* start = nullptr) {
+                                double* mismatch_out = nullptr, const double* start = nullptr,
+                                double* ysum_out = nullptr) {
   using Sh = GradShape<JR, JC>;
   constexpr int J = Sh::J, SZ = Sh::SZ, M = JR + JC, NG = Sh::NG;
   double S[SZ], f[J], Sb[SZ], fb[J];
@@ -770,6 +773,7 @@ CLR_HD void grad_backward_chunk(const Problem<JR, JC>& p, Src& src, int L, int N
   CLR_UNROLL
   for (int i = 0; i < J; ++i) { f[i] = end_state[SZ + i]; fb[i] = end_adj[SZ + i]; }
   double g_k0 = 0.0;                       // sum of Dbar: jitter, and every a_real / a_comp
+  double g_y = 0.0;                        // sum of xbar: the adjoint of y
   double g_ar[nz(JR)], g_cr[nz(JR)], g_ac[nz(JC)], g_bc[nz(JC)], g_cc[nz(JC)], g_dc[nz(JC)];
   CLR_UNROLL
   for (int j = 0; j < JR; ++j) { g_ar[j] = 0.0; g_cr[j] = 0.0; }
@@ -927,6 +931,7 @@ CLR_HD void grad_backward_chunk(const Problem<JR, JC>& p, Src& src, int L, int N
     }
     const double Dbar = invD - (x * invD) * (x * invD) - wbw * invD;
     g_k0 += Dbar;
+    g_y += xbar;
     double qb[J], qh[J], ub[J];
     CLR_UNROLL
     for (int j = 0; j < J; ++j) {
@@ -971,6 +976,7 @@ CLR_HD void grad_backward_chunk(const Problem<JR, JC>& p, Src& src, int L, int N
   }
   (void)NG;
   if (mismatch_out) *mismatch_out = drift;
+  if (ysum_out) *ysum_out = g_y;
   if (adj0_out) {
     CLR_UNROLL
     for (int i = 0; i < SZ; ++i) adj0_out[i] = Sb[i];

@@ -294,7 +294,8 @@ __global__ void __launch_bounds__(64) grad_backward_kernel(const BatchParams P) 
   grad_backward_chunk<JR, JC, FAST>(p, src, P.g_m * P.L, P.N, c * P.g_m * P.L, P.g_ends + slot * Wd::START,
                                     P.g_adj + slot * Wd::START, P.g_rec + b * P.g_rec_stride + c, P.g_nchunk,
                                     P.g_part + slot * Sh::NG, P.g_adj0 + slot * Wd::START, grad_store(P, b, c), &drift,
-                                    c > 0 ? P.starts + ((long)b * P.nchunk + (long)c * P.g_m) * Wd::START : nullptr);
+                                    c > 0 ? P.starts + ((long)b * P.nchunk + (long)c * P.g_m) * Wd::START : nullptr,
+                                    P.g_ysum ? P.g_ysum + slot : nullptr);
   if (P.g_K == 1) drift = 0.0;  // (every state is a stored one: no reconstructed state is used)
   P.g_drift[slot] = drift;
 }

@@ -132,10 +132,15 @@ __global__ void __launch_bounds__(256) factor_generic_kernel(GenericProblem g, d
 // Batched fused log-likelihood with general terms: factor_generic_kernel's recurrence with the forward sweep of
 // dot_solve (cholesky.h:343-357) carried along -- f <- phi (f + W_{n-1} x_{n-1}), x_n = y_n - u~_n . f -- one
 // workgroup per problem (blockIdx.x), S in LDS.  status 2 = a pivot D_n < 0 with n >= 1 (cholesky.h:176).
+// MEAN: d loglike / d mu = 1^T K^-1 r = sum_n x1_n x_n / D_n instead (clr_batch_grad_mean; G.y holds the residual r):
+// a second forward substitution, of the ones (x1 = L^-1 1), carried beside that of r; dmean[b] = 0 where a pivot fails;
+// problem = idx[blockIdx.x] when idx is given.  Nothing else is written.
 // ---------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) generic_loglike_batch_kernel(const GenericBatch G) {
+template <bool MEAN>
+__global__ void __launch_bounds__(256) generic_loglike_batch_kernel(const GenericBatch G, double* dmean,
+                                                                    const int* idx) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int b = blockIdx.x, N = G.N, tid = threadIdx.x, nt = blockDim.x;
+  const int b = (MEAN && idx) ? idx[blockIdx.x] : (int)blockIdx.x, N = G.N, tid = threadIdx.x, nt = blockDim.x;
   GenericProblem g;
   g.N = N;
   g.J_real = G.J_real; g.J_comp = G.J_comp; g.J_general = G.J_general;
@@ -159,7 +164,9 @@ __global__ void __launch_bounds__(256) generic_loglike_batch_kernel(const Generi
   double* sp = sq + J;
   double* sf = sp + J;   // f of dot_solve
   double* sg = sf + J;   // u~ . f partial products
-  double* sscal = sg + J;  // [0] = D_n, [1] = failure flag, [2] = x_n
+  double* sf1 = sg + J;                   // (MEAN) f of the substitution of the ones
+  double* sg1 = MEAN ? sf1 + J : sf1;     // (MEAN) u~ . f1 partial products
+  double* sscal = MEAN ? sg1 + J : sg + J;  // [0] = D_n, [1] = failure flag, [2] = x_n, [3] = x1_n (MEAN)
 
   // K(0) summed in the reference's order (cholesky.h:98-99): diag + sum a_real + sum a_comp + jitter (+ A)
   double sum_ar = 0.0, sum_ac = 0.0;
@@ -174,13 +181,16 @@ __global__ void __launch_bounds__(256) generic_loglike_batch_kernel(const Generi
 
   for (int i = tid; i < J * J; i += nt) S[i] = 0.0;
   for (int j = tid; j < J; j += nt) sf[j] = 0.0;
+  if (MEAN)
+    for (int j = tid; j < J; j += nt) sf1[j] = 0.0;
   if (tid == 0) sscal[1] = 0.0;
 
   // sample 0: cholesky.h:100-117, :346-347
   double Dprev = diagonal(0);
   double ld = log(Dprev);
-  double xm1 = y[0];
+  double xm1 = y[0], x1m1 = 1.0;
   double quad = xm1 * (xm1 / Dprev);
+  double acc = x1m1 * (xm1 / Dprev);  // (MEAN) sum_n x1_n x_n / D_n
   {
     const double value = 1.0 / Dprev;
     for (int j = tid; j < J; j += nt) {
@@ -202,60 +212,109 @@ __global__ void __launch_bounds__(256) generic_loglike_batch_kernel(const Generi
       const double f = ph * (sf[j] + swp[j] * xm1);  // cholesky.h:350-352
       sf[j] = f;
       sg[j] = uu * f;
+      if (MEAN) {
+        const double f1 = ph * (sf1[j] + swp[j] * x1m1);
+        sf1[j] = f1;
+        sg1[j] = uu * f1;
+      }
     }
     __syncthreads();
-    for (int idx = tid; idx < J * J; idx += nt) {  // cholesky.h:154-160
-      const int k = idx % J, j = idx / J;
+    for (int idx2 = tid; idx2 < J * J; idx2 += nt) {  // cholesky.h:154-160
+      const int k = idx2 % J, j = idx2 / J;
       if (k <= j) {
         const double xj = Dprev * swp[j];
-        S[idx] = sphi[j] * (sphi[k] * (S[idx] + xj * swp[k]));
+        S[idx2] = sphi[j] * (sphi[k] * (S[idx2] + xj * swp[k]));
       }
     }
     __syncthreads();
     for (int j = tid; j < J; j += nt) {  // q = S u~ ; cholesky.h:163-175
-      double acc = 0.0;
-      for (int k = 0; k < J; ++k) acc += (k <= j ? S[k + (long)J * j] : S[j + (long)J * k]) * su[k];
-      sq[j] = acc;
-      sp[j] = su[j] * acc;
+      double a2 = 0.0;
+      for (int k = 0; k < J; ++k) a2 += (k <= j ? S[k + (long)J * j] : S[j + (long)J * k]) * su[k];
+      sq[j] = a2;
+      sp[j] = su[j] * a2;
     }
     __syncthreads();
     if (tid < 64) {
-      double part = 0.0, xpart = 0.0;
-      for (int j = tid; j < J; j += 64) { part += sp[j]; xpart += sg[j]; }
+      double part = 0.0, xpart = 0.0, x1part = 0.0;
+      for (int j = tid; j < J; j += 64) {
+        part += sp[j];
+        xpart += sg[j];
+        if (MEAN) x1part += sg1[j];
+      }
       part = wave_sum(part);
       xpart = wave_sum(xpart);
+      if (MEAN) x1part = wave_sum(x1part);
       if (tid == 0) {
         const double Dn = diagonal(n) - part;
         if (Dn < 0.0) sscal[1] = 1.0;  // cholesky.h:176
         sscal[0] = Dn;
         sscal[2] = y[n] - xpart;       // :353-354
+        if (MEAN) sscal[3] = 1.0 - x1part;
       }
     }
     __syncthreads();
     if (sscal[1] != 0.0) {
       if (tid == 0) {
-        G.out_status[b] = 2;
-        G.out_ll[b] = -INFINITY;
-        G.out_logdet[b] = NAN;
-        G.out_quad[b] = NAN;
+        if (MEAN) {
+          dmean[b] = 0.0;
+        } else {
+          G.out_status[b] = 2;
+          G.out_ll[b] = -INFINITY;
+          G.out_logdet[b] = NAN;
+          G.out_quad[b] = NAN;
+        }
       }
       return;
     }
     const double Dn = sscal[0], x = sscal[2];
-    ld += log(Dn);
-    quad += x * x / Dn;  // :356
+    if (MEAN) {
+      const double x1 = sscal[3];
+      acc += x1 * (x / Dn);
+      x1m1 = x1;
+    } else {
+      ld += log(Dn);
+      quad += x * x / Dn;  // :356
+    }
     xm1 = x;
     for (int j = tid; j < J; j += nt) swp[j] = (sv[j] - sq[j]) / Dn;  // cholesky.h:170-178
     Dprev = Dn;
     __syncthreads();
   }
   if (tid == 0) {
-    G.out_status[b] = 0;
-    G.out_logdet[b] = ld;
-    G.out_quad[b] = quad;
-    double ll = -0.5 * (quad + ld + N * 1.8378770664093453);
-    if (!isfinite(ld) || !isfinite(ll)) ll = -INFINITY;  // celerite.py:211-218
-    G.out_ll[b] = ll;
+    if (MEAN) {
+      dmean[b] = acc;
+    } else {
+      G.out_status[b] = 0;
+      G.out_logdet[b] = ld;
+      G.out_quad[b] = quad;
+      double ll = -0.5 * (quad + ld + N * 1.8378770664093453);
+      if (!isfinite(ld) || !isfinite(ll)) ll = -INFINITY;  // celerite.py:211-218
+      G.out_ll[b] = ll;
+    }
+  }
+}
+
+// clr_batch_grad_mean on the narrow reverse route: dmean[b] = 1/2 sum over the gradient chunks, in order, of the sweep's
+// per-chunk sums of the adjoint of y (grad_backward_chunk: ysum_out) -- for the problems the sweep ran (level[b] < 2)
+__global__ void __launch_bounds__(64) mean_reduce_kernel(const double* __restrict__ ysum, int B, int nchunk,
+                                                         const int* __restrict__ level, double* __restrict__ dmean) {
+  const int b = blockIdx.x * 64 + threadIdx.x;
+  if (b >= B || level[b] >= 2) return;
+  const double* s = ysum + (long)b * nchunk;
+  double acc = 0.0;
+  for (int c = 0; c < nchunk; ++c) acc += s[c];
+  dmean[b] = 0.5 * acc;
+}
+
+__global__ void __launch_bounds__(256) residual_kernel(const double* __restrict__ y, long y_stride,
+                                                       const double* __restrict__ mu, long mu_stride, int nout,
+                                                       int N, double* __restrict__ r) {
+  for (long p = blockIdx.y; p < nout; p += gridDim.y) {
+    const double m = mu[p * mu_stride];
+    const double* src = y + p * y_stride;
+    double* dst = r + p * (long)N;
+    for (long n = (long)blockIdx.x * blockDim.x + threadIdx.x; n < N; n += (long)gridDim.x * blockDim.x)
+      dst[n] = src[n] - m;
   }
 }
 
@@ -657,10 +716,32 @@ void launch_generic_loglike_batch(const GenericBatch& G, hipStream_t s) {
   const size_t J = (size_t)G.J_real + 2 * (size_t)G.J_comp + (size_t)G.J_general;
   const size_t lds = sizeof(double) * (J * J + 8 * J + 4);
   if (lds > 64 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&generic_loglike_batch_kernel),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&generic_loglike_batch_kernel<false>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   const int threads = J <= 8 ? 64 : 256;
-  hipLaunchKernelGGL(generic_loglike_batch_kernel, dim3(G.B), dim3(threads), lds, s, G);
+  hipLaunchKernelGGL(generic_loglike_batch_kernel<false>, dim3(G.B), dim3(threads), lds, s, G, nullptr, nullptr);
+}
+
+void launch_mean_partial_batch(const GenericBatch& G, const int* idx, int count, double* dmean, hipStream_t s) {
+  if (count <= 0) return;
+  const size_t J = (size_t)G.J_real + 2 * (size_t)G.J_comp + (size_t)G.J_general;
+  const size_t lds = sizeof(double) * (J * J + 10 * J + 4);
+  if (lds > 64 * 1024)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&generic_loglike_batch_kernel<true>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  const int threads = J <= 8 ? 64 : 256;
+  hipLaunchKernelGGL(generic_loglike_batch_kernel<true>, dim3(count), dim3(threads), lds, s, G, dmean, idx);
+}
+
+void launch_mean_reduce(const double* ysum, int B, int nchunk, const int* level, double* dmean, hipStream_t s) {
+  hipLaunchKernelGGL(mean_reduce_kernel, dim3((B + 63) / 64), dim3(64), 0, s, ysum, B, nchunk, level, dmean);
+}
+
+void launch_residual(const double* y, long y_stride, const double* mu, long mu_stride, int nout, int N, double* r,
+                     hipStream_t s) {
+  const int bx = std::min((N + 255) / 256, 64);
+  hipLaunchKernelGGL(residual_kernel, dim3(bx, std::min(nout, 65535)), dim3(256), 0, s, y, y_stride, mu, mu_stride,
+                     nout, N, r);
 }
 
 void launch_diag_only(int N, const double* diag, double jitter, double* D, double* log_det,

@@ -26,6 +26,7 @@
 // A device may be listed more than once: the shards then share that GPU.  That is how the
 // sharding is tested on a one-GPU box (tests/test_gpu_batch.py: 1, 2, 3, 8 shards must give
 // bit-identical results).
+#include <cmath>
 #include <condition_variable>
 #include <functional>
 #include <memory>
@@ -472,6 +473,36 @@ int clr_sharded_evaluate(clr_sharded* h, const double* jitter, const double* a_r
     const long lo = h->lo[s];
     return clr_batch_get_results(h->plan[s], loglike ? loglike + lo : nullptr, logdet ? logdet + lo : nullptr,
                                  quad ? quad + lo : nullptr, status ? status + lo : nullptr);
+  });
+}
+
+int clr_sharded_set_mean(clr_sharded* h, const double* mu, long mu_stride) {
+  if (mu && mu_stride != 0 && mu_stride != 1) return CLR_INVALID_ARGUMENT;
+  const long n = mu ? (mu_stride ? h->B : 1) : 0;
+  for (long i = 0; i < n; ++i)  // (checked here: an invalid mean leaves EVERY shard unchanged)
+    if (!std::isfinite(mu[i])) return CLR_INVALID_ARGUMENT;
+  const int st = resolve_all(h);  // (an evaluation in flight is settled on ITS residual)
+  if (st != CLR_OK) return st;
+  return h->all([=](int s) { return clr_batch_set_mean(h->plan[s], mu ? mu + h->lo[s] * mu_stride : nullptr, mu_stride); });
+}
+
+int clr_sharded_evaluate_mean(clr_sharded* h, const double* mean, long mean_stride, const double* jitter,
+                              const double* a_real, const double* c_real, const double* a_comp, const double* b_comp,
+                              const double* c_comp, const double* d_comp, double* loglike, double* logdet,
+                              double* quad, int* status) {
+  const int st = clr_sharded_set_mean(h, mean, mean_stride);
+  if (st != CLR_OK) return st;
+  return clr_sharded_evaluate(h, jitter, a_real, c_real, a_comp, b_comp, c_comp, d_comp, loglike, logdet, quad, status);
+}
+
+int clr_sharded_grad_mean(clr_sharded* h, double* value, double* grad, double* dmean, int* status) {
+  const long NG = 1 + 2 * (long)h->J_real + 4 * (long)h->J_comp;
+  const int st0 = resolve_all(h);
+  if (st0 != CLR_OK) return st0;
+  return h->all([=](int s) {
+    const long lo = h->lo[s];
+    return clr_batch_grad_mean(h->plan[s], value ? value + lo : nullptr, grad ? grad + lo * NG : nullptr,
+                               dmean ? dmean + lo : nullptr, status ? status + lo : nullptr);
   });
 }
 

@@ -458,6 +458,20 @@ int clr_batch_get_results(clr_batch* h, double* loglike, double* logdet,
 int clr_batch_evaluate(clr_batch* h, const double* jitter, const double* a_real, const double* c_real,
                        const double* a_comp, const double* b_comp, const double* c_comp, const double* d_comp,
                        double* loglike, double* logdet, double* quad, int* status);
+/* A constant mean per problem (GP(kernel, mean=mu) of celerite.py for B problems): every route that reads y -- the
+ * evaluation, clr_batch_solve with b == NULL, clr_batch_predict, the gradient -- then sees the residual r = y - mu[p].
+ * mu_stride 1: mu[B], one value per problem; 0: mu[0] for every problem; mu == NULL removes the mean.  The caller's y
+ * stays on the device untouched; the residual is formed there by one elementwise pass (a shared series with a
+ * per-problem mean becomes a per-problem residual), and clr_batch_set_series keeps the mean in force and applies it to
+ * the new series.  A non-finite value or a stride other than 0 / 1: CLR_INVALID_ARGUMENT, the plan unchanged.
+ * clr_batch_predict returns mu[p] + K_* K^-1 r (celerite.py:279). */
+int clr_batch_set_mean(clr_batch* h, const double* mu, long mu_stride);
+/* clr_batch_evaluate with the mean as one more input (clr_batch_set_mean(h, mean, mean_stride) first): one library call
+ * per optimiser step over (kernel parameters, mean). */
+int clr_batch_evaluate_mean(clr_batch* h, const double* mean, long mean_stride, const double* jitter,
+                            const double* a_real, const double* c_real, const double* a_comp, const double* b_comp,
+                            const double* c_comp, const double* d_comp, double* loglike, double* logdet, double* quad,
+                            int* status);
 /* CholeskySolver::solve (cholesky.h:218-318) for every problem of the plan at once: x = K_p^-1 b_p from the factor of
  * the last materialising run (clr_batch_enqueue(h, 1); either factor layout), parallel in n -- forward substitution,
  * division by D and backward substitution as two chunked affine scans whose chunk maps are formed once and shared by
@@ -557,6 +571,14 @@ int clr_batch_grad_log_likelihood(int B, int N, int J_real, int J_comp, const do
  * run the sequential tangent kernel on their resident arrays (every problem counted in clr_batch_get_grad_fallbacks);
  * above 64: CLR_UNSUPPORTED (CholeskySolver.grad_log_likelihood takes any width). */
 int clr_batch_grad(clr_batch* h, double* value, double* grad, int* status);
+/* clr_batch_grad plus the mean's partial: dmean[b] = d loglike_b / d mu_b = 1^T K_b^-1 r_b (0 where status[b] != 0),
+ * r_b the residual of clr_batch_set_mean (y itself when no mean is set).  value, grad and status are clr_batch_grad's.
+ * Narrow plans in reverse mode (the default at widths 1..8): dmean = 1/2 sum_n xbar_n, xbar the adjoint of y, summed by
+ * the reverse sweep itself (one add per sample and one double per chunk) -- parallel in n.  Every other problem (forward
+ * mode, wide plans, general terms, problems settled sequentially or redone forwards): one pass of the reference
+ * recurrence (cholesky.h:154-178) carrying both forward substitutions, x = L^-1 r and x1 = L^-1 1:
+ * dmean = sum_n x1_n x_n / D_n; one workgroup per problem, sequential in n. */
+int clr_batch_grad_mean(clr_batch* h, double* value, double* grad, double* dmean, int* status);
 int clr_batch_get_grad_fallbacks(const clr_batch* h, int* count);
 /* How clr_batch_grad differentiates.  mode 0 (default): REVERSE mode -- the riders pass also records w, D, x per
  * sample and the state every K steps, the adjoint at every chunk end follows from the riders in a walk backwards over
@@ -644,6 +666,14 @@ int clr_sharded_grad(clr_sharded* h, double* value, double* grad, int* status);
 int clr_sharded_evaluate(clr_sharded* h, const double* jitter, const double* a_real, const double* c_real,
                          const double* a_comp, const double* b_comp, const double* c_comp,
                          const double* d_comp, double* loglike, double* logdet, double* quad, int* status);
+/* clr_batch_set_mean / _evaluate_mean / _grad_mean over the whole batch: every shard takes its slice of mu (mu_stride
+ * 1) or the one value (0); an invalid mean leaves every shard unchanged.  dmean is [B]. */
+int clr_sharded_set_mean(clr_sharded* h, const double* mu, long mu_stride);
+int clr_sharded_evaluate_mean(clr_sharded* h, const double* mean, long mean_stride, const double* jitter,
+                              const double* a_real, const double* c_real, const double* a_comp, const double* b_comp,
+                              const double* c_comp, const double* d_comp, double* loglike, double* logdet,
+                              double* quad, int* status);
+int clr_sharded_grad_mean(clr_sharded* h, double* value, double* grad, double* dmean, int* status);
 /* The consumers of the factor on a sharded batch (GP.apply_inverse / .sample / .predict for B problems over several
  * GPUs): clr_sharded_materialize runs clr_batch_enqueue(plan, 1) on every shard, settles the evaluation with the
  * batch-wide counts (results as clr_sharded_get_results; any pointer may be NULL) and leaves every shard's factor in
