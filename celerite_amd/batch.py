@@ -17,11 +17,13 @@ import os
 import numpy as np
 
 __all__ = ["BatchedGP", "ShardedBatchedGP", "shard_bounds", "batch_log_likelihood", "batch_grad_log_likelihood",
-           "kernel_coefficient_table", "kernel_coefficient_jacobian_table", "chain_gradient", "LIB_PATH"]
+           "kernel_coefficient_table", "kernel_coefficient_jacobian_table", "chain_gradient", "compile_kernel",
+           "CompiledKernel", "LIB_PATH"]
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libcelerite_hip.so")
 
 CLR_OK, CLR_NOT_POSITIVE_DEFINITE = 0, 2
+CLR_DIMENSION_MISMATCH, CLR_INVALID_ARGUMENT = 1, 6
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int)
@@ -104,6 +106,21 @@ def _load():
     lib.clr_sharded_set_mean.argtypes = [C.c_void_p, _dp, C.c_long]
     lib.clr_sharded_evaluate_mean.argtypes = [C.c_void_p, _dp, C.c_long] + [_dp] * 10 + [_ip]
     lib.clr_sharded_grad_mean.argtypes = [C.c_void_p, _dp, _dp, _dp, _ip]
+    lib.clr_kernel_create.argtypes = [C.c_int, _ip, C.c_int, _dp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+    lib.clr_kernel_destroy.argtypes = [C.c_void_p]
+    lib.clr_kernel_destroy.restype = None
+    lib.clr_kernel_coefficients.argtypes = [C.c_void_p, C.c_int] + [_dp] * 8 + [_ip]
+    lib.clr_kernel_jacobian.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _ip]
+    lib.clr_batch_set_kernel.argtypes = [C.c_void_p, C.c_void_p]
+    lib.clr_batch_set_parameters.argtypes = [C.c_void_p, _dp]
+    lib.clr_batch_get_parameter_status.argtypes = [C.c_void_p, _ip]
+    lib.clr_batch_evaluate_params.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_long] + [C.c_void_p] * 4
+    lib.clr_batch_grad_params.argtypes = [C.c_void_p, _dp, _dp, _ip, C.c_int]
+    lib.clr_batch_get_coefficients.argtypes = [C.c_void_p] + [_dp] * 7
+    lib.clr_sharded_set_kernel.argtypes = [C.c_void_p, C.c_void_p]
+    lib.clr_sharded_evaluate_params.argtypes = [C.c_void_p, _dp, _dp, C.c_long, _dp, _dp, _dp, _ip]
+    lib.clr_sharded_grad_params.argtypes = [C.c_void_p, _dp, _dp, _ip, C.c_int]
+    lib.clr_sharded_get_coefficients.argtypes = [C.c_void_p] + [_dp] * 7
     lib.clr_device_info.argtypes = [C.c_char_p, C.c_size_t, _ip, C.POINTER(C.c_size_t)]
     lib.clr_set_device.argtypes = [C.c_int]
     _lib = lib
@@ -376,6 +393,64 @@ class BatchedGP(object):
             self._evaluate_fn = fn
         _check(fn(self._h, jit.ctypes.data, *([a.ctypes.data for a in tabs] + [ll.ctypes.data, ld.ctypes.data, q.ctypes.data, st.ctypes.data])))
         return ll, ld, q, st
+
+    # -- evaluation straight from `terms` kernel parameters ----------------------------------------------------------
+    def set_kernel(self, kernel):
+        """Compile a ``terms`` kernel of built-in terms (:func:`compile_kernel`; or take a :class:`CompiledKernel`) and
+        hand the program to the plan (``clr_batch_set_kernel``): :meth:`evaluate_parameters` then needs only the
+        parameter vectors per step.  ``ValueError`` when the kernel cannot be compiled or its ``(J_real, J_comp)`` at
+        its current parameters is not the plan's."""
+        prog = kernel if isinstance(kernel, CompiledKernel) else compile_kernel(kernel)
+        if (prog.J_real, prog.J_comp) != (self.J_real, self.J_comp):
+            raise ValueError("dimension mismatch: the kernel has (J_real, J_comp) = (%d, %d), the plan (%d, %d)"
+                             % (prog.J_real, prog.J_comp, self.J_real, self.J_comp))
+        self._set_kernel_handle(prog)
+        self.kernel_program = prog
+        self.kernel = prog.kernel
+        return prog
+
+    def _set_kernel_handle(self, prog):
+        _check(_load().clr_batch_set_kernel(self._h, prog._k))
+
+    def _params_arg(self, params):
+        prog = getattr(self, "kernel_program", None)
+        if prog is None:
+            raise RuntimeError("no kernel is set: call set_kernel first")
+        p = np.ascontiguousarray(params, dtype=np.float64)
+        if p.shape != (self.B, prog.n_params):
+            raise ValueError("dimension mismatch")
+        return p
+
+    def evaluate_parameters(self, params, mean=None):
+        """One optimiser / MCMC evaluation from kernel parameters (``clr_batch_evaluate_params``): ``params`` is
+        ``(B, kernel.vector_size)`` in ``get_parameter_vector()`` order, ``mean`` as in :meth:`evaluate`.  The
+        coefficients are formed on the device and never leave it.  Returns ``(loglike, logdet, quad, status)``; a draw
+        the program refuses (an SHO term across Q = 1/2, a non-finite parameter or coefficient) has status
+        ``CLR_INVALID_ARGUMENT`` and NaN results, the other problems are not affected."""
+        p = self._params_arg(params)
+        ll, ld, q, st = np.empty(self.B), np.empty(self.B), np.empty(self.B), np.empty(self.B, dtype=np.int32)
+        m, stride = _mean_arg(mean, self.B)
+        _check(_load().clr_batch_evaluate_params(self._h, p.ctypes.data, None if m is None else m.ctypes.data, stride,
+                                                 ll.ctypes.data, ld.ctypes.data, q.ctypes.data, st.ctypes.data))
+        return ll, ld, q, st
+
+    def grad_parameters(self, mean_partial=False):
+        """``(value[B], grad[B, P], status[B])`` at the parameters of the last :meth:`evaluate_parameters`: the
+        batched coefficient gradient chained to the kernel's parameters on the device (``clr_batch_grad_params``).
+        ``mean_partial=True``: ``grad[B, P + 1]`` with ``d loglike / d mean`` last (the reference's order)."""
+        P = self.kernel_program.n_params + (1 if mean_partial else 0)
+        value, grad, st = np.empty(self.B), np.empty((self.B, P)), np.empty(self.B, dtype=np.int32)
+        _check(_load().clr_batch_grad_params(self._h, _ptr(value), _ptr(grad), st.ctypes.data_as(_ip), int(bool(mean_partial))))
+        return value, grad, st
+
+    def coefficients(self):
+        """The coefficients in force, read back from the device (``clr_batch_get_coefficients``):
+        ``(a_real, c_real, a_comp, b_comp, c_comp, d_comp, jitter)``, the arguments of :meth:`evaluate`."""
+        B, JR, JC = self.B, self.J_real, self.J_comp
+        out = [np.empty((B, JR)), np.empty((B, JR))] + [np.empty((B, JC)) for _ in range(4)]
+        jit = np.empty(B)
+        _check(_load().clr_batch_get_coefficients(self._h, _ptr(jit), *[_ptr(a) for a in out]))
+        return tuple(out) + (jit,)
 
     def log_likelihood(self, materialize=False):
         """Evaluate all B problems; returns ``(loglike, logdet, quad, status)``."""
@@ -933,6 +1008,37 @@ class ShardedBatchedGP(object):
                                               [_ptr(ll), _ptr(ld), _ptr(q), st.ctypes.data_as(_ip)])))
         return ll, ld, q, st
 
+    set_kernel = BatchedGP.set_kernel
+    _params_arg = BatchedGP._params_arg
+
+    def _set_kernel_handle(self, prog):
+        self._ok(_load().clr_sharded_set_kernel(self._h, prog._k))
+
+    def evaluate_parameters(self, params, mean=None):
+        """:meth:`BatchedGP.evaluate_parameters` over the shards (``clr_sharded_evaluate_params``): every shard forms the
+        coefficients of its slice of ``params`` on its own device."""
+        p = self._params_arg(params)
+        ll, ld, q, st = self._out()
+        m, stride = _mean_arg(mean, self.B)
+        self._ok(_load().clr_sharded_evaluate_params(self._h, _ptr(p), None if m is None else _ptr(m), stride,
+                                                     _ptr(ll), _ptr(ld), _ptr(q), st.ctypes.data_as(_ip)))
+        return ll, ld, q, st
+
+    def grad_parameters(self, mean_partial=False):
+        """:meth:`BatchedGP.grad_parameters` over the shards (``clr_sharded_grad_params``)."""
+        P = self.kernel_program.n_params + (1 if mean_partial else 0)
+        value, grad, st = np.empty(self.B), np.empty((self.B, P)), np.empty(self.B, dtype=np.int32)
+        self._ok(_load().clr_sharded_grad_params(self._h, _ptr(value), _ptr(grad), st.ctypes.data_as(_ip), int(bool(mean_partial))))
+        return value, grad, st
+
+    def coefficients(self):
+        """The coefficients in force on every shard (``clr_sharded_get_coefficients``), as :meth:`BatchedGP.coefficients`."""
+        B, JR, JC = self.B, self.J_real, self.J_comp
+        out = [np.empty((B, JR)), np.empty((B, JR))] + [np.empty((B, JC)) for _ in range(4)]
+        jit = np.empty(B)
+        self._ok(_load().clr_sharded_get_coefficients(self._h, _ptr(jit), *[_ptr(a) for a in out]))
+        return tuple(out) + (jit,)
+
     def materialize(self):
         """A materialising evaluation on every shard (``clr_sharded_materialize``): ``(loglike, logdet, quad, status)``
         as :meth:`log_likelihood`, and every shard's factor left in its HBM for :meth:`solve`, :meth:`dot_L`,
@@ -1054,14 +1160,214 @@ def batch_grad_log_likelihood(a_real, c_real, a_comp, b_comp, c_comp, d_comp, t,
     return value, grad, st
 
 
-def kernel_coefficient_table(kernel, parameter_vectors):
+# ---- a `terms` kernel as a program (include/celerite_hip.h, "kernel programs") -------------------------------------
+_KP_REAL, _KP_COMPLEX, _KP_COMPLEX_B0, _KP_SHO_OVER, _KP_SHO_UNDER, _KP_MATERN32, _KP_JITTER = 1, 2, 3, 4, 5, 6, 7
+_KP_MUL_RR, _KP_MUL_RC, _KP_MUL_CC = 8, 9, 10
+
+
+class CompiledKernel(object):
+    """A ``terms`` kernel compiled by :func:`compile_kernel`: the program (``ops``, ``consts``), its input size
+    ``n_params`` (= ``kernel.vector_size`` at compile time) and output shape ``(J_real, J_comp)``, evaluated through
+    ``clr_kernel_coefficients`` / ``clr_kernel_jacobian`` on the host -- no GPU needed -- and by the plans on the device."""
+
+    def __init__(self, kernel, ops, consts, n_params, J_real, J_comp):
+        self.kernel = kernel
+        self.ops = np.ascontiguousarray(ops, dtype=np.int32)
+        self.consts = np.ascontiguousarray(consts, dtype=np.float64)
+        self.n_params, self.J_real, self.J_comp = int(n_params), int(J_real), int(J_comp)
+        self._k = _create_kernel(self.ops, self.consts, self.n_params, self.J_real, self.J_comp)
+
+    def close(self):
+        if getattr(self, "_k", None):
+            _load().clr_kernel_destroy(self._k)
+            self._k = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _params(self, parameter_vectors):
+        p = np.ascontiguousarray(np.atleast_2d(parameter_vectors), dtype=np.float64)
+        if p.ndim != 2 or p.shape[1] != self.n_params:
+            raise ValueError("dimension mismatch")
+        return p
+
+    def coefficients(self, parameter_vectors, status=False):
+        """``(a_real, c_real, a_comp, b_comp, c_comp, d_comp, jitter)`` of the draws ``(B, n_params)``.  A draw the
+        program refuses raises ``ValueError`` -- or, with ``status=True``, is a row of NaN and the per-draw status array
+        is returned as an eighth element."""
+        p = self._params(parameter_vectors)
+        B, JR, JC = p.shape[0], self.J_real, self.J_comp
+        out = [np.empty((B, JR)), np.empty((B, JR))] + [np.empty((B, JC)) for _ in range(4)] + [np.empty(B)]
+        st = np.zeros(B, dtype=np.int32)
+        _check(_load().clr_kernel_coefficients(self._k, B, _ptr(p), *([_ptr(a) for a in out] + [st.ctypes.data_as(_ip)])))
+        if status:
+            return tuple(out) + (st,)
+        if st.any():
+            raise ValueError("the draws do not share one (J_real, J_comp) shape, or are not finite")
+        return tuple(out)
+
+    def jacobian(self, parameter_vectors, status=False):
+        """``(jac[B, P, 2 J_real + 4 J_comp], jitter_jac[B, P])`` of the draws, as
+        :func:`kernel_coefficient_jacobian_table` lays them out."""
+        p = self._params(parameter_vectors)
+        B, P, NC = p.shape[0], self.n_params, 2 * self.J_real + 4 * self.J_comp
+        jac, jj = np.empty((B, P, NC)), np.empty((B, P))
+        st = np.zeros(B, dtype=np.int32)
+        _check(_load().clr_kernel_jacobian(self._k, B, _ptr(p), _ptr(jac), _ptr(jj), st.ctypes.data_as(_ip)))
+        if status:
+            return jac, jj, st
+        if st.any():
+            raise ValueError("the draws do not share one (J_real, J_comp) shape, or are not finite")
+        return jac, jj
+
+
+def _create_kernel(ops, consts, n_params, J_real, J_comp):
+    """``clr_kernel_create``: the handle, or ``RuntimeError`` (``CLR_INVALID_ARGUMENT``) for a malformed program."""
+    lib = _load()
+    ops = np.ascontiguousarray(ops, dtype=np.int32)
+    consts = np.ascontiguousarray(consts, dtype=np.float64)
+    k = C.c_void_p()
+    _check(lib.clr_kernel_create(len(ops), ops.ctypes.data_as(_ip), len(consts), _ptr(consts), int(n_params),
+                                 int(J_real), int(J_comp), C.byref(k)))
+    return k
+
+
+def compile_kernel(kernel):
+    """Compile a ``terms`` tree of built-in terms -- ``RealTerm``, ``ComplexTerm``, ``SHOTerm``, ``Matern32Term``,
+    ``JitterTerm``, sums and products of them, nested in any way -- into a :class:`CompiledKernel`.
+
+    The program's input is the kernel's unfrozen parameter vector (``get_parameter_vector()`` order); frozen
+    parameters are baked in with their current value, and every ``SHOTerm`` is fixed in the regime (Q below or not
+    below 1/2) of its current value, which fixes ``(J_real, J_comp)``.  The output order is that of
+    ``kernel.coefficients``.  A term whose class overrides the coefficient formulas, or a user-defined term, cannot be
+    compiled: ``ValueError`` naming it."""
+    from . import terms
+
+    full = np.asarray(kernel.get_parameter_vector(include_frozen=True), dtype=np.float64)
+    mask = np.asarray(kernel.unfrozen_mask, dtype=bool)
+    unfrozen_index = np.cumsum(mask) - 1
+    ops, consts = [], []
+    count = {"r": 0, "c": 0, "tr": 0, "tc": 0}
+
+    def const(x):
+        consts.append(float(x))
+        return len(consts) - 1
+
+    def ref(i):
+        return int(unfrozen_index[i]) if mask[i] else -(const(full[i]) + 1)
+
+    def dst(kind, top):
+        key = kind if top else "t" + kind
+        count[key] += 1
+        return count[key] - 1 if top else -count[key]
+
+    def cannot(term):
+        raise ValueError("cannot compile %s %r: only the built-in terms with their own coefficient formulas"
+                         % (type(term).__name__, term))
+
+    def emit(term, at, top):
+        """instructions of `term` (its parameters at `at` in the full vector); returns its (real, complex) term ids"""
+        if isinstance(term, terms.TermSum):
+            if not term._formulas_are(terms.TermSum):
+                cannot(term)
+            reals, comps = [], []
+            for sub in term.terms:
+                r, c = emit(sub, at, top)
+                reals += r
+                comps += c
+                at += sub.full_size
+            return reals, comps
+        if isinstance(term, terms.TermProduct):
+            if not term._formulas_are(terms.TermProduct):
+                cannot(term)
+            k1, k2 = term.models["k1"], term.models["k2"]
+            r1, c1 = emit(k1, at, False)
+            r2, c2 = emit(k2, at + k1.full_size, False)
+            tmp = lambda ids: [-(i + 1) for i in ids]      # (a temporary's index as a product reads it)
+            r1, c1, r2, c2 = tmp(r1), tmp(c1), tmp(r2), tmp(c2)
+            reals, comps = [], []
+            for x in r1:
+                for y in r2:
+                    reals.append(dst("r", top))
+                    ops.extend([_KP_MUL_RR, reals[-1], x, y])
+            for rs, cs in ((r1, c2), (r2, c1)):
+                for x in rs:
+                    for y in cs:
+                        comps.append(dst("c", top))
+                        ops.extend([_KP_MUL_RC, comps[-1], x, y])
+            for x in c1:
+                for y in c2:
+                    dm, dp = dst("c", top), dst("c", top)
+                    comps += [dm, dp]
+                    ops.extend([_KP_MUL_CC, dm, dp, x, y])
+            return reals, comps
+        if isinstance(term, terms.JitterTerm) and term._formulas_are(terms.JitterTerm):
+            ops.extend([_KP_JITTER, ref(at)])
+            return [], []
+        if isinstance(term, terms.RealTerm) and term._formulas_are(terms.RealTerm):
+            d = dst("r", top)
+            ops.extend([_KP_REAL, d, ref(at), ref(at + 1)])
+            return [d], []
+        if isinstance(term, terms.ComplexTerm) and term._formulas_are(terms.ComplexTerm):
+            d = dst("c", top)
+            if term.fit_b:
+                ops.extend([_KP_COMPLEX, d] + [ref(at + i) for i in range(4)])
+            else:
+                ops.extend([_KP_COMPLEX_B0, d] + [ref(at + i) for i in range(3)])
+            return [], [d]
+        if isinstance(term, terms.SHOTerm) and term._formulas_are(terms.SHOTerm):
+            if np.exp(full[at + 1]) < 0.5:
+                d0, d1 = dst("r", top), dst("r", top)
+                ops.extend([_KP_SHO_OVER, d0, d1] + [ref(at + i) for i in range(3)])
+                return [d0, d1], []
+            d = dst("c", top)
+            ops.extend([_KP_SHO_UNDER, d] + [ref(at + i) for i in range(3)])
+            return [], [d]
+        if isinstance(term, terms.Matern32Term) and term._formulas_are(terms.Matern32Term):
+            d = dst("c", top)
+            ops.extend([_KP_MATERN32, d, ref(at), ref(at + 1), const(term.eps)])
+            return [], [d]
+        cannot(term)
+
+    emit(kernel, 0, True)
+    if max(count["tr"], count["tc"]) > 16:
+        raise ValueError("cannot compile %r: more than 16 factor terms of one kind inside products" % (kernel,))
+    return CompiledKernel(kernel, ops, consts, int(mask.sum()), count["r"], count["c"])
+
+
+def _compiled_for(kernel, compiled):
+    """The program behind the ``compiled=`` switch of the two table functions: None for the Python loop."""
+    if compiled is False:
+        return None
+    if isinstance(compiled, CompiledKernel):
+        return compiled
+    try:
+        return compile_kernel(kernel)
+    except ValueError:
+        if compiled is None:
+            return None
+        raise
+
+
+def kernel_coefficient_table(kernel, parameter_vectors, compiled=False):
     """Coefficient tables for many hyper-parameter draws of one ``terms.Term``.
 
     ``parameter_vectors``: ``(B, kernel.vector_size)``.  Returns
     ``(a_real, c_real, a_comp, b_comp, c_comp, d_comp, jitter)`` ready for
     :meth:`BatchedGP.set_coefficients`.  The kernel's parameters are restored.
     Every draw must give the same number of real / complex terms.
+
+    ``compiled``: ``False`` (default) the Python loop over the draws; ``True`` the compiled program
+    (:func:`compile_kernel`, evaluated by ``clr_kernel_coefficients`` -- equal to the loop up to the last bits of
+    ``exp``); ``None`` the program when the kernel can be compiled, the loop otherwise.  The program's shape is the one
+    of the kernel's CURRENT parameters; draws of another shape raise ``ValueError`` either way.
     """
+    prog = _compiled_for(kernel, compiled)
+    if prog is not None:
+        return prog.coefficients(parameter_vectors)
     saved = kernel.get_parameter_vector()
     rows, jit = [], []
     try:
@@ -1078,7 +1384,7 @@ def kernel_coefficient_table(kernel, parameter_vectors):
     return tuple(blocks) + (np.array(jit),)
 
 
-def kernel_coefficient_jacobian_table(kernel, parameter_vectors):
+def kernel_coefficient_jacobian_table(kernel, parameter_vectors, compiled=False):
     """The chain rule's other half for :func:`kernel_coefficient_table`: for every draw the Jacobian of the
     coefficients with respect to the kernel's (unfrozen) parameters.
 
@@ -1086,7 +1392,11 @@ def kernel_coefficient_jacobian_table(kernel, parameter_vectors):
     in the order of the batched gradient's columns 1.. (``a_real, c_real, a_comp, b_comp, c_comp, d_comp``, each
     block contiguous: ``Term.get_coeffs_jacobian``, terms.py:206-215) and ``jitter_jac[b, p]`` = d jitter / d
     parameter (``get_jitter_jacobian``, :197-204).  Built-in terms need no autograd (their formulas are evaluated
-    on dual numbers, ``terms._dual_coefficients``)."""
+    on dual numbers, ``terms._dual_coefficients``).  ``compiled``: as in :func:`kernel_coefficient_table`
+    (``clr_kernel_jacobian``: the same formulas on duals)."""
+    prog = _compiled_for(kernel, compiled)
+    if prog is not None:
+        return prog.jacobian(parameter_vectors)
     saved = kernel.get_parameter_vector()
     jac, jit = [], []
     try:

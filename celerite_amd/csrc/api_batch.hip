@@ -3,6 +3,7 @@
 #include "api_internal.h"
 #include "clr_options.h"
 #include "clr_group_hooks.h"
+#include "clr_kernel.h"
 
 #include <functional>
 
@@ -472,15 +473,44 @@ static int reserve_pinned(clr_batch* h, size_t doubles) {
   return h->pin.reserve(doubles);
 }
 
-int clr_batch_set_coefficients(clr_batch* h, const double* jitter, const double* a_real,
-                               const double* c_real, const double* a_comp, const double* b_comp,
-                               const double* c_comp, const double* d_comp) {
+// Coefficients come in two ways -- as tables from the host (clr_batch_set_coefficients) or formed on the device from
+// kernel parameters (clr_batch_set_parameters) -- and both go through the same two halves: the statistics the
+// selection looks at (largest frequency and decay rate of the batch, smallest / largest decay rate and jitter per
+// problem) -> warm_select, then the coefficients placed in h->coeffs with the warm path's K per problem behind them.
+static int begin_coefficients(clr_batch* h) {
   int st = require_device(h->device);
   if (st != CLR_OK) return st;
   if ((st = warm_resolve(h, nullptr)) != CLR_OK) return st;  // (pending problems of the evaluation in flight: at ITS coefficients)
-  const size_t B = (size_t)h->B, nr = B * h->J_real, nc = B * h->J_comp;
   h->factor_inputs_changed = true;
   h->pin_results = false;  // (the staging buffer is about to carry the coefficients)
+  h->kp_in_force = false;
+  return CLR_OK;
+}
+
+// doubles of the pinned staging buffer a coefficient upload needs; the warm path's K per problem sits at warm_K_offset
+static size_t warm_K_offset(const clr_batch* h) {
+  const size_t B = (size_t)h->B;
+  return std::max(B * (2 * (size_t)h->J_real + 4 * (size_t)h->J_comp + 1), 3 * B + (B + 1) / 2);
+}
+
+static int place_warm_K(clr_batch* h) {
+  const size_t B = (size_t)h->B;
+  if (h->warm_active) {  // K per problem, behind the coefficients in the staging buffer
+    int* kk = reinterpret_cast<int*>(h->pin.p + warm_K_offset(h));
+    memcpy(kk, h->warm_K.data(), B * sizeof(int));
+    HIP_TRY(hipMemcpyAsync(h->wints.p + (size_t)h->B * h->wnchunk + B, kk, B * sizeof(int), hipMemcpyHostToDevice, h->stream.get()));
+    h->warm_K_dirty = false;
+  }
+  h->have_coeffs = true;
+  return CLR_OK;
+}
+
+int clr_batch_set_coefficients(clr_batch* h, const double* jitter, const double* a_real,
+                               const double* c_real, const double* a_comp, const double* b_comp,
+                               const double* c_comp, const double* d_comp) {
+  int st = begin_coefficients(h);
+  if (st != CLR_OK) return st;
+  const size_t B = (size_t)h->B, nr = B * h->J_real, nc = B * h->J_comp;
   h->dmax = 0.0;
   h->cmax = 0.0;
   for (size_t i = 0; i < nc; ++i) {
@@ -506,25 +536,165 @@ int clr_batch_set_coefficients(clr_batch* h, const double* jitter, const double*
     for (int j = 0; j < h->J_comp; ++j) { const double c = c_comp[b * h->J_comp + j]; if (!(c >= cmin)) cmin = c; }
     h->host_cmin[b] = cmin;
   }
+  if (jitter) h->host_jitter.assign(jitter, jitter + B);
+  else h->host_jitter.assign(B, 0.0);  // NULL: no jitter
   warm_select(h);
   // one pinned staging buffer, one copy: a_real c_real a_comp b_comp c_comp d_comp | jitter
   const size_t total = 2 * nr + 4 * nc + B;
-  if ((st = reserve_pinned(h, std::max(total, 3 * B + (B + 1) / 2) + (B + 1) / 2)) != CLR_OK) return st;
+  if ((st = reserve_pinned(h, warm_K_offset(h) + (B + 1) / 2)) != CLR_OK) return st;
   HIP_TRY(hipStreamSynchronize(h->stream.get()));  // (a previous upload may still read the staging buffer)
   double* w = h->pin.p;
   auto put = [&](const double* p, size_t n) { if (n) memcpy(w, p, n * sizeof(double)); w += n; };
   put(a_real, nr); put(c_real, nr); put(a_comp, nc); put(b_comp, nc); put(c_comp, nc); put(d_comp, nc);
-  if (jitter) { put(jitter, B); h->host_jitter.assign(jitter, jitter + B); }
-  else { memset(w, 0, B * sizeof(double)); w += B; h->host_jitter.assign(B, 0.0); }  // NULL: no jitter
+  if (jitter) put(jitter, B);
+  else memset(w, 0, B * sizeof(double));
   if ((st = h->coeffs.reserve(total)) != CLR_OK) return st;
   HIP_TRY(hipMemcpyAsync(h->coeffs.p, h->pin.p, total * sizeof(double), hipMemcpyHostToDevice, h->stream.get()));
-  if (h->warm_active) {  // K per problem, behind the coefficients in the staging buffer
-    int* kk = reinterpret_cast<int*>(h->pin.p + std::max(total, 3 * B + (B + 1) / 2));
-    memcpy(kk, h->warm_K.data(), B * sizeof(int));
-    HIP_TRY(hipMemcpyAsync(h->wints.p + (size_t)h->B * h->wnchunk + B, kk, B * sizeof(int), hipMemcpyHostToDevice, h->stream.get()));
-    h->warm_K_dirty = false;
+  return place_warm_K(h);
+}
+
+/* ---- coefficients from kernel parameters, formed on the device (kernel_program.hip) ------------------------------ */
+int clr_batch_set_kernel(clr_batch* h, const clr_kernel* k) {
+  int st = require_device(h->device);
+  if (st != CLR_OK) return st;
+  if (!k) {
+    h->have_kernel = false;
+    h->kp_in_force = false;
+    return CLR_OK;
   }
-  h->have_coeffs = true;
+  if (k->J_real != h->J_real || k->J_comp != h->J_comp)
+    return fail(CLR_DIMENSION_MISMATCH, "clr_batch_set_kernel: the kernel's (J_real, J_comp) is not the plan's");
+  if ((st = h->kp_ops.reserve(k->ops.size())) != CLR_OK) return st;
+  if ((st = h->kp_consts.reserve(k->consts.size())) != CLR_OK) return st;
+  HIP_TRY(hipStreamSynchronize(h->stream.get()));  // (a kernel in flight may still read the previous program)
+  h->kp = *k;
+  if (!k->ops.empty()) HIP_TRY(hipMemcpy(h->kp_ops.p, k->ops.data(), k->ops.size() * sizeof(int), hipMemcpyHostToDevice));
+  if (!k->consts.empty()) HIP_TRY(hipMemcpy(h->kp_consts.p, k->consts.data(), k->consts.size() * sizeof(double), hipMemcpyHostToDevice));
+  h->have_kernel = true;
+  h->kp_in_force = false;
+  return CLR_OK;
+}
+
+static clr::KernelProgramDevice device_program(const clr_batch* h) {
+  return clr::KernelProgramDevice{h->kp_ops.p, h->kp_consts.p, (int)h->kp.ops.size(), (int)h->kp.consts.size(),
+                                  h->kp.n_params, h->kp.J_real, h->kp.J_comp};
+}
+
+int clr_batch_set_parameters(clr_batch* h, const double* params) {
+  int st = begin_coefficients(h);
+  if (st != CLR_OK) return st;
+  if (!h->have_kernel) return fail(CLR_NOT_COMPUTED, "clr_batch_set_parameters: no kernel is set (clr_batch_set_kernel)");
+  const size_t B = (size_t)h->B, P = (size_t)h->kp.n_params, NC = 2 * (size_t)h->J_real + 4 * (size_t)h->J_comp;
+  if (!params && P > 0) return fail(CLR_INVALID_ARGUMENT, "clr_batch_set_parameters: params is null");
+  const size_t nstat = clr::KP_NSTAT * B;
+  if ((st = reserve_pinned(h, std::max(warm_K_offset(h) + (B + 1) / 2, B * P + nstat))) != CLR_OK) return st;
+  if ((st = h->kp_params.reserve(B * P + nstat)) != CLR_OK) return st;
+  if ((st = h->coeffs.reserve(B * NC + B)) != CLR_OK) return st;
+  HIP_TRY(hipStreamSynchronize(h->stream.get()));  // (a previous upload may still read the staging buffer)
+  if (P) memcpy(h->pin.p, params, B * P * sizeof(double));
+  if (P) HIP_TRY(hipMemcpyAsync(h->kp_params.p, h->pin.p, B * P * sizeof(double), hipMemcpyHostToDevice, h->stream.get()));
+  double* dstats = h->kp_params.p + B * P;
+  clr::launch_kernel_program_eval(device_program(h), h->B, h->kp_params.p, h->coeffs.p, dstats, h->stream.get());
+  HIP_TRY(hipGetLastError());
+  // the statistics of the coefficients just formed: one small block, one transfer
+  const double* s = h->pin.p + B * P;
+  HIP_TRY(hipMemcpyAsync(h->pin.p + B * P, dstats, nstat * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
+  HIP_TRY(hipStreamSynchronize(h->stream.get()));
+  h->dmax = 0.0;
+  h->cmax = 0.0;
+  for (size_t b = 0; b < B; ++b) {
+    const double m = s[clr::KP_STAT_DMAX * B + b], c = s[clr::KP_STAT_CMAX * B + b];
+    if (!(m <= h->dmax)) h->dmax = m;
+    if (!(c <= h->cmax)) h->cmax = c;
+  }
+  h->host_cmin.assign(s + clr::KP_STAT_CMIN * B, s + clr::KP_STAT_CMIN * B + B);
+  h->host_cmax.assign(s + clr::KP_STAT_CMAX * B, s + clr::KP_STAT_CMAX * B + B);
+  h->host_jitter.assign(s + clr::KP_STAT_JITTER * B, s + clr::KP_STAT_JITTER * B + B);
+  h->kp_refused.resize(B);
+  for (size_t b = 0; b < B; ++b) h->kp_refused[b] = s[clr::KP_STAT_ERROR * B + b] != 0.0;
+  warm_select(h);
+  if ((st = place_warm_K(h)) != CLR_OK) return st;
+  h->kp_in_force = true;
+  return CLR_OK;
+}
+
+// draws the program refused (evaluated at their stand-in coefficients): NaN and CLR_INVALID_ARGUMENT
+static void mark_refused(const clr_batch* h, double* a, double* b, double* c, int* status) {
+  if (!h->kp_in_force) return;
+  for (size_t i = 0; i < (size_t)h->B; ++i) {
+    if (!h->kp_refused[i]) continue;
+    if (a) a[i] = NAN;
+    if (b) b[i] = NAN;
+    if (c) c[i] = NAN;
+    if (status) status[i] = CLR_INVALID_ARGUMENT;
+  }
+}
+
+int clr_batch_get_coefficients(clr_batch* h, double* jitter, double* a_real, double* c_real, double* a_comp,
+                               double* b_comp, double* c_comp, double* d_comp) {
+  int st = require_device(h->device);
+  if (st != CLR_OK) return st;
+  if (!h->have_coeffs) return fail(CLR_NOT_COMPUTED, "clr_batch_get_coefficients: no coefficients are set");
+  const size_t B = (size_t)h->B, nr = B * h->J_real, nc = B * h->J_comp, total = 2 * nr + 4 * nc + B;
+  std::vector<double> back(total);
+  HIP_TRY(hipMemcpyAsync(back.data(), h->coeffs.p, total * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
+  HIP_TRY(hipStreamSynchronize(h->stream.get()));
+  const double* r = back.data();
+  auto get = [&](double* p, size_t n) { if (p && n) memcpy(p, r, n * sizeof(double)); r += n; };
+  get(a_real, nr); get(c_real, nr); get(a_comp, nc); get(b_comp, nc); get(c_comp, nc); get(d_comp, nc);
+  get(jitter, B);
+  return CLR_OK;
+}
+
+int clr_batch_get_parameter_status(const clr_batch* h, int* status) {
+  if (!status) return fail(CLR_INVALID_ARGUMENT, "status is null");
+  if (!h->kp_in_force) return fail(CLR_NOT_COMPUTED, "the coefficients in force were not formed from parameters");
+  for (size_t b = 0; b < (size_t)h->B; ++b) status[b] = h->kp_refused[b] ? CLR_INVALID_ARGUMENT : CLR_OK;
+  return CLR_OK;
+}
+
+int clr_batch_evaluate_params(clr_batch* h, const double* params, const double* mean, long mean_stride,
+                              double* loglike, double* logdet, double* quad, int* status) {
+  int st = mean ? clr_batch_set_mean(h, mean, mean_stride) : CLR_OK;
+  if (st == CLR_OK) st = clr_batch_set_parameters(h, params);
+  if (st == CLR_OK) st = clr_batch_enqueue(h, 0);
+  if (st == CLR_OK) st = clr_batch_get_results(h, loglike, logdet, quad, status);
+  if (st == CLR_OK) mark_refused(h, loglike, logdet, quad, status);
+  return st;
+}
+
+int clr_batch_grad_params(clr_batch* h, double* value, double* grad_params, int* status, int with_mean) {
+  int st = require_device(h->device);
+  if (st != CLR_OK) return st;
+  if (!h->have_kernel || !h->kp_in_force)
+    return fail(CLR_NOT_COMPUTED, "clr_batch_grad_params: the coefficients in force were not formed from parameters");
+  const size_t B = (size_t)h->B, P = (size_t)h->kp.n_params, NG = 1 + 2 * (size_t)h->J_real + 4 * (size_t)h->J_comp;
+  const size_t ncol = P + (with_mean ? 1 : 0);
+  // the coefficient gradient is assembled on the host from whichever route settled each problem (clr_batch_grad): it
+  // goes back up as one block grad[B][NG] | dmean[B], so that the chain rule is the same kernel on every route
+  std::vector<double> up(B * NG + B), val(B);
+  std::vector<int> stt(B);
+  st = with_mean ? clr_batch_grad_mean(h, val.data(), up.data(), up.data() + B * NG, stt.data())
+                 : clr_batch_grad(h, val.data(), up.data(), stt.data());
+  if (st != CLR_OK) return st;
+  std::vector<double> back(B * ncol);
+  if ((st = h->kp_grad.reserve(B * NG + B + B * ncol)) != CLR_OK) return st;
+  double* dgrad = h->kp_grad.p;
+  double* dout = dgrad + B * NG + B;
+  HIP_TRY(hipMemcpyAsync(dgrad, up.data(), up.size() * sizeof(double), hipMemcpyHostToDevice, h->stream.get()));
+  clr::launch_kernel_program_vjp(device_program(h), h->B, h->kp_params.p, dgrad, with_mean ? dgrad + B * NG : nullptr, dout,
+                                 h->stream.get());
+  HIP_TRY(hipGetLastError());
+  if (ncol) HIP_TRY(hipMemcpyAsync(back.data(), dout, back.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
+  HIP_TRY(hipStreamSynchronize(h->stream.get()));
+  for (size_t b = 0; b < B; ++b) {
+    const bool refused = h->kp_refused[b];
+    if (value) value[b] = refused ? NAN : val[b];
+    if (status) status[b] = refused ? (int)CLR_INVALID_ARGUMENT : stt[b];
+    if (!grad_params) continue;
+    for (size_t p = 0; p < ncol; ++p) grad_params[b * ncol + p] = refused ? NAN : back[b * ncol + p];
+    if (with_mean && P == 0 && !refused) grad_params[b * ncol] = up[B * NG + b];
+  }
   return CLR_OK;
 }
 
@@ -2060,6 +2230,10 @@ void set_warm_eligible_total(clr_batch* h, long eligible_total) {
   h->warm_eligible_total = eligible_total;
   h->warm_active = selectable && eligible_total * 2 >= (long)h->group_B;
   h->warm_K_dirty = h->warm_active;  // (K per problem goes up with the next enqueue)
+}
+
+void mark_refused(const clr_batch* h, double* loglike, double* logdet, double* quad, int* status) {
+  ::mark_refused(h, loglike, logdet, quad, status);
 }
 
 bool in_flight(const clr_batch* h) { return h->res_open || h->warm_inflight || h->small_inflight || h->rescue_inflight; }

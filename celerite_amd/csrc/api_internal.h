@@ -28,6 +28,7 @@
 #include "clr_wide.h"
 #include "clr_options.h"
 #include "clr_handles.h"
+#include "clr_kernel.h"
 
 // the last error message of the calling thread (clr_last_error) and its current device: ONE object per thread for the
 // whole library (defined in api_misc.hip)
@@ -242,6 +243,14 @@ struct clr_batch {
   DevBuf mean_dev, y_src, mean_out;   // the mean on the device; the caller's y; clr_batch_grad_mean's partials [B]
   long y_src_stride = 0;
   bool relayout_y_pending = false;    // only the residual changed: the interleaved copy of y alone is rebuilt
+  // clr_batch_set_kernel / _set_parameters: the program (host copy and in HBM), the last parameter rows with the
+  // evaluation kernel's statistics block behind them, the chain rule's staging (grad | dmean | result)
+  bool have_kernel = false;
+  bool kp_in_force = false;           // the coefficients in force were formed from kp_params by the program
+  clr_kernel kp;
+  DevArray<int> kp_ops;
+  DevBuf kp_consts, kp_params, kp_grad;
+  std::vector<char> kp_refused;       // [B] draws of the last clr_batch_set_parameters the program refused
   clr::PinnedBuffer<double> mean_pin; // pinned staging of the mean's upload ...
   clr::Event mean_ev;                 // ... recorded behind it: the staging is rewritten only once the copy has run
   // clr_batch_grad_mean: the narrow reverse sweep sums the adjoint of y per chunk (BatchParams::g_ysum) and reduces it

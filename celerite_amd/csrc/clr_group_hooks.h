@@ -30,4 +30,8 @@ bool in_flight(const clr_batch* h);  // (host state only)
 int resolve_begin(clr_batch* h, long* pending, long* eligible);
 int resolve_finish(clr_batch* h, long pending_total, long eligible_total);
 
+// coefficients formed from kernel parameters (clr_batch_set_parameters): the draws the program refused get NaN results
+// and CLR_INVALID_ARGUMENT in this plan's slice of the result arrays; no-op for coefficients set as tables
+void mark_refused(const clr_batch* h, double* loglike, double* logdet, double* quad, int* status);
+
 }  // namespace clr_group

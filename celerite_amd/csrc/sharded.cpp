@@ -102,6 +102,7 @@ thread_local std::string g_sharded_error;
 
 struct clr_sharded {
   int B = 0, N = 0, J_real = 0, J_comp = 0;
+  int n_params = 0;  // of the kernel set by clr_sharded_set_kernel
   std::vector<int> device, lo, hi;
   std::vector<clr_batch*> plan;
   std::vector<std::unique_ptr<Worker>> worker;
@@ -503,6 +504,84 @@ int clr_sharded_grad_mean(clr_sharded* h, double* value, double* grad, double* d
     const long lo = h->lo[s];
     return clr_batch_grad_mean(h->plan[s], value ? value + lo : nullptr, grad ? grad + lo * NG : nullptr,
                                dmean ? dmean + lo : nullptr, status ? status + lo : nullptr);
+  });
+}
+
+/* ---- coefficients from kernel parameters: clr_batch_set_kernel / _evaluate_params / _grad_params over the shards ---- */
+int clr_sharded_set_kernel(clr_sharded* h, const clr_kernel* k) {
+  const int st = resolve_all(h);
+  if (st != CLR_OK) return st;
+  h->n_params = 0;
+  if (k && clr_kernel_get_shape(k, &h->n_params, nullptr, nullptr) != CLR_OK) return CLR_INVALID_ARGUMENT;
+  return h->all([=](int s) { return clr_batch_set_kernel(h->plan[s], k); });
+}
+
+int clr_sharded_evaluate_params(clr_sharded* h, const double* params, const double* mean, long mean_stride,
+                                double* loglike, double* logdet, double* quad, int* status) {
+  int st = mean ? clr_sharded_set_mean(h, mean, mean_stride) : resolve_all(h);
+  if (st != CLR_OK) return st;
+  // every shard forms the coefficients of its slice on its device; the largest frequency and decay rate of the WHOLE
+  // batch then go to every shard, as clr_sharded_set_coefficients hands them out from the host tables
+  const long P = h->n_params;
+  st = h->all([=](int s) { return clr_batch_set_parameters(h->plan[s], params ? params + h->lo[s] * P : nullptr); });
+  if (st != CLR_OK) return st;
+  double dmax = 0.0, cmax = 0.0;
+  for (clr_batch* p : h->plan) {
+    double d = 0.0, c = 0.0;
+    clr_batch_get_selection_bounds(p, nullptr, nullptr, &d, &c, nullptr);
+    if (!(d <= dmax)) dmax = d;
+    if (!(c <= cmax)) cmax = c;
+  }
+  for (clr_batch* p : h->plan) clr_batch_set_selection_bounds(p, -1.0, -1.0, dmax, cmax);
+  reselect_all(h);
+  auto results = [=](int s) {
+    const long lo = h->lo[s];
+    double* ll = loglike ? loglike + lo : nullptr;
+    double* ld = logdet ? logdet + lo : nullptr;
+    double* q = quad ? quad + lo : nullptr;
+    int* stt = status ? status + lo : nullptr;
+    const int r = clr_batch_get_results(h->plan[s], ll, ld, q, stt);
+    if (r == CLR_OK) clr_group::mark_refused(h->plan[s], ll, ld, q, stt);
+    return r;
+  };
+  if (h->plan.size() < 2)
+    return h->all([=](int s) {
+      const int e = clr_batch_enqueue(h->plan[s], 0);
+      return e != CLR_OK ? e : results(s);
+    });
+  const size_t S = h->plan.size();
+  std::vector<long> pend(S, 0), elig(S, 0);
+  long* pp = pend.data();
+  long* ee = elig.data();
+  st = h->all([=](int s) {
+    const int e = clr_batch_enqueue(h->plan[s], 0);
+    return e != CLR_OK ? e : clr_group::resolve_begin(h->plan[s], pp + s, ee + s);
+  });
+  if (st != CLR_OK) return st;
+  return resolve_finish_all(h, pend, elig, results);
+}
+
+int clr_sharded_grad_params(clr_sharded* h, double* value, double* grad_params, int* status, int with_mean) {
+  const long ncol = h->n_params + (with_mean ? 1 : 0);
+  const int st0 = resolve_all(h);
+  if (st0 != CLR_OK) return st0;
+  return h->all([=](int s) {
+    const long lo = h->lo[s];
+    return clr_batch_grad_params(h->plan[s], value ? value + lo : nullptr, grad_params ? grad_params + lo * ncol : nullptr,
+                                 status ? status + lo : nullptr, with_mean);
+  });
+}
+
+int clr_sharded_get_coefficients(clr_sharded* h, double* jitter, double* a_real, double* c_real, double* a_comp,
+                                 double* b_comp, double* c_comp, double* d_comp) {
+  const long JR = h->J_real, JC = h->J_comp;
+  const int st0 = resolve_all(h);
+  if (st0 != CLR_OK) return st0;
+  auto at = [](double* p, long off) { return p ? p + off : nullptr; };
+  return h->all([=](int s) {
+    const long lo = h->lo[s];
+    return clr_batch_get_coefficients(h->plan[s], at(jitter, lo), at(a_real, lo * JR), at(c_real, lo * JR), at(a_comp, lo * JC),
+                                      at(b_comp, lo * JC), at(c_comp, lo * JC), at(d_comp, lo * JC));
   });
 }
 

@@ -611,6 +611,76 @@ int clr_batch_get_grad_info(const clr_batch* h, int* reverse_used, int* forward_
  * kernel selection, the prefix plan, the warm-started recurrence's activation and adaptation, side
  * plan or inline replay of level-1 problems and the side plan's chunk count -- is taken once, from
  * the counts over the WHOLE batch (csrc/sharded.cpp, csrc/clr_group_hooks.h). */
+/* ---- kernel programs: a `terms` kernel as a fixed formula from its parameter vector to the coefficients -------------
+ *
+ * A tree of built-in terms (RealTerm, ComplexTerm, SHOTerm, Matern32Term, JitterTerm, sums and products of them) is
+ * compiled once (celerite_amd.batch.compile_kernel) into a flat program and evaluated per draw: on the host by
+ * clr_kernel_coefficients / clr_kernel_jacobian (no GPU needed), on the device by a plan (clr_batch_set_kernel,
+ * clr_batch_evaluate_params, clr_batch_grad_params), where the coefficients never leave HBM.
+ *
+ * Encoding.  `ops` is a sequence of instructions of int words, `opcode, operands...`; `consts` holds doubles:
+ *
+ *    1 REAL        dst  pa pc             a = exp(pa), c = exp(pc)
+ *    2 COMPLEX     dst  pa pb pc pd       a, b, c, d = exp(.)
+ *    3 COMPLEX_B0  dst  pa pc pd          the same with b = 0
+ *    4 SHO_OVER    dst0 dst1 pS pQ pw     SHOTerm with Q <  1/2: two real terms
+ *    5 SHO_UNDER   dst  pS pQ pw          SHOTerm with Q >= 1/2: one complex term
+ *    6 MATERN32    dst  ps pr keps        Matern32Term, eps = consts[keps]
+ *    7 JITTER      ps                     jitter += exp(2 ps)
+ *    8 MUL_RR      dst  r1 r2             real x real:       (a1 a2, c1 + c2)
+ *    9 MUL_RC      dst  r1 c2             real x complex:    (a1 a2, a1 b2, c1 + c2, d2)
+ *   10 MUL_CC      dstm dstp c1 c2        complex x complex: the two terms at d1 - d2 and d1 + d2
+ *
+ * A parameter operand p* >= 0 is an index into the draw's parameter vector (the kernel's unfrozen parameters, in
+ * get_parameter_vector() order); p* < 0 is the constant consts[-(p + 1)] (a frozen parameter).  A destination dst >= 0
+ * is the index of a real (complex) term in the output blocks a_real, c_real (a_comp, b_comp, c_comp, d_comp); dst < 0
+ * is the temporary real (complex) term -(dst + 1), at most 16 of each kind.  The factors r*, c* of a product are
+ * temporaries written by an earlier instruction, given by their index >= 0.  An SHO instruction fixes its regime: a
+ * draw on the other side of Q = 1/2 is refused for that draw (status[b]), never evaluated to another shape.
+ *
+ * clr_kernel_create validates the program -- known opcodes, every operand in range, temporaries written once and
+ * before they are read, every output term written exactly once -- and refuses it with CLR_INVALID_ARGUMENT otherwise
+ * (at most 2048 words, 256 constants, 256 parameters). */
+typedef struct clr_kernel clr_kernel;
+int clr_kernel_create(int n_ops, const int* ops, int n_consts, const double* consts, int n_params, int J_real,
+                      int J_comp, clr_kernel** kernel);
+void clr_kernel_destroy(clr_kernel* kernel);
+int clr_kernel_get_shape(const clr_kernel* kernel, int* n_params, int* J_real, int* J_comp);
+/* The coefficient tables of B draws: params[B][n_params] -> a_real, c_real [B][J_real], a_comp .. d_comp [B][J_comp],
+ * jitter[B] (what clr_batch_set_coefficients takes).  status[b] = CLR_INVALID_ARGUMENT and a row of NaN for a draw the
+ * program refuses: a non-finite parameter or coefficient, an SHO term in the other regime.  The other rows are not
+ * affected.  status and jitter may be NULL. */
+int clr_kernel_coefficients(const clr_kernel* kernel, int B, const double* params, double* a_real, double* c_real,
+                            double* a_comp, double* b_comp, double* c_comp, double* d_comp, double* jitter,
+                            int* status);
+/* The Jacobians of the same formulas, evaluated on forward dual numbers: jac[B][n_params][2 J_real + 4 J_comp] with the
+ * coefficients in the column order of the batched gradient (a_real | c_real | a_comp | b_comp | c_comp | d_comp) and
+ * jitter_jac[B][n_params].  Either may be NULL. */
+int clr_kernel_jacobian(const clr_kernel* kernel, int B, const double* params, double* jac, double* jitter_jac,
+                        int* status);
+/* A plan evaluated straight from kernel parameters.  clr_batch_set_kernel copies the program to the plan's device
+ * (CLR_DIMENSION_MISMATCH when its J_real, J_comp are not the plan's; NULL removes it).  clr_batch_set_parameters is
+ * clr_batch_set_coefficients for params[B][n_params]: kernel_program_eval_kernel forms the coefficients in the plan's
+ * resident block, and the statistics the kernel selection looks at come back from the same kernel in one small
+ * transfer -- the routes and the warm-start decision are the ones clr_batch_set_coefficients takes for the same
+ * coefficients.  A draw the program refuses is given stand-in coefficients on the device (every term exp(-tau), no
+ * jitter), so that it disturbs no other problem, and is reported by clr_batch_evaluate_params / _grad_params /
+ * clr_batch_get_parameter_status with CLR_INVALID_ARGUMENT and NaN results.
+ * clr_batch_evaluate_params: [clr_batch_set_mean +] clr_batch_set_parameters + clr_batch_enqueue + clr_batch_get_results
+ * in one call (mean == NULL: the mean in force stays).
+ * clr_batch_grad_params: after it, clr_batch_grad (with_mean: clr_batch_grad_mean) chained to the parameters on the
+ * device: grad_params[B][n_params (+ 1)] = jitter_jac grad[0] + sum_c jac[.][c] grad[1 + c], the mean's partial last.
+ * Needs coefficients formed by clr_batch_set_parameters (CLR_NOT_COMPUTED otherwise).
+ * clr_batch_get_coefficients reads the resident block back (any pointer may be NULL), however it was set. */
+int clr_batch_set_kernel(clr_batch* h, const clr_kernel* kernel);
+int clr_batch_set_parameters(clr_batch* h, const double* params);
+int clr_batch_get_parameter_status(const clr_batch* h, int* status);
+int clr_batch_evaluate_params(clr_batch* h, const double* params, const double* mean, long mean_stride,
+                              double* loglike, double* logdet, double* quad, int* status);
+int clr_batch_grad_params(clr_batch* h, double* value, double* grad_params, int* status, int with_mean);
+int clr_batch_get_coefficients(clr_batch* h, double* jitter, double* a_real, double* c_real, double* a_comp,
+                               double* b_comp, double* c_comp, double* d_comp);
+
 typedef struct clr_sharded clr_sharded;
 
 /* [lo, hi) of `shard` when `total` problems are cut into `nshards` contiguous slices
@@ -674,6 +744,14 @@ int clr_sharded_evaluate_mean(clr_sharded* h, const double* mean, long mean_stri
                               const double* c_comp, const double* d_comp, double* loglike, double* logdet,
                               double* quad, int* status);
 int clr_sharded_grad_mean(clr_sharded* h, double* value, double* grad, double* dmean, int* status);
+/* clr_batch_set_kernel / _evaluate_params / _grad_params / _get_coefficients over the whole batch: every shard forms the
+ * coefficients of its slice of params[B][n_params] on its own device; the selection bounds are taken over the batch. */
+int clr_sharded_set_kernel(clr_sharded* h, const clr_kernel* kernel);
+int clr_sharded_evaluate_params(clr_sharded* h, const double* params, const double* mean, long mean_stride,
+                                double* loglike, double* logdet, double* quad, int* status);
+int clr_sharded_grad_params(clr_sharded* h, double* value, double* grad_params, int* status, int with_mean);
+int clr_sharded_get_coefficients(clr_sharded* h, double* jitter, double* a_real, double* c_real, double* a_comp,
+                                 double* b_comp, double* c_comp, double* d_comp);
 /* The consumers of the factor on a sharded batch (GP.apply_inverse / .sample / .predict for B problems over several
  * GPUs): clr_sharded_materialize runs clr_batch_enqueue(plan, 1) on every shard, settles the evaluation with the
  * batch-wide counts (results as clr_sharded_get_results; any pointer may be NULL) and leaves every shard's factor in
