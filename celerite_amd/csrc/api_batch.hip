@@ -1120,6 +1120,15 @@ int clr_batch_get_profile(clr_batch* h, double* kernel_ms /* [6] */, int* steps)
   return CLR_OK;
 }
 
+// the parameters of everything around the warm path -- the warm kernel, the one-launch kernel, the scan behind them for
+// the problems they leave pending --: the plan's row-major arrays, the single-wave summarize, pending problems only
+static int fallback_params(clr_batch* h, clr::BatchParams& P) {
+  h->in_fallback = true;
+  const int st = batch_params(h, 0, P);
+  h->in_fallback = false;
+  return st;
+}
+
 // a batch of short, narrow problems: the whole fused evaluation in ONE launch, one workgroup per problem
 // (small_batch_kernel, small_kernels.hip); problems it cannot certify stay pending for the scan pipeline
 static bool small_runs(const clr_batch* h, int materialize) {
@@ -1143,21 +1152,15 @@ static bool small_runs(const clr_batch* h, int materialize) {
 // [problem][i][chunk] made once per set_series (launch_relayout with the path's own chunking, padded as the plan's copy):
 // one coalesced 512-B load per array, wave and step.
 static int small_params(clr_batch* h, clr::BatchParams& Sp) {
-  h->in_fallback = true;  // (the plan's row-major arrays, no role split)
-  int st = batch_params(h, 0, Sp);
-  h->in_fallback = false;
+  int st = fallback_params(h, Sp);
   if (st != CLR_OK) return st;
   const int T = 256, L = (h->N + T - 1) / T;
   const long cells = (long)L * T;
-  auto nsrc = [&](long sd) { return (size_t)(sd == 0 ? 1 : h->B); };
-  if ((st = h->sT.reserve(nsrc(h->t_stride) * cells)) != CLR_OK) return st;
-  if ((st = h->sD.reserve(nsrc(h->diag_stride) * cells)) != CLR_OK) return st;
-  if ((st = h->sY.reserve(nsrc(h->y_stride) * cells)) != CLR_OK) return st;
+  SeriesCopies copies(h, h->sT, h->sD, h->sY, (size_t)cells);
+  if ((st = copies.reserve()) != CLR_OK) return st;
   if (h->small_copy_pending) {
-    struct { DevBuf* src; DevBuf* dst; long stride; int pad; } jobs[3] = {
-        {&h->t, &h->sT, h->t_stride, 1}, {&h->diag, &h->sD, h->diag_stride, 2}, {&h->y, &h->sY, h->y_stride, 0}};
-    for (auto& j : jobs)
-      clr::launch_relayout(j.src->p, j.stride, j.dst->p, j.stride ? cells : 0, j.stride ? h->B : 1, h->N, L, T, j.pad, h->stream.get());
+    for (auto& j : copies.job)
+      clr::launch_relayout(j.src, j.stride, j.dst->p, j.dst_stride, j.nsrc, h->N, L, T, j.pad, h->stream.get());
     h->small_copy_pending = false;
   }
   Sp.t = h->sT.p; Sp.diag = h->sD.p; Sp.y = h->sY.p;
@@ -1176,17 +1179,12 @@ static bool warm_runs(const clr_batch* h, int materialize) {
 // the warm kernel's copy of the series, (re)built when the series or the warm chunking changed
 static int warm_copy(clr_batch* h) {
   if (!h->warm_copy_pending) return CLR_OK;
-  const size_t cells = (size_t)h->wrows * h->wnchunk;
-  auto nsrc = [&](long sd) { return (size_t)(sd == 0 ? 1 : h->B); };
-  int st;
-  if ((st = h->wT.reserve(nsrc(h->t_stride) * cells)) != CLR_OK) return st;
-  if ((st = h->wD.reserve(nsrc(h->diag_stride) * cells)) != CLR_OK) return st;
-  if ((st = h->wY.reserve(nsrc(h->y_stride) * cells)) != CLR_OK) return st;
-  struct { DevBuf* src; DevBuf* dst; long stride; int pad; } jobs[3] = {
-      {&h->t, &h->wT, h->t_stride, 1}, {&h->diag, &h->wD, h->diag_stride, 2}, {&h->y, &h->wY, h->y_stride, 0}};
-  for (auto& j : jobs)
-    clr::launch_relayout_warm(j.src->p, j.stride, j.dst->p, j.stride ? (long)cells : 0, j.stride ? h->B : 1, h->N,
-                              h->wL, h->wnchunk, h->wKpad, h->wrows, j.pad, h->stream.get());
+  SeriesCopies copies(h, h->wT, h->wD, h->wY, (size_t)h->wrows * h->wnchunk);
+  const int st = copies.reserve();
+  if (st != CLR_OK) return st;
+  for (auto& j : copies.job)
+    clr::launch_relayout_warm(j.src, j.stride, j.dst->p, j.dst_stride, j.nsrc, h->N, h->wL, h->wnchunk, h->wKpad, h->wrows,
+                              j.pad, h->stream.get());
   h->warm_copy_pending = false;
   return CLR_OK;
 }
@@ -1200,24 +1198,6 @@ static int warm_upload_K(clr_batch* h) {
   h->warm_K_dirty = false;
   return CLR_OK;
 }
-
-// the scan pipeline for the problems the warm path left pending (single-wave summarize on the row-major arrays)
-static int warm_fallback(clr_batch* h) {
-  clr::BatchParams P;
-  h->in_fallback = true;
-  int st = batch_params(h, 0, P);
-  h->in_fallback = false;
-  if (st != CLR_OK) return st;
-  h->launch->summarize(P, h->stream.get());
-  h->launch->prefix(P, h->stream.get());
-  h->launch->correct(P, h->stream.get());
-  h->launch->replay(P, 0, h->stream.get());
-  h->launch->sequential(P, 0, h->stream.get());
-  clr::launch_finalize(P, h->stream.get());
-  HIP_TRY(hipGetLastError());
-  return CLR_OK;
-}
-
 
 // replay mode of a materialising run: 2 the four arrays chunk-interleaved, 3 the lean layout (W, D only)
 static int replay_mode(const clr_batch* h, int materialize) {
@@ -1273,42 +1253,85 @@ static void factor_written(clr_batch* h, bool lean) {
   h->factor_is_lean = lean; h->factor_inputs_changed = false; h->factor_valid = true; h->bs_M_valid = false;
 }
 
-int clr_batch_enqueue(clr_batch* h, int materialize) {
-  int st = require_device(h->device);
-  if (st != CLR_OK) return st;
-  clr::BatchParams P;
-  if ((st = batch_params(h, materialize, P)) != CLR_OK) return st;
-  // profiling: one event per kernel boundary of this evaluation, on the plan's stream
+// "Record event i of this step now": the step's PROF_NK + 1 events on the plan's stream (null: none) and which of them
+// are wanted.  A record that fails is not reported here: reading an elapsed time off it is (clr_batch_get_profile,
+// clr_batch_run_timed).
+struct StepMarks {
   const clr::Event* ev = nullptr;
-  if (h->prof_on && h->prof_steps < PROF_MAX_STEPS) {
-    const size_t need = (size_t)(h->prof_steps + 1) * (PROF_NK + 1);
-    while (h->prof_events.size() < need) {
-      clr::Event e;
-      HIP_TRY(clr::create_event(e));
-      h->prof_events.push_back(std::move(e));
-    }
-    ev = &h->prof_events[(size_t)h->prof_steps * (PROF_NK + 1)];
-    ++h->prof_steps;
+  unsigned mask = ~0u;
+  void operator()(int i, hipStream_t s) const {
+    if (ev && (mask >> i & 1)) (void)hipEventRecord(ev[i].get(), s);
   }
-  if (!P.defer_level1) h->rescue_last = 0;  // (nothing is re-planned behind this evaluation)
-  h->pin_results = false;
-  const bool all_marks = h->prof_on != 2;
-  auto mark = [&](int i) { if (ev && (all_marks || i == 1 || i == 2)) (void)hipEventRecord(ev[i].get(), h->stream.get()); };
+  void from(int i, hipStream_t s) const {
+    for (; i <= PROF_NK; ++i) (*this)(i, s);
+  }
+};
+
+// The scan pipeline of a narrow plan (widths 1..8), the one place its order is written down: summarize -> prefix ->
+// correct -> replay -> chunk heads -> sequential -> finalize.  `from_replay`: the tail only, on the start states and
+// the routing an evaluation has left (rescue_inline).
+static void narrow_scan(clr_batch* h, clr::BatchParams& P, int materialize, const StepMarks& mark, bool from_replay = false) {
+  hipStream_t s = h->stream.get();
+  const int mode = replay_mode(h, materialize);
+  if (!from_replay) {
+    mark(1, s);
+    h->launch->summarize(P, s);
+    mark(2, s);
+    h->launch->prefix(P, s);
+    mark(3, s);
+    h->launch->correct(P, s);  // (also on forced-exact runs: flags + conditioning record)
+    mark(4, s);
+  }
+  // forced-exact / materialising runs only.  The replay reads the series where the summarize did: from the role split's
+  // chunk-interleaved copy 4.41 ms = 65 % of HBM for the materialising replay at B = 1024, N = 1e5, width 8, against
+  // 4.77 ms from the row-major arrays through LDS-staged tiles (profiles/r03a_prefix_ab.txt)
+  h->launch->replay(P, mode, s);
+  if (P.ends) refine_chunk_heads(h, P, materialize, s);
+  h->launch->sequential(P, mode, s);  // flagged / ill-conditioned problems only
+  if (materialize) factor_written(h, h->factor_layout == 1);
+  mark(5, s);
+  clr::launch_finalize(P, s);
+  mark(6, s);
+  // (capturing these launches in a hipGraph was measured: no gain -- the gaps between
+  //  dependent kernels are on the device side; profiles/r01r_small_batches.log)
+}
+
+// the scan pipeline for the problems the warm path left pending (single-wave summarize on the row-major arrays)
+static int warm_fallback(clr_batch* h) {
+  clr::BatchParams P;
+  const int st = fallback_params(h, P);
+  if (st != CLR_OK) return st;
+  narrow_scan(h, P, 0, StepMarks());
+  HIP_TRY(hipGetLastError());
+  return CLR_OK;
+}
+
+// the chunk-interleaved copy the scan reads, rebuilt if the series -- or only the residual y -- changed since it was made
+static void relayout_if_pending(clr_batch* h) {
+  if (h->relayout_pending && batch_relayout(h)) h->relayout_pending = h->relayout_y_pending = false;
+  else if (h->relayout_y_pending && relayout_residual(h)) h->relayout_y_pending = false;
+}
+
+// ONE evaluation of the plan on the parameters P of batch_params(h, materialize, P): the route test and every launch, for
+// clr_batch_enqueue and for each step of clr_batch_run_timed alike.  `fresh_series`: the step stands for one on a new
+// series -- the copy of the series its route reads is rebuilt inside it whether pending or not (the pending flags are the
+// caller's to settle); otherwise only a pending copy is rebuilt.  The *_inflight flags describe this evaluation afterwards
+// (every state-changing entry point resolves an evaluation in flight first, so none of an earlier one is relied on).
+static int launch_step(clr_batch* h, int materialize, clr::BatchParams& P, const StepMarks& mark, bool fresh_series) {
+  hipStream_t s = h->stream.get();
+  int st;
   h->evaluated = true;
+  h->warm_inflight = h->small_inflight = h->rescue_inflight = false;
   if (h->J_general > 0 || h->J > clr::wide_max_width()) {
     // general terms -- and (round 5) celerite-only kernels of widths 65..128, which have no wave-per-problem kernel --: the
     // any-width sequential recurrence, one workgroup per problem with S in LDS (generic_loglike_batch_kernel)
     if (materialize) return fail(CLR_UNSUPPORTED, "materialising runs with general terms or above width 64: use CholeskySolver");
-    h->warm_inflight = false;
-    h->small_inflight = false;
+    mark(0, s);
     if (h->gen_nchunk > 0 && h->general_route != 1) {
       // the wide kernels with the general rows as a third row class (chunked scan up to total width 32)
       clr::BatchParams W;
       general_wide_params(h, P, W);
-      mark(0);
-      if ((st = wide_flow(W, h->J_real, h->J_comp, h->stream.get(), ev)) != CLR_OK) return st;
-      HIP_TRY(hipGetLastError());
-      return CLR_OK;
+      return wide_flow(W, h->J_real, h->J_comp, s, mark.ev);
     }
     clr::GenericBatch G;
     memset(&G, 0, sizeof(G));
@@ -1320,78 +1343,75 @@ int clr_batch_enqueue(clr_batch* h, int materialize) {
     G.A = h->gA.p; G.U = h->gU.p; G.V = h->gV.p;
     G.A_stride = h->gA_stride; G.U_stride = h->gU_stride; G.V_stride = h->gV_stride;
     G.out_ll = P.out_ll; G.out_logdet = P.out_logdet; G.out_quad = P.out_quad; G.out_status = P.out_status;
-    mark(0); mark(1);
+    mark(1, s);
     // (round 6) total widths 33 .. 128: S in the registers of the problem's workgroup (rows_kernels.hip: 1.6 us per sample at
     // width 128 where the LDS-resident kernel takes 20)
     if (clr::factor_rows_batch_supported(h->J + h->J_general) && !clr::option("CLR_NO_ROWS_KERNEL"))
-      clr::launch_factor_rows_batch(G, P.fast_trig, h->stream.get());
+      clr::launch_factor_rows_batch(G, P.fast_trig, s);
     else
-    clr::launch_generic_loglike_batch(G, h->stream.get());
-    mark(2); mark(3); mark(4); mark(5); mark(6);
-    HIP_TRY(hipGetLastError());
+      clr::launch_generic_loglike_batch(G, s);
+    mark.from(2, s);
     return CLR_OK;
   }
-  if (!h->launch) {
-    mark(0);
-    if ((st = wide_launch(h, P, ev)) != CLR_OK) return st;
+  mark(0, s);
+  if (!h->launch) {  // wide path (one chunk: the whole sweep is in the "replay" slot)
+    if ((st = wide_flow(P, h->J_real, h->J_comp, s, mark.ev)) != CLR_OK) return st;
     if (materialize) factor_written(h, false);
     h->rescue_inflight = P.defer_level1 != 0;
-    HIP_TRY(hipGetLastError());
     return CLR_OK;
   }
-  mark(0);
-  h->warm_inflight = false;
-  h->small_inflight = false;
-  h->rescue_inflight = false;
-  if (!warm_runs(h, materialize) && small_runs(h, materialize)) {
+  if (!warm_runs(h, materialize) && small_runs(h, materialize)) {  // (one launch, in the "summarize" slot)
     clr::BatchParams Sp;
+    if (fresh_series) h->small_copy_pending = true;
     if ((st = small_params(h, Sp)) != CLR_OK) return st;
-    mark(1);
-    clr::launch_small_batch(h->J_real, h->J_comp, Sp, 256, h->stream.get());
-    mark(2); mark(3); mark(4); mark(5); mark(6);
+    mark(1, s);
+    clr::launch_small_batch(h->J_real, h->J_comp, Sp, 256, s);
+    mark.from(2, s);
     h->small_inflight = true;  // (pending problems are settled like the warm path's: warm_resolve)
-    HIP_TRY(hipGetLastError());
     return CLR_OK;
   }
   if (warm_runs(h, materialize)) {
-    // series that forget: the plain recurrence per chunk with a warm-up + the boundary check; problems it cannot
-    // settle are marked pending and go through the scan pipeline when the results are asked for
+    // series that forget: the plain recurrence per chunk with a warm-up + the boundary check, in the "summarize" slot;
+    // problems it cannot settle are marked pending and go through the scan pipeline when the results are asked for
     clr::BatchParams Wp;
+    if (fresh_series) h->warm_copy_pending = true;
     if ((st = warm_copy(h)) != CLR_OK) return st;
     if ((st = warm_upload_K(h)) != CLR_OK) return st;
-    h->in_fallback = true;  // (the row-major arrays, no role split)
-    st = batch_params(h, 0, Wp);
-    h->in_fallback = false;
-    if (st != CLR_OK) return st;
-    mark(1);
-    h->launch->warm(Wp, h->stream.get());
-    mark(2); mark(3); mark(4); mark(5); mark(6);
+    if ((st = fallback_params(h, Wp)) != CLR_OK) return st;
+    mark(1, s);
+    h->launch->warm(Wp, s);
+    mark.from(2, s);
     h->warm_inflight = true;
-    HIP_TRY(hipGetLastError());
     return CLR_OK;
   }
-  if (h->relayout_pending && batch_relayout(h)) h->relayout_pending = h->relayout_y_pending = false;
-  else if (h->relayout_y_pending && relayout_residual(h)) h->relayout_y_pending = false;
-  mark(1);
-  h->launch->summarize(P, h->stream.get());
-  mark(2);
-  h->launch->prefix(P, h->stream.get());
-  mark(3);
-  h->launch->correct(P, h->stream.get());  // (also on forced-exact runs: flags + conditioning record)
-  mark(4);
-  // forced-exact / materialising runs only.  The replay reads the series where the summarize did: from the role split's
-  // chunk-interleaved copy 4.41 ms = 65 % of HBM for the materialising replay at B = 1024, N = 1e5, width 8, against
-  // 4.77 ms from the row-major arrays through LDS-staged tiles (profiles/r03a_prefix_ab.txt)
-  h->launch->replay(P, replay_mode(h, materialize), h->stream.get());
-  if (P.ends) refine_chunk_heads(h, P, materialize, h->stream.get());
-  h->launch->sequential(P, replay_mode(h, materialize), h->stream.get());  // flagged / ill-conditioned problems only
-  if (materialize) factor_written(h, h->factor_layout == 1);
-  mark(5);
-  clr::launch_finalize(P, h->stream.get());
-  mark(6);
+  if (fresh_series) batch_relayout(h);
+  else relayout_if_pending(h);
+  narrow_scan(h, P, materialize, mark);
   h->rescue_inflight = P.defer_level1 != 0;
-  // (capturing these five launches in a hipGraph was measured: no gain -- the gaps between
-  //  dependent kernels are on the device side; profiles/r01r_small_batches.log)
+  return CLR_OK;
+}
+
+int clr_batch_enqueue(clr_batch* h, int materialize) {
+  int st = require_device(h->device);
+  if (st != CLR_OK) return st;
+  clr::BatchParams P;
+  if ((st = batch_params(h, materialize, P)) != CLR_OK) return st;
+  // profiling: one event per kernel boundary of this evaluation, on the plan's stream (mode 2: events 1 and 2 only)
+  StepMarks mark;
+  if (h->prof_on && h->prof_steps < PROF_MAX_STEPS) {
+    const size_t need = (size_t)(h->prof_steps + 1) * (PROF_NK + 1);
+    while (h->prof_events.size() < need) {
+      clr::Event e;
+      HIP_TRY(clr::create_event(e));
+      h->prof_events.push_back(std::move(e));
+    }
+    mark.ev = &h->prof_events[(size_t)h->prof_steps * (PROF_NK + 1)];
+    if (h->prof_on == 2) mark.mask = 1u << 1 | 1u << 2;
+    ++h->prof_steps;
+  }
+  if (!P.defer_level1) h->rescue_last = 0;  // (nothing is re-planned behind this evaluation)
+  h->pin_results = false;
+  if ((st = launch_step(h, materialize, P, mark, false)) != CLR_OK) return st;
   HIP_TRY(hipGetLastError());
   return CLR_OK;
 }
@@ -1443,9 +1463,7 @@ static int rescue_inline(clr_batch* h) {
     S.nchunk = 1; S.L = P.N; S.L0 = 0; S.seq_only = 1; S.force_exact = 1;
     clr::launch_wide_loglike(S, h->J_real, h->J_comp, h->stream.get());
   } else {
-    h->launch->replay(P, 0, h->stream.get());
-    h->launch->sequential(P, 0, h->stream.get());
-    clr::launch_finalize(P, h->stream.get());
+    narrow_scan(h, P, 0, StepMarks(), true);
   }
   HIP_TRY(hipGetLastError());
   return CLR_OK;
@@ -1551,6 +1569,14 @@ static int rescue_run(clr_batch* h, const std::vector<int>& idx, long n_total) {
 // Two halves (a plan that is a slice of a larger batch has the sharded layer add up the counts between them,
 // clr_group_hooks.h): resolve_begin waits for the evaluation and counts, resolve_finish acts on the counts of the
 // whole batch.
+// the results in HBM (ll | logdet | quad | status) -> the pinned staging buffer, waited for
+static int fetch_results(clr_batch* h) {
+  const size_t B = (size_t)h->B, words = 3 * B + (B + 1) / 2;
+  HIP_TRY(hipMemcpyAsync(h->pin.p, h->out.p, words * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
+  HIP_TRY(hipStreamSynchronize(h->stream.get()));
+  return CLR_OK;
+}
+
 static int resolve_begin(clr_batch* h, long* pending_out, long* eligible_out) {
   if (pending_out) *pending_out = 0;
   if (eligible_out) *eligible_out = 0;
@@ -1570,8 +1596,7 @@ static int resolve_begin(clr_batch* h, long* pending_out, long* eligible_out) {
   const size_t B = (size_t)h->B, words = 3 * B + (B + 1) / 2;
   int st;
   if ((st = reserve_pinned(h, words)) != CLR_OK) return st;
-  HIP_TRY(hipMemcpyAsync(h->pin.p, h->out.p, words * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
-  HIP_TRY(hipStreamSynchronize(h->stream.get()));
+  if ((st = fetch_results(h)) != CLR_OK) return st;
   const int* stw = reinterpret_cast<const int*>(h->pin.p + 3 * B);
   long pending = 0;
   for (size_t b = 0; b < B; ++b) pending += stw[b] == clr::CLR_PENDING_STATUS;
@@ -1591,7 +1616,7 @@ static int resolve_begin(clr_batch* h, long* pending_out, long* eligible_out) {
 static int resolve_finish(clr_batch* h, long pending_total, long eligible_total) {
   if (!h->res_open) return CLR_OK;
   h->res_open = false;
-  const size_t B = (size_t)h->B, words = 3 * B + (B + 1) / 2;
+  const size_t B = (size_t)h->B;
   const bool was_warm = h->res_was_warm, was_rescue = h->res_was_rescue;
   const long pending = h->res_pending;
   const int* stw = reinterpret_cast<const int*>(h->pin.p + 3 * B);
@@ -1604,8 +1629,7 @@ static int resolve_finish(clr_batch* h, long pending_total, long eligible_total)
       for (size_t b = 0; b < B; ++b) if (stw[b] == clr::CLR_PENDING_STATUS) idx.push_back((int)b);
       h->pin_results = false;
       if ((st = rescue_run(h, idx, pending_total)) != CLR_OK) return st;
-      HIP_TRY(hipMemcpyAsync(h->pin.p, h->out.p, words * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
-      HIP_TRY(hipStreamSynchronize(h->stream.get()));
+      if ((st = fetch_results(h)) != CLR_OK) return st;
       h->pin_results = true;
     }
     return CLR_OK;
@@ -1613,8 +1637,7 @@ static int resolve_finish(clr_batch* h, long pending_total, long eligible_total)
   if (pending) {
     h->pin_results = false;
     if ((st = warm_fallback(h)) != CLR_OK) return st;
-    HIP_TRY(hipMemcpyAsync(h->pin.p, h->out.p, words * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
-    HIP_TRY(hipStreamSynchronize(h->stream.get()));
+    if ((st = fetch_results(h)) != CLR_OK) return st;
     h->pin_results = true;
   }
   if (pending_total) {
@@ -1664,10 +1687,7 @@ int clr_batch_get_results(clr_batch* h, double* loglike, double* logdet, double*
   // copy into the pinned staging buffer (ll | logdet | quad | status), then host memcpys
   bool pin_current = false;
   if ((st = warm_resolve(h, &pin_current)) != CLR_OK) return st;
-  if (!pin_current) {
-    HIP_TRY(hipMemcpyAsync(h->pin.p, h->out.p, words * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
-    HIP_TRY(hipStreamSynchronize(h->stream.get()));
-  }
+  if (!pin_current && (st = fetch_results(h)) != CLR_OK) return st;
   if (loglike) memcpy(loglike, h->pin.p, B * sizeof(double));
   if (logdet) memcpy(logdet, h->pin.p + B, B * sizeof(double));
   if (quad) memcpy(quad, h->pin.p + 2 * B, B * sizeof(double));
@@ -2067,7 +2087,6 @@ int clr_batch_run_timed(clr_batch* h, int materialize, int steps, int relayout_e
   clr::BatchParams P;
   if ((st = batch_params(h, materialize, P)) != CLR_OK) return st;
   if (steps < 1) steps = 1;
-  h->evaluated = true;
   h->pin_results = false;
   if (h->J_general > 0 || h->J > clr::wide_max_width()) {
     // (plans on the any-width sequential kernel or with general terms: the evaluation itself, `steps` times, as one "replay" slot)
@@ -2085,68 +2104,20 @@ int clr_batch_run_timed(clr_batch* h, int materialize, int steps, int relayout_e
     if (kernel_ms) { for (int j = 0; j < 6; ++j) kernel_ms[j] = 0.0; kernel_ms[4] = tot; }
     return CLR_OK;
   }
-  if (!warm_runs(h, materialize) && h->relayout_pending && !relayout_each_step && batch_relayout(h))
-    h->relayout_pending = h->relayout_y_pending = false;
-  else if (!warm_runs(h, materialize) && h->relayout_y_pending && !relayout_each_step && relayout_residual(h))
-    h->relayout_y_pending = false;
+  if (!relayout_each_step && !warm_runs(h, materialize)) relayout_if_pending(h);  // (in front of the timed steps)
   // one event per kernel boundary per step, all recorded on the handle's stream
-  const int NK = 6;
+  const int NK = PROF_NK;
   std::vector<clr::Event> ev((size_t)steps * (NK + 1));
   for (clr::Event& e : ev) HIP_TRY(clr::create_event(e));
   for (int i = 0; i < steps; ++i) {
     const clr::Event* e = &ev[(size_t)i * (NK + 1)];
-    HIP_TRY(hipEventRecord(e[0].get(), h->stream.get()));
-    if (!h->launch) {  // wide path (one chunk: the whole sweep is reported in the "replay" slot)
-      if ((st = wide_launch(h, P, e)) != CLR_OK) return st;
-      if (materialize) factor_written(h, false);
-      // (a plan that re-planned level-1 problems at its last evaluation does so inside every timed step: the step's
-      //  time then includes the side plan -- at the price of a host round trip per step)
-      if (P.defer_level1 && h->rescue_last != 0) { h->rescue_inflight = true; if ((st = warm_resolve(h, nullptr)) != CLR_OK) return st; HIP_TRY(hipEventRecord(e[6].get(), h->stream.get())); }
-      else h->rescue_inflight = P.defer_level1 != 0;
-      continue;
+    if ((st = launch_step(h, materialize, P, StepMarks{e}, relayout_each_step != 0)) != CLR_OK) return st;
+    // (a plan that re-planned level-1 problems at its last evaluation does so inside every timed step: the step's
+    //  time then includes the side plan -- at the price of a host round trip per step)
+    if (h->rescue_inflight && h->rescue_last != 0) {
+      if ((st = warm_resolve(h, nullptr)) != CLR_OK) return st;
+      HIP_TRY(hipEventRecord(e[NK].get(), h->stream.get()));
     }
-    if (!warm_runs(h, materialize) && small_runs(h, materialize)) {  // (one launch, in the "summarize" slot)
-      clr::BatchParams Sp;
-      if (relayout_each_step) h->small_copy_pending = true;  // (new series every step: the copy is rebuilt inside it)
-      if ((st = small_params(h, Sp)) != CLR_OK) return st;
-      HIP_TRY(hipEventRecord(e[1].get(), h->stream.get()));
-      clr::launch_small_batch(h->J_real, h->J_comp, Sp, 256, h->stream.get());
-      for (int j = 2; j <= 6; ++j) HIP_TRY(hipEventRecord(e[j].get(), h->stream.get()));
-      h->small_inflight = true;
-      continue;
-    }
-    if (warm_runs(h, materialize)) {  // (the warm path: recurrence + boundary check in the "summarize" slot)
-      clr::BatchParams Wp;
-      if (relayout_each_step) h->warm_copy_pending = true;  // (new series every step: the copy is rebuilt inside it)
-      if ((st = warm_copy(h)) != CLR_OK) return st;
-      if ((st = warm_upload_K(h)) != CLR_OK) return st;
-      h->in_fallback = true;
-      st = batch_params(h, 0, Wp);
-      h->in_fallback = false;
-      if (st != CLR_OK) return st;
-      HIP_TRY(hipEventRecord(e[1].get(), h->stream.get()));
-      h->launch->warm(Wp, h->stream.get());
-      for (int j = 2; j <= 6; ++j) HIP_TRY(hipEventRecord(e[j].get(), h->stream.get()));
-      h->warm_inflight = true;
-      continue;
-    }
-    if (relayout_each_step) batch_relayout(h);
-    HIP_TRY(hipEventRecord(e[1].get(), h->stream.get()));
-    h->launch->summarize(P, h->stream.get());
-    HIP_TRY(hipEventRecord(e[2].get(), h->stream.get()));
-    h->launch->prefix(P, h->stream.get());
-    HIP_TRY(hipEventRecord(e[3].get(), h->stream.get()));
-    h->launch->correct(P, h->stream.get());
-    HIP_TRY(hipEventRecord(e[4].get(), h->stream.get()));
-    h->launch->replay(P, replay_mode(h, materialize), h->stream.get());
-    if (P.ends) refine_chunk_heads(h, P, materialize, h->stream.get());
-    h->launch->sequential(P, replay_mode(h, materialize), h->stream.get());
-    if (materialize) factor_written(h, h->factor_layout == 1);
-    HIP_TRY(hipEventRecord(e[5].get(), h->stream.get()));
-    clr::launch_finalize(P, h->stream.get());
-    if (P.defer_level1 && h->rescue_last != 0) { h->rescue_inflight = true; if ((st = warm_resolve(h, nullptr)) != CLR_OK) return st; }
-    else h->rescue_inflight = P.defer_level1 != 0;
-    HIP_TRY(hipEventRecord(e[6].get(), h->stream.get()));
   }
   if (relayout_each_step && !warm_runs(h, materialize) && (h->layout == 1 || split_active(h)) && h->nchunk > 1)
     h->relayout_pending = h->relayout_y_pending = false;

@@ -446,6 +446,29 @@ bool defer_runs(const clr_batch* h, int materialize) {
   return h->L >= 1024;
 }
 
+// The plan's three series arrays and a chunk-interleaved copy of each, `cells` doubles per series (a shared series has
+// ONE copy): the plan's own (tT, dT, yT), the one-launch path's, the warm kernel's.  reserve() sizes the copies; whoever
+// builds them launches its relayout kernel per job (pad: how the cells past the series' end are filled).
+struct SeriesCopies {
+  struct Job { const double* src; long stride; DevBuf* dst; int pad; int nsrc; long dst_stride; } job[3];
+  size_t cells;
+  SeriesCopies(const clr_batch* h, DevBuf& T, DevBuf& D, DevBuf& Y, size_t cells_) : cells(cells_) {
+    auto make = [&](const DevBuf& src, long stride, DevBuf& dst, int pad) {
+      return Job{src.p, stride, &dst, pad, stride ? h->B : 1, stride ? (long)cells : 0};
+    };
+    job[0] = make(h->t, h->t_stride, T, 1);
+    job[1] = make(h->diag, h->diag_stride, D, 2);
+    job[2] = make(h->y, h->y_stride, Y, 0);
+  }
+  int reserve() {
+    for (Job& j : job) {
+      const int st = j.dst->reserve((size_t)j.nsrc * cells);
+      if (st != CLR_OK) return st;
+    }
+    return CLR_OK;
+  }
+};
+
 int batch_params(clr_batch* h, int materialize, clr::BatchParams& P) {
   if (!h->have_series || !h->have_coeffs)
     return fail(CLR_INVALID_ARGUMENT, "set_series and set_coefficients must be called first");
@@ -489,10 +512,7 @@ int batch_params(clr_batch* h, int materialize, clr::BatchParams& P) {
   // (the wide kernels, the warm-started recurrence and the scan behind it read the row-major arrays)
   if (h->launch && (h->layout == 1 || split) && h->nchunk > 1 && !h->in_fallback) {
     const long cells = (long)h->nchunk * h->L;
-    auto nsrc = [&](long sd) { return (size_t)(sd == 0 ? 1 : h->B); };
-    if ((st = h->tT.reserve(nsrc(h->t_stride) * cells)) != CLR_OK) return st;
-    if ((st = h->dT.reserve(nsrc(h->diag_stride) * cells)) != CLR_OK) return st;
-    if ((st = h->yT.reserve(nsrc(h->y_stride) * cells)) != CLR_OK) return st;
+    if ((st = SeriesCopies(h, h->tT, h->dT, h->yT, (size_t)cells).reserve()) != CLR_OK) return st;
     P.t = h->tT.p; P.diag = h->dT.p; P.y = h->yT.p;
     P.t_stride = h->t_stride ? cells : 0;
     P.diag_stride = h->diag_stride ? cells : 0;
@@ -561,12 +581,9 @@ int batch_params(clr_batch* h, int materialize, clr::BatchParams& P) {
 // (a new coefficient draw can switch the summarize kernel) with the series unchanged.
 bool batch_relayout(clr_batch* h) {
   if (!((h->layout == 1 || split_active(h)) && h->nchunk > 1)) return false;
-  const long cells = (long)h->nchunk * h->L;
-  struct { DevBuf* src; DevBuf* dst; long stride; int pad; } jobs[3] = {
-      {&h->t, &h->tT, h->t_stride, 1}, {&h->diag, &h->dT, h->diag_stride, 2}, {&h->y, &h->yT, h->y_stride, 0}};
-  for (auto& j : jobs)
-    clr::launch_relayout(j.src->p, j.stride, j.dst->p, j.stride ? cells : 0, j.stride ? h->B : 1,
-                         h->N, h->L, h->nchunk, j.pad, h->stream.get());
+  const SeriesCopies copies(h, h->tT, h->dT, h->yT, (size_t)h->nchunk * h->L);
+  for (auto& j : copies.job)
+    clr::launch_relayout(j.src, j.stride, j.dst->p, j.dst_stride, j.nsrc, h->N, h->L, h->nchunk, j.pad, h->stream.get());
   return true;
 }
 
@@ -629,9 +646,6 @@ int wide_flow(clr::BatchParams& P, int J_real, int J_comp, hipStream_t stream, c
   mark(5);
   mark(6);
   return CLR_OK;
-}
-int wide_launch(clr_batch* h, clr::BatchParams& P, const clr::Event* ev) {
-  return wide_flow(P, h->J_real, h->J_comp, h->stream.get(), ev);
 }
 
 const int PROF_NK = 6, PROF_MAX_STEPS = 4096;

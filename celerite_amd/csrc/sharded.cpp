@@ -169,6 +169,56 @@ int on_slices(clr_sharded* h, bool valid, const std::function<int(clr_batch*, lo
   return h->all([=](int s) { return f(h->plan[s], h->lo[s]); });
 }
 
+template <class T>
+T* at(T* p, long off) { return p ? p + off : nullptr; }
+
+// clr_batch_get_results of shard s into its slice of the caller's arrays (any of them may be null)
+int slice_results(clr_sharded* h, int s, double* loglike, double* logdet, double* quad, int* status) {
+  const long lo = h->lo[s];
+  return clr_batch_get_results(h->plan[s], at(loglike, lo), at(logdet, lo), at(quad, lo), at(status, lo));
+}
+
+// two of the shards' selection maxima (the series' max |t| and largest step, or the coefficients' largest frequency and
+// decay rate) over the WHOLE batch -> every shard
+void spread_maxima(clr_sharded* h, bool of_series) {
+  double m0 = 0.0, m1 = 0.0;
+  for (clr_batch* p : h->plan) {
+    double a = 0.0, b = 0.0;
+    if (of_series) clr_batch_get_selection_bounds(p, &a, &b, nullptr, nullptr, nullptr);
+    else clr_batch_get_selection_bounds(p, nullptr, nullptr, &a, &b, nullptr);
+    if (!(a <= m0)) m0 = a;
+    if (!(b <= m1)) m1 = b;
+  }
+  for (clr_batch* p : h->plan) {
+    if (of_series) clr_batch_set_selection_bounds(p, m0, m1, -1.0, -1.0);
+    else clr_batch_set_selection_bounds(p, -1.0, -1.0, m0, m1);
+  }
+}
+
+// One evaluation of the whole batch, then results(shard) on every shard.  One shard: its plan is the whole batch and
+// resolves by itself -- one job, with `before` (when given: the new coefficients) in front of the launch.  Several: two
+// rounds of jobs with the batch-wide sums between them -- launches + the first half of the resolve (then the pending /
+// eligible counts of the whole batch); the second half + the results.
+int evaluate_rounds(clr_sharded* h, int materialize, const std::function<int(int)>& results,
+                    const std::function<int(int)>& before = nullptr) {
+  if (h->plan.size() < 2)
+    return h->all([=](int s) {
+      int st = before ? before(s) : (int)CLR_OK;
+      if (st == CLR_OK) st = clr_batch_enqueue(h->plan[s], materialize);
+      return st == CLR_OK ? results(s) : st;
+    });
+  const size_t S = h->plan.size();
+  std::vector<long> pend(S, 0), elig(S, 0);
+  long* pp = pend.data();
+  long* ee = elig.data();
+  const int st = h->all([=](int s) {
+    const int e = clr_batch_enqueue(h->plan[s], materialize);
+    return e != CLR_OK ? e : clr_group::resolve_begin(h->plan[s], pp + s, ee + s);
+  });
+  if (st != CLR_OK) return st;
+  return resolve_finish_all(h, pend, elig, results);
+}
+
 }  // namespace
 
 extern "C" {
@@ -331,14 +381,7 @@ int clr_sharded_set_series(clr_sharded* h, const double* t, long t_stride, const
   });
   if (st != CLR_OK) return st;
   // the series' maxima over the WHOLE batch (every shard scanned its own slice during the upload)
-  double tmax = 0.0, dxmax = 0.0;
-  for (clr_batch* p : h->plan) {
-    double a = 0.0, b = 0.0;
-    clr_batch_get_selection_bounds(p, &a, &b, nullptr, nullptr, nullptr);
-    if (!(a <= tmax)) tmax = a;
-    if (!(b <= dxmax)) dxmax = b;
-  }
-  for (clr_batch* p : h->plan) clr_batch_set_selection_bounds(p, tmax, dxmax, -1.0, -1.0);
+  spread_maxima(h, true);
   reselect_all(h);
   return CLR_OK;
 }
@@ -424,11 +467,7 @@ int clr_sharded_synchronize(clr_sharded* h) {
 int clr_sharded_get_results(clr_sharded* h, double* loglike, double* logdet, double* quad, int* status) {
   const int st0 = resolve_all(h);
   if (st0 != CLR_OK) return st0;
-  return h->all([=](int s) {
-    const long lo = h->lo[s];
-    return clr_batch_get_results(h->plan[s], loglike ? loglike + lo : nullptr, logdet ? logdet + lo : nullptr,
-                                 quad ? quad + lo : nullptr, status ? status + lo : nullptr);
-  });
+  return h->all([=](int s) { return slice_results(h, s, loglike, logdet, quad, status); });
 }
 
 // value + gradient of every problem at the coefficients in force: clr_batch_grad on every shard concurrently
@@ -446,35 +485,17 @@ int clr_sharded_grad(clr_sharded* h, double* value, double* grad, int* status) {
 int clr_sharded_evaluate(clr_sharded* h, const double* jitter, const double* a_real, const double* c_real,
                          const double* a_comp, const double* b_comp, const double* c_comp,
                          const double* d_comp, double* loglike, double* logdet, double* quad, int* status) {
-  if (h->plan.size() < 2) {  // one shard: the plan is the whole batch, one job
+  // one shard: coefficients, launch and results in ONE job (the headline loop saves two worker round trips); several: the
+  // coefficients first (then the warm path's activation over the whole batch)
+  std::function<int(int)> coefficients;
+  if (h->plan.size() < 2) {
     global_coefficient_bounds(h, c_real, c_comp, d_comp);
-    return h->all([=](int s) {
-      clr_batch* p = h->plan[s];
-      int st = clr_batch_set_coefficients(p, jitter, a_real, c_real, a_comp, b_comp, c_comp, d_comp);
-      if (st == CLR_OK) st = clr_batch_enqueue(p, 0);
-      if (st == CLR_OK) st = clr_batch_get_results(p, loglike, logdet, quad, status);
-      return st;
-    });
+    coefficients = [=](int s) { return clr_batch_set_coefficients(h->plan[s], jitter, a_real, c_real, a_comp, b_comp, c_comp, d_comp); };
+  } else {
+    const int st = clr_sharded_set_coefficients(h, jitter, a_real, c_real, a_comp, b_comp, c_comp, d_comp);
+    if (st != CLR_OK) return st;
   }
-  // several shards, three rounds of jobs with the batch-wide sums between them: coefficients in (then the warm path's
-  // activation over the whole batch); launches + the first half of the resolve (then the pending / eligible counts of
-  // the whole batch); the second half + the results
-  int st = clr_sharded_set_coefficients(h, jitter, a_real, c_real, a_comp, b_comp, c_comp, d_comp);
-  if (st != CLR_OK) return st;
-  const size_t S = h->plan.size();
-  std::vector<long> pend(S, 0), elig(S, 0);
-  long* pp = pend.data();
-  long* ee = elig.data();
-  st = h->all([=](int s) {
-    const int e = clr_batch_enqueue(h->plan[s], 0);
-    return e != CLR_OK ? e : clr_group::resolve_begin(h->plan[s], pp + s, ee + s);
-  });
-  if (st != CLR_OK) return st;
-  return resolve_finish_all(h, pend, elig, [=](int s) {
-    const long lo = h->lo[s];
-    return clr_batch_get_results(h->plan[s], loglike ? loglike + lo : nullptr, logdet ? logdet + lo : nullptr,
-                                 quad ? quad + lo : nullptr, status ? status + lo : nullptr);
-  });
+  return evaluate_rounds(h, 0, [=](int s) { return slice_results(h, s, loglike, logdet, quad, status); }, coefficients);
 }
 
 int clr_sharded_set_mean(clr_sharded* h, const double* mu, long mu_stride) {
@@ -525,40 +546,14 @@ int clr_sharded_evaluate_params(clr_sharded* h, const double* params, const doub
   const long P = h->n_params;
   st = h->all([=](int s) { return clr_batch_set_parameters(h->plan[s], params ? params + h->lo[s] * P : nullptr); });
   if (st != CLR_OK) return st;
-  double dmax = 0.0, cmax = 0.0;
-  for (clr_batch* p : h->plan) {
-    double d = 0.0, c = 0.0;
-    clr_batch_get_selection_bounds(p, nullptr, nullptr, &d, &c, nullptr);
-    if (!(d <= dmax)) dmax = d;
-    if (!(c <= cmax)) cmax = c;
-  }
-  for (clr_batch* p : h->plan) clr_batch_set_selection_bounds(p, -1.0, -1.0, dmax, cmax);
+  spread_maxima(h, false);
   reselect_all(h);
-  auto results = [=](int s) {
+  return evaluate_rounds(h, 0, [=](int s) {
     const long lo = h->lo[s];
-    double* ll = loglike ? loglike + lo : nullptr;
-    double* ld = logdet ? logdet + lo : nullptr;
-    double* q = quad ? quad + lo : nullptr;
-    int* stt = status ? status + lo : nullptr;
-    const int r = clr_batch_get_results(h->plan[s], ll, ld, q, stt);
-    if (r == CLR_OK) clr_group::mark_refused(h->plan[s], ll, ld, q, stt);
+    const int r = slice_results(h, s, loglike, logdet, quad, status);
+    if (r == CLR_OK) clr_group::mark_refused(h->plan[s], at(loglike, lo), at(logdet, lo), at(quad, lo), at(status, lo));
     return r;
-  };
-  if (h->plan.size() < 2)
-    return h->all([=](int s) {
-      const int e = clr_batch_enqueue(h->plan[s], 0);
-      return e != CLR_OK ? e : results(s);
-    });
-  const size_t S = h->plan.size();
-  std::vector<long> pend(S, 0), elig(S, 0);
-  long* pp = pend.data();
-  long* ee = elig.data();
-  st = h->all([=](int s) {
-    const int e = clr_batch_enqueue(h->plan[s], 0);
-    return e != CLR_OK ? e : clr_group::resolve_begin(h->plan[s], pp + s, ee + s);
   });
-  if (st != CLR_OK) return st;
-  return resolve_finish_all(h, pend, elig, results);
 }
 
 int clr_sharded_grad_params(clr_sharded* h, double* value, double* grad_params, int* status, int with_mean) {
@@ -577,7 +572,6 @@ int clr_sharded_get_coefficients(clr_sharded* h, double* jitter, double* a_real,
   const long JR = h->J_real, JC = h->J_comp;
   const int st0 = resolve_all(h);
   if (st0 != CLR_OK) return st0;
-  auto at = [](double* p, long off) { return p ? p + off : nullptr; };
   return h->all([=](int s) {
     const long lo = h->lo[s];
     return clr_batch_get_coefficients(h->plan[s], at(jitter, lo), at(a_real, lo * JR), at(c_real, lo * JR), at(a_comp, lo * JC),
@@ -590,26 +584,7 @@ int clr_sharded_get_coefficients(clr_sharded* h, double* jitter, double* a_real,
 int clr_sharded_materialize(clr_sharded* h, double* loglike, double* logdet, double* quad, int* status) {
   const int st0 = resolve_all(h);
   if (st0 != CLR_OK) return st0;
-  auto results = [=](int s) {
-    const long lo = h->lo[s];
-    return clr_batch_get_results(h->plan[s], loglike ? loglike + lo : nullptr, logdet ? logdet + lo : nullptr,
-                                 quad ? quad + lo : nullptr, status ? status + lo : nullptr);
-  };
-  if (h->plan.size() < 2)
-    return h->all([=](int s) {
-      const int e = clr_batch_enqueue(h->plan[s], 1);
-      return e != CLR_OK ? e : results(s);
-    });
-  const size_t S = h->plan.size();
-  std::vector<long> pend(S, 0), elig(S, 0);
-  long* pp = pend.data();
-  long* ee = elig.data();
-  const int st = h->all([=](int s) {
-    const int e = clr_batch_enqueue(h->plan[s], 1);
-    return e != CLR_OK ? e : clr_group::resolve_begin(h->plan[s], pp + s, ee + s);
-  });
-  if (st != CLR_OK) return st;
-  return resolve_finish_all(h, pend, elig, results);
+  return evaluate_rounds(h, 1, [=](int s) { return slice_results(h, s, loglike, logdet, quad, status); });
 }
 
 int clr_sharded_solve(clr_sharded* h, int nrhs, const double* b, double* x) {
