@@ -115,10 +115,7 @@ int clr_batch_set_chunks(clr_batch* h, int nchunk) {
     const long first = (long)h->N - (long)(nc - 1) * L;
     if (L >= 64 && first >= L) { h->L = L; h->L0 = (int)first; }
   }
-  h->relayout_pending = true;
-  h->grad_span_valid = false;
-  h->have_factor = false;  // its layout depends on the chunking
-  h->factor_valid = false;
+  chunking_replaced(h);
   const size_t pc = (size_t)h->B * h->nchunk;
   h->plan = clr::plan_prefix(h->nchunk, 0, 0);
   h->scan_ws_doubles = 0;
@@ -152,7 +149,6 @@ int clr_batch_set_chunks(clr_batch* h, int nchunk) {
   // the conditioning record
   HIP_TRY(hipMemsetAsync(h->flags.p, 0, (2 * pc + (size_t)h->B) * sizeof(int), h->stream.get()));
   HIP_TRY(hipMemsetAsync(h->cond.p, 0, pc * 4 * sizeof(double), h->stream.get()));
-  h->evaluated = false;
   if ((st = warm_plan_chunks(h)) != CLR_OK) return st;
   if (h->J_general > 0 && (st = plan_general_chunks(h)) != CLR_OK) return st;  // (its chunking follows the plan's settings)
   return CLR_OK;
@@ -177,8 +173,7 @@ static int warm_plan_chunks(clr_batch* h) {
   h->wnchunk = (int)nc;
   h->wKpad = std::min(128, h->wL / 2);  // rows of warm-up every chunk's column carries (the largest candidate)
   h->wrows = h->wKpad + h->wL + 8;
-  h->warm_copy_pending = true;
-  h->small_copy_pending = true;
+  warm_chunking_replaced(h);
   const size_t pc = (size_t)h->B * nc, START = (size_t)h->launch->start_doubles;
   int st;
   if ((st = h->wstarts.reserve(pc * START)) != CLR_OK) return st;
@@ -283,22 +278,8 @@ static int apply_mean(clr_batch* h) {
   HIP_TRY(hipEventRecord(h->mean_ev.get(), h->stream.get()));
   clr::launch_residual(h->y_src.p, h->y_src_stride, h->mean_dev.p, h->mean_stride, nout, (int)N, h->y.p, h->stream.get());
   HIP_TRY(hipGetLastError());
-  const long stride = per_problem ? N : 0;
-  if (stride != h->y_stride) h->relayout_pending = true;
-  h->y_stride = stride;
-  h->relayout_y_pending = true;
-  h->small_copy_pending = true;
-  h->warm_copy_pending = true;
+  residual_replaced(h, per_problem ? N : 0);
   return CLR_OK;
-}
-
-// the chunk-interleaved copy of `y` alone (a new mean on an unchanged series): batch_relayout's y job
-static bool relayout_residual(clr_batch* h) {
-  if (!((h->layout == 1 || split_active(h)) && h->nchunk > 1)) return false;
-  const long cells = (long)h->nchunk * h->L;
-  clr::launch_relayout(h->y.p, h->y_stride, h->yT.p, h->y_stride ? cells : 0, h->y_stride ? h->B : 1, h->N, h->L,
-                       h->nchunk, 0, h->stream.get());
-  return true;
 }
 
 int clr_batch_set_mean(clr_batch* h, const double* mu, long mu_stride) {
@@ -318,11 +299,7 @@ int clr_batch_set_mean(clr_batch* h, const double* mu, long mu_stride) {
     h->host_mean.clear();
     if (h->have_series) {  // the caller's series is the pipeline's again
       std::swap(h->y, h->y_src);
-      if (h->y_src_stride != h->y_stride) h->relayout_pending = true;
-      h->y_stride = h->y_src_stride;
-      h->relayout_y_pending = true;
-      h->small_copy_pending = true;
-      h->warm_copy_pending = true;
+      residual_replaced(h, h->y_src_stride);
     }
     return CLR_OK;
   }
@@ -360,13 +337,7 @@ int clr_batch_set_series(clr_batch* h, const double* t, long t_stride, const dou
   // succeeded (a failed upload must not leave have_series set over half-written arrays), and nothing derived from
   // the old one -- interleaved copies, warm-up spans and their selection -- survives
   h->have_series = false;
-  h->factor_inputs_changed = true;
-  h->warm_active = false;
-  h->warm_span.clear();
-  h->relayout_pending = true;
-  h->warm_copy_pending = true;
-  h->small_copy_pending = true;
-  h->grad_span_valid = false;
+  series_replaced(h);
   const clr::CopyJob jobs[3] = {{h->t.p, t, count(t_stride)}, {h->diag.p, diag, count(diag_stride)}, {h->y.p, y, count(y_stride)}};
   const size_t total = (jobs[0].n + jobs[1].n + jobs[2].n) * sizeof(double);
   bool staged = false;
@@ -422,10 +393,6 @@ int clr_batch_set_series(clr_batch* h, const double* t, long t_stride, const dou
   }
   if ((st = warm_scan_spans(h)) != CLR_OK) { h->have_series = false; return st; }
   h->set_series_host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - host_t0).count();
-  h->grad_span_valid = false;
-  h->relayout_pending = true;
-  h->warm_copy_pending = true;
-  h->small_copy_pending = true;
   // a new series: the warm-ups chosen for the previous one's spans do not apply, nor does its history of fallbacks
   if (h->warm_mode < 0) h->warm_boost = 0;
   warm_select(h);
@@ -481,9 +448,7 @@ static int begin_coefficients(clr_batch* h) {
   int st = require_device(h->device);
   if (st != CLR_OK) return st;
   if ((st = warm_resolve(h, nullptr)) != CLR_OK) return st;  // (pending problems of the evaluation in flight: at ITS coefficients)
-  h->factor_inputs_changed = true;
-  h->pin_results = false;  // (the staging buffer is about to carry the coefficients)
-  h->kp_in_force = false;
+  coefficients_replaced(h);
   return CLR_OK;
 }
 
@@ -890,7 +855,7 @@ int clr_batch_debug_compose_check(clr_batch* h, int group, double* max_abs_diff,
   if (!h->launch || group < 2 || !h->evaluated)
     return fail(CLR_INVALID_ARGUMENT, "compose check: widths 1..8, group >= 2, after an evaluation");
   clr::BatchParams P;
-  if ((st = batch_params(h, 0, P)) != CLR_OK) return st;
+  if ((st = batch_params(h, 0, P, false)) != CLR_OK) return st;
   const size_t np = (size_t)(h->nchunk + group - 1) / group, E = (size_t)h->launch->elem_doubles;
   const size_t n = (size_t)h->B * np * E;
   DevBuf a, b;
@@ -929,7 +894,7 @@ int clr_batch_debug_compose_check(clr_batch* h, int group, double* max_abs_diff,
 
 int clr_batch_set_summarize_mode(clr_batch* h, int mode) {
   if (mode < -1 || mode > 2) return fail(CLR_INVALID_ARGUMENT, "summarize mode must be -1, 0, 1 or 2");
-  if (mode != h->summarize_mode) h->relayout_pending = true;
+  if (mode != h->summarize_mode) scan_reader_changed(h);
   h->summarize_mode = mode;
   if (mode >= 0) h->pipeline_pinned = true;
   return CLR_OK;
@@ -937,7 +902,7 @@ int clr_batch_set_summarize_mode(clr_batch* h, int mode) {
 
 int clr_batch_get_summarize_kernel(const clr_batch* h, int* kind) {
   if (!kind) return fail(CLR_INVALID_ARGUMENT, "kind is null");
-  *kind = split_active(h) ? ((h->summarize_mode != 1 && lazy_eligible(h)) ? 2 : 1) : 0;
+  *kind = split_active(h, false) ? ((h->summarize_mode != 1 && lazy_eligible(h)) ? 2 : 1) : 0;
   if (!h->launch)  // wide plans: plain or lazy flavour of the one-wave-per-chunk summarize
     *kind = (h->nchunk > 1 && (h->summarize_mode < 0 || h->summarize_mode == 2) &&
              (h->J_general > 0 ? lazy_eligible(h) : lazy_eligible_wide(h))) ? 2 : 0;
@@ -1082,7 +1047,7 @@ int clr_batch_get_warm_start(const clr_batch* h, int* active, int* nchunk, int* 
 int clr_batch_set_layout(clr_batch* h, int layout) {
   if (layout < 0 || layout > 2) return fail(CLR_INVALID_ARGUMENT, "layout must be 0, 1 or 2");
   h->layout = layout;
-  h->relayout_pending = true;
+  scan_reader_changed(h);
   h->pipeline_pinned = true;
   return CLR_OK;
 }
@@ -1122,12 +1087,7 @@ int clr_batch_get_profile(clr_batch* h, double* kernel_ms /* [6] */, int* steps)
 
 // the parameters of everything around the warm path -- the warm kernel, the one-launch kernel, the scan behind them for
 // the problems they leave pending --: the plan's row-major arrays, the single-wave summarize, pending problems only
-static int fallback_params(clr_batch* h, clr::BatchParams& P) {
-  h->in_fallback = true;
-  const int st = batch_params(h, 0, P);
-  h->in_fallback = false;
-  return st;
-}
+static int fallback_params(clr_batch* h, clr::BatchParams& P) { return batch_params(h, 0, P, true); }
 
 // a batch of short, narrow problems: the whole fused evaluation in ONE launch, one workgroup per problem
 // (small_batch_kernel, small_kernels.hip); problems it cannot certify stay pending for the scan pipeline
@@ -1150,20 +1110,21 @@ static bool small_runs(const clr_batch* h, int materialize) {
 // from L2 sixteen times (BASELINE configs[1]: 3.8 MB per problem through a 64-B/clk port -- the summarize phase was
 // bound by exactly that, profiles/r06l_config1_ab.txt).  The kernel therefore reads a chunk-interleaved copy
 // [problem][i][chunk] made once per set_series (launch_relayout with the path's own chunking, padded as the plan's copy):
-// one coalesced 512-B load per array, wave and step.
-static int small_params(clr_batch* h, clr::BatchParams& Sp) {
+// one coalesced 512-B load per array, wave and step.  The copy is rebuilt here when it is stale, or `regardless`.
+static int small_params(clr_batch* h, clr::BatchParams& Sp, bool regardless) {
   int st = fallback_params(h, Sp);
   if (st != CLR_OK) return st;
   const int T = 256, L = (h->N + T - 1) / T;
   const long cells = (long)L * T;
-  SeriesCopies copies(h, h->sT, h->sD, h->sY, (size_t)cells);
-  if ((st = copies.reserve()) != CLR_OK) return st;
-  if (h->small_copy_pending) {
-    for (auto& j : copies.job)
+  SeriesCopy& c = h->small_series;
+  SeriesJobs jobs(h, c, (size_t)cells);
+  if ((st = jobs.reserve()) != CLR_OK) return st;
+  if (c.stale || regardless) {
+    for (auto& j : jobs.job)
       clr::launch_relayout(j.src, j.stride, j.dst->p, j.dst_stride, j.nsrc, h->N, L, T, j.pad, h->stream.get());
-    h->small_copy_pending = false;
+    c.stale = false;
   }
-  Sp.t = h->sT.p; Sp.diag = h->sD.p; Sp.y = h->sY.p;
+  Sp.t = c.T.p; Sp.diag = c.D.p; Sp.y = c.Y.p;
   Sp.t_stride = h->t_stride ? cells : 0;
   Sp.diag_stride = h->diag_stride ? cells : 0;
   Sp.y_stride = h->y_stride ? cells : 0;
@@ -1176,16 +1137,16 @@ static bool warm_runs(const clr_batch* h, int materialize) {
   return h->launch && h->warm_active && !materialize && !h->force_exact && h->nchunk > 1 && h->wnchunk > 1;
 }
 
-// the warm kernel's copy of the series, (re)built when the series or the warm chunking changed
-static int warm_copy(clr_batch* h) {
-  if (!h->warm_copy_pending) return CLR_OK;
-  SeriesCopies copies(h, h->wT, h->wD, h->wY, (size_t)h->wrows * h->wnchunk);
-  const int st = copies.reserve();
+// the warm kernel's copy of the series, (re)built when the series or the warm chunking changed -- or `regardless`
+static int warm_copy(clr_batch* h, bool regardless) {
+  if (!h->warm_series.stale && !regardless) return CLR_OK;
+  SeriesJobs jobs(h, h->warm_series, (size_t)h->wrows * h->wnchunk);
+  const int st = jobs.reserve();
   if (st != CLR_OK) return st;
-  for (auto& j : copies.job)
+  for (auto& j : jobs.job)
     clr::launch_relayout_warm(j.src, j.stride, j.dst->p, j.dst_stride, j.nsrc, h->N, h->wL, h->wnchunk, h->wKpad, h->wrows,
                               j.pad, h->stream.get());
-  h->warm_copy_pending = false;
+  h->warm_series.stale = false;
   return CLR_OK;
 }
 
@@ -1230,7 +1191,7 @@ int clr_batch_get_rescue(const clr_batch* h, int* last_count, long* total, int* 
 int clr_batch_set_factor_layout(clr_batch* h, int layout) {
   if (layout != 0 && layout != 1) return fail(CLR_INVALID_ARGUMENT, "factor layout: 0 (phi, u, W, D) or 1 (lean: W, D)");
   if (layout == 1 && !h->launch) return fail(CLR_UNSUPPORTED, "the lean factor layout covers widths 1..8 (wider plans write the reference's storage)");
-  if (layout != h->factor_layout) { h->have_factor = false; h->factor_valid = false; }
+  if (layout != h->factor_layout) factor_dropped(h);
   h->factor_layout = layout;
   return CLR_OK;
 }
@@ -1246,11 +1207,6 @@ int clr_batch_get_factor_bytes(const clr_batch* h, size_t* bytes_per_problem) {
   const size_t cells = h->launch ? (size_t)h->L * h->nchunk : (size_t)h->N, J = (size_t)h->J;
   *bytes_per_problem = 8 * cells * ((h->launch && h->factor_layout == 1) ? (J + 1) : (3 * J + 1));
   return CLR_OK;
-}
-
-// a materialising run has queued the writes of the factor, in the lean layout or the reference's
-static void factor_written(clr_batch* h, bool lean) {
-  h->factor_is_lean = lean; h->factor_inputs_changed = false; h->factor_valid = true; h->bs_M_valid = false;
 }
 
 // "Record event i of this step now": the step's PROF_NK + 1 events on the plan's stream (null: none) and which of them
@@ -1306,16 +1262,10 @@ static int warm_fallback(clr_batch* h) {
   return CLR_OK;
 }
 
-// the chunk-interleaved copy the scan reads, rebuilt if the series -- or only the residual y -- changed since it was made
-static void relayout_if_pending(clr_batch* h) {
-  if (h->relayout_pending && batch_relayout(h)) h->relayout_pending = h->relayout_y_pending = false;
-  else if (h->relayout_y_pending && relayout_residual(h)) h->relayout_y_pending = false;
-}
-
 // ONE evaluation of the plan on the parameters P of batch_params(h, materialize, P): the route test and every launch, for
 // clr_batch_enqueue and for each step of clr_batch_run_timed alike.  `fresh_series`: the step stands for one on a new
-// series -- the copy of the series its route reads is rebuilt inside it whether pending or not (the pending flags are the
-// caller's to settle); otherwise only a pending copy is rebuilt.  The *_inflight flags describe this evaluation afterwards
+// series -- the copy of the series its route reads is rebuilt inside it whether stale or not; otherwise only a stale copy
+// is (the copy a step rebuilt is fresh afterwards, and no other).  The *_inflight flags describe this evaluation afterwards
 // (every state-changing entry point resolves an evaluation in flight first, so none of an earlier one is relied on).
 static int launch_step(clr_batch* h, int materialize, clr::BatchParams& P, const StepMarks& mark, bool fresh_series) {
   hipStream_t s = h->stream.get();
@@ -1362,8 +1312,7 @@ static int launch_step(clr_batch* h, int materialize, clr::BatchParams& P, const
   }
   if (!warm_runs(h, materialize) && small_runs(h, materialize)) {  // (one launch, in the "summarize" slot)
     clr::BatchParams Sp;
-    if (fresh_series) h->small_copy_pending = true;
-    if ((st = small_params(h, Sp)) != CLR_OK) return st;
+    if ((st = small_params(h, Sp, fresh_series)) != CLR_OK) return st;
     mark(1, s);
     clr::launch_small_batch(h->J_real, h->J_comp, Sp, 256, s);
     mark.from(2, s);
@@ -1374,8 +1323,7 @@ static int launch_step(clr_batch* h, int materialize, clr::BatchParams& P, const
     // series that forget: the plain recurrence per chunk with a warm-up + the boundary check, in the "summarize" slot;
     // problems it cannot settle are marked pending and go through the scan pipeline when the results are asked for
     clr::BatchParams Wp;
-    if (fresh_series) h->warm_copy_pending = true;
-    if ((st = warm_copy(h)) != CLR_OK) return st;
+    if ((st = warm_copy(h, fresh_series)) != CLR_OK) return st;
     if ((st = warm_upload_K(h)) != CLR_OK) return st;
     if ((st = fallback_params(h, Wp)) != CLR_OK) return st;
     mark(1, s);
@@ -1384,8 +1332,7 @@ static int launch_step(clr_batch* h, int materialize, clr::BatchParams& P, const
     h->warm_inflight = true;
     return CLR_OK;
   }
-  if (fresh_series) batch_relayout(h);
-  else relayout_if_pending(h);
+  build_scan_series(h, fresh_series);
   narrow_scan(h, P, materialize, mark);
   h->rescue_inflight = P.defer_level1 != 0;
   return CLR_OK;
@@ -1395,7 +1342,7 @@ int clr_batch_enqueue(clr_batch* h, int materialize) {
   int st = require_device(h->device);
   if (st != CLR_OK) return st;
   clr::BatchParams P;
-  if ((st = batch_params(h, materialize, P)) != CLR_OK) return st;
+  if ((st = batch_params(h, materialize, P, false)) != CLR_OK) return st;
   // profiling: one event per kernel boundary of this evaluation, on the plan's stream (mode 2: events 1 and 2 only)
   StepMarks mark;
   if (h->prof_on && h->prof_steps < PROF_MAX_STEPS) {
@@ -1422,7 +1369,7 @@ int clr_batch_fp32_probe(clr_batch* h, double* logdet, double* quad, double* ms)
   if (h->launch || h->J > clr::wide_f32_probe_max_width())
     return fail(CLR_UNSUPPORTED, "the fp32 probe covers widths 9..32");
   clr::BatchParams P;
-  if ((st = batch_params(h, 0, P)) != CLR_OK) return st;
+  if ((st = batch_params(h, 0, P, false)) != CLR_OK) return st;
   const size_t B = (size_t)h->B;
   DevBuf tmp;
   if ((st = tmp.reserve(2 * B)) != CLR_OK) return st;
@@ -1452,7 +1399,7 @@ int clr_batch_fp32_probe(clr_batch* h, double* logdet, double* quad, double* ms)
 static int rescue_inline(clr_batch* h) {
   // too many pending problems for a side plan to pay: the inline chunked replay after all (the flow's own tail)
   clr::BatchParams P;
-  int st = batch_params(h, 0, P);
+  int st = batch_params(h, 0, P, false);
   if (st != CLR_OK) return st;
   P.defer_level1 = 0;
   if (!h->launch) {
@@ -1540,11 +1487,7 @@ static int rescue_run(clr_batch* h, const std::vector<int>& idx, long n_total) {
     }
   }
   r->have_series = true;
-  r->relayout_pending = true;
-  r->warm_copy_pending = true;
-  r->small_copy_pending = true;
-  r->grad_span_valid = false;
-  r->factor_inputs_changed = true;
+  series_replaced(r);
   const size_t total = (size_t)n * (2 * h->J_real + 4 * h->J_comp + 1);
   if ((st = r->coeffs.reserve(total)) != CLR_OK) return st;
   clr::launch_gather_coeffs(h->coeffs.p, r->coeffs.p, h->rescue_idx.p, h->B, n, h->J_real, h->J_comp, r->stream.get());
@@ -1722,7 +1665,7 @@ static int require_celerite_width(const clr_batch* h, const char* entry) {
 // evaluation stages them through LDS (solve, dot_L), or always (`row_major`, clr_batch_dot: it must not depend on an
 // evaluation having made the role-split summarize's chunk-interleaved copy)
 static int consumer_params(clr_batch* h, bool row_major, clr::BatchParams& P) {
-  const int st = batch_params(h, 0, P);
+  const int st = batch_params(h, 0, P, false);
   if (st != CLR_OK) return st;
   if (row_major || P.staged) { P.t = h->t.p; P.t_stride = h->t_stride; P.lane_is = 1; P.lane_cs = h->L; P.staged = 0; }
   return CLR_OK;
@@ -1797,7 +1740,7 @@ int clr_batch_get_factor(clr_batch* h, int p, double* phi, double* u, double* W,
       // the lean layout holds W and D; phi and u are regenerated from the plan's times and the coefficients in force --
       // which must still be the ones of the materialising run (require_factor)
       clr::BatchParams P;
-      if ((st = batch_params(h, 0, P)) != CLR_OK) return st;
+      if ((st = batch_params(h, 0, P, false)) != CLR_OK) return st;
       h->launch->expand(P, p, h->t.p + (size_t)p * (size_t)h->t_stride, h->fphi.p, h->fu.p, h->fW.p, h->fD.p, h->stream.get());
     } else {
       clr::launch_deinterleave_factor(h->phi.p + p * J * cells, h->u.p + p * J * cells,
@@ -2040,7 +1983,7 @@ int clr_batch_predict(clr_batch* h, int M, const double* xs, long xs_stride, dou
   if (M == 0) return CLR_OK;
   if ((st = batch_solve_impl(h, 1, nullptr, nullptr)) != CLR_OK) return st;  // alpha = K^-1 y -> bs_rm [B][N]
   clr::BatchParams P;
-  if ((st = batch_params(h, 0, P)) != CLR_OK) return st;
+  if ((st = batch_params(h, 0, P, false)) != CLR_OK) return st;
   const size_t B = (size_t)h->B, Mm = (size_t)M, nsrc = xs_stride == 0 ? 1 : B;
   DevBuf dxs, dpred, ws;
   if ((st = dxs.reserve(nsrc * Mm)) != CLR_OK) return st;
@@ -2085,7 +2028,7 @@ int clr_batch_run_timed(clr_batch* h, int materialize, int steps, int relayout_e
   int st = require_device(h->device);
   if (st != CLR_OK) return st;
   clr::BatchParams P;
-  if ((st = batch_params(h, materialize, P)) != CLR_OK) return st;
+  if ((st = batch_params(h, materialize, P, false)) != CLR_OK) return st;
   if (steps < 1) steps = 1;
   h->pin_results = false;
   if (h->J_general > 0 || h->J > clr::wide_max_width()) {
@@ -2104,7 +2047,7 @@ int clr_batch_run_timed(clr_batch* h, int materialize, int steps, int relayout_e
     if (kernel_ms) { for (int j = 0; j < 6; ++j) kernel_ms[j] = 0.0; kernel_ms[4] = tot; }
     return CLR_OK;
   }
-  if (!relayout_each_step && !warm_runs(h, materialize)) relayout_if_pending(h);  // (in front of the timed steps)
+  if (!relayout_each_step && !warm_runs(h, materialize)) build_scan_series(h, false);  // (in front of the timed steps)
   // one event per kernel boundary per step, all recorded on the handle's stream
   const int NK = PROF_NK;
   std::vector<clr::Event> ev((size_t)steps * (NK + 1));
@@ -2119,8 +2062,6 @@ int clr_batch_run_timed(clr_batch* h, int materialize, int steps, int relayout_e
       HIP_TRY(hipEventRecord(e[NK].get(), h->stream.get()));
     }
   }
-  if (relayout_each_step && !warm_runs(h, materialize) && (h->layout == 1 || split_active(h)) && h->nchunk > 1)
-    h->relayout_pending = h->relayout_y_pending = false;
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(h->stream.get()));
   double k[NK] = {0, 0, 0, 0, 0, 0};

@@ -78,7 +78,7 @@ static int wide_batch_grad(clr_batch* h, double* value, double* grad, int* statu
   }
   if (st != CLR_OK) return st;
   clr::BatchParams P0, P;
-  if ((st = batch_params(h, 0, P0)) != CLR_OK) return st;
+  if ((st = batch_params(h, 0, P0, false)) != CLR_OK) return st;
   if (general) general_wide_params(h, P0, P); else P = P0;
   const size_t B = (size_t)h->B, NG = 1 + 2 * (size_t)h->J_real + 4 * (size_t)h->J_comp;
   const int JP = Wt <= 16 ? 16 : (Wt <= 32 ? 32 : 64);
@@ -154,11 +154,9 @@ int clr_batch_grad(clr_batch* h, double* value, double* grad, int* status) {
   h->grad_scan_only = false;
   if (st != CLR_OK) return st;
   clr::BatchParams P, Pi;
-  h->in_fallback = true;  // (the row-major arrays)
-  st = batch_params(h, 0, P);
-  h->in_fallback = false;
+  st = batch_params(h, 0, P, true);  // (the row-major arrays)
   if (st != CLR_OK) return st;
-  if ((st = batch_params(h, 0, Pi)) != CLR_OK) return st;  // (the evaluation's own view: interleaved copy if it has one)
+  if ((st = batch_params(h, 0, Pi, false)) != CLR_OK) return st;  // (the evaluation's own view: interleaved copy if it has one)
   const bool scan_grad = P.fast_trig != 0;  // (only the fast-sincos flavour of the gradient kernels is built)
   // mode: reverse (one sweep for all partials, needs the per-sample record in HBM) unless asked otherwise or the
   // record does not fit; forward (one tangent per partial) as the fallback and the cross-check
@@ -481,9 +479,7 @@ int clr_batch_grad_mean(clr_batch* h, double* value, double* grad, double* dmean
   for (size_t b = 0; b < B; ++b)
     if (stat[b] == CLR_OK && !h->grad_mean_done[b]) rest.push_back((int)b);
   clr::BatchParams P;
-  h->in_fallback = true;  // (the row-major arrays)
-  st = batch_params(h, 0, P);
-  h->in_fallback = false;
+  st = batch_params(h, 0, P, true);  // (the row-major arrays)
   if (st != CLR_OK) return st;
   int* didx = reinterpret_cast<int*>(h->mean_out.p + B);
   if (!rest.empty())

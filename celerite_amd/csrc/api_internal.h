@@ -214,6 +214,15 @@ struct clr_solver {
   }
 };
 
+// A chunk-interleaved copy of a plan's three series arrays, and whether it still matches them.  Each of a plan's three
+// has ONE function that builds it (build_scan_series; api_batch.hip: warm_copy, small_params) and that alone marks it
+// fresh, exactly when it has queued the rebuild; only the cause functions below the plan (series_replaced, ...) mark it stale.
+struct SeriesCopy {
+  DevBuf T, D, Y;
+  bool stale = true;     // the arrays, or the chunking the copy follows, changed since it was built (or it never was)
+  bool y_stale = false;  // the scan's copy only: the residual y alone changed -- Y alone is rebuilt
+};
+
 struct clr_batch {
   int device = 0;
   clr::Stream stream;
@@ -233,7 +242,7 @@ struct clr_batch {
   const clr::BatchLaunchers* launch = nullptr;
   DevBuf coeffs, t, diag, y;          // coefficients (| jitter at the end); series in the API's row-major layout
   clr::PinnedBuffer<double> pin;      // pinned host staging: coefficient uploads, result downloads
-  DevBuf tT, dT, yT;                  // chunk-interleaved copies the kernels read
+  SeriesCopy scan_series;             // the chunk-interleaved copy the scan's kernels read (scan_reads_copy)
   long t_stride = 0, diag_stride = 0, y_stride = 0;
   // clr_batch_set_mean: with a mean in force `y` holds the residual y - mu that every route reads, and `y_src` the
   // caller's series as uploaded (y_src_stride: its stride)
@@ -242,7 +251,6 @@ struct clr_batch {
   std::vector<double> host_mean;      // [B] or [1]
   DevBuf mean_dev, y_src, mean_out;   // the mean on the device; the caller's y; clr_batch_grad_mean's partials [B]
   long y_src_stride = 0;
-  bool relayout_y_pending = false;    // only the residual changed: the interleaved copy of y alone is rebuilt
   // clr_batch_set_kernel / _set_parameters: the program (host copy and in HBM), the last parameter rows with the
   // evaluation kernel's statistics block behind them, the chain rule's staging (grad | dmean | result)
   bool have_kernel = false;
@@ -308,23 +316,19 @@ struct clr_batch {
   bool warm_active = false;           // the current (series, coefficients) pair runs the warm path
   bool warm_inflight = false;         // results of a warm evaluation have not been looked at yet
   bool small_inflight = false;        // ... of a one-launch evaluation (small_batch_kernel): pending problems, no warm statistics
-  bool in_fallback = false;           // building the parameters of the scan behind the warm path
   int warm_boost = 0;                 // candidates skipped after an evaluation with many fallbacks
   int warm_clean = 0;                 // consecutive warm evaluations without a fallback (decays warm_boost)
   int warm_settled = 0, warm_fallbacks = 0;  // of the last evaluation
   DevBuf wstarts, wends, wpart, wresid;
-  DevBuf wT, wD, wY;                  // the warm kernel's padded chunk-interleaved copy of the series
+  SeriesCopy warm_series;             // the warm kernel's padded chunk-interleaved copy of the series
   int wKpad = 0, wrows = 0;
-  bool warm_copy_pending = true;
-  DevBuf sT, sD, sY;                  // the one-launch path's chunk-interleaved copy of the series (small_params, api_batch.hip)
-  bool small_copy_pending = true;
+  SeriesCopy small_series;            // the one-launch path's chunk-interleaved copy of the series (small_params, api_batch.hip)
   DevArray<int> wints;                // wflags [B * wnchunk] | need_scan [B] | K [B]
   // general terms for the whole batch (clr_batch_set_general): the plan then evaluates through the any-width sequential
   // kernel, one workgroup per problem (generic_kernels.hip: generic_loglike_batch_kernel)
   int J_general = 0;
   DevBuf gA, gU, gV;
   long gA_stride = 0, gU_stride = 0, gV_stride = 0;
-  bool relayout_pending = true;
   bool have_series = false, have_coeffs = false, have_factor = false;
   bool evaluated = false;             // an evaluation has been enqueued since the plan was (re)chunked
   DevBuf elems, starts, part, partx, cond, out;  // out: ll | logdet | quad | status (B ints)
@@ -378,6 +382,47 @@ struct clr_batch {
 
 
 
+// ---- what a replaced input of a plan leaves stale: one function per cause, called by the entry points ----------
+namespace {
+// a materialising run has queued the writes of the factor, in the lean layout or the reference's
+void factor_written(clr_batch* h, bool lean) {
+  h->factor_is_lean = lean; h->factor_inputs_changed = false; h->factor_valid = true; h->bs_M_valid = false;
+}
+// the factor's layout in HBM no longer is the one a materialising run would write (chunking, factor layout)
+void factor_dropped(clr_batch* h) { h->have_factor = h->factor_valid = false; }
+
+// t, diag and y are being overwritten: nothing derived from the old ones survives
+void series_replaced(clr_batch* h) {
+  h->scan_series.stale = h->warm_series.stale = h->small_series.stale = true;
+  h->grad_span_valid = false;
+  h->factor_inputs_changed = true;
+  h->warm_active = false;  // (the warm path's spans and the warm-ups selected from them)
+  h->warm_span.clear();
+}
+// `y` holds another residual, of stride `y_stride` (a mean set, changed or removed): of the scan's copy Y alone is
+// rebuilt unless the stride changed (a shared series became a per-problem residual, or back)
+void residual_replaced(clr_batch* h, long y_stride) {
+  if (y_stride != h->y_stride) h->scan_series.stale = true;
+  h->y_stride = y_stride;
+  h->scan_series.y_stale = true;
+  h->warm_series.stale = h->small_series.stale = true;
+}
+// nchunk and L changed: the scan's copy, the gradient's spans and the factor's layout follow them
+void chunking_replaced(clr_batch* h) {
+  h->scan_series.stale = true;
+  h->grad_span_valid = false;
+  factor_dropped(h);
+  h->evaluated = false;
+}
+// ... and the warm path's own chunking was planned again (warm_plan_chunks)
+void warm_chunking_replaced(clr_batch* h) { h->warm_series.stale = h->small_series.stale = true; }
+void coefficients_replaced(clr_batch* h) {  // (pin_results: the staging buffer is about to carry the coefficients)
+  h->factor_inputs_changed = true; h->pin_results = false; h->kp_in_force = false;
+}
+// the layout or the summarize mode changed: whether the scan reads its copy may have changed with it
+void scan_reader_changed(clr_batch* h) { h->scan_series.stale = true; }
+}  // namespace
+
 // ---- a plan's state as kernel parameters -----------------------------------------------------------------------
 namespace {
 // the maxima the kernel selection looks at: the plan's own, raised to the floors of a sharded parent
@@ -417,7 +462,9 @@ bool lazy_eligible_wide(const clr_batch* h) {
   return h->have_series && h->have_coeffs && cmax * dxmax < 2.0 && lazy_phases_ok(h);
 }
 
-bool split_active(const clr_batch* h) {
+// `behind_fast_path` (here, in defer_runs and in batch_params): the question is asked for the scan behind the warm or
+// the one-launch path -- the plan's row-major arrays, the single-wave summarize, pending problems only
+bool split_active(const clr_batch* h, bool behind_fast_path) {
   // explicit modes 1 / 2, or auto (-1):
   //  * widths 7 and 8 on a densely sampled series: the split kernel with the decay factored out of the state
   //    (lazy) beats the single-wave kernel for every shape (2.0-2.5 ms against 2.3-3.6, profiles/r02zzz_split_ab_shapes.txt);
@@ -425,7 +472,7 @@ bool split_active(const clr_batch* h) {
   //    width 8 with at least two complex terms (3.1-3.2 against 3.8-4.2; profiles/r02zzz_sparse_ab.txt).  With
   //    fewer complex terms at width 8 its trajectory wave spills ((8,0), (6,1): 4.1-4.2 against 3.7): single wave.
   if (!(h->launch && h->nchunk > 1 && clr::have_summarize_split(h->J_real, h->J_comp))) return false;
-  if (h->in_fallback) return false;  // the scan behind the warm path: single-wave kernels on the row-major arrays
+  if (behind_fast_path) return false;
   if (h->summarize_mode > 0) return true;
   if (h->summarize_mode < 0 && h->J >= 7 && lazy_eligible(h)) return true;
   return h->summarize_mode < 0 && (h->J == 7 || (h->J == 8 && h->J_comp >= 2));
@@ -436,8 +483,8 @@ bool split_active(const clr_batch* h) {
 // chunk-time (config 4: +11 ms on 12.7; profiles/r04zz_wide_midbatch.txt) -- a re-plan is three passes over chunks a
 // tenth as long.  Never on forced-exact / materialising runs (they replay everything), inside the gradient's own
 // evaluation, behind the warm path, or on a side plan.
-bool defer_runs(const clr_batch* h, int materialize) {
-  if (h->rescue_mode == 0 || h->is_rescue_plan || materialize || h->force_exact || h->grad_scan_only || h->in_fallback) return false;
+bool defer_runs(const clr_batch* h, int materialize, bool behind_fast_path) {
+  if (h->rescue_mode == 0 || h->is_rescue_plan || materialize || h->force_exact || h->grad_scan_only || behind_fast_path) return false;
   if (h->nchunk < 2 || h->J_general > 0 || sel_B(h) < 2) return false;
   if (h->rescue_mode == 1) return true;
   // widths 33..64: a side plan is itself <= 16 chunks chained by a walk of ~0.6 ms each -- it does not beat the inline
@@ -446,19 +493,19 @@ bool defer_runs(const clr_batch* h, int materialize) {
   return h->L >= 1024;
 }
 
-// The plan's three series arrays and a chunk-interleaved copy of each, `cells` doubles per series (a shared series has
-// ONE copy): the plan's own (tT, dT, yT), the one-launch path's, the warm kernel's.  reserve() sizes the copies; whoever
-// builds them launches its relayout kernel per job (pad: how the cells past the series' end are filled).
-struct SeriesCopies {
+// The plan's three series arrays and where each goes in the copy `c`, `cells` doubles per series (a shared series has
+// ONE copy).  reserve() sizes the copy; the function that builds it launches its relayout kernel per job (pad: how the
+// cells past the series' end are filled).
+struct SeriesJobs {
   struct Job { const double* src; long stride; DevBuf* dst; int pad; int nsrc; long dst_stride; } job[3];
   size_t cells;
-  SeriesCopies(const clr_batch* h, DevBuf& T, DevBuf& D, DevBuf& Y, size_t cells_) : cells(cells_) {
+  SeriesJobs(const clr_batch* h, SeriesCopy& c, size_t cells_) : cells(cells_) {
     auto make = [&](const DevBuf& src, long stride, DevBuf& dst, int pad) {
       return Job{src.p, stride, &dst, pad, stride ? h->B : 1, stride ? (long)cells : 0};
     };
-    job[0] = make(h->t, h->t_stride, T, 1);
-    job[1] = make(h->diag, h->diag_stride, D, 2);
-    job[2] = make(h->y, h->y_stride, Y, 0);
+    job[0] = make(h->t, h->t_stride, c.T, 1);
+    job[1] = make(h->diag, h->diag_stride, c.D, 2);
+    job[2] = make(h->y, h->y_stride, c.Y, 0);
   }
   int reserve() {
     for (Job& j : job) {
@@ -469,7 +516,13 @@ struct SeriesCopies {
   }
 };
 
-int batch_params(clr_batch* h, int materialize, clr::BatchParams& P) {
+// whether the scan's kernels read the chunk-interleaved copy (the wide kernels, the warm-started recurrence and the scan
+// behind it read the row-major arrays)
+bool scan_reads_copy(const clr_batch* h) {
+  return h->launch && (h->layout == 1 || split_active(h, false)) && h->nchunk > 1;
+}
+
+int batch_params(clr_batch* h, int materialize, clr::BatchParams& P, bool behind_fast_path) {
   if (!h->have_series || !h->have_coeffs)
     return fail(CLR_INVALID_ARGUMENT, "set_series and set_coefficients must be called first");
   int st = CLR_OK;
@@ -502,18 +555,18 @@ int batch_params(clr_batch* h, int materialize, clr::BatchParams& P) {
   P.d_comp = P.c_comp + nc;
   // role-split summarize (two waves per SIMD, clr_split_kernels.h) for the widths whose element
   // does not fit one wave's registers; it reads the chunk-interleaved copy of the series
-  const bool split = split_active(h);
+  const bool split = split_active(h, behind_fast_path);
   P.split = split ? 1 : 0;
   P.split_lazy = (split && h->summarize_mode != 1 && lazy_eligible(h)) ? 1 : 0;
   // wide plans: the lazy-decay flavour of the wide summarize on dense series (mode 0 / 1 switch it off)
   // (1: dense everywhere -- the strict rule; 2: only the relaxed one: the flavour with the per-batch range test)
   if (!h->launch && h->nchunk > 1 && (h->summarize_mode < 0 || h->summarize_mode == 2) && lazy_eligible_wide(h))
     P.split_lazy = lazy_eligible(h) ? 1 : 2;
-  // (the wide kernels, the warm-started recurrence and the scan behind it read the row-major arrays)
-  if (h->launch && (h->layout == 1 || split) && h->nchunk > 1 && !h->in_fallback) {
+  if (!behind_fast_path && scan_reads_copy(h)) {
     const long cells = (long)h->nchunk * h->L;
-    if ((st = SeriesCopies(h, h->tT, h->dT, h->yT, (size_t)cells).reserve()) != CLR_OK) return st;
-    P.t = h->tT.p; P.diag = h->dT.p; P.y = h->yT.p;
+    SeriesCopy& c = h->scan_series;
+    if ((st = SeriesJobs(h, c, (size_t)cells).reserve()) != CLR_OK) return st;
+    P.t = c.T.p; P.diag = c.D.p; P.y = c.Y.p;
     P.t_stride = h->t_stride ? cells : 0;
     P.diag_stride = h->diag_stride ? cells : 0;
     P.y_stride = h->y_stride ? cells : 0;
@@ -523,7 +576,7 @@ int batch_params(clr_batch* h, int materialize, clr::BatchParams& P) {
     P.t = h->t.p; P.diag = h->diag.p; P.y = h->y.p;
     P.t_stride = h->t_stride; P.diag_stride = h->diag_stride; P.y_stride = h->y_stride;
     P.lane_is = 1; P.lane_cs = h->L;
-    P.staged = ((h->layout == 2 || h->in_fallback) && h->nchunk > 1) ? 1 : 0;
+    P.staged = ((h->layout == 2 || behind_fast_path) && h->nchunk > 1) ? 1 : 0;
   }
   P.elems = h->elems.p; P.starts = h->starts.p; P.part = h->part.p; P.flags = h->flags.p;
   P.cond = h->cond.p;
@@ -548,12 +601,12 @@ int batch_params(clr_batch* h, int materialize, clr::BatchParams& P) {
     P.wstarts = h->wstarts.p; P.wends = h->wends.p; P.wpart = h->wpart.p; P.wresid = h->wresid.p;
     P.warm_resid = h->cert_resid;
     const long cells = (long)h->wrows * h->wnchunk;
-    P.wt = h->wT.p; P.wdiag = h->wD.p; P.wy = h->wY.p;
+    P.wt = h->warm_series.T.p; P.wdiag = h->warm_series.D.p; P.wy = h->warm_series.Y.p;
     P.wt_stride = h->t_stride ? cells : 0; P.wdiag_stride = h->diag_stride ? cells : 0; P.wy_stride = h->y_stride ? cells : 0;
     P.wKpad = h->wKpad; P.wrows = h->wrows;
   }
-  P.only_pending = h->in_fallback ? 1 : 0;
-  P.defer_level1 = defer_runs(h, materialize) ? 1 : 0;
+  P.only_pending = behind_fast_path ? 1 : 0;
+  P.defer_level1 = defer_runs(h, materialize, behind_fast_path) ? 1 : 0;
   P.wide_materialize = (materialize && !h->launch) ? 1 : 0;
   P.ends = nullptr; P.ends_alt = nullptr; P.ends_in = nullptr;
   P.fixup_steps = 0;
@@ -576,14 +629,19 @@ int batch_params(clr_batch* h, int materialize, clr::BatchParams& P) {
   return CLR_OK;
 }
 
-// Row-major API layout -> chunk-interleaved layout (3 tiled transposes).  Returns whether the copy
-// was (re)built: `relayout_pending` may only be cleared then -- the need for the copy can appear later
-// (a new coefficient draw can switch the summarize kernel) with the series unchanged.
-bool batch_relayout(clr_batch* h) {
-  if (!((h->layout == 1 || split_active(h)) && h->nchunk > 1)) return false;
-  const SeriesCopies copies(h, h->tT, h->dT, h->yT, (size_t)h->nchunk * h->L);
-  for (auto& j : copies.job)
-    clr::launch_relayout(j.src, j.stride, j.dst->p, j.dst_stride, j.nsrc, h->N, h->L, h->nchunk, j.pad, h->stream.get());
+// Row-major API layout -> the chunk-interleaved copy the scan reads (sized by batch_params), if it is stale or
+// `regardless`: 3 tiled transposes, Y alone when only the residual changed.  Returns whether the rebuild was queued: a
+// copy that no route reads is not built and STAYS stale -- the need for it can appear later (a new coefficient draw can
+// switch the summarize kernel, another evaluation can take another route) with the series unchanged.
+bool build_scan_series(clr_batch* h, bool regardless) {
+  SeriesCopy& c = h->scan_series;
+  if (!(regardless || c.stale || c.y_stale) || !scan_reads_copy(h)) return false;
+  const bool y_only = !regardless && !c.stale;
+  const SeriesJobs jobs(h, c, (size_t)h->nchunk * h->L);
+  for (auto& j : jobs.job)
+    if (!y_only || j.dst == &c.Y)
+      clr::launch_relayout(j.src, j.stride, j.dst->p, j.dst_stride, j.nsrc, h->N, h->L, h->nchunk, j.pad, h->stream.get());
+  c.stale = c.y_stale = false;
   return true;
 }
 

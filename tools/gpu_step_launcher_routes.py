@@ -1,6 +1,9 @@
 """Workload for `rocprofv3 --kernel-trace --stats`: every route of tests/test_gpu_step_launcher.py -- each through
 ``enqueue`` and through ``run_timed(2)`` -- on the build in the current directory.  Two builds launch the same kernels
-when tools/rocpd_kernel_counts.py prints the same table for both (profiles/step_launcher_kernel_counts.txt)."""
+when tools/rocpd_kernel_counts.py prints the same table for both (profiles/step_launcher_kernel_counts.txt).  With
+``--plan-reuse``: the sequences of tests/test_gpu_plan_reuse.py behind them -- every change of an input or a setting
+between two evaluations of one plan (profiles/plan_state_kernel_counts.txt) -- without its last case, which is wrong
+on builds before the plan's copies of the series kept their own staleness."""
 import os
 import sys
 
@@ -31,4 +34,11 @@ T.test_mean_set_after_the_series(6, 1, dict(nchunk=64, kernel="role split, lazy 
 T.test_mean_set_after_the_series(2, 1, dict(nchunk=24))
 for w in ("narrow scan", "one launch", "wide"):
     T.test_profile_of_enqueued_evaluations(w)
+if "--plan-reuse" in sys.argv[1:]:
+    import test_gpu_plan_reuse as R  # noqa: E402
+    for route in list(R.ROUTES) + [r + ", materialising" for r in R.MATERIALISING]:
+        for change in R.CHANGES:
+            R.test_reused_plan_equals_fresh_plan(route, change)
+    for first in ("dense", "not dense"):
+        R.test_coefficient_draw_switches_the_summarize_kernel(first)
 print("routes ok")
