@@ -487,11 +487,13 @@ class BatchedGP(object):
         _check(lib.clr_batch_solve(self._h, int(nrhs), _ptr(b), _ptr(x)))
         return x
 
-    def predict(self, xs):
+    def predict(self, xs, return_var=False):
         """The conditional mean ``mu_p + K_p(x*, t_p) K_p^-1 (y_p - mu_p)`` of every problem (``mu_p`` the mean of
         :meth:`set_mean`, zero without one; ``GP.predict``, celerite.py:279) at the prediction points ``xs`` --
         ``(M,)`` shared by all problems or ``(B, M)`` -- from the factor of the last materialising run
-        (``clr_batch_predict``; ``CholeskySolver.predict``, cholesky.h:599-698, for B problems).  Returns ``(B, M)``."""
+        (``clr_batch_predict``; ``CholeskySolver.predict``, cholesky.h:599-698, for B problems).  Returns ``(B, M)``.
+        ``return_var=True``: ``(mu, var)`` with the conditional variance ``k_p(0) - k*^T K_p^-1 k*`` of every point
+        (``clr_batch_predict_var``; celerite.py:465-470), both ``(B, M)``: only ``xs`` goes up and ``var`` comes down."""
         lib = _load()
         lib.clr_batch_predict.argtypes = [C.c_void_p, C.c_int, _dp, C.c_long, _dp]
         xs = _f64(xs)
@@ -504,7 +506,19 @@ class BatchedGP(object):
         M = xs.shape[-1]
         pred = np.empty((self.B, M))
         _check(lib.clr_batch_predict(self._h, int(M), _ptr(xs), stride, _ptr(pred)))
-        return pred
+        if not return_var:
+            return pred
+        lib.clr_batch_predict_var.argtypes = [C.c_void_p, C.c_int, _dp, C.c_long, _dp]
+        var = np.empty((self.B, M))
+        _check(lib.clr_batch_predict_var(self._h, int(M), _ptr(xs), stride, _ptr(var)))
+        return pred, var
+
+    def set_predict_tile(self, points=0):
+        """Prediction points per tile of ``predict(xs, return_var=True)`` (``clr_batch_set_predict_tile``); 0:
+        automatic.  The results do not depend on it."""
+        lib = _load()
+        lib.clr_batch_set_predict_tile.argtypes = [C.c_void_p, C.c_int]
+        _check(lib.clr_batch_set_predict_tile(self._h, int(points)))
 
     def dot_L(self, z):
         """``L_p z_p`` with ``K_p = L_p L_p^T`` for every problem from the factor of the last materialising run
@@ -1088,8 +1102,9 @@ class ShardedBatchedGP(object):
         self._ok(lib.clr_sharded_dot(self._h, int(nrhs), _ptr(z), _ptr(y)))
         return y
 
-    def predict(self, xs):
-        """The conditional mean of every problem at ``xs`` (``(M,)`` shared or ``(B, M)``), as :meth:`BatchedGP.predict`."""
+    def predict(self, xs, return_var=False):
+        """The conditional mean of every problem at ``xs`` (``(M,)`` shared or ``(B, M)``) and, with ``return_var=True``,
+        the conditional variance beside it, as :meth:`BatchedGP.predict`."""
         lib = _load()
         lib.clr_sharded_predict.argtypes = [C.c_void_p, C.c_int, _dp, C.c_long, _dp]
         xs = _f64(xs)
@@ -1102,7 +1117,12 @@ class ShardedBatchedGP(object):
         M = xs.shape[-1]
         pred = np.empty((self.B, M))
         self._ok(lib.clr_sharded_predict(self._h, int(M), _ptr(xs), stride, _ptr(pred)))
-        return pred
+        if not return_var:
+            return pred
+        lib.clr_sharded_predict_var.argtypes = [C.c_void_p, C.c_int, _dp, C.c_long, _dp]
+        var = np.empty((self.B, M))
+        self._ok(lib.clr_sharded_predict_var(self._h, int(M), _ptr(xs), stride, _ptr(var)))
+        return pred, var
 
     def run_timed(self, steps):
         """``steps`` evaluations on every shard concurrently; per-shard HIP-event ms."""

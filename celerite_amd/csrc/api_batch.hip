@@ -2018,6 +2018,148 @@ int clr_batch_predict(clr_batch* h, int M, const double* xs, long xs_stride, dou
   return CLR_OK;
 }
 
+// ---- clr_batch_predict_var: the conditional variance of GP.predict for every problem of the plan
+
+// widths 9..64: the tile's cross-covariances k_p(x*_r - t_{p,n}) row-major [problem][rhs][n] (grid: n, rhs, problem);
+// `fast`: the phases stay below CLR_FAST_TRIG_LIMIT (a launch-uniform branch: registers are no concern here)
+__global__ void __launch_bounds__(256) predvar_cross_rowmajor_kernel(const double* a_real, const double* c_real, const double* a_comp,
+                                                                     const double* b_comp, const double* c_comp, const double* d_comp,
+                                                                     int JR, int JC, const double* t, long t_stride, int N,
+                                                                     const double* xs, long xs_stride, int nrhs, int fast, double* out) {
+  const long n = (long)blockIdx.x * 256 + threadIdx.x, r = blockIdx.y, b = blockIdx.z;
+  if (n >= N) return;
+  const double tau = xs[b * xs_stride + r] - t[b * t_stride + n];
+  const double *ar = a_real + b * JR, *cr = c_real + b * JR, *ac = a_comp + b * JC, *bc = b_comp + b * JC, *cc = c_comp + b * JC,
+               *dc = d_comp + b * JC;
+  out[(b * nrhs + r) * N + n] = fast ? clr::cross_covariance<true>(ar, cr, JR, ac, bc, cc, dc, JC, tau)
+                                     : clr::cross_covariance<false>(ar, cr, JR, ac, bc, cc, dc, JC, tau);
+}
+
+// widths 9..64: var = k_p(0) - sum_n x_n^2 / D_n of one (problem, rhs) per workgroup (grid: rhs, problem) in a fixed
+// order -- thread i sums the samples i, i + 256, ... in order, then a fixed tree over the 256 threads
+__global__ void __launch_bounds__(256) predvar_reduce_kernel(const double* x, const double* D, int N, int nrhs, const double* a_real,
+                                                             const double* a_comp, int JR, int JC, double* var, long var_stride) {
+  __shared__ double sh[256];
+  const long r = blockIdx.x, b = blockIdx.y;
+  const double* xp = x + (b * nrhs + r) * N;
+  const double* Dp = D + b * N;
+  double s = 0.0;
+  for (int n = threadIdx.x; n < N; n += 256) s += xp[n] * xp[n] / Dp[n];
+  sh[threadIdx.x] = s;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    double sr = 0.0, sc = 0.0;
+    for (int j = 0; j < JR; ++j) sr += a_real[b * JR + j];
+    for (int j = 0; j < JC; ++j) sc += a_comp[b * JC + j];
+    var[b * var_stride + r] = (sr + sc) - sh[0];
+  }
+}
+
+int clr_batch_set_predict_tile(clr_batch* h, int points) {
+  h->predict_tile = points > 0 ? points : 0;
+  return CLR_OK;
+}
+
+// points per tile: the caller's (clr_batch_set_predict_tile), or the most whose buffers -- `per_point` doubles each --
+// fit in 1 GiB; never above grid.z's 65535 nor M, at least 1
+static int predict_tile(const clr_batch* h, int M, size_t per_point) {
+  const size_t budget = (size_t)1 << 27;  // doubles
+  size_t R = h->predict_tile > 0 ? (size_t)h->predict_tile : std::max<size_t>(1, budget / std::max<size_t>(1, per_point));
+  return (int)std::min<size_t>(std::min<size_t>(R, 65535), (size_t)M);
+}
+
+// The conditional variance of GP.predict (celerite.py:465-470) for every problem of the plan at M points each:
+// var = k(0) - k*^T K^-1 k* = k(0) - sum_n z_n^2 / D_n with z = L^-1 k* -- the forward half of a solve per point, on
+// right-hand sides formed on the device from the plan's times, the coefficients in force and the points, a tile of
+// points at a time.  Narrow plans: clr_bpredvar_kernels.h on the chunk-interleaved factor (either layout), the chunk maps
+// shared with clr_batch_solve.  Wide plans (widths 9..64): the cross-covariances row-major, the forward sweep of
+// wide_batch_solve (launch_wsweep_scan, backward = 0) and one workgroup per (problem, point) for the quadratic form.
+int clr_batch_predict_var(clr_batch* h, int M, const double* xs, long xs_stride, double* var) {
+  int st = require_device(h->device);
+  if (st != CLR_OK) return st;
+  if (M < 0 || (M > 0 && (!xs || !var))) return fail(CLR_INVALID_ARGUMENT, "clr_batch_predict_var: M >= 0, the points and an output array");
+  if (xs_stride != 0 && xs_stride != M) return fail(CLR_INVALID_ARGUMENT, "clr_batch_predict_var: the points' stride is 0 (shared by all problems) or M");
+  if ((st = require_celerite_width(h, "clr_batch_predict_var")) != CLR_OK) return st;
+  if (M == 0) return CLR_OK;
+  if ((st = require_factor(h, true)) != CLR_OK) return st;
+  if (!h->launch && !clr::wsweep_scan_supported(h->N, h->J))
+    return fail(CLR_UNSUPPORTED, "clr_batch_predict_var on a wide plan needs N >= 512 (shorter series: GP.predict)");
+  if (h->launch && h->nchunk < 2) return fail(CLR_UNSUPPORTED, "clr_batch_predict_var needs a chunked plan (N >= 128)");
+  clr::BatchParams P;  // (wide plans read its coefficients only)
+  if ((st = consumer_params(h, false, P)) != CLR_OK) return st;
+  const size_t B = (size_t)h->B, N = (size_t)h->N, J = (size_t)h->J, Mm = (size_t)M, nsrc = xs_stride == 0 ? 1 : B;
+  // the phases of the cross-covariances: |d| |x* - t| <= max|d| (max|x*| + max|t|), under the plan's own rule
+  double xmax = 0.0;
+  for (size_t k = 0; k < nsrc * Mm; ++k) {
+    const double a = std::fabs(xs[k]);
+    if (a > xmax || a != a) xmax = a;  // (a NaN stays: the library sincos)
+  }
+  const int cross_fast = (sel_max(h->dmax, h->floor_dmax) * (sel_max(h->tmax, h->floor_tmax) + xmax) < CLR_FAST_TRIG_LIMIT) ? 1 : 0;
+  DevBuf dxs, dvar;
+  if ((st = dxs.reserve(nsrc * Mm)) != CLR_OK) return st;
+  if ((st = dvar.reserve(B * Mm)) != CLR_OK) return st;
+  if (!h->launch) {  // wide plans
+    int want = std::min(clr::wsweep_chunks(h->N, h->J), std::max(2, (int)(2048 / B)));
+    if (want > (h->N - 1) / 64) want = std::max(1, (h->N - 1) / 64);
+    clr::SweepParams W = wide_sweep_params(h, 1, want);
+    const size_t ws_point = clr::wsweep_workspace_doubles(h->J, W.nchunk, 2) - clr::wsweep_workspace_doubles(h->J, W.nchunk, 1);
+    const int R = predict_tile(h, M, B * (2 * N + ws_point));
+    const size_t ws = clr::wsweep_workspace_doubles(h->J, W.nchunk, R);
+    if ((st = h->bs_M.reserve(B * ws)) != CLR_OK) return st;
+    if ((st = h->bs_x.reserve(B * R * N)) != CLR_OK) return st;   // the forward sweep's output (undivided)
+    if ((st = h->bs_rm.reserve(B * R * N)) != CLR_OK) return st;  // the tile's cross-covariances
+    ConsumerFrame frame{h};
+    HIP_TRY(hipMemcpyAsync(dxs.p, xs, nsrc * Mm * sizeof(double), hipMemcpyHostToDevice, h->stream.get()));
+    HIP_TRY(frame.start());
+    for (int m0 = 0; m0 < M; m0 += R) {
+      const int nr = std::min(R, M - m0);
+      const dim3 cgrid((unsigned)((N + 255) / 256), nr, (unsigned)B);
+      hipLaunchKernelGGL(predvar_cross_rowmajor_kernel, cgrid, dim3(256), 0, h->stream.get(), P.a_real, P.c_real, P.a_comp, P.b_comp, P.c_comp, P.d_comp,
+                         h->J_real, h->J_comp, h->t.p, h->t_stride, h->N, dxs.p + m0, xs_stride, nr, cross_fast, h->bs_rm.p);
+      W.nrhs = nr; W.stride_in = W.stride_out = (long)nr * (long)N;
+      W.stride_ws = (long)clr::wsweep_workspace_doubles(h->J, W.nchunk, nr);
+      W.in = h->bs_rm.p; W.out = h->bs_x.p; W.backward = 0;
+      clr::launch_wsweep_scan(W, h->bs_M.p, h->stream.get());
+      hipLaunchKernelGGL(predvar_reduce_kernel, dim3(nr, (unsigned)B), dim3(256), 0, h->stream.get(), h->bs_x.p, h->D.p, h->N, nr,
+                         P.a_real, P.a_comp, h->J_real, h->J_comp, dvar.p + m0, (long)M);
+    }
+    HIP_TRY(frame.stop());
+    return frame.finish(var, dvar.p, B * Mm);
+  }
+  const size_t cells = (size_t)h->L * h->nchunk, nc = (size_t)h->nchunk;
+  const int R = predict_tile(h, M, B * (cells + 2 * nc * J));
+  if ((st = h->bs_x.reserve(B * R * cells)) != CLR_OK) return st;
+  if ((st = h->bs_M.reserve(B * nc * J * J)) != CLR_OK) return st;
+  if ((st = h->bs_off.reserve(B * R * nc * J)) != CLR_OK) return st;
+  if ((st = h->bs_starts.reserve(B * R * nc * J)) != CLR_OK) return st;
+  ConsumerFrame frame{h};
+  HIP_TRY(hipMemcpyAsync(dxs.p, xs, nsrc * Mm * sizeof(double), hipMemcpyHostToDevice, h->stream.get()));
+  HIP_TRY(frame.start());
+  clr::BPredVarParams S;
+  S.lean = h->factor_is_lean ? 1 : 0; S.cross_fast = cross_fast;
+  // (the chunk maps are the batched solve's, under its validity rule: formed by the first tile after a materialising run
+  //  unless a solve has formed them, and counted as formed only once this call's kernels have run to completion)
+  S.have_M = h->bs_M_valid ? 1 : 0;
+  h->bs_M_valid = false;
+  S.xs_stride = xs_stride; S.t = h->t.p; S.t_stride = h->t_stride;
+  S.xT = h->bs_x.p; S.M = h->bs_M.p; S.off = h->bs_off.p; S.starts = h->bs_starts.p;
+  S.part = h->bs_off.p;  // (the walk has consumed the offsets by the time the forward recurrence writes its sums)
+  S.var_stride = (long)M;
+  for (int m0 = 0; m0 < M; m0 += R) {
+    S.nrhs = std::min(R, M - m0); S.xs = dxs.p + m0; S.var = dvar.p + m0;
+    h->launch->bpredvar(P, S, h->stream.get());
+    S.have_M = 1;
+  }
+  HIP_TRY(frame.stop());
+  if ((st = frame.finish(var, dvar.p, B * Mm)) != CLR_OK) return st;
+  h->bs_M_valid = true;
+  return CLR_OK;
+}
+
 int clr_batch_get_solve_ms(const clr_batch* h, double* device_ms) {
   if (device_ms) *device_ms = h->solve_device_ms;
   return CLR_OK;

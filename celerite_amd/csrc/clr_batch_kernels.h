@@ -1006,6 +1006,7 @@ __global__ void __launch_bounds__(64) warm_check_kernel(const BatchParams P) {
 #include "clr_bsolve_kernels.h"
 #include "clr_bdotl_kernels.h"
 #include "clr_bdot_kernels.h"
+#include "clr_bpredvar_kernels.h"
 namespace clr {
 
 // One table entry per (JR, JC): host-callable launchers.
@@ -1027,6 +1028,9 @@ struct BatchLaunchers {
   void (*bdotl)(const BatchParams&, BDotLParams S, hipStream_t);
   // K z for all problems and right-hand sides from the plan's times and coefficients (clr_bdot_kernels.h): S.zT -> S.yT
   void (*bdot)(const BatchParams&, BDotParams S, hipStream_t);
+  // k(0) - k*^T K^-1 k* for all problems at one tile of prediction points from the materialised factor
+  // (clr_bpredvar_kernels.h): S.xs -> S.var
+  void (*bpredvar)(const BatchParams&, BPredVarParams S, hipStream_t);
   // lean factor of problem b (replay mode 3) -> the reference's storage, phi and u regenerated (t: the problem's row-major times)
   void (*expand)(const BatchParams&, int b, const double* t, double* phi, double* u, double* W, double* D, hipStream_t);
   int elem_doubles, start_doubles;
@@ -1153,6 +1157,32 @@ struct BatchImpl {
   static void bdot(const BatchParams& P, BDotParams S, hipStream_t s) {
     if (P.fast_trig) bdot_go<true>(P, S, s); else bdot_go<false>(P, S, s);
   }
+  // the batched predictive variance of one tile of points: cross-covariances, forward offsets (the chunk maps once per
+  // factor, by the first right-hand side alone), the walk, the forward recurrence with the quadratic form, the finish
+  template <bool LEAN, bool FAST>
+  static void bpredvar_go(const BatchParams& P, const BPredVarParams& S, hipStream_t s) {
+    constexpr int J = JR + 2 * JC, RPL = bpredvar_rhs_per_lane(J);
+    const unsigned lanes = (unsigned)((P.nchunk + 63) / 64), R = (unsigned)S.nrhs;
+    const dim3 cgrid((unsigned)(((long)P.L * P.nchunk + 255) / 256), P.B, R), pgrid((unsigned)(((long)P.B * S.nrhs + 63) / 64));
+    if (S.cross_fast) hipLaunchKernelGGL((bpredvar_cross_kernel<JR, JC, true>), cgrid, dim3(256), 0, s, P, S);
+    else hipLaunchKernelGGL((bpredvar_cross_kernel<JR, JC, false>), cgrid, dim3(256), 0, s, P, S);
+    BSolveParams Q;
+    Q.nrhs = S.nrhs; Q.r = 0; Q.lean = S.lean; Q.have_M = S.have_M;
+    Q.xT = S.xT; Q.M = S.M; Q.off = S.off; Q.starts = S.starts;
+    if (!S.have_M) {
+      hipLaunchKernelGGL((bsolve_summarize_kernel<JR, JC, LEAN, FAST, true>), dim3(lanes, P.B, 1), dim3(64), 0, s, P, Q);
+      Q.r = 1;
+    }
+    if (Q.r < S.nrhs)
+      hipLaunchKernelGGL((bsolve_summarize_kernel<JR, JC, LEAN, FAST, false>), dim3(lanes, P.B, R - Q.r), dim3(64), 0, s, P, Q);
+    hipLaunchKernelGGL((bsolve_prefix_kernel<J, false>), pgrid, dim3(64), 0, s, P, Q);
+    hipLaunchKernelGGL((bpredvar_forward_kernel<JR, JC, LEAN, FAST, RPL>), dim3(lanes, P.B, (R + RPL - 1) / RPL), dim3(64), 0, s, P, S);
+    hipLaunchKernelGGL((bpredvar_finish_kernel<JR, JC>), pgrid, dim3(64), 0, s, P, S);
+  }
+  static void bpredvar(const BatchParams& P, BPredVarParams S, hipStream_t s) {
+    if (S.lean) { if (P.fast_trig) bpredvar_go<true, true>(P, S, s); else bpredvar_go<true, false>(P, S, s); }
+    else bpredvar_go<false, true>(P, S, s);  // (the stored phi, u: no trigonometry)
+  }
   static void compose_check(const BatchParams& P, int g, double* coop, double* ref, hipStream_t s) {
     constexpr int J = JR + 2 * JC;
     const int np = (P.nchunk + g - 1) / g;
@@ -1205,7 +1235,7 @@ struct BatchImpl {
   }
   static BatchLaunchers table() {
     return BatchLaunchers{&summarize, &prefix, &correct, &replay, &sequential, &compose_check, &warm, &grad, &grad_reverse,
-                          &bsolve, &bdotl, &bdot, &expand, Widths<JR, JC>::ELEM, Widths<JR, JC>::START};
+                          &bsolve, &bdotl, &bdot, &bpredvar, &expand, Widths<JR, JC>::ELEM, Widths<JR, JC>::START};
   }
 };
 

@@ -85,15 +85,15 @@ __device__ __forceinline__ FactorSlots<JR, JC, LEAN, FAST> make_slots(const Batc
   return s;
 }
 
-// 1. chunk maps M (WITH_M) and forward offsets a of right-hand side S.r
+// 1. chunk maps M (WITH_M) and forward offsets a of right-hand side S.r + blockIdx.z (grid.z = 1: of S.r)
 template <int JR, int JC, bool LEAN, bool FAST, bool WITH_M>
 __global__ void __launch_bounds__(64) bsolve_summarize_kernel(const BatchParams P, const BSolveParams S) {
   constexpr int J = JR + 2 * JC;
-  const int b = blockIdx.y, c = blockIdx.x * 64 + threadIdx.x;
+  const int b = blockIdx.y, c = blockIdx.x * 64 + threadIdx.x, r = S.r + blockIdx.z;
   if (c >= P.nchunk) return;
   const auto F = make_slots<JR, JC, LEAN, FAST>(P, b, c);
   const long cells = (long)P.L * P.nchunk;
-  const double* x = S.xT + ((long)b * S.nrhs + S.r) * cells + c;
+  const double* x = S.xT + ((long)b * S.nrhs + r) * cells + c;
   double M[WITH_M ? J * J : 1], a[J];
   if (WITH_M) {
 #pragma unroll
@@ -154,7 +154,7 @@ __global__ void __launch_bounds__(64) bsolve_summarize_kernel(const BatchParams 
 #pragma unroll
     for (int k = 0; k < J * J; ++k) o[k] = M[k];
   }
-  double* oa = S.off + (((long)b * S.nrhs + S.r) * P.nchunk + c) * J;
+  double* oa = S.off + (((long)b * S.nrhs + r) * P.nchunk + c) * J;
 #pragma unroll
   for (int j = 0; j < J; ++j) oa[j] = a[j];
 }

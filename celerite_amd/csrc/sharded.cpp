@@ -614,6 +614,12 @@ int clr_sharded_predict(clr_sharded* h, int M, const double* xs, long xs_stride,
   });
 }
 
+int clr_sharded_predict_var(clr_sharded* h, int M, const double* xs, long xs_stride, double* var) {
+  return on_slices(h, M >= 0 && (M == 0 || (xs && var)) && (xs_stride == 0 || xs_stride == M), [=](clr_batch* p, long lo) {
+    return clr_batch_predict_var(p, M, xs + lo * xs_stride, xs_stride, var + lo * (long)M);
+  });
+}
+
 int clr_sharded_run_timed(clr_sharded* h, int steps, double* shard_ms /* [nshards] or NULL */) {
   // (a timing tool: every shard times its own steps and settles them by its own counts)
   const int st0 = resolve_all(h);

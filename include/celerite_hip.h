@@ -491,6 +491,25 @@ int clr_batch_solve(clr_batch* h, int nrhs, const double* b, double* x);
  * the prediction points are the object API's chunked diagonal scans on the plan's resident times and coefficients
  * (sorted points: parallel in n; unsorted: the sequential walk of the reference). */
 int clr_batch_predict(clr_batch* h, int M, const double* xs, long xs_stride, double* pred);
+/* The other half of GP.predict (return_var=True, celerite.py:465-470): the conditional variance
+ *     var_p(x*) = k_p(0) - k*^T K_p^-1 k* ,  k*_n = k_p(x* - t_{p,n}) ,  k_p(0) = sum a_real + sum a_comp
+ * (no jitter, no observational variance) for every problem of the plan at M points each; xs as for clr_batch_predict
+ * (host [B][M] with xs_stride = M, or M shared points with xs_stride = 0; the points need not be sorted), var host
+ * [B][M].  Only xs goes up and only var comes down: the cross-covariances are formed on the device from the plan's
+ * times, the coefficients in force and the points, and k*^T K^-1 k* = sum_n z_n^2 / D_n with z = L^-1 k* needs the
+ * forward half of a solve only, on the factor of the last materialising run (either layout).  The points are worked
+ * through in tiles (clr_batch_set_predict_tile), so device scratch is bounded whatever M is, and a point's result does
+ * not depend on the tile size or on the tile it falls in (bit for bit).  Widths 1..8: csrc/clr_bpredvar_kernels.h on
+ * chunked plans (N >= 128), the chunk maps shared with clr_batch_solve; widths 9..64: the forward sweep of
+ * clr_batch_solve's wide route, N >= 512 (else CLR_UNSUPPORTED).  A mean (clr_batch_set_mean) does not enter.  A
+ * problem whose materialising run reported CLR_NOT_POSITIVE_DEFINITE has no factor: its var, like its pred, is
+ * undefined (usually non-finite) -- read the statuses.  clr_batch_get_solve_ms then reports this call's device time. */
+int clr_batch_predict_var(clr_batch* h, int M, const double* xs, long xs_stride, double* var);
+/* Prediction points per tile of clr_batch_predict_var; points <= 0 (the default): automatic -- the most whose
+ * right-hand-side, offset and start-state buffers fit in 1 GiB, at most 65535 (grid.z), at least 1.  The 1 GiB rule
+ * bounds the automatic choice only: a tile set here is taken as given up to 65535 and M, and clr_batch_predict_var
+ * returns the allocation's status if the device cannot hold its buffers. */
+int clr_batch_set_predict_tile(clr_batch* h, int points);
 /* CholeskySolver::dot_L (cholesky.h:409-431: y = L z with K = L L^T, what GP.sample draws, celerite.py:422-451) for
  * every problem of the plan from the factor of its last materialising run (either layout): z, y host [B][nrhs][N].
  * Widths 1..8: a chunked diagonal scan on the chunk-interleaved factor, lane = (problem, chunk)
@@ -755,7 +774,8 @@ int clr_sharded_get_coefficients(clr_sharded* h, double* jitter, double* a_real,
 /* The consumers of the factor on a sharded batch (GP.apply_inverse / .sample / .predict for B problems over several
  * GPUs): clr_sharded_materialize runs clr_batch_enqueue(plan, 1) on every shard, settles the evaluation with the
  * batch-wide counts (results as clr_sharded_get_results; any pointer may be NULL) and leaves every shard's factor in
- * its HBM; clr_sharded_solve / _dot_L / _dot / _predict are clr_batch_solve / _dot_L / _dot / _predict on every shard concurrently,
+ * its HBM; clr_sharded_solve / _dot_L / _dot / _predict / _predict_var are clr_batch_solve / _dot_L / _dot / _predict / _predict_var on every
+ * shard concurrently,
  * each on its contiguous slice of the host arrays ([B][nrhs][N]; xs [B][M] or shared with xs_stride = 0).  No
  * collective: every problem's state is its own (cholesky.h:703-706). */
 int clr_sharded_materialize(clr_sharded* h, double* loglike, double* logdet, double* quad, int* status);
@@ -763,6 +783,7 @@ int clr_sharded_solve(clr_sharded* h, int nrhs, const double* b, double* x);
 int clr_sharded_dot_L(clr_sharded* h, int nrhs, const double* z, double* y);
 int clr_sharded_dot(clr_sharded* h, int nrhs, const double* z, double* y);
 int clr_sharded_predict(clr_sharded* h, int M, const double* xs, long xs_stride, double* pred);
+int clr_sharded_predict_var(clr_sharded* h, int M, const double* xs, long xs_stride, double* var);
 /* `steps` back-to-back evaluations on every shard concurrently (HIP events per shard);
  * shard_ms[s] = that shard's first-to-last event time. */
 int clr_sharded_run_timed(clr_sharded* h, int steps, double* shard_ms);
