@@ -106,6 +106,13 @@ def _load():
     lib.clr_sharded_set_mean.argtypes = [C.c_void_p, _dp, C.c_long]
     lib.clr_sharded_evaluate_mean.argtypes = [C.c_void_p, _dp, C.c_long] + [_dp] * 10 + [_ip]
     lib.clr_sharded_grad_mean.argtypes = [C.c_void_p, _dp, _dp, _dp, _ip]
+    lib.clr_batch_set_mean_basis.argtypes = [C.c_void_p, C.c_int, _dp, C.c_long]
+    lib.clr_batch_set_mean_weights.argtypes = [C.c_void_p, _dp]
+    lib.clr_batch_grad_mean_weights.argtypes = [C.c_void_p, _dp, _ip]
+    lib.clr_batch_get_mean_project_ms.argtypes = [C.c_void_p, _dp]
+    lib.clr_sharded_set_mean_basis.argtypes = [C.c_void_p, C.c_int, _dp, C.c_long]
+    lib.clr_sharded_set_mean_weights.argtypes = [C.c_void_p, _dp]
+    lib.clr_sharded_grad_mean_weights.argtypes = [C.c_void_p, _dp, _ip]
     lib.clr_kernel_create.argtypes = [C.c_int, _ip, C.c_int, _dp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
     lib.clr_kernel_destroy.argtypes = [C.c_void_p]
     lib.clr_kernel_destroy.restype = None
@@ -229,6 +236,62 @@ def _mean_arg(mu, B):
     return np.ascontiguousarray(m), 1
 
 
+MAX_MEAN_BASIS = 16      # CLR_MAX_MEAN_BASIS of include/celerite_hip.h
+
+
+def _basis_arg(Phi, B, N):
+    """``(array, stride, K)`` of a linear mean's basis for ``clr_*_set_mean_basis``: ``(K, N)`` shared by all problems
+    (stride 0) or ``(B, K, N)`` (stride ``K * N``), ``1 <= K <= MAX_MEAN_BASIS``; ``None``: ``(None, 0, 0)`` (no linear
+    mean)."""
+    if Phi is None:
+        return None, 0, 0
+    a = np.ascontiguousarray(Phi, dtype=np.float64)
+    if a.ndim == 2 and a.shape[1] == N:
+        stride = 0
+    elif a.ndim == 3 and a.shape[0] == B and a.shape[2] == N:
+        stride = a.shape[1] * N
+    else:
+        raise ValueError("dimension mismatch")
+    K = a.shape[-2]
+    if not 1 <= K <= MAX_MEAN_BASIS:
+        raise ValueError("dimension mismatch: a linear mean has 1..%d basis functions" % MAX_MEAN_BASIS)
+    return a, stride, K
+
+
+def _weights_arg(w, B, K):
+    """The weights of a linear mean as a contiguous ``(B, K)`` array: ``(B, K)``, or ``(K,)`` for all problems."""
+    a = np.asarray(w, dtype=np.float64)
+    if K < 1 or a.shape not in ((K,), (B, K)):
+        raise ValueError("dimension mismatch")
+    return np.ascontiguousarray(np.broadcast_to(a, (B, K)))
+
+
+def _exclusive_means(mean, mean_weights):
+    if mean is not None and mean_weights is not None:
+        raise ValueError("mean and mean_weights are mutually exclusive: a plan has a constant mean or a linear one")
+
+
+def _linear_mean_at(plan, mean_basis, M):
+    """``sum_k w[b, k] basis_k`` at ``M`` prediction points, ``(B, M)``, added up in the order of the device's residual
+    (``k = 0, 1, ...``); ``None`` when the plan has no linear mean."""
+    K = getattr(plan, "_mean_K", 0)
+    if not K:
+        if mean_basis is not None:
+            raise ValueError("mean_basis without a linear mean (set_mean_basis)")
+        return None
+    if mean_basis is None:
+        raise ValueError("a linear mean is in force: predict needs mean_basis, the basis at the prediction points")
+    a, _, Kb = _basis_arg(mean_basis, plan.B, M)
+    if Kb != K:
+        raise ValueError("dimension mismatch")
+    a = np.broadcast_to(a, (plan.B, K, M))
+    w = plan._mean_w
+    m = w[:, 0, None] * a[:, 0]
+    for k in range(1, K):
+        m = m + w[:, k, None] * a[:, k]
+    return m
+
+
 class BatchedGP(object):
     """Device-resident plan for B problems of N samples and a fixed kernel shape.
 
@@ -249,6 +312,7 @@ class BatchedGP(object):
             raise RuntimeError("clr_batch_create failed: " + lib.clr_last_error().decode())
         self._h = C.c_void_p(self._h)
         self._evaluate_fn = None
+        self._mean_K, self._mean_w = 0, None
 
     def close(self):
         if getattr(self, "_h", None):
@@ -297,6 +361,49 @@ class BatchedGP(object):
         gradient -- then sees the residual ``y - mu_b``, formed on the device from the uploaded ``y``."""
         m, stride = _mean_arg(mu, self.B)
         _check(_load().clr_batch_set_mean(self._h, None if m is None else _ptr(m), stride))
+
+    def set_mean_basis(self, Phi):
+        """A mean that is linear in its parameters, ``mean_b(t_n) = sum_k w[b, k] Phi_k(t_n)``
+        (``clr_batch_set_mean_basis``): ``Phi`` is the basis at the plan's times, ``(K, N)`` for all problems or
+        ``(B, K, N)``, ``K <= 16`` -- a polynomial trend, per-instrument offsets, a sinusoid of fixed period, a transit
+        template.  It is uploaded once and stays on the device; the weights start at zero.  ``None`` removes the linear
+        mean.  Not together with :meth:`set_mean` (a constant is the basis function 1)."""
+        a, stride, K = _basis_arg(Phi, self.B, self.N)
+        self._set_mean_basis(K, a, stride)
+        self._mean_K, self._mean_w = K, (np.zeros((self.B, K)) if K else None)
+
+    def _set_mean_basis(self, K, a, stride):
+        _check(_load().clr_batch_set_mean_basis(self._h, K, None if a is None else _ptr(a), stride))
+
+    def set_mean_weights(self, w):
+        """The weights of the linear mean, ``(B, K)`` or ``(K,)`` for all problems (``clr_batch_set_mean_weights``):
+        every route that reads ``y`` then sees ``y - sum_k w[b, k] Phi_k``, formed on the device from the uploaded ``y``
+        -- B x K numbers go up per optimiser step, not a new ``y``.  The factor of a materialising run stays valid."""
+        a = _weights_arg(w, self.B, self._mean_K)
+        self._set_mean_weights(a)
+        self._mean_w = a
+
+    def _set_mean_weights(self, a):
+        _check(_load().clr_batch_set_mean_weights(self._h, _ptr(a)))
+
+    def grad_mean_weights(self):
+        """``(dw[B, K], status[B])``: ``d loglike_b / d w[b, k] = Phi_k^T K_b^-1 r_b`` at the weights in force, from the
+        factor of the last materialising run (``clr_batch_grad_mean_weights``): the batched solve of the residual and
+        one projection pass on the device.  A problem whose status is not 0 has a row of zeros."""
+        dw, st = np.empty((self.B, self._mean_K)), np.empty(self.B, dtype=np.int32)
+        self._grad_mean_weights(dw, st)
+        return dw, st
+
+    def _grad_mean_weights(self, dw, st):
+        if not self._mean_K:
+            raise RuntimeError("no basis is set: call set_mean_basis first")
+        _check(_load().clr_batch_grad_mean_weights(self._h, _ptr(dw), st.ctypes.data_as(_ip)))
+
+    def mean_project_ms(self):
+        """Device time of the projection pass of the last :meth:`grad_mean_weights` (its solve: :meth:`solve_device_ms`)."""
+        ms = C.c_double()
+        _check(_load().clr_batch_get_mean_project_ms(self._h, C.byref(ms)))
+        return ms.value
 
     def set_coefficients(self, a_real, c_real, a_comp, b_comp, c_comp, d_comp, jitter=0.0):
         """Coefficient tables ``(B, J_real)`` / ``(B, J_comp)``; ``jitter`` scalar or ``(B,)``."""
@@ -363,12 +470,16 @@ class BatchedGP(object):
                                              st.ctypes.data_as(_ip)))
         return ll, ld, q, st
 
-    def evaluate(self, a_real, c_real, a_comp, b_comp, c_comp, d_comp, jitter=0.0, mean=None):
+    def evaluate(self, a_real, c_real, a_comp, b_comp, c_comp, d_comp, jitter=0.0, mean=None, mean_weights=None):
         """One optimiser / MCMC evaluation in ONE library call (``clr_batch_evaluate``): new coefficient tables in,
         ``(loglike, logdet, quad, status)`` of all B problems out -- ``set_coefficients`` + ``enqueue`` + ``results``
         without two of the three trips through ctypes.  Arrays that already are C-contiguous float64 of the right shape
         are passed as they are.  ``mean`` (a scalar or ``(B,)``): :meth:`set_mean` in the same call
-        (``clr_batch_evaluate_mean``); ``None`` leaves the mean in force as it is."""
+        (``clr_batch_evaluate_mean``); ``None`` leaves the mean in force as it is.  ``mean_weights``:
+        :meth:`set_mean_weights` first (a linear mean, :meth:`set_mean_basis`); not together with ``mean``."""
+        _exclusive_means(mean, mean_weights)
+        if mean_weights is not None:
+            self.set_mean_weights(mean_weights)
         B, JR, JC = self.B, self.J_real, self.J_comp
         tabs = []
         for a, w in ((a_real, JR), (c_real, JR), (a_comp, JC), (b_comp, JC), (c_comp, JC), (d_comp, JC)):
@@ -421,12 +532,15 @@ class BatchedGP(object):
             raise ValueError("dimension mismatch")
         return p
 
-    def evaluate_parameters(self, params, mean=None):
+    def evaluate_parameters(self, params, mean=None, mean_weights=None):
         """One optimiser / MCMC evaluation from kernel parameters (``clr_batch_evaluate_params``): ``params`` is
-        ``(B, kernel.vector_size)`` in ``get_parameter_vector()`` order, ``mean`` as in :meth:`evaluate`.  The
-        coefficients are formed on the device and never leave it.  Returns ``(loglike, logdet, quad, status)``; a draw
-        the program refuses (an SHO term across Q = 1/2, a non-finite parameter or coefficient) has status
-        ``CLR_INVALID_ARGUMENT`` and NaN results, the other problems are not affected."""
+        ``(B, kernel.vector_size)`` in ``get_parameter_vector()`` order, ``mean`` and ``mean_weights`` as in
+        :meth:`evaluate`.  The coefficients are formed on the device and never leave it.  Returns ``(loglike, logdet,
+        quad, status)``; a draw the program refuses (an SHO term across Q = 1/2, a non-finite parameter or coefficient)
+        has status ``CLR_INVALID_ARGUMENT`` and NaN results, the other problems are not affected."""
+        _exclusive_means(mean, mean_weights)
+        if mean_weights is not None:
+            self.set_mean_weights(mean_weights)
         p = self._params_arg(params)
         ll, ld, q, st = np.empty(self.B), np.empty(self.B), np.empty(self.B), np.empty(self.B, dtype=np.int32)
         m, stride = _mean_arg(mean, self.B)
@@ -487,11 +601,13 @@ class BatchedGP(object):
         _check(lib.clr_batch_solve(self._h, int(nrhs), _ptr(b), _ptr(x)))
         return x
 
-    def predict(self, xs, return_var=False):
+    def predict(self, xs, return_var=False, mean_basis=None):
         """The conditional mean ``mu_p + K_p(x*, t_p) K_p^-1 (y_p - mu_p)`` of every problem (``mu_p`` the mean of
         :meth:`set_mean`, zero without one; ``GP.predict``, celerite.py:279) at the prediction points ``xs`` --
         ``(M,)`` shared by all problems or ``(B, M)`` -- from the factor of the last materialising run
         (``clr_batch_predict``; ``CholeskySolver.predict``, cholesky.h:599-698, for B problems).  Returns ``(B, M)``.
+        With a linear mean in force (:meth:`set_mean_basis`) ``mean_basis`` is required: the basis at ``xs``, ``(K, M)``
+        or ``(B, K, M)``; its product with the weights is added to the conditional mean of the residual.
         ``return_var=True``: ``(mu, var)`` with the conditional variance ``k_p(0) - k*^T K_p^-1 k*`` of every point
         (``clr_batch_predict_var``; celerite.py:465-470), both ``(B, M)``: only ``xs`` goes up and ``var`` comes down."""
         lib = _load()
@@ -504,8 +620,11 @@ class BatchedGP(object):
         else:
             raise ValueError("dimension mismatch")
         M = xs.shape[-1]
+        model = _linear_mean_at(self, mean_basis, M)
         pred = np.empty((self.B, M))
         _check(lib.clr_batch_predict(self._h, int(M), _ptr(xs), stride, _ptr(pred)))
+        if model is not None:
+            pred = model + pred
         if not return_var:
             return pred
         lib.clr_batch_predict_var.argtypes = [C.c_void_p, C.c_int, _dp, C.c_long, _dp]
@@ -857,6 +976,7 @@ class ShardedBatchedGP(object):
         if not h:
             raise RuntimeError("clr_sharded_create failed: " + lib.clr_sharded_last_error().decode())
         self._h = C.c_void_p(h)
+        self._mean_K, self._mean_w = 0, None
 
     def _ok(self, status):
         if status != CLR_OK:
@@ -972,6 +1092,21 @@ class ShardedBatchedGP(object):
         m, stride = _mean_arg(mu, self.B)
         self._ok(_load().clr_sharded_set_mean(self._h, None if m is None else _ptr(m), stride))
 
+    set_mean_basis = BatchedGP.set_mean_basis
+    set_mean_weights = BatchedGP.set_mean_weights
+    grad_mean_weights = BatchedGP.grad_mean_weights
+
+    def _set_mean_basis(self, K, a, stride):
+        self._ok(_load().clr_sharded_set_mean_basis(self._h, K, None if a is None else _ptr(a), stride))
+
+    def _set_mean_weights(self, a):
+        self._ok(_load().clr_sharded_set_mean_weights(self._h, _ptr(a)))
+
+    def _grad_mean_weights(self, dw, st):
+        if not self._mean_K:
+            raise RuntimeError("no basis is set: call set_mean_basis first")
+        self._ok(_load().clr_sharded_grad_mean_weights(self._h, _ptr(dw), st.ctypes.data_as(_ip)))
+
     def grad_log_likelihood(self, mean_partial=False):
         """``(value[B], grad[B, 1 + 2 J_real + 4 J_comp], status[B])`` at the coefficients in force: every shard's
         plan gradient concurrently (``clr_sharded_grad``).  ``mean_partial=True``: ``(value, grad, dmean, status)``
@@ -1007,10 +1142,13 @@ class ShardedBatchedGP(object):
         self.enqueue()
         return self.results()
 
-    def evaluate(self, a_real, c_real, a_comp, b_comp, c_comp, d_comp, jitter=0.0, mean=None):
+    def evaluate(self, a_real, c_real, a_comp, b_comp, c_comp, d_comp, jitter=0.0, mean=None, mean_weights=None):
         """One optimiser / MCMC evaluation: new coefficients in, ``(loglike, logdet,
-        quad, status)`` of all B problems out.  ``mean``: as :meth:`BatchedGP.evaluate`
-        (``clr_sharded_evaluate_mean``)."""
+        quad, status)`` of all B problems out.  ``mean``, ``mean_weights``: as :meth:`BatchedGP.evaluate`
+        (``clr_sharded_evaluate_mean``; :meth:`set_mean_weights` first)."""
+        _exclusive_means(mean, mean_weights)
+        if mean_weights is not None:
+            self.set_mean_weights(mean_weights)
         jit, blocks = self._coeff_blocks(a_real, c_real, a_comp, b_comp, c_comp, d_comp, jitter)
         ll, ld, q, st = self._out()
         if mean is not None:
@@ -1028,9 +1166,12 @@ class ShardedBatchedGP(object):
     def _set_kernel_handle(self, prog):
         self._ok(_load().clr_sharded_set_kernel(self._h, prog._k))
 
-    def evaluate_parameters(self, params, mean=None):
+    def evaluate_parameters(self, params, mean=None, mean_weights=None):
         """:meth:`BatchedGP.evaluate_parameters` over the shards (``clr_sharded_evaluate_params``): every shard forms the
         coefficients of its slice of ``params`` on its own device."""
+        _exclusive_means(mean, mean_weights)
+        if mean_weights is not None:
+            self.set_mean_weights(mean_weights)
         p = self._params_arg(params)
         ll, ld, q, st = self._out()
         m, stride = _mean_arg(mean, self.B)
@@ -1102,9 +1243,10 @@ class ShardedBatchedGP(object):
         self._ok(lib.clr_sharded_dot(self._h, int(nrhs), _ptr(z), _ptr(y)))
         return y
 
-    def predict(self, xs, return_var=False):
+    def predict(self, xs, return_var=False, mean_basis=None):
         """The conditional mean of every problem at ``xs`` (``(M,)`` shared or ``(B, M)``) and, with ``return_var=True``,
-        the conditional variance beside it, as :meth:`BatchedGP.predict`."""
+        the conditional variance beside it, as :meth:`BatchedGP.predict` (``mean_basis``: the linear mean's basis at
+        ``xs``, required while one is in force)."""
         lib = _load()
         lib.clr_sharded_predict.argtypes = [C.c_void_p, C.c_int, _dp, C.c_long, _dp]
         xs = _f64(xs)
@@ -1115,8 +1257,11 @@ class ShardedBatchedGP(object):
         else:
             raise ValueError("dimension mismatch")
         M = xs.shape[-1]
+        model = _linear_mean_at(self, mean_basis, M)
         pred = np.empty((self.B, M))
         self._ok(lib.clr_sharded_predict(self._h, int(M), _ptr(xs), stride, _ptr(pred)))
+        if model is not None:
+            pred = model + pred
         if not return_var:
             return pred
         lib.clr_sharded_predict_var.argtypes = [C.c_void_p, C.c_int, _dp, C.c_long, _dp]

@@ -4,6 +4,7 @@
 #include "clr_options.h"
 #include "clr_group_hooks.h"
 #include "clr_kernel.h"
+#include "clr_bmean_kernels.h"
 
 #include <functional>
 
@@ -257,26 +258,33 @@ static void warm_select(clr_batch* h) {
   h->warm_K_dirty = h->warm_active;  // (uploaded behind the next coefficients, or by the next enqueue)
 }
 
-// The residual y - mu of clr_batch_set_mean from the caller's series in `y_src`: one elementwise pass into `y`, where
-// every route reads its series; the copies derived from `y` are then stale (a shared series with a per-problem mean
-// becomes a per-problem residual: the copies are re-sized by the launches that rebuild them).
+// The residual y - mu of clr_batch_set_mean -- or y - sum_k w_k Phi_k of clr_batch_set_mean_weights -- from the caller's
+// series in `y_src`: one elementwise pass into `y`, where every route reads its series; the copies derived from `y` are
+// then stale (a shared series with a per-problem mean becomes a per-problem residual: the copies are re-sized by the
+// launches that rebuild them).  The factor of a materialising run does not depend on y and stays.
 static int apply_mean(clr_batch* h) {
   const long N = h->N;
-  const bool per_problem = h->y_src_stride != 0 || h->mean_stride != 0;
+  const bool linear = h->mean_K > 0;  // (its weights are per problem)
+  const bool per_problem = linear || h->y_src_stride != 0 || h->mean_stride != 0;
   const int nout = per_problem ? h->B : 1;
   int st;
   if ((st = h->y.reserve((size_t)nout * N)) != CLR_OK) return st;
-  const size_t nm = h->host_mean.size();
+  const std::vector<double>& host = linear ? h->host_weights : h->host_mean;
+  const size_t nm = host.size();
   if ((st = h->mean_dev.reserve(nm)) != CLR_OK) return st;
   // through pinned staging: the copy is asynchronous, and only the previous upload -- not the stream -- is waited for
   // before the staging is rewritten
   if (h->mean_ev) HIP_TRY(hipEventSynchronize(h->mean_ev.get()));
   else HIP_TRY(clr::create_event(h->mean_ev, hipEventDisableTiming));
   if ((st = h->mean_pin.reserve(nm)) != CLR_OK) return st;
-  std::copy(h->host_mean.begin(), h->host_mean.end(), h->mean_pin.p);
+  std::copy(host.begin(), host.end(), h->mean_pin.p);
   HIP_TRY(hipMemcpyAsync(h->mean_dev.p, h->mean_pin.p, nm * sizeof(double), hipMemcpyHostToDevice, h->stream.get()));
   HIP_TRY(hipEventRecord(h->mean_ev.get(), h->stream.get()));
-  clr::launch_residual(h->y_src.p, h->y_src_stride, h->mean_dev.p, h->mean_stride, nout, (int)N, h->y.p, h->stream.get());
+  if (linear)
+    clr::launch_linear_residual(h->y_src.p, h->y_src_stride, h->basis_dev.p, h->basis_stride, h->mean_dev.p, h->mean_K, nout,
+                                (int)N, h->y.p, h->stream.get());
+  else
+    clr::launch_residual(h->y_src.p, h->y_src_stride, h->mean_dev.p, h->mean_stride, nout, (int)N, h->y.p, h->stream.get());
   HIP_TRY(hipGetLastError());
   residual_replaced(h, per_problem ? N : 0);
   return CLR_OK;
@@ -289,6 +297,9 @@ int clr_batch_set_mean(clr_batch* h, const double* mu, long mu_stride) {
   const size_t n = mu ? (mu_stride ? (size_t)h->B : 1) : 0;
   for (size_t i = 0; i < n; ++i)
     if (!std::isfinite(mu[i])) return fail(CLR_INVALID_ARGUMENT, "clr_batch_set_mean: a non-finite mean");
+  if (mu && h->mean_K > 0)
+    return fail(CLR_INVALID_ARGUMENT, "clr_batch_set_mean: a linear mean is in force (clr_batch_set_mean_basis) -- the two means "
+                                      "are mutually exclusive: remove it first, or make the constant a basis function");
   if (mu && h->have_mean && h->have_series && h->mean_stride == mu_stride && h->host_mean.size() == n &&
       memcmp(h->host_mean.data(), mu, n * sizeof(double)) == 0)
     return CLR_OK;  // (the residual in HBM is this mean's)
@@ -313,6 +324,70 @@ int clr_batch_set_mean(clr_batch* h, const double* mu, long mu_stride) {
   if (!h->have_series) return CLR_OK;  // (clr_batch_set_series applies it)
   if ((st = apply_mean(h)) != CLR_OK) {
     h->have_series = false;  // (no half-formed residual is ever evaluated: set the series again)
+    return st;
+  }
+  return CLR_OK;
+}
+
+/* ---- a mean linear in its parameters: clr_batch_set_mean_basis / _set_mean_weights / _grad_mean_weights ------------ */
+int clr_batch_set_mean_basis(clr_batch* h, int K, const double* phi, long phi_stride) {
+  int st = require_device(h->device);
+  if (st != CLR_OK) return st;
+  if (K <= 0 || !phi) {  // remove the linear mean: the caller's series is the pipeline's again
+    if (K < 0) return fail(CLR_INVALID_ARGUMENT, "clr_batch_set_mean_basis: K >= 0");
+    if (h->mean_K == 0) return CLR_OK;
+    if ((st = warm_resolve(h, nullptr)) != CLR_OK) return st;  // (an evaluation in flight is settled on ITS residual)
+    h->mean_K = 0;
+    h->host_weights.clear();
+    if (h->have_series) {
+      std::swap(h->y, h->y_src);
+      residual_replaced(h, h->y_src_stride);
+    }
+    return CLR_OK;
+  }
+  if (K > CLR_MAX_MEAN_BASIS) return fail(CLR_INVALID_ARGUMENT, "clr_batch_set_mean_basis: at most CLR_MAX_MEAN_BASIS = 16 basis functions");
+  const size_t per = (size_t)K * (size_t)h->N;
+  if (phi_stride != 0 && phi_stride != (long)per)
+    return fail(CLR_INVALID_ARGUMENT, "clr_batch_set_mean_basis: phi_stride is 0 (phi[K][N], shared) or K * N (phi[B][K][N])");
+  if (h->have_mean)
+    return fail(CLR_INVALID_ARGUMENT, "clr_batch_set_mean_basis: a constant mean is in force (clr_batch_set_mean) -- the two means "
+                                      "are mutually exclusive: remove it first, or make the constant a basis function");
+  const size_t n = phi_stride ? per * (size_t)h->B : per;
+  for (size_t i = 0; i < n; ++i)
+    if (!std::isfinite(phi[i])) return fail(CLR_INVALID_ARGUMENT, "clr_batch_set_mean_basis: a non-finite basis entry");
+  if ((st = warm_resolve(h, nullptr)) != CLR_OK) return st;
+  HIP_TRY(hipStreamSynchronize(h->stream.get()));  // (a residual pass in flight may still read the previous basis)
+  if ((st = h->basis_dev.reserve(n)) != CLR_OK) return st;
+  HIP_TRY(hipMemcpy(h->basis_dev.p, phi, n * sizeof(double), hipMemcpyHostToDevice));
+  if (h->mean_K == 0 && h->have_series) {  // the caller's series moves aside, `y` will hold the residual
+    std::swap(h->y, h->y_src);
+    h->y_src_stride = h->y_stride;
+  }
+  h->mean_K = K;
+  h->basis_stride = phi_stride;
+  h->host_weights.assign((size_t)h->B * K, 0.0);  // (a new basis starts from zero weights: the residual is y)
+  if (!h->have_series) return CLR_OK;  // (clr_batch_set_series applies it)
+  if ((st = apply_mean(h)) != CLR_OK) {
+    h->have_series = false;  // (no half-formed residual is ever evaluated: set the series again)
+    return st;
+  }
+  return CLR_OK;
+}
+
+int clr_batch_set_mean_weights(clr_batch* h, const double* w) {
+  int st = require_device(h->device);
+  if (st != CLR_OK) return st;
+  if (h->mean_K == 0) return fail(CLR_INVALID_ARGUMENT, "clr_batch_set_mean_weights: no basis is set (clr_batch_set_mean_basis)");
+  if (!w) return fail(CLR_INVALID_ARGUMENT, "clr_batch_set_mean_weights: w is null");
+  const size_t n = (size_t)h->B * h->mean_K;
+  for (size_t i = 0; i < n; ++i)
+    if (!std::isfinite(w[i])) return fail(CLR_INVALID_ARGUMENT, "clr_batch_set_mean_weights: a non-finite weight");
+  if (memcmp(h->host_weights.data(), w, n * sizeof(double)) == 0) return CLR_OK;  // (the residual in force is these weights')
+  if ((st = warm_resolve(h, nullptr)) != CLR_OK) return st;  // (an evaluation in flight is settled on ITS residual)
+  h->host_weights.assign(w, w + n);
+  if (!h->have_series) return CLR_OK;  // (clr_batch_set_series applies them)
+  if ((st = apply_mean(h)) != CLR_OK) {
+    h->have_series = false;
     return st;
   }
   return CLR_OK;
@@ -386,7 +461,7 @@ int clr_batch_set_series(clr_batch* h, const double* t, long t_stride, const dou
     h->dtmin = (finite_min < 0.0) ? finite_min : (nan ? NAN : finite_min);
   }
   h->have_series = true;
-  if (h->have_mean) {  // (the upload went to `y`: it becomes the caller's series, `y` the residual)
+  if (h->have_mean || h->mean_K > 0) {  // (the upload went to `y`: it becomes the caller's series, `y` the residual)
     std::swap(h->y, h->y_src);
     h->y_src_stride = y_stride;
     if ((st = apply_mean(h)) != CLR_OK) { h->have_series = false; return st; }
@@ -2010,7 +2085,9 @@ int clr_batch_predict(clr_batch* h, int M, const double* xs, long xs_stride, dou
   }
   if (frame.finish(pred, dpred.p, B * Mm) != CLR_OK)
     return fail(CLR_HIP_ERROR, "clr_batch_predict: kernels or the download failed");
-  if (h->have_mean)  // the mean plus the conditional mean of the residual (celerite.py:279)
+  // the mean plus the conditional mean of the residual (celerite.py:279); under a linear mean (clr_batch_set_mean_basis) the
+  // conditional mean of the residual alone -- the basis at the prediction points is the caller's
+  if (h->have_mean)
     for (size_t p = 0; p < B; ++p) {
       const double m = h->host_mean[h->mean_stride ? p : 0];
       for (size_t k = 0; k < Mm; ++k) pred[p * Mm + k] = m + pred[p * Mm + k];
@@ -2057,6 +2134,47 @@ __global__ void __launch_bounds__(256) predvar_reduce_kernel(const double* x, co
     for (int j = 0; j < JC; ++j) sc += a_comp[b * JC + j];
     var[b * var_stride + r] = (sr + sc) - sh[0];
   }
+}
+
+// d loglike / d w[b][k] = Phi_k^T K_b^-1 r_b: the batched solve of the residual in `y` on the factor in HBM, left row-major
+// in bs_rm, then the projection onto the resident basis (clr_bmean_kernels.h).  The gradient sweeps are not involved: the
+// log-likelihood depends on the weights through r alone, d (-1/2 r^T K^-1 r) / d w_k = Phi_k^T K^-1 r.
+int clr_batch_grad_mean_weights(clr_batch* h, double* dw, int* status) {
+  int st = require_device(h->device);
+  if (st != CLR_OK) return st;
+  if (h->mean_K == 0) return fail(CLR_INVALID_ARGUMENT, "clr_batch_grad_mean_weights: no basis is set (clr_batch_set_mean_basis)");
+  if (!dw) return fail(CLR_INVALID_ARGUMENT, "clr_batch_grad_mean_weights: an output array");
+  if ((st = batch_solve_impl(h, 1, nullptr, nullptr)) != CLR_OK) return st;  // K^-1 r -> bs_rm [B][N]
+  const size_t B = (size_t)h->B, K = (size_t)h->mean_K;
+  if ((st = h->proj_part.reserve(clr::mean_project_workspace(h->B, h->N, h->mean_K))) != CLR_OK) return st;
+  if ((st = h->proj_out.reserve(B * K)) != CLR_OK) return st;
+  for (clr::Event& e : h->proj_ev)
+    if (!e) HIP_TRY(clr::create_event(e));
+  {
+    ConsumerFrame frame{h};  // (untimed: solve_device_ms stays the solve's; the projection has its own events)
+    HIP_TRY(hipEventRecord(h->proj_ev[0].get(), h->stream.get()));
+    if (!clr::launch_mean_project(h->basis_dev.p, h->basis_stride, h->bs_rm.p, h->mean_K, h->B, h->N, h->proj_part.p,
+                                  h->proj_out.p, h->stream.get()))
+      return fail(CLR_UNSUPPORTED, "clr_batch_grad_mean_weights: B x N / 4096 workgroups do not fit one launch");
+    HIP_TRY(hipEventRecord(h->proj_ev[1].get(), h->stream.get()));
+    if ((st = frame.finish(dw, h->proj_out.p, B * K)) != CLR_OK) return st;
+  }
+  float ms = 0.f;
+  HIP_TRY(hipEventElapsedTime(&ms, h->proj_ev[0].get(), h->proj_ev[1].get()));
+  h->project_device_ms = ms;
+  // the statuses of the evaluation in force; a problem without a factor (or refused by the kernel program): zeros
+  std::vector<int> stat(B);
+  if ((st = clr_batch_get_results(h, nullptr, nullptr, nullptr, stat.data())) != CLR_OK) return st;
+  mark_refused(h, nullptr, nullptr, nullptr, stat.data());
+  for (size_t b = 0; b < B; ++b)
+    if (stat[b] != CLR_OK) std::fill(dw + b * K, dw + (b + 1) * K, 0.0);  // (the gradient's quiet semantics)
+  if (status) std::copy(stat.begin(), stat.end(), status);
+  return CLR_OK;
+}
+
+int clr_batch_get_mean_project_ms(const clr_batch* h, double* device_ms) {
+  if (device_ms) *device_ms = h->project_device_ms;
+  return CLR_OK;
 }
 
 int clr_batch_set_predict_tile(clr_batch* h, int points) {

@@ -461,6 +461,9 @@ int clr_batch_grad_log_likelihood(int B, int N, int J_real, int J_comp, const do
 int clr_batch_grad_mean(clr_batch* h, double* value, double* grad, double* dmean, int* status) {
   int st = require_device(h->device);
   if (st != CLR_OK) return st;
+  if (dmean && h->mean_K > 0)
+    return fail(CLR_UNSUPPORTED, "clr_batch_grad_mean: a linear mean is in force (clr_batch_set_mean_basis): its partials are "
+                                 "clr_batch_grad_mean_weights'");
   const size_t B = (size_t)h->B;
   std::vector<int> stat(B);
   // [B] partials | [B] ints: the problems left to the recurrence below

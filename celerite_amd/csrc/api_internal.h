@@ -251,6 +251,15 @@ struct clr_batch {
   std::vector<double> host_mean;      // [B] or [1]
   DevBuf mean_dev, y_src, mean_out;   // the mean on the device; the caller's y; clr_batch_grad_mean's partials [B]
   long y_src_stride = 0;
+  // clr_batch_set_mean_basis / _set_mean_weights: a mean linear in its parameters, sum_k w[b][k] Phi_k (mean_K > 0; never
+  // together with have_mean).  `y` holds the residual and `y_src` the caller's series as for the constant mean; the
+  // weights go up through mean_pin into mean_dev; the basis stays resident
+  int mean_K = 0;
+  long basis_stride = 0;              // 0: one basis [K][N] for all problems, K * N: [B][K][N]
+  std::vector<double> host_weights;   // [B][K] (zero until clr_batch_set_mean_weights)
+  DevBuf basis_dev, proj_part, proj_out;  // the basis; clr_batch_grad_mean_weights' slab partials and its result [B][K]
+  clr::Event proj_ev[2];              // ... its two timing events around the projection's kernels
+  double project_device_ms = 0.0;     // ... and their difference at the last call
   // clr_batch_set_kernel / _set_parameters: the program (host copy and in HBM), the last parameter rows with the
   // evaluation kernel's statistics block behind them, the chain rule's staging (grad | dmean | result)
   bool have_kernel = false;

@@ -103,6 +103,7 @@ thread_local std::string g_sharded_error;
 struct clr_sharded {
   int B = 0, N = 0, J_real = 0, J_comp = 0;
   int n_params = 0;  // of the kernel set by clr_sharded_set_kernel
+  int mean_K = 0;    // of the basis set by clr_sharded_set_mean_basis
   std::vector<int> device, lo, hi;
   std::vector<clr_batch*> plan;
   std::vector<std::unique_ptr<Worker>> worker;
@@ -525,6 +526,44 @@ int clr_sharded_grad_mean(clr_sharded* h, double* value, double* grad, double* d
     const long lo = h->lo[s];
     return clr_batch_grad_mean(h->plan[s], value ? value + lo : nullptr, grad ? grad + lo * NG : nullptr,
                                dmean ? dmean + lo : nullptr, status ? status + lo : nullptr);
+  });
+}
+
+/* ---- a linear mean: clr_batch_set_mean_basis / _set_mean_weights / _grad_mean_weights over the shards ---- */
+int clr_sharded_set_mean_basis(clr_sharded* h, int K, const double* phi, long phi_stride) {
+  const bool remove = K == 0 || !phi;
+  const long per = (long)K * h->N;
+  if (!remove) {  // (checked here: an invalid basis leaves EVERY shard unchanged)
+    g_sharded_error = "clr_sharded_set_mean_basis: 1 <= K <= CLR_MAX_MEAN_BASIS = 16, phi_stride 0 or K * N, finite entries";
+    if (K < 0 || K > CLR_MAX_MEAN_BASIS || (phi_stride != 0 && phi_stride != per)) return CLR_INVALID_ARGUMENT;
+    const long n = phi_stride ? per * h->B : per;
+    for (long i = 0; i < n; ++i)
+      if (!std::isfinite(phi[i])) return CLR_INVALID_ARGUMENT;
+  }
+  int st = resolve_all(h);  // (an evaluation in flight is settled on ITS residual)
+  if (st != CLR_OK) return st;
+  st = h->all([=](int s) {
+    return clr_batch_set_mean_basis(h->plan[s], remove ? 0 : K, remove ? nullptr : phi + h->lo[s] * phi_stride, phi_stride);
+  });
+  if (st == CLR_OK) h->mean_K = remove ? 0 : K;
+  return st;
+}
+
+int clr_sharded_set_mean_weights(clr_sharded* h, const double* w) {
+  const long K = h->mean_K;
+  g_sharded_error = "clr_sharded_set_mean_weights: a basis must be set (clr_sharded_set_mean_basis) and the weights finite";
+  if (K == 0 || !w) return CLR_INVALID_ARGUMENT;
+  for (long i = 0; i < K * h->B; ++i)
+    if (!std::isfinite(w[i])) return CLR_INVALID_ARGUMENT;
+  const int st = resolve_all(h);
+  if (st != CLR_OK) return st;
+  return h->all([=](int s) { return clr_batch_set_mean_weights(h->plan[s], w + h->lo[s] * K); });
+}
+
+int clr_sharded_grad_mean_weights(clr_sharded* h, double* dw, int* status) {
+  const long K = h->mean_K;
+  return on_slices(h, K > 0 && dw, [=](clr_batch* p, long lo) {
+    return clr_batch_grad_mean_weights(p, dw + lo * K, status ? status + lo : nullptr);
   });
 }
 

@@ -472,6 +472,46 @@ int clr_batch_evaluate_mean(clr_batch* h, const double* mean, long mean_stride, 
                             const double* a_real, const double* c_real, const double* a_comp, const double* b_comp,
                             const double* c_comp, const double* d_comp, double* loglike, double* logdet, double* quad,
                             int* status);
+/* A mean that is LINEAR IN ITS PARAMETERS, mean_p(t_n) = sum_k w[p][k] Phi_k(t_n) with K <= CLR_MAX_MEAN_BASIS basis
+ * functions: what a celerite.modeling.Model subclass passed as GP(kernel, mean=model, fit_mean=True) is when its
+ * get_value(t) is linear in the parameter vector (a polynomial trend, per-instrument offsets, a sinusoid of fixed period,
+ * a transit template; celerite.py:202 subtracts mean.get_value(t) on every evaluation).  The caller evaluates the basis
+ * once; the plan keeps it in HBM, and an optimiser step sends B x K weights instead of a new y.
+ *
+ * clr_batch_set_mean_basis -- the model's design matrix, d get_value(t) / d parameter: phi is host [K][N] with
+ * phi_stride == 0 (one basis for all problems) or [B][K][N] with phi_stride == K * N; uploaded once.  The weights start at
+ * zero (the residual is y), also when a basis replaces another.  K == 0 or phi == NULL removes the linear mean and
+ * restores the caller's y.  CLR_INVALID_ARGUMENT, the plan unchanged: a non-finite entry, K > CLR_MAX_MEAN_BASIS, another
+ * stride, or a constant mean in force -- the two means are mutually exclusive (clr_batch_set_mean likewise refuses while
+ * a basis is in force; a constant is the basis function 1).  Before or after clr_batch_set_series: a later
+ * clr_batch_set_series keeps basis and weights in force and applies them to the new series.
+ *
+ * clr_batch_set_mean_weights -- mean.set_parameter_vector for B problems: w is host [B][K].  Every route that reads y --
+ * the evaluation, clr_batch_solve with b == NULL, clr_batch_predict, the gradient -- then sees the residual
+ *     r[p][n] = y[p][n] - m ,   m = w[p][0] Phi_0[n] ,  m = m + w[p][k] Phi_k[n]  (k = 1 .. K - 1, in this order),
+ * every product and sum rounded on its own (no FMA): the bits of the same expression in NumPy.  It is formed on the
+ * device by one elementwise pass over the caller's y, which stays in HBM untouched (a shared y becomes a per-problem
+ * residual).  The factor of a materialising run does not depend on y and stays valid.  Weights equal to the ones in
+ * force: nothing is done.  CLR_INVALID_ARGUMENT: a non-finite weight, or no basis set.
+ *
+ * clr_batch_grad_mean_weights -- the mean's block of GP.grad_log_likelihood (celerite.py: fit_mean): dw host [B][K],
+ *     dw[p][k] = d loglike_p / d w[p][k] = Phi_k^T K_p^-1 r_p ,
+ * from the factor of the last materialising run (CLR_NOT_COMPUTED without one, as clr_batch_solve): the batched solve of
+ * the residual, left on the device, and one projection pass onto the resident basis -- workgroups over fixed slabs of
+ * 4096 samples, their partials added in order, no atomics: the same bits on every run, for any batch size and any
+ * sharding.  New weights need no new materialising run.  status (may be NULL) receives the statuses of the evaluation in
+ * force; a problem whose status is not CLR_OK gets a row of zeros (clr_batch_grad's quiet semantics).  Plans of widths
+ * 1..64, as clr_batch_solve (its errors otherwise).  clr_batch_get_solve_ms then reports the solve's device time and
+ * clr_batch_get_mean_project_ms the projection's.
+ *
+ * With a linear mean in force clr_batch_grad_mean and clr_batch_grad_params(..., with_mean = 1) -- the constant mean's
+ * partial -- return CLR_UNSUPPORTED, and clr_batch_predict returns the conditional mean OF THE RESIDUAL, K_* K^-1 r: the
+ * caller adds sum_k w[p][k] Phi_k(x*), the model at the prediction points (celerite.py:279). */
+#define CLR_MAX_MEAN_BASIS 16
+int clr_batch_set_mean_basis(clr_batch* h, int K, const double* phi, long phi_stride);
+int clr_batch_set_mean_weights(clr_batch* h, const double* w);
+int clr_batch_grad_mean_weights(clr_batch* h, double* dw, int* status);
+int clr_batch_get_mean_project_ms(const clr_batch* h, double* device_ms);
 /* CholeskySolver::solve (cholesky.h:218-318) for every problem of the plan at once: x = K_p^-1 b_p from the factor of
  * the last materialising run (clr_batch_enqueue(h, 1); either factor layout), parallel in n -- forward substitution,
  * division by D and backward substitution as two chunked affine scans whose chunk maps are formed once and shared by
@@ -489,7 +529,8 @@ int clr_batch_solve(clr_batch* h, int nrhs, const double* b, double* x);
  * set of M points shared by all problems (xs_stride = 0); pred host [B][M].  alpha = K^-1 y comes from the batched solve
  * on the factor of the last materialising run (any layout, widths 1..64) and stays on the device; the two passes over
  * the prediction points are the object API's chunked diagonal scans on the plan's resident times and coefficients
- * (sorted points: parallel in n; unsorted: the sequential walk of the reference). */
+ * (sorted points: parallel in n; unsorted: the sequential walk of the reference).  Under a linear mean
+ * (clr_batch_set_mean_basis) y is the residual and pred its conditional mean alone: the model at x* is the caller's. */
 int clr_batch_predict(clr_batch* h, int M, const double* xs, long xs_stride, double* pred);
 /* The other half of GP.predict (return_var=True, celerite.py:465-470): the conditional variance
  *     var_p(x*) = k_p(0) - k*^T K_p^-1 k* ,  k*_n = k_p(x* - t_{p,n}) ,  k_p(0) = sum a_real + sum a_comp
@@ -763,6 +804,12 @@ int clr_sharded_evaluate_mean(clr_sharded* h, const double* mean, long mean_stri
                               const double* c_comp, const double* d_comp, double* loglike, double* logdet,
                               double* quad, int* status);
 int clr_sharded_grad_mean(clr_sharded* h, double* value, double* grad, double* dmean, int* status);
+/* clr_batch_set_mean_basis / _set_mean_weights / _grad_mean_weights over the whole batch: every shard takes its slice of
+ * phi (phi_stride K * N) or the one basis (0), of w[B][K] and of dw[B][K]; an invalid basis or weight leaves every shard
+ * unchanged.  The results are those of the unsharded plan, bit for bit (given one chunk count, as above). */
+int clr_sharded_set_mean_basis(clr_sharded* h, int K, const double* phi, long phi_stride);
+int clr_sharded_set_mean_weights(clr_sharded* h, const double* w);
+int clr_sharded_grad_mean_weights(clr_sharded* h, double* dw, int* status);
 /* clr_batch_set_kernel / _evaluate_params / _grad_params / _get_coefficients over the whole batch: every shard forms the
  * coefficients of its slice of params[B][n_params] on its own device; the selection bounds are taken over the batch. */
 int clr_sharded_set_kernel(clr_sharded* h, const clr_kernel* kernel);
