@@ -11,6 +11,7 @@ semantics for matrices that are not positive definite (``status[p] == 2`` and
 file is plumbing (ctypes).  There is no CPU fallback: without an MI355X every
 call raises ``RuntimeError``.
 """
+import collections
 import ctypes as C
 import os
 
@@ -18,7 +19,7 @@ import numpy as np
 
 __all__ = ["BatchedGP", "ShardedBatchedGP", "shard_bounds", "batch_log_likelihood", "batch_grad_log_likelihood",
            "kernel_coefficient_table", "kernel_coefficient_jacobian_table", "chain_gradient", "compile_kernel",
-           "CompiledKernel", "LIB_PATH"]
+           "CompiledKernel", "MeanFit", "gram_solve", "LIB_PATH"]
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libcelerite_hip.so")
 
@@ -113,6 +114,11 @@ def _load():
     lib.clr_sharded_set_mean_basis.argtypes = [C.c_void_p, C.c_int, _dp, C.c_long]
     lib.clr_sharded_set_mean_weights.argtypes = [C.c_void_p, _dp]
     lib.clr_sharded_grad_mean_weights.argtypes = [C.c_void_p, _dp, _ip]
+    lib.clr_batch_fit_mean_weights.argtypes = [C.c_void_p, C.c_double] + [_dp] * 5 + [_ip]
+    lib.clr_sharded_fit_mean_weights.argtypes = [C.c_void_p, C.c_double] + [_dp] * 5 + [_ip]
+    lib.clr_batch_set_mean_fit_tile.argtypes = [C.c_void_p, C.c_int]
+    lib.clr_batch_get_mean_fit_ms.argtypes = [C.c_void_p, _dp, _dp, _dp]
+    lib.clr_gram_solve.argtypes = [C.c_int, C.c_int, _dp, _dp, C.c_double] + [_dp] * 4 + [_ip]
     lib.clr_kernel_create.argtypes = [C.c_int, _ip, C.c_int, _dp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
     lib.clr_kernel_destroy.argtypes = [C.c_void_p]
     lib.clr_kernel_destroy.restype = None
@@ -266,6 +272,51 @@ def _weights_arg(w, B, K):
     return np.ascontiguousarray(np.broadcast_to(a, (B, K)))
 
 
+MeanFit = collections.namedtuple("MeanFit", ["weights", "covariance", "gram", "quad", "logdet_gram", "loglike",
+                                             "loglike_marginal", "status"])
+MeanFit.__doc__ = """The generalised-least-squares fit of a linear mean's weights (``fit_mean_weights``): ``weights[B, K]``,
+their ``covariance[B, K, K]`` = ``G^-1``, the bordered Gram matrix ``gram[B, K + 1, K + 1]`` = ``[[G, d], [d^T, q]]``, the
+profiled quadratic form ``quad[B]``, ``logdet_gram[B]`` = ``log det G``, the profiled log-likelihood ``loglike[B]``, the
+log-likelihood marginalised over the weights under a flat prior ``loglike_marginal[B]``, and ``status[B]``."""
+
+
+def _check_min_pivot(min_pivot):
+    p = float(min_pivot)
+    if not (np.isfinite(p) and 0.0 <= p < 1.0):
+        raise ValueError("min_pivot must be finite and lie in [0, 1)")
+    return p
+
+
+def gram_solve(gram, w0=None, min_pivot=1e-10):
+    """The small solve of :meth:`BatchedGP.fit_mean_weights` on the host (``clr_gram_solve``; no GPU): from bordered Gram
+    matrices ``gram[n, K + 1, K + 1]`` = ``[[G, d], [d^T, q]]`` and the weights ``w0[n, K]`` the residual was formed at
+    (``None``: zeros), ``(weights, covariance, quad, logdet_gram, status)`` -- the routine the device runs per problem,
+    the same bits."""
+    g = np.ascontiguousarray(gram, dtype=np.float64)
+    if g.ndim == 2:
+        g = g[None]
+    if g.ndim != 3 or g.shape[1] != g.shape[2] or not 2 <= g.shape[1] <= MAX_MEAN_BASIS + 1:
+        raise ValueError("dimension mismatch")
+    n, K = g.shape[0], g.shape[1] - 1
+    p = _check_min_pivot(min_pivot)
+    w = np.zeros((n, K)) if w0 is None else np.ascontiguousarray(np.broadcast_to(np.asarray(w0, dtype=np.float64), (n, K)))
+    w_hat, cov, quad, ld = np.empty((n, K)), np.empty((n, K, K)), np.empty(n), np.empty(n)
+    st = np.empty(n, dtype=np.int32)
+    _check(_load().clr_gram_solve(n, K, _ptr(g), _ptr(w), p, _ptr(w_hat), _ptr(cov), _ptr(quad), _ptr(ld),
+                                  st.ctypes.data_as(_ip)))
+    return w_hat, cov, quad, ld, st
+
+
+def _mean_fit(w_hat, cov, gram, quad, ld_gram, status, logdet_K, N):
+    """The :class:`MeanFit` of the library's outputs and ``log det K`` of the evaluation in force:
+    ``loglike = -1/2 (quad + log det K + N log 2 pi)``, ``loglike_marginal = loglike - 1/2 log det G + 1/2 K log 2 pi``
+    (refused problems: NaN, through their NaN ``quad``)."""
+    K = w_hat.shape[1]
+    log2pi = np.log(2.0 * np.pi)
+    ll = -0.5 * (quad + logdet_K + N * log2pi)
+    return MeanFit(w_hat, cov, gram, quad, ld_gram, ll, ll - 0.5 * ld_gram + 0.5 * K * log2pi, status)
+
+
 def _exclusive_means(mean, mean_weights):
     if mean is not None and mean_weights is not None:
         raise ValueError("mean and mean_weights are mutually exclusive: a plan has a constant mean or a linear one")
@@ -398,6 +449,43 @@ class BatchedGP(object):
         if not self._mean_K:
             raise RuntimeError("no basis is set: call set_mean_basis first")
         _check(_load().clr_batch_grad_mean_weights(self._h, _ptr(dw), st.ctypes.data_as(_ip)))
+
+    def fit_mean_weights(self, apply=False, min_pivot=1e-10):
+        """The weights of the linear mean that maximise every problem's log-likelihood at the coefficients in force, as a
+        :class:`MeanFit` (``clr_batch_fit_mean_weights``).  The log-likelihood is exactly quadratic in the weights: with
+        ``r`` the residual at the weights in force, ``G = Phi^T K^-1 Phi`` and ``d = Phi^T K^-1 r``, the optimum is
+        ``w + G^-1 d`` -- one generalised-least-squares solve from the factor of the last materialising run, its right-hand
+        sides formed on the device from the resident basis.  No optimiser step over the weights is ever needed, and
+        ``covariance`` = ``G^-1`` and the marginal likelihood come with it.  ``min_pivot``: a problem whose scaled Gram
+        matrix has a Cholesky pivot below it (a rank-deficient basis) is refused -- status 2, its weights unchanged, NaN
+        elsewhere but in ``gram``.  ``apply=True``: :meth:`set_mean_weights` of the result (refused rows keep their
+        weights); the next evaluation's ``loglike`` is then ``MeanFit.loglike``."""
+        if not self._mean_K:
+            raise RuntimeError("no basis is set: call set_mean_basis first")
+        p = _check_min_pivot(min_pivot)
+        B, K = self.B, self._mean_K
+        w, cov, gram = np.empty((B, K)), np.empty((B, K, K)), np.empty((B, K + 1, K + 1))
+        quad, ld, st = np.empty(B), np.empty(B), np.empty(B, dtype=np.int32)
+        self._fit_mean_weights(p, w, cov, gram, quad, ld, st)
+        fit = _mean_fit(w, cov, gram, quad, ld, st, self.results()[1], self.N)
+        if apply:
+            self.set_mean_weights(w)
+        return fit
+
+    def _fit_mean_weights(self, p, w, cov, gram, quad, ld, st):
+        _check(_load().clr_batch_fit_mean_weights(self._h, p, _ptr(w), _ptr(cov), _ptr(gram), _ptr(quad), _ptr(ld),
+                                                  st.ctypes.data_as(_ip)))
+
+    def set_mean_fit_tile(self, rhs=0):
+        """Right-hand sides per tile of :meth:`fit_mean_weights` (``clr_batch_set_mean_fit_tile``); 0: automatic.  The
+        results do not depend on it."""
+        _check(_load().clr_batch_set_mean_fit_tile(self._h, int(rhs)))
+
+    def mean_fit_ms(self):
+        """``(solve_ms, gram_ms, small_ms)``: device time of the three parts of the last :meth:`fit_mean_weights`."""
+        a, b, c = C.c_double(), C.c_double(), C.c_double()
+        _check(_load().clr_batch_get_mean_fit_ms(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
 
     def mean_project_ms(self):
         """Device time of the projection pass of the last :meth:`grad_mean_weights` (its solve: :meth:`solve_device_ms`)."""
@@ -1095,6 +1183,14 @@ class ShardedBatchedGP(object):
     set_mean_basis = BatchedGP.set_mean_basis
     set_mean_weights = BatchedGP.set_mean_weights
     grad_mean_weights = BatchedGP.grad_mean_weights
+    fit_mean_weights = BatchedGP.fit_mean_weights
+    # (set_mean_fit_tile / mean_fit_ms are BatchedGP's alone: the tile and the three device times belong to one plan's
+    #  stream, and the sharded C ABI has no entry point for them -- every shard sizes its tile automatically, which no
+    #  result depends on)
+
+    def _fit_mean_weights(self, p, w, cov, gram, quad, ld, st):
+        self._ok(_load().clr_sharded_fit_mean_weights(self._h, p, _ptr(w), _ptr(cov), _ptr(gram), _ptr(quad), _ptr(ld),
+                                                      st.ctypes.data_as(_ip)))
 
     def _set_mean_basis(self, K, a, stride):
         self._ok(_load().clr_sharded_set_mean_basis(self._h, K, None if a is None else _ptr(a), stride))

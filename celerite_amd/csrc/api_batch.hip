@@ -7,6 +7,7 @@
 #include "clr_bmean_kernels.h"
 
 #include <functional>
+#include <limits>
 
 extern "C" {
 
@@ -1845,6 +1846,32 @@ static clr::SweepParams wide_sweep_params(const clr_batch* h, int nrhs, int want
   return P;
 }
 
+// the batched solve's sweeps on a wide plan: chunks per problem about two rounds of the chip's SIMDs over the batch
+// (2048 / B, at most the single solver's 1024, at least 2), chunks of at least 64 steps -- shared by clr_batch_solve,
+// clr_batch_predict_var and clr_batch_fit_mean_weights
+static clr::SweepParams wide_solve_params(const clr_batch* h, int nrhs) {
+  int want = std::min(clr::wsweep_chunks(h->N, h->J), std::max(2, 2048 / h->B));
+  if (want > (h->N - 1) / 64) want = std::max(1, (h->N - 1) / 64);
+  return wide_sweep_params(h, nrhs, want);
+}
+
+// the two sweeps of CholeskySolver::solve on `nrhs` right-hand sides per problem, row-major in `in` (problems `stride_in`
+// apart): forward into bs_x (undivided), backward into bs_rm [B][nrhs][N]; the workspace in bs_M.  The caller has
+// reserved the three for at least nrhs right-hand sides.
+static void wide_solve_sweeps(clr_batch* h, clr::SweepParams P, int nrhs, const double* in, long stride_in) {
+  P.nrhs = nrhs;
+  P.stride_out = (long)nrhs * (long)h->N;
+  P.stride_ws = (long)clr::wsweep_workspace_doubles(h->J, P.nchunk, nrhs);
+  P.in = in; P.stride_in = stride_in;
+  P.out = h->bs_x.p;
+  P.backward = 0;
+  clr::launch_wsweep_scan(P, h->bs_M.p, h->stream.get());
+  P.in = h->bs_x.p; P.stride_in = P.stride_out;
+  P.out = h->bs_rm.p;
+  P.backward = 1;
+  clr::launch_wsweep_scan(P, h->bs_M.p, h->stream.get());
+}
+
 // clr_batch_solve on a wide plan (widths 9..64): the factor lies in the reference's storage, problem after problem
 // (wide_scan_kernel, MODE 0), and the two sweeps of CholeskySolver::solve are the object API's chunked affine scans
 // (wsweep_kernels.hip: one wave per chunk, one lane per column of the chunk's map) launched ONCE for the whole batch --
@@ -1855,9 +1882,7 @@ static int wide_batch_solve(clr_batch* h, int nrhs, const double* b, double* x) 
   if ((st = require_celerite_width(h, "clr_batch_solve")) != CLR_OK) return st;
   if (!clr::wsweep_scan_supported(h->N, h->J)) return fail(CLR_UNSUPPORTED, "clr_batch_solve on a wide plan needs N >= 512 (shorter series: CholeskySolver.solve)");
   const size_t B = (size_t)h->B, N = (size_t)h->N, R = (size_t)nrhs;
-  int want = std::min(clr::wsweep_chunks(h->N, h->J), std::max(2, (int)(2048 / B)));
-  if (want > (h->N - 1) / 64) want = std::max(1, (h->N - 1) / 64);
-  clr::SweepParams P = wide_sweep_params(h, nrhs, want);
+  const clr::SweepParams P = wide_solve_params(h, nrhs);
   const size_t ws = clr::wsweep_workspace_doubles(h->J, P.nchunk, nrhs);
   if ((st = h->bs_M.reserve(B * ws)) != CLR_OK) return st;
   if ((st = h->bs_x.reserve(B * R * N)) != CLR_OK) return st;   // the forward sweep's output (undivided)
@@ -1865,17 +1890,33 @@ static int wide_batch_solve(clr_batch* h, int nrhs, const double* b, double* x) 
   ConsumerFrame frame{h};
   if (b) HIP_TRY(hipMemcpyAsync(h->bs_rm.p, b, B * R * N * sizeof(double), hipMemcpyHostToDevice, h->stream.get()));
   HIP_TRY(frame.start());
-  P.stride_ws = (long)ws;
-  P.in = b ? h->bs_rm.p : h->y.p; P.stride_in = b ? (long)(R * N) : h->y_stride;
-  P.out = h->bs_x.p;
-  P.backward = 0;
-  clr::launch_wsweep_scan(P, h->bs_M.p, h->stream.get());
-  P.in = h->bs_x.p; P.stride_in = (long)(R * N);
-  P.out = h->bs_rm.p;
-  P.backward = 1;
-  clr::launch_wsweep_scan(P, h->bs_M.p, h->stream.get());
+  wide_solve_sweeps(h, P, nrhs, b ? h->bs_rm.p : h->y.p, b ? (long)(R * N) : h->y_stride);
   HIP_TRY(frame.stop());
   return frame.finish(x, h->bs_rm.p, B * R * N);  // (x null: the result stays in bs_rm)
+}
+
+// the narrow batched solve's buffers for R right-hand sides per problem: the chunk-interleaved right-hand sides and
+// solutions, the chunk maps, the offsets and start states -- clr_batch_solve and clr_batch_fit_mean_weights
+static int reserve_narrow_solve(clr_batch* h, size_t R) {
+  const size_t B = (size_t)h->B, J = (size_t)h->J, nc = (size_t)h->nchunk;
+  int st;
+  if ((st = h->bs_x.reserve(B * R * (size_t)h->L * nc)) != CLR_OK) return st;
+  if ((st = h->bs_M.reserve(B * nc * J * J)) != CLR_OK) return st;
+  if ((st = h->bs_off.reserve(B * R * nc * J)) != CLR_OK) return st;
+  return h->bs_starts.reserve(B * R * nc * J);
+}
+
+// ... and its parameters on those buffers.  The chunk maps depend on the factor only: formed by the first solve after a
+// materialising run; they count as formed only once that solve's kernels have run to completion -- a failed launch or
+// copy must not leave the next solve reading uninitialised maps.  So this CLEARS bs_M_valid, and the caller sets it
+// again after its frame has finished.
+static clr::BSolveParams narrow_solve_begin(clr_batch* h, int nrhs) {
+  clr::BSolveParams S;
+  S.nrhs = nrhs; S.r = 0; S.lean = h->factor_is_lean ? 1 : 0;
+  S.have_M = h->bs_M_valid ? 1 : 0;
+  h->bs_M_valid = false;
+  S.xT = h->bs_x.p; S.M = h->bs_M.p; S.off = h->bs_off.p; S.starts = h->bs_starts.p;
+  return S;
 }
 
 // x == null: the result stays on the device, row-major [B][nrhs][N] in bs_rm (clr_batch_predict)
@@ -1889,23 +1930,13 @@ static int batch_solve_impl(clr_batch* h, int nrhs, const double* b, double* x) 
   if (h->nchunk < 2) return fail(CLR_UNSUPPORTED, "clr_batch_solve needs a chunked plan (N >= 128)");
   clr::BatchParams P;
   if ((st = consumer_params(h, false, P)) != CLR_OK) return st;
-  const size_t B = (size_t)h->B, N = (size_t)h->N, J = (size_t)h->J, R = (size_t)nrhs, cells = (size_t)h->L * h->nchunk;
-  if ((st = h->bs_x.reserve(B * R * cells)) != CLR_OK) return st;
+  const size_t B = (size_t)h->B, N = (size_t)h->N, R = (size_t)nrhs;
+  if ((st = reserve_narrow_solve(h, R)) != CLR_OK) return st;
   if ((st = h->bs_rm.reserve(B * R * N)) != CLR_OK) return st;
-  if ((st = h->bs_M.reserve(B * h->nchunk * J * J)) != CLR_OK) return st;
-  if ((st = h->bs_off.reserve(B * R * h->nchunk * J)) != CLR_OK) return st;
-  if ((st = h->bs_starts.reserve(B * R * h->nchunk * J)) != CLR_OK) return st;
   ConsumerFrame frame{h};
   if (b) HIP_TRY(hipMemcpyAsync(h->bs_rm.p, b, B * R * N * sizeof(double), hipMemcpyHostToDevice, h->stream.get()));
   HIP_TRY(frame.start());
-  clr::BSolveParams S;
-  S.nrhs = nrhs; S.r = 0; S.lean = h->factor_is_lean ? 1 : 0;
-  // (the chunk maps depend on the factor only: formed by the first solve after a materialising run; they count as
-  //  formed only once that solve's kernels have run to completion -- a failed launch or copy must not leave the next
-  //  solve reading uninitialised maps)
-  S.have_M = h->bs_M_valid ? 1 : 0;
-  h->bs_M_valid = false;
-  S.xT = h->bs_x.p; S.M = h->bs_M.p; S.off = h->bs_off.p; S.starts = h->bs_starts.p;
+  const clr::BSolveParams S = narrow_solve_begin(h, nrhs);
   narrow_kernels(h, nrhs, b ? h->bs_rm.p : h->y.p, b ? (long)N : h->y_stride, h->bs_x.p, h->bs_x.p,
                  [&] { h->launch->bsolve(P, S, h->stream.get()); });
   HIP_TRY(frame.stop());
@@ -2221,9 +2252,7 @@ int clr_batch_predict_var(clr_batch* h, int M, const double* xs, long xs_stride,
   if ((st = dxs.reserve(nsrc * Mm)) != CLR_OK) return st;
   if ((st = dvar.reserve(B * Mm)) != CLR_OK) return st;
   if (!h->launch) {  // wide plans
-    int want = std::min(clr::wsweep_chunks(h->N, h->J), std::max(2, (int)(2048 / B)));
-    if (want > (h->N - 1) / 64) want = std::max(1, (h->N - 1) / 64);
-    clr::SweepParams W = wide_sweep_params(h, 1, want);
+    clr::SweepParams W = wide_solve_params(h, 1);
     const size_t ws_point = clr::wsweep_workspace_doubles(h->J, W.nchunk, 2) - clr::wsweep_workspace_doubles(h->J, W.nchunk, 1);
     const int R = predict_tile(h, M, B * (2 * N + ws_point));
     const size_t ws = clr::wsweep_workspace_doubles(h->J, W.nchunk, R);
@@ -2275,6 +2304,153 @@ int clr_batch_predict_var(clr_batch* h, int M, const double* xs, long xs_stride,
   HIP_TRY(frame.stop());
   if ((st = frame.finish(var, dvar.p, B * Mm)) != CLR_OK) return st;
   h->bs_M_valid = true;
+  return CLR_OK;
+}
+
+// ---- clr_batch_fit_mean_weights: the generalised-least-squares fit of a linear mean's weights
+
+int clr_batch_set_mean_fit_tile(clr_batch* h, int rhs) {
+  h->mean_fit_tile = rhs > 0 ? rhs : 0;
+  return CLR_OK;
+}
+
+int clr_batch_get_mean_fit_ms(const clr_batch* h, double* solve_ms, double* gram_ms, double* small_ms) {
+  if (solve_ms) *solve_ms = h->fit_solve_ms;
+  if (gram_ms) *gram_ms = h->fit_gram_ms;
+  if (small_ms) *small_ms = h->fit_small_ms;
+  return CLR_OK;
+}
+
+// right-hand sides per tile: the caller's (clr_batch_set_mean_fit_tile), or the most whose buffers -- `per_rhs` doubles
+// each -- fit in predict_tile's 1 GiB; never above `most` (the K + 1 there are, or what a grid axis takes), at least 1
+static int fit_tile(const clr_batch* h, size_t most, size_t per_rhs) {
+  const size_t budget = (size_t)1 << 27;  // doubles
+  const size_t R = h->mean_fit_tile > 0 ? (size_t)h->mean_fit_tile : std::max<size_t>(1, budget / std::max<size_t>(1, per_rhs));
+  return (int)std::max<size_t>(1, std::min(R, most));
+}
+
+// For every problem of a plan with a linear mean: the weights that maximise the log-likelihood at the coefficients in
+// force, w = w0 + G^-1 d with G = Phi^T K^-1 Phi, d = Phi^T K^-1 r, r the residual at the weights w0 in force -- the
+// log-likelihood is exactly quadratic in the weights, so this one Newton step from any w0 is the optimum.  The K + 1
+// right-hand sides (Phi_0 .. Phi_K-1, r) are formed on the device from the resident basis and residual, a tile of columns
+// at a time, and solved on the factor in HBM by the batched solve's kernels (narrow plans: launch->bsolve on the
+// chunk-interleaved factor, either layout, the chunk maps under clr_batch_solve's validity rule; wide plans: the two
+// sweeps of wide_batch_solve); every tile's solutions go through the bordered Gram pass (clr_bmean_kernels.h), and one
+// thread per problem runs the small solve (clr_gram_solve.h).  The weights in force stay as they are.
+int clr_batch_fit_mean_weights(clr_batch* h, double min_pivot, double* w_hat, double* cov, double* gram, double* quad_profiled,
+                               double* logdet_gram, int* status) {
+  int st = require_device(h->device);
+  if (st != CLR_OK) return st;
+  if (!std::isfinite(min_pivot) || min_pivot < 0.0 || min_pivot >= 1.0)
+    return fail(CLR_INVALID_ARGUMENT, "clr_batch_fit_mean_weights: min_pivot is finite and in [0, 1)");
+  if (h->have_mean)
+    return fail(CLR_INVALID_ARGUMENT, "clr_batch_fit_mean_weights: a constant mean is in force (clr_batch_set_mean): the fit is "
+                                      "the linear mean's -- make the constant a basis function");
+  if (h->mean_K == 0) return fail(CLR_INVALID_ARGUMENT, "clr_batch_fit_mean_weights: no basis is set (clr_batch_set_mean_basis)");
+  if ((st = require_celerite_width(h, "clr_batch_fit_mean_weights")) != CLR_OK) return st;
+  if ((st = require_factor(h, true)) != CLR_OK) return st;
+  if (h->B > 65535) return fail(CLR_UNSUPPORTED, "clr_batch_fit_mean_weights: at most 65535 problems per plan (a grid axis): shard the batch");
+  if (!h->launch && !clr::wsweep_scan_supported(h->N, h->J))
+    return fail(CLR_UNSUPPORTED, "clr_batch_fit_mean_weights on a wide plan needs N >= 512");
+  if (h->launch && h->nchunk < 2) return fail(CLR_UNSUPPORTED, "clr_batch_fit_mean_weights needs a chunked plan (N >= 128)");
+  const size_t B = (size_t)h->B, N = (size_t)h->N, J = (size_t)h->J, K = (size_t)h->mean_K, K1 = K + 1;
+  const size_t nout = clr::gram_solve_out_doubles(h->mean_K);
+  clr::BatchParams P;  // (wide plans do not read it)
+  clr::SweepParams W;
+  int R;
+  if (h->launch) {
+    if ((st = consumer_params(h, false, P)) != CLR_OK) return st;
+    const size_t cells = (size_t)h->L * h->nchunk, nc = (size_t)h->nchunk;
+    // (rows of the relayouts ride on grid.z: B * R <= 65535; a column's buffers: its chunk-interleaved cells, its
+    //  row-major solution in bs_rm, offsets and start states)
+    R = fit_tile(h, std::min<size_t>(K1, 65535 / B), B * (cells + N + 2 * nc * J));
+    if ((st = reserve_narrow_solve(h, (size_t)R)) != CLR_OK) return st;
+  } else {
+    W = wide_solve_params(h, 1);
+    const size_t ws_rhs = clr::wsweep_workspace_doubles(h->J, W.nchunk, 2) - clr::wsweep_workspace_doubles(h->J, W.nchunk, 1);
+    R = fit_tile(h, K1, B * (2 * N + ws_rhs));
+    if ((st = h->bs_M.reserve(B * clr::wsweep_workspace_doubles(h->J, W.nchunk, R))) != CLR_OK) return st;
+    if ((st = h->bs_x.reserve(B * R * N)) != CLR_OK) return st;  // the forward sweep's output (undivided)
+  }
+  if ((st = h->bs_rm.reserve(B * R * N)) != CLR_OK) return st;  // the tile's solutions, row-major
+  if ((st = h->fit_part.reserve(clr::mean_gram_workspace(h->B, h->N, h->mean_K))) != CLR_OK) return st;
+  if ((st = h->fit_gram.reserve(B * K1 * K1)) != CLR_OK) return st;
+  if ((st = h->fit_w0.reserve(B * K)) != CLR_OK) return st;
+  if ((st = h->fit_out.reserve(B * nout)) != CLR_OK) return st;
+  if ((st = h->fit_work.reserve(clr::gram_solve_workspace(h->B, h->mean_K))) != CLR_OK) return st;
+  if ((st = h->fit_status.reserve(B)) != CLR_OK) return st;
+  const int ntile = ((int)K1 + R - 1) / R;
+  if (h->fit_ev.size() < (size_t)(2 * ntile + 3)) h->fit_ev.resize(2 * ntile + 3);
+  for (int i = 0; i < 2 * ntile + 3; ++i)
+    if (!h->fit_ev[i]) HIP_TRY(clr::create_event(h->fit_ev[i]));
+  const std::vector<double> w0 = h->host_weights;  // (the copy below is drained before this call returns)
+  std::vector<double> out(B * nout);
+  std::vector<int> solve_status(B);
+  const clr::FitRhs rhs{h->basis_dev.p, h->basis_stride, h->y.p, h->y_stride, h->mean_K, h->N};
+  {
+    ConsumerFrame frame{h};  // (untimed: the three parts have their own events)
+    hipStream_t s = h->stream.get();
+    HIP_TRY(hipMemcpyAsync(h->fit_w0.p, w0.data(), B * K * sizeof(double), hipMemcpyHostToDevice, s));
+    clr::BSolveParams S;  // (narrow plans: the chunk maps are the batched solve's, formed by the first tile unless a solve left them)
+    if (h->launch) S = narrow_solve_begin(h, R);
+    HIP_TRY(hipEventRecord(h->fit_ev[0].get(), s));
+    for (int t = 0, c0 = 0; t < ntile; ++t, c0 += R) {
+      const int nr = std::min(R, (int)K1 - c0);
+      if (h->launch) {
+        const long cells = (long)h->L * h->nchunk;
+        clr::launch_fit_rhs_interleaved(rhs, c0, nr, h->B, h->L, h->nchunk, h->bs_x.p, cells, s);
+        S.nrhs = nr;
+        h->launch->bsolve(P, S, s);
+        S.have_M = 1;
+        clr::launch_relayout_back(h->bs_x.p, cells, h->bs_rm.p, (long)h->N, h->B * nr, h->N, h->L, h->nchunk, s);
+      } else {
+        clr::launch_fit_rhs_rowmajor(rhs, c0, nr, h->B, h->bs_rm.p, s);
+        wide_solve_sweeps(h, W, nr, h->bs_rm.p, (long)nr * (long)N);
+      }
+      HIP_TRY(hipEventRecord(h->fit_ev[2 * t + 1].get(), s));
+      clr::launch_mean_gram(rhs, h->bs_rm.p, c0, nr, h->B, h->fit_part.p, s);
+      HIP_TRY(hipEventRecord(h->fit_ev[2 * t + 2].get(), s));
+    }
+    clr::launch_mean_gram_finish(h->fit_part.p, h->mean_K, h->B, h->N, h->fit_gram.p, s);
+    HIP_TRY(hipEventRecord(h->fit_ev[2 * ntile + 1].get(), s));
+    clr::launch_gram_solve(h->fit_gram.p, h->fit_w0.p, min_pivot, h->mean_K, h->B, h->fit_out.p, h->fit_status.p, h->fit_work.p, s);
+    HIP_TRY(hipEventRecord(h->fit_ev[2 * ntile + 2].get(), s));
+    HIP_TRY(hipGetLastError());
+    if (gram) HIP_TRY(hipMemcpyAsync(gram, h->fit_gram.p, B * K1 * K1 * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(solve_status.data(), h->fit_status.p, B * sizeof(int), hipMemcpyDeviceToHost, s));
+    if ((st = frame.finish(out.data(), h->fit_out.p, B * nout)) != CLR_OK) return st;
+  }
+  if (h->launch) h->bs_M_valid = true;
+  double ms_solve = 0.0, ms_gram = 0.0;
+  float ms = 0.f;
+  for (int t = 0; t < ntile; ++t) {
+    HIP_TRY(hipEventElapsedTime(&ms, h->fit_ev[2 * t].get(), h->fit_ev[2 * t + 1].get()));
+    ms_solve += ms;
+    HIP_TRY(hipEventElapsedTime(&ms, h->fit_ev[2 * t + 1].get(), h->fit_ev[2 * t + 2].get()));
+    ms_gram += ms;
+  }
+  HIP_TRY(hipEventElapsedTime(&ms, h->fit_ev[2 * ntile].get(), h->fit_ev[2 * ntile + 1].get()));
+  ms_gram += ms;
+  HIP_TRY(hipEventElapsedTime(&ms, h->fit_ev[2 * ntile + 1].get(), h->fit_ev[2 * ntile + 2].get()));
+  h->fit_solve_ms = ms_solve; h->fit_gram_ms = ms_gram; h->fit_small_ms = ms;
+  // the statuses of the evaluation in force come first: a problem without a factor (or refused by the kernel program)
+  // keeps its weights, and everything else of it is NaN
+  std::vector<int> stat(B);
+  if ((st = clr_batch_get_results(h, nullptr, nullptr, nullptr, stat.data())) != CLR_OK) return st;
+  mark_refused(h, nullptr, nullptr, nullptr, stat.data());
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  for (size_t b = 0; b < B; ++b) {
+    const double* o = out.data() + b * nout;
+    const bool evaluated = stat[b] == CLR_OK;
+    const double* w = evaluated ? o : w0.data() + b * K;  // (a refused small solve has written w0 there itself)
+    if (w_hat) std::copy(w, w + K, w_hat + b * K);
+    if (cov && evaluated) std::copy(o + K, o + K + K * K, cov + b * K * K);
+    if (cov && !evaluated) std::fill(cov + b * K * K, cov + (b + 1) * K * K, nan);
+    if (gram && !evaluated) std::fill(gram + b * K1 * K1, gram + (b + 1) * K1 * K1, nan);
+    if (quad_profiled) quad_profiled[b] = evaluated ? o[K + K * K] : nan;
+    if (logdet_gram) logdet_gram[b] = evaluated ? o[K + K * K + 1] : nan;
+    if (status) status[b] = evaluated ? solve_status[b] : stat[b];
+  }
   return CLR_OK;
 }
 

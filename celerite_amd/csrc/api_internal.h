@@ -260,6 +260,13 @@ struct clr_batch {
   DevBuf basis_dev, proj_part, proj_out;  // the basis; clr_batch_grad_mean_weights' slab partials and its result [B][K]
   clr::Event proj_ev[2];              // ... its two timing events around the projection's kernels
   double project_device_ms = 0.0;     // ... and their difference at the last call
+  // clr_batch_fit_mean_weights: the Gram pass' slab partials, the bordered Gram matrices [B][K+1][K+1], the weights in
+  // force, the small solve's results (clr_bmean_kernels.h: gram_solve_out_doubles per problem), statuses and workspace
+  DevBuf fit_part, fit_gram, fit_w0, fit_out, fit_work;
+  DevArray<int> fit_status;
+  std::vector<clr::Event> fit_ev;     // ... its timing events: one in front, two per tile of right-hand sides, two behind
+  int mean_fit_tile = 0;              // clr_batch_set_mean_fit_tile: right-hand sides per tile (0: automatic)
+  double fit_solve_ms = 0.0, fit_gram_ms = 0.0, fit_small_ms = 0.0;  // device time of the last call's three parts
   // clr_batch_set_kernel / _set_parameters: the program (host copy and in HBM), the last parameter rows with the
   // evaluation kernel's statistics block behind them, the chain rule's staging (grad | dmean | result)
   bool have_kernel = false;

@@ -1,5 +1,6 @@
 // celerite_amd/csrc/mean_kernels.hip -- the two passes of a linear mean model on batched plans (clr_bmean_kernels.h).
 #include "clr_bmean_kernels.h"
+#include "clr_gram_solve.h"
 
 #include <algorithm>
 
@@ -83,7 +84,139 @@ __global__ void __launch_bounds__(256) mean_project_finish_kernel(const double* 
   g[i] = s;
 }
 
+// ---- the generalised-least-squares fit of the weights (clr_batch_fit_mean_weights)
+
+__device__ inline const double* fit_rhs_column(const FitRhs& R, long b, int c) {
+  return c < R.K ? R.phi + b * R.phi_stride + (long)c * R.N : R.y + b * R.y_stride;
+}
+
+// relayout_kernel (api_kernels.hip) reading row z = b * nr + r from column c0 + r of problem b's right-hand sides
+__global__ void __launch_bounds__(256) fit_rhs_interleaved_kernel(FitRhs R, int c0, int nr, int L, int nchunk,
+                                                                  double* __restrict__ dst, long cells) {
+  __shared__ double tile[32][33];
+  const int row = blockIdx.z, i0 = blockIdx.x * 32, ch0 = blockIdx.y * 32;
+  const double* in = fit_rhs_column(R, row / nr, c0 + row % nr);
+  double* out = dst + (long)row * cells;
+  for (int r = threadIdx.y; r < 32; r += 8) {
+    const int c = ch0 + r, i = i0 + threadIdx.x;
+    const long n = (long)c * L + i;
+    tile[r][threadIdx.x] = (c < nchunk && i < L && n < R.N) ? in[n] : 0.0;
+  }
+  __syncthreads();
+  for (int r = threadIdx.y; r < 32; r += 8) {
+    const int i = i0 + r, c = ch0 + threadIdx.x;
+    if (i < L && c < nchunk) out[(long)i * nchunk + c] = tile[threadIdx.x][r];
+  }
+}
+
+__global__ void __launch_bounds__(256) fit_rhs_rowmajor_kernel(FitRhs R, int c0, int nr, double* __restrict__ dst) {
+  const long b = blockIdx.z;
+  const int r = blockIdx.y;
+  const double* in = fit_rhs_column(R, b, c0 + r);
+  double* out = dst + (b * nr + r) * (long)R.N;
+  for (long n = (long)blockIdx.x * 256 + threadIdx.x; n < R.N; n += (long)gridDim.x * 256) out[n] = in[n];
+}
+
+// mean_project_kernel with the K + 1 right-hand sides in the place of the basis: the workgroup (slab, column k, problem
+// b) sums R_j Z_k over its slab for j = 0 .. K (KT: the instantiation's register count, K + 1 <= KT).  partial:
+// [b][slab][k][j].
+template <int KT>
+__global__ void __launch_bounds__(256) mean_gram_kernel(FitRhs R, const double* __restrict__ z, int c0, int nr, long nslab,
+                                                        double* __restrict__ partial) {
+  __shared__ double sh[4][KT];
+  const long b = blockIdx.z, slab = blockIdx.x;
+  const int K1 = R.K + 1, k = c0 + blockIdx.y, N = R.N;
+  const double* zb = z + (b * nr + blockIdx.y) * (long)N;
+  const double* pb = R.phi + b * R.phi_stride;
+  const double* yb = R.y + b * R.y_stride;
+  double acc[KT];
+#pragma unroll
+  for (int j = 0; j < KT; ++j) acc[j] = 0.0;
+  const long n0 = slab * CLR_MEAN_SLAB + threadIdx.x;
+#pragma unroll 4
+  for (int i = 0; i < CLR_MEAN_SLAB / 256; ++i) {
+    const long n = n0 + i * 256;
+    if (n < N) {
+      const double zn = zb[n];
+#pragma unroll
+      for (int j = 0; j < KT; ++j)
+        if (j < K1) acc[j] = fma(j < R.K ? pb[(long)j * N + n] : yb[n], zn, acc[j]);
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < KT; ++j)
+    if (j < K1)
+      for (int off = 32; off > 0; off >>= 1) acc[j] += __shfl_down(acc[j], off, 64);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) {
+#pragma unroll
+    for (int j = 0; j < KT; ++j)
+      if (j < K1) sh[wave][j] = acc[j];
+  }
+  __syncthreads();
+  const int j = threadIdx.x;
+  if (j < K1) partial[((b * nslab + slab) * K1 + k) * K1 + j] = ((sh[0][j] + sh[1][j]) + sh[2][j]) + sh[3][j];
+}
+
+// one thread per (problem, j, k): S_jk and S_kj, each the slabs' partials in slab order, then their mean
+__global__ void __launch_bounds__(256) mean_gram_finish_kernel(const double* __restrict__ partial, long nslab, int K1, long total,
+                                                               double* __restrict__ gram) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const long KK = (long)K1 * K1, b = i / KK, j = (i % KK) / K1, k = i % K1;
+  const double* p = partial + b * nslab * KK;
+  double sjk = 0.0, skj = 0.0;
+  for (long c = 0; c < nslab; ++c) {
+    sjk += p[c * KK + k * K1 + j];
+    skj += p[c * KK + j * K1 + k];
+  }
+  gram[i] = 0.5 * (sjk + skj);
+}
+
+__global__ void __launch_bounds__(64) gram_solve_kernel(const double* __restrict__ gram, const double* __restrict__ w0, double min_pivot,
+                                                        int K, int B, double* __restrict__ out, int* __restrict__ status,
+                                                        double* __restrict__ work) {
+  const long b = (long)blockIdx.x * 64 + threadIdx.x;
+  if (b >= B) return;
+  const long K1 = K + 1, no = (long)K + (long)K * K + 2;
+  double* o = out + b * no;
+  status[b] = gram_solve(K, gram + b * K1 * K1, w0 + b * K, min_pivot, o, o + K, o + K + (long)K * K, o + K + (long)K * K + 1,
+                         work + b * gram_solve_work(K));
+}
+
 }  // namespace
+
+void launch_fit_rhs_interleaved(const FitRhs& R, int c0, int nr, int B, int L, int nchunk, double* dst, long cells, hipStream_t s) {
+  const dim3 grid((L + 31) / 32, (nchunk + 31) / 32, (unsigned)(B * nr));
+  hipLaunchKernelGGL(fit_rhs_interleaved_kernel, grid, dim3(32, 8), 0, s, R, c0, nr, L, nchunk, dst, cells);
+}
+
+void launch_fit_rhs_rowmajor(const FitRhs& R, int c0, int nr, int B, double* dst, hipStream_t s) {
+  const dim3 grid((unsigned)std::min((R.N + 255) / 256, 256), (unsigned)nr, (unsigned)B);
+  hipLaunchKernelGGL(fit_rhs_rowmajor_kernel, grid, dim3(256), 0, s, R, c0, nr, dst);
+}
+
+void launch_mean_gram(const FitRhs& R, const double* z, int c0, int nr, int B, double* partial, hipStream_t s) {
+  const long nslab = mean_project_slabs(R.N);
+  const dim3 grid((unsigned)nslab, (unsigned)nr, (unsigned)B), block(256);
+  const int K1 = R.K + 1;
+  if (K1 <= 4) hipLaunchKernelGGL(mean_gram_kernel<4>, grid, block, 0, s, R, z, c0, nr, nslab, partial);
+  else if (K1 <= 8) hipLaunchKernelGGL(mean_gram_kernel<8>, grid, block, 0, s, R, z, c0, nr, nslab, partial);
+  else hipLaunchKernelGGL(mean_gram_kernel<CLR_MAX_MEAN_RHS>, grid, block, 0, s, R, z, c0, nr, nslab, partial);
+}
+
+void launch_mean_gram_finish(const double* partial, int K, int B, int N, double* gram, hipStream_t s) {
+  const long K1 = K + 1, total = (long)B * K1 * K1;
+  hipLaunchKernelGGL(mean_gram_finish_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, partial,
+                     mean_project_slabs(N), (int)K1, total, gram);
+}
+
+size_t gram_solve_workspace(int B, int K) { return (size_t)B * (size_t)gram_solve_work(K); }
+
+void launch_gram_solve(const double* gram, const double* w0, double min_pivot, int K, int B, double* out, int* status,
+                       double* work, hipStream_t s) {
+  hipLaunchKernelGGL(gram_solve_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, gram, w0, min_pivot, K, B, out, status, work);
+}
 
 void launch_linear_residual(const double* y, long y_stride, const double* phi, long phi_stride, const double* w, int K,
                             int nout, int N, double* r, hipStream_t s) {

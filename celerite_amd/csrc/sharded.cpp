@@ -567,6 +567,17 @@ int clr_sharded_grad_mean_weights(clr_sharded* h, double* dw, int* status) {
   });
 }
 
+// clr_batch_fit_mean_weights, every shard on its slice (a problem's fit does not depend on the sharding)
+int clr_sharded_fit_mean_weights(clr_sharded* h, double min_pivot, double* w_hat, double* cov, double* gram,
+                                 double* quad_profiled, double* logdet_gram, int* status) {
+  const long K = h->mean_K, K1 = K + 1;
+  g_sharded_error = "clr_sharded_fit_mean_weights: a basis must be set (clr_sharded_set_mean_basis), min_pivot finite and in [0, 1)";
+  return on_slices(h, K > 0 && std::isfinite(min_pivot) && min_pivot >= 0.0 && min_pivot < 1.0, [=](clr_batch* p, long lo) {
+    return clr_batch_fit_mean_weights(p, min_pivot, at(w_hat, lo * K), at(cov, lo * K * K), at(gram, lo * K1 * K1),
+                                      at(quad_profiled, lo), at(logdet_gram, lo), at(status, lo));
+  });
+}
+
 /* ---- coefficients from kernel parameters: clr_batch_set_kernel / _evaluate_params / _grad_params over the shards ---- */
 int clr_sharded_set_kernel(clr_sharded* h, const clr_kernel* k) {
   const int st = resolve_all(h);

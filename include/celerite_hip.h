@@ -512,6 +512,43 @@ int clr_batch_set_mean_basis(clr_batch* h, int K, const double* phi, long phi_st
 int clr_batch_set_mean_weights(clr_batch* h, const double* w);
 int clr_batch_grad_mean_weights(clr_batch* h, double* dw, int* status);
 int clr_batch_get_mean_project_ms(const clr_batch* h, double* device_ms);
+/* clr_batch_fit_mean_weights -- the weights that MAXIMISE the log-likelihood of every problem at the coefficients in
+ * force.  The log-likelihood is exactly quadratic in the weights, so they need no optimiser: with r = y - Phi w0 the
+ * residual at the weights w0 in force,
+ *     G = Phi^T K^-1 Phi ,  d = Phi^T K^-1 r ,  w_hat = w0 + G^-1 d ,  cov(w_hat) = G^-1 ,
+ *     quad_profiled = r^T K^-1 r - d^T G^-1 d     (the quadratic form at w_hat),
+ * one generalised-least-squares solve from the factor of the last materialising run (CLR_NOT_COMPUTED without one, as
+ * clr_batch_solve; new weights or a new y need no new run).  The K + 1 right-hand sides (Phi_0 .. Phi_K-1, r) are formed on
+ * the device from the resident basis and residual -- nothing is uploaded but the B x K weights in force -- and solved by
+ * the batched solve's kernels a tile of columns at a time (clr_batch_set_mean_fit_tile: right-hand sides per tile, 0 =
+ * as many as fit 1 GiB of buffers; no result depends on it); a Gram pass over fixed slabs of 4096 samples, partials
+ * added in order, no atomics, forms the bordered matrix [[G, d], [d^T, q]] with its symmetric part stored; one thread per
+ * problem then scales G to unit diagonal, factors it by an unpivoted Cholesky and solves.  A problem's bits depend on
+ * neither the batch size, the tile, a sharding nor the run.
+ *   w_hat host [B][K], cov [B][K][K], gram [B][K+1][K+1] (the bordered matrix), quad_profiled [B], logdet_gram [B]
+ *   (log det G), status [B]; any of them may be NULL.  min_pivot: finite, in [0, 1).
+ * Per problem: when the status of the evaluation in force is not CLR_OK (no factor, or a draw the kernel program refused)
+ * the problem reports that status, w_hat is the weights in force and every other output of it is NaN.  When a diagonal
+ * entry of G is not positive, or a pivot of the scaled G is not positive or lies below min_pivot (a rank-deficient
+ * basis), the status is CLR_NOT_POSITIVE_DEFINITE, w_hat is the weights in force, cov, quad_profiled and logdet_gram are
+ * NaN, and gram is still returned.  No problem's refusal changes another's bits.
+ * With a flat prior on the weights the marginal log-likelihood follows on the host:
+ *     loglike_profiled = -1/2 (quad_profiled + log det K + N log 2 pi) ,
+ *     loglike_marginal = loglike_profiled - 1/2 log det G + 1/2 K log 2 pi .
+ * The weights in force are NOT changed (clr_batch_set_mean_weights(w_hat) applies them).  CLR_INVALID_ARGUMENT, the plan
+ * unchanged: no basis set, a constant mean in force, min_pivot out of range.  CLR_UNSUPPORTED: what clr_batch_solve
+ * refuses (general terms, widths above 64, unchunked plans), or more than 65535 problems in the plan (a grid axis).
+ * clr_batch_get_mean_fit_ms: the device time of the last call's solves, Gram pass (with its finish) and small solve.
+ *
+ * clr_gram_solve -- the small solve alone, on the host (no GPU): the routine the device runs per problem, the same bits.
+ * gram_bordered [nprob][K+1][K+1], w0 [nprob][K] (NULL: zeros); outputs as above, any may be NULL; 1 <= K <=
+ * CLR_MAX_MEAN_BASIS.  Returns CLR_INVALID_ARGUMENT for a bad K or min_pivot; refusals are per problem, in status. */
+int clr_batch_fit_mean_weights(clr_batch* h, double min_pivot, double* w_hat, double* cov, double* gram,
+                               double* quad_profiled, double* logdet_gram, int* status);
+int clr_batch_set_mean_fit_tile(clr_batch* h, int rhs);
+int clr_batch_get_mean_fit_ms(const clr_batch* h, double* solve_ms, double* gram_ms, double* small_ms);
+int clr_gram_solve(int nprob, int K, const double* gram_bordered, const double* w0, double min_pivot, double* w_hat,
+                   double* cov, double* quad_profiled, double* logdet_gram, int* status);
 /* CholeskySolver::solve (cholesky.h:218-318) for every problem of the plan at once: x = K_p^-1 b_p from the factor of
  * the last materialising run (clr_batch_enqueue(h, 1); either factor layout), parallel in n -- forward substitution,
  * division by D and backward substitution as two chunked affine scans whose chunk maps are formed once and shared by
@@ -810,6 +847,9 @@ int clr_sharded_grad_mean(clr_sharded* h, double* value, double* grad, double* d
 int clr_sharded_set_mean_basis(clr_sharded* h, int K, const double* phi, long phi_stride);
 int clr_sharded_set_mean_weights(clr_sharded* h, const double* w);
 int clr_sharded_grad_mean_weights(clr_sharded* h, double* dw, int* status);
+/* clr_batch_fit_mean_weights over the whole batch: every shard fits its slice; the same bits as the unsharded plan */
+int clr_sharded_fit_mean_weights(clr_sharded* h, double min_pivot, double* w_hat, double* cov, double* gram,
+                                 double* quad_profiled, double* logdet_gram, int* status);
 /* clr_batch_set_kernel / _evaluate_params / _grad_params / _get_coefficients over the whole batch: every shard forms the
  * coefficients of its slice of params[B][n_params] on its own device; the selection bounds are taken over the batch. */
 int clr_sharded_set_kernel(clr_sharded* h, const clr_kernel* kernel);
