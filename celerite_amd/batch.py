@@ -118,6 +118,9 @@ def _load():
     lib.clr_sharded_fit_mean_weights.argtypes = [C.c_void_p, C.c_double] + [_dp] * 5 + [_ip]
     lib.clr_batch_set_mean_fit_tile.argtypes = [C.c_void_p, C.c_int]
     lib.clr_batch_get_mean_fit_ms.argtypes = [C.c_void_p, _dp, _dp, _dp]
+    lib.clr_batch_leave_one_out.argtypes = [C.c_void_p, _dp, _dp, _dp, _ip]
+    lib.clr_sharded_leave_one_out.argtypes = [C.c_void_p, _dp, _dp, _dp, _ip]
+    lib.clr_batch_get_leave_one_out_ms.argtypes = [C.c_void_p, _dp, _dp, _dp]
     lib.clr_gram_solve.argtypes = [C.c_int, C.c_int, _dp, _dp, C.c_double] + [_dp] * 4 + [_ip]
     lib.clr_kernel_create.argtypes = [C.c_int, _ip, C.c_int, _dp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
     lib.clr_kernel_destroy.argtypes = [C.c_void_p]
@@ -315,6 +318,50 @@ def _mean_fit(w_hat, cov, gram, quad, ld_gram, status, logdet_K, N):
     log2pi = np.log(2.0 * np.pi)
     ll = -0.5 * (quad + logdet_K + N * log2pi)
     return MeanFit(w_hat, cov, gram, quad, ld_gram, ll, ll - 0.5 * ld_gram + 0.5 * K * log2pi, status)
+
+
+LeaveOneOut = collections.namedtuple("LeaveOneOut", ["residual", "variance", "logpdf", "kinv_diag", "alpha", "status"])
+LeaveOneOut.__doc__ = """The leave-one-out predictive distribution of every sample (``leave_one_out``): ``residual[B, N]`` =
+``y_n - mu_-n`` = ``alpha_n / c_n``, ``variance[B, N]`` = ``sigma^2_-n`` = ``1 / c_n``, ``logpdf[B]`` = ``sum_n log p(y_n |
+y_-n)``, ``kinv_diag[B, N]`` = ``c`` = ``diag(K^-1)``, ``alpha[B, N]`` = ``K^-1 r`` and ``status[B]``."""
+
+
+def _loo_args(c, alpha, logpdf, st):
+    """The four output pointers of ``clr_*_leave_one_out``: ``None`` stays a null pointer (not asked for)."""
+    return [None if a is None else _ptr(a) for a in (c, alpha, logpdf)] + [None if st is None else st.ctypes.data_as(_ip)]
+
+
+def leave_one_out_from(kinv_diag, alpha):
+    """``(residual, variance, logpdf)`` of the leave-one-out predictive distribution from ``c = diag(K^-1)`` and
+    ``alpha = K^-1 r``, both ``(N,)`` or ``(B, N)`` (no GPU):
+
+        ``residual_n = y_n - mu_-n = alpha_n / c_n``, ``variance_n = sigma^2_-n = 1 / c_n``,
+        ``logpdf = sum_n -1/2 log(2 pi / c_n) - 1/2 alpha_n^2 / c_n``.
+
+    The sum runs in the order of the device's reduction (``clr_batch_leave_one_out``): 256 partial sums over the samples
+    ``i, i + 256, ...`` in order, then a tree over the 256 -- host and device agree to the rounding of ``log``."""
+    c = np.asarray(kinv_diag, dtype=np.float64)
+    a = np.asarray(alpha, dtype=np.float64)
+    if c.shape != a.shape or c.ndim not in (1, 2) or c.shape[-1] < 1:
+        raise ValueError("dimension mismatch")
+    single = c.ndim == 1
+    c2, a2 = np.atleast_2d(c), np.atleast_2d(a)
+    B, N = c2.shape
+    terms = -0.5 * np.log(6.283185307179586 / c2) - 0.5 * a2 * a2 / c2
+    rows = (N + 255) // 256
+    padded = np.zeros((B, rows * 256))
+    padded[:, :N] = terms
+    padded = padded.reshape(B, rows, 256)
+    part = np.zeros((B, 256))
+    for r in range(rows):
+        part = part + padded[:, r, :]
+    w = 128
+    while w > 0:
+        part[:, :w] = part[:, :w] + part[:, w:2 * w]
+        w >>= 1
+    logpdf = part[:, 0].copy()
+    residual, variance = a / c, 1.0 / c
+    return (residual, variance, logpdf[0]) if single else (residual, variance, logpdf)
 
 
 def _exclusive_means(mean, mean_weights):
@@ -726,6 +773,47 @@ class BatchedGP(object):
         lib = _load()
         lib.clr_batch_set_predict_tile.argtypes = [C.c_void_p, C.c_int]
         _check(lib.clr_batch_set_predict_tile(self._h, int(points)))
+
+    def inverse_diagonal(self):
+        """``diag(K_p^-1)`` of every problem, ``(B, N)``, from the factor of the last materialising run
+        (``clr_batch_leave_one_out``): all N entries by one backward matrix recurrence, O(N J^2) per problem.  With
+        ``c = diag(K^-1)``, ``alpha = K^-1 r`` (:meth:`solve`) and ``s_n = diag_n + jitter`` the in-sample answer of
+        ``GP.predict(y)`` (celerite.py:270-272) is ``mu_n = y_n - s_n alpha_n``, ``var_n = s_n - s_n^2 c_n`` -- no O(N^2)
+        work.  Rows of problems whose status is not 0 are NaN."""
+        c = np.empty((self.B, self.N))
+        self._leave_one_out(c, None, None, None)
+        return c
+
+    def leave_one_out(self, arrays=True):
+        """The leave-one-out predictive distribution of every sample of every problem, a :class:`LeaveOneOut`
+        (``clr_batch_leave_one_out``), from the factor of the last materialising run.  With ``c_n = (K^-1)_nn`` and
+        ``alpha = K^-1 r``, ``r = y`` less the mean in force (:meth:`set_mean`, :meth:`set_mean_weights`):
+
+            ``residual_n = y_n - mu_-n = alpha_n / c_n``, ``variance_n = sigma^2_-n = 1 / c_n``,
+            ``log p(y_n | y_-n) = -1/2 log(2 pi / c_n) - 1/2 alpha_n^2 / c_n``, ``logpdf = `` their sum over n
+
+        (``residual`` and ``variance`` are formed on the host from the two downloaded arrays; see
+        :func:`leave_one_out_from`).  The in-sample ``GP.predict(y)`` (celerite.py:270-272) follows without O(N^2) work:
+        ``mu_n = y_n - s_n alpha_n``, ``var_n = s_n - s_n^2 c_n`` with ``s_n = diag_n + jitter``.
+        ``arrays=False`` downloads ``logpdf[B]`` and ``status[B]`` only -- the step of a leave-one-out cross-validation
+        model comparison; the array fields are then ``None``.  Rows of problems whose status is not 0 are NaN."""
+        logpdf, st = np.empty(self.B), np.empty(self.B, dtype=np.int32)
+        if not arrays:
+            self._leave_one_out(None, None, logpdf, st)
+            return LeaveOneOut(None, None, logpdf, None, None, st)
+        c, alpha = np.empty((self.B, self.N)), np.empty((self.B, self.N))
+        self._leave_one_out(c, alpha, logpdf, st)
+        return LeaveOneOut(alpha / c, 1.0 / c, logpdf, c, alpha, st)
+
+    def _leave_one_out(self, c, alpha, logpdf, st):
+        _check(_load().clr_batch_leave_one_out(self._h, *_loo_args(c, alpha, logpdf, st)))
+
+    def leave_one_out_ms(self):
+        """``(diag_ms, solve_ms, reduce_ms)``: device time of the three parts of the last :meth:`leave_one_out` or
+        :meth:`inverse_diagonal` (a part that did not run: 0)."""
+        a, b, c = C.c_double(), C.c_double(), C.c_double()
+        _check(_load().clr_batch_get_leave_one_out_ms(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
 
     def dot_L(self, z):
         """``L_p z_p`` with ``K_p = L_p L_p^T`` for every problem from the factor of the last materialising run
@@ -1364,6 +1452,12 @@ class ShardedBatchedGP(object):
         var = np.empty((self.B, M))
         self._ok(lib.clr_sharded_predict_var(self._h, int(M), _ptr(xs), stride, _ptr(var)))
         return pred, var
+
+    inverse_diagonal = BatchedGP.inverse_diagonal
+    leave_one_out = BatchedGP.leave_one_out
+
+    def _leave_one_out(self, c, alpha, logpdf, st):
+        self._ok(_load().clr_sharded_leave_one_out(self._h, *_loo_args(c, alpha, logpdf, st)))
 
     def run_timed(self, steps):
         """``steps`` evaluations on every shard concurrently; per-shard HIP-event ms."""

@@ -2307,6 +2307,189 @@ int clr_batch_predict_var(clr_batch* h, int M, const double* xs, long xs_stride,
   return CLR_OK;
 }
 
+// ---- clr_batch_leave_one_out: diag(K^-1), K^-1 r and the leave-one-out log predictive density of every problem
+
+// widths 9..64: diag(K^-1) of one problem per wave from the factor in the reference's storage, sequential in n (the
+// recurrence of clr_binvdiag_kernels.h: Q_n = P - u v^T - v u^T + c_n u u^T, c_n = 1 / D_n + g^T Q_{n+1} g).  Lane k holds
+// column k of Q (JP doubles, the width padded with zeros); (Q g)_k is lane-local by symmetry, s one wave reduction; the
+// steps' phi, g = phi o W and u are staged through LDS a tile of TILE samples at a time, v per step.
+extern "C++" {
+template <int JP>
+__global__ void __launch_bounds__(64) wide_invdiag_kernel(const double* __restrict__ phi, const double* __restrict__ u,
+                                                          const double* __restrict__ W, const double* __restrict__ D, int N, int J,
+                                                          double* __restrict__ out) {
+  constexpr int TILE = 16;
+  __shared__ double s_phi[TILE][JP], s_g[TILE][JP], s_u[TILE][JP], s_v[2][JP], s_d[TILE];
+  const long b = blockIdx.x;
+  const int lane = threadIdx.x;
+  const bool live = lane < JP;
+  const int k = live ? lane : 0;
+  const double *php = phi + b * (long)J * (N - 1), *up = u + b * (long)J * (N - 1), *Wp = W + b * (long)J * N, *Dp = D + b * (long)N;
+  double* op = out + b * (long)N;
+  double Q[JP];
+#pragma unroll
+  for (int j = 0; j < JP; ++j) Q[j] = 0.0;
+  for (int hi = N; hi > 0; hi -= TILE) {
+    const int lo = hi > TILE ? hi - TILE : 0, cnt = hi - lo;
+    __syncthreads();  // (the previous tile has been read)
+    for (int e = lane; e < cnt * JP; e += 64) {
+      const int i = e / JP, j = e % JP, n = lo + i;
+      double ph = 0.0, ww = 0.0, uu = 0.0;
+      if (j < J) {
+        ww = Wp[(long)n * J + j];
+        if (n < N - 1) ph = php[(long)n * J + j];   // (the last sample's transition is 0)
+        if (n >= 1) uu = up[(long)(n - 1) * J + j];  // (u_(:, n-1) = U~(t_n); U~(t_0) enters no entry)
+      }
+      s_phi[i][j] = ph; s_g[i][j] = ph * ww; s_u[i][j] = uu;
+    }
+    if (lane < cnt) s_d[lane] = Dp[lo + lane];
+    __syncthreads();
+    for (int i = cnt - 1; i >= 0; --i) {
+      double qg = 0.0;
+#pragma unroll
+      for (int j = 0; j < JP; ++j) qg = fma(Q[j], s_g[i][j], qg);
+      const double phk = s_phi[i][k], uk = s_u[i][k];
+      double s = live ? s_g[i][k] * qg : 0.0;
+      const double vk = phk * qg;
+      if (live) s_v[i & 1][k] = vk;
+#pragma unroll
+      for (int w = 32; w > 0; w >>= 1) s += __shfl_xor(s, w, 64);
+      const double cn = 1.0 / s_d[i] + s;
+      if (lane == 0) op[lo + i] = cn;
+      __syncthreads();
+      {
+#pragma clang fp contract(off)  // (entries (j, k) and (k, j) round alike: Q stays symmetric to the bit)
+#pragma unroll
+        for (int j = 0; j < JP; ++j) {
+          const double pj = s_phi[i][j], uj = s_u[i][j], vj = s_v[i & 1][j];
+          Q[j] = (pj * phk) * Q[j] - (uj * vk + vj * uk) + cn * (uj * uk);
+        }
+      }
+    }
+  }
+}
+}  // extern "C++"
+
+// sum_n -1/2 log(2 pi / c_n) - 1/2 alpha_n^2 / c_n of one problem per workgroup in a fixed order -- thread i sums the
+// samples i, i + 256, ... in order, then a fixed tree over the 256 threads (batch.leave_one_out_from does the same on the host)
+__global__ void __launch_bounds__(256) loo_reduce_kernel(const double* __restrict__ c, const double* __restrict__ alpha, int N,
+                                                         double* __restrict__ out) {
+#pragma clang fp contract(off)
+  __shared__ double sh[256];
+  const long b = blockIdx.x;
+  const double *cp = c + b * N, *ap = alpha + b * N;
+  double s = 0.0;
+  for (int n = threadIdx.x; n < N; n += 256) {
+    const double cn = cp[n], an = ap[n];
+    s += -0.5 * log(6.283185307179586 / cn) - 0.5 * an * an / cn;
+  }
+  sh[threadIdx.x] = s;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[b] = sh[0];
+}
+
+int clr_batch_get_leave_one_out_ms(const clr_batch* h, double* diag_ms, double* solve_ms, double* reduce_ms) {
+  if (diag_ms) *diag_ms = h->loo_diag_ms;
+  if (solve_ms) *solve_ms = h->loo_solve_ms;
+  if (reduce_ms) *reduce_ms = h->loo_reduce_ms;
+  return CLR_OK;
+}
+
+// c = diag(K^-1), alpha = K^-1 r and sum_n log p(y_n | y_-n) = sum_n -1/2 log(2 pi / c_n) - 1/2 alpha_n^2 / c_n for every
+// problem from the factor of the last materialising run.  c: narrow plans, the backward matrix recurrence of
+// clr_binvdiag_kernels.h on the chunk-interleaved factor (either layout), the chunk maps shared with clr_batch_solve under
+// its validity rule; wide plans (widths 9..64), one wave per problem, sequential in n (wide_invdiag_kernel).  alpha: the
+// batched solve of the residual in force, left row-major in bs_rm.  The sum: one workgroup per problem, no atomics.
+int clr_batch_leave_one_out(clr_batch* h, double* kinv_diag, double* alpha, double* loo_logpdf, int* status) {
+  int st = require_device(h->device);
+  if (st != CLR_OK) return st;
+  if (!kinv_diag && !alpha && !loo_logpdf && !status)
+    return fail(CLR_INVALID_ARGUMENT, "clr_batch_leave_one_out: at least one output array");
+  if ((st = require_celerite_width(h, "clr_batch_leave_one_out")) != CLR_OK) return st;
+  if ((st = require_factor(h, true)) != CLR_OK) return st;
+  if (!h->launch && !clr::wsweep_scan_supported(h->N, h->J))
+    return fail(CLR_UNSUPPORTED, "clr_batch_leave_one_out on a wide plan needs N >= 512");
+  if (h->launch && h->nchunk < 2) return fail(CLR_UNSUPPORTED, "clr_batch_leave_one_out needs a chunked plan (N >= 128)");
+  const size_t B = (size_t)h->B, N = (size_t)h->N, J = (size_t)h->J;
+  const bool need_c = kinv_diag || loo_logpdf, need_alpha = alpha || loo_logpdf;
+  for (clr::Event& e : h->loo_ev)
+    if (!e) HIP_TRY(clr::create_event(e));
+  h->loo_diag_ms = h->loo_solve_ms = h->loo_reduce_ms = 0.0;
+  float ms = 0.f;
+  if (need_c) {
+    if ((st = h->loo_c.reserve(B * N)) != CLR_OK) return st;
+    clr::BatchParams P;
+    if (h->launch) {
+      if ((st = consumer_params(h, false, P)) != CLR_OK) return st;
+      const size_t nc = (size_t)h->nchunk;
+      if ((st = h->bs_x.reserve(B * (size_t)h->L * nc)) != CLR_OK) return st;
+      if ((st = h->bs_M.reserve(B * nc * J * J)) != CLR_OK) return st;
+      if ((st = h->bs_off.reserve(B * nc * J)) != CLR_OK) return st;
+      if ((st = h->loo_Q.reserve(B * nc * (J * (J + 1) / 2))) != CLR_OK) return st;
+    }
+    ConsumerFrame frame{h};  // (untimed: the parts have their own events)
+    hipStream_t s = h->stream.get();
+    HIP_TRY(hipEventRecord(h->loo_ev[0].get(), s));
+    if (h->launch) {
+      clr::BInvDiagParams S;
+      S.lean = h->factor_is_lean ? 1 : 0;
+      // (the chunk maps are the batched solve's, under its validity rule: formed here unless a solve has formed them, and
+      //  counted as formed only once this call's kernels have run to completion)
+      S.have_M = h->bs_M_valid ? 1 : 0;
+      h->bs_M_valid = false;
+      S.cT = h->bs_x.p; S.M = h->bs_M.p; S.Q = h->loo_Q.p; S.off = h->bs_off.p;
+      h->launch->binvdiag(P, S, s);
+      clr::launch_relayout_back(h->bs_x.p, (long)h->L * h->nchunk, h->loo_c.p, (long)N, h->B, h->N, h->L, h->nchunk, s);
+    } else {
+      const int JP = clr::wide_padded_width(h->J);
+#define CLR_GO(WIDTH) hipLaunchKernelGGL((wide_invdiag_kernel<WIDTH>), dim3((unsigned)B), dim3(64), 0, s, h->phi.p, h->u.p, h->W.p, h->D.p, h->N, h->J, h->loo_c.p)
+      if (JP == 16) CLR_GO(16); else if (JP == 32) CLR_GO(32); else CLR_GO(64);
+#undef CLR_GO
+    }
+    HIP_TRY(hipEventRecord(h->loo_ev[1].get(), s));
+    if ((st = frame.finish(kinv_diag, h->loo_c.p, B * N)) != CLR_OK) return st;
+    if (h->launch) h->bs_M_valid = true;
+    HIP_TRY(hipEventElapsedTime(&ms, h->loo_ev[0].get(), h->loo_ev[1].get()));
+    h->loo_diag_ms = ms;
+  }
+  if (need_alpha) {
+    if ((st = batch_solve_impl(h, 1, nullptr, nullptr)) != CLR_OK) return st;  // alpha = K^-1 r -> bs_rm [B][N]
+    h->loo_solve_ms = h->solve_device_ms;
+    if (loo_logpdf && (st = h->loo_out.reserve(B)) != CLR_OK) return st;
+    ConsumerFrame frame{h};  // (untimed)
+    hipStream_t s = h->stream.get();
+    if (loo_logpdf) {
+      HIP_TRY(hipEventRecord(h->loo_ev[2].get(), s));
+      hipLaunchKernelGGL(loo_reduce_kernel, dim3((unsigned)B), dim3(256), 0, s, h->loo_c.p, h->bs_rm.p, h->N, h->loo_out.p);
+      HIP_TRY(hipEventRecord(h->loo_ev[3].get(), s));
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipMemcpyAsync(loo_logpdf, h->loo_out.p, B * sizeof(double), hipMemcpyDeviceToHost, s));
+    }
+    if ((st = frame.finish(alpha, h->bs_rm.p, B * N)) != CLR_OK) return st;
+    if (loo_logpdf) {
+      HIP_TRY(hipEventElapsedTime(&ms, h->loo_ev[2].get(), h->loo_ev[3].get()));
+      h->loo_reduce_ms = ms;
+    }
+  }
+  // the statuses of the evaluation in force; a problem without a factor (or refused by the kernel program): NaN everywhere
+  std::vector<int> stat(B);
+  if ((st = clr_batch_get_results(h, nullptr, nullptr, nullptr, stat.data())) != CLR_OK) return st;
+  mark_refused(h, nullptr, nullptr, nullptr, stat.data());
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  for (size_t b = 0; b < B; ++b) {
+    if (stat[b] == CLR_OK) continue;
+    if (kinv_diag) std::fill(kinv_diag + b * N, kinv_diag + (b + 1) * N, nan);
+    if (alpha) std::fill(alpha + b * N, alpha + (b + 1) * N, nan);
+    if (loo_logpdf) loo_logpdf[b] = nan;
+  }
+  if (status) std::copy(stat.begin(), stat.end(), status);
+  return CLR_OK;
+}
+
 // ---- clr_batch_fit_mean_weights: the generalised-least-squares fit of a linear mean's weights
 
 int clr_batch_set_mean_fit_tile(clr_batch* h, int rhs) {

@@ -355,6 +355,12 @@ struct clr_batch {
   DevBuf bs_rm, bs_x, bs_M, bs_off, bs_starts;  // clr_batch_solve: right-hand sides row-major / chunk-interleaved, chunk maps, offsets, start states
   bool bs_M_valid = false;                      // bs_M holds the chunk maps of the factor in HBM (they depend on the factor only)
   double solve_device_ms = 0.0;                 // device time of the last clr_batch_solve (HIP events around its kernels)
+  // clr_batch_leave_one_out: diag(K^-1) row-major [B][N], the chunks' offsets / start matrices of its recurrence
+  // [B][nchunk][J (J + 1) / 2] (narrow plans), the log predictive densities [B]; timing events around the diagonal's
+  // kernels and the reduction, and the device time of the last call's three parts
+  DevBuf loo_c, loo_Q, loo_out;
+  clr::Event loo_ev[4];
+  double loo_diag_ms = 0.0, loo_solve_ms = 0.0, loo_reduce_ms = 0.0;
   int predict_tile = 0;                         // clr_batch_set_predict_tile: prediction points per tile of clr_batch_predict_var (0: automatic)
   clr::Event bs_ev[2];                          // ... its two timing events, created by the first solve, kept for the plan's life
   int factor_layout = 0;      // clr_batch_set_factor_layout: 0 the reference's four arrays, 1 lean (W, D; phi, u regenerated)

@@ -1007,6 +1007,7 @@ __global__ void __launch_bounds__(64) warm_check_kernel(const BatchParams P) {
 #include "clr_bdotl_kernels.h"
 #include "clr_bdot_kernels.h"
 #include "clr_bpredvar_kernels.h"
+#include "clr_binvdiag_kernels.h"
 namespace clr {
 
 // One table entry per (JR, JC): host-callable launchers.
@@ -1031,6 +1032,8 @@ struct BatchLaunchers {
   // k(0) - k*^T K^-1 k* for all problems at one tile of prediction points from the materialised factor
   // (clr_bpredvar_kernels.h): S.xs -> S.var
   void (*bpredvar)(const BatchParams&, BPredVarParams S, hipStream_t);
+  // diag(K^-1) for all problems from the materialised factor (clr_binvdiag_kernels.h): -> S.cT
+  void (*binvdiag)(const BatchParams&, BInvDiagParams S, hipStream_t);
   // lean factor of problem b (replay mode 3) -> the reference's storage, phi and u regenerated (t: the problem's row-major times)
   void (*expand)(const BatchParams&, int b, const double* t, double* phi, double* u, double* W, double* D, hipStream_t);
   int elem_doubles, start_doubles;
@@ -1183,6 +1186,25 @@ struct BatchImpl {
     if (S.lean) { if (P.fast_trig) bpredvar_go<true, true>(P, S, s); else bpredvar_go<true, false>(P, S, s); }
     else bpredvar_go<false, true>(P, S, s);  // (the stored phi, u: no trigonometry)
   }
+  // diag(K^-1): the chunk maps by the solve's own summarize unless they are formed, the chunks' offsets, the walk, the
+  // recurrence from the start matrices
+  template <bool LEAN, bool FAST>
+  static void binvdiag_go(const BatchParams& P, const BInvDiagParams& S, hipStream_t s) {
+    const dim3 grid((P.nchunk + 63) / 64, P.B);
+    if (!S.have_M) {  // (the right-hand side it reads beside is whatever cT holds: its offsets go to S.off and are not used)
+      BSolveParams Q;
+      Q.nrhs = 1; Q.r = 0; Q.lean = S.lean; Q.have_M = 0;
+      Q.xT = S.cT; Q.M = S.M; Q.off = S.off; Q.starts = nullptr;
+      hipLaunchKernelGGL((bsolve_summarize_kernel<JR, JC, LEAN, FAST, true>), grid, dim3(64), 0, s, P, Q);
+    }
+    hipLaunchKernelGGL((binvdiag_kernel<JR, JC, LEAN, FAST, false>), grid, dim3(64), 0, s, P, S);
+    hipLaunchKernelGGL((binvdiag_walk_kernel<JR + 2 * JC>), dim3((P.B + 63) / 64), dim3(64), 0, s, P, S);
+    hipLaunchKernelGGL((binvdiag_kernel<JR, JC, LEAN, FAST, true>), grid, dim3(64), 0, s, P, S);
+  }
+  static void binvdiag(const BatchParams& P, BInvDiagParams S, hipStream_t s) {
+    if (S.lean) { if (P.fast_trig) binvdiag_go<true, true>(P, S, s); else binvdiag_go<true, false>(P, S, s); }
+    else binvdiag_go<false, true>(P, S, s);  // (the stored phi, u: no trigonometry)
+  }
   static void compose_check(const BatchParams& P, int g, double* coop, double* ref, hipStream_t s) {
     constexpr int J = JR + 2 * JC;
     const int np = (P.nchunk + g - 1) / g;
@@ -1235,7 +1257,7 @@ struct BatchImpl {
   }
   static BatchLaunchers table() {
     return BatchLaunchers{&summarize, &prefix, &correct, &replay, &sequential, &compose_check, &warm, &grad, &grad_reverse,
-                          &bsolve, &bdotl, &bdot, &bpredvar, &expand, Widths<JR, JC>::ELEM, Widths<JR, JC>::START};
+                          &bsolve, &bdotl, &bdot, &bpredvar, &binvdiag, &expand, Widths<JR, JC>::ELEM, Widths<JR, JC>::START};
   }
 };
 

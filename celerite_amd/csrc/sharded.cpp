@@ -670,6 +670,13 @@ int clr_sharded_predict_var(clr_sharded* h, int M, const double* xs, long xs_str
   });
 }
 
+int clr_sharded_leave_one_out(clr_sharded* h, double* kinv_diag, double* alpha, double* loo_logpdf, int* status) {
+  const long N = h->N;
+  return on_slices(h, kinv_diag || alpha || loo_logpdf || status, [=](clr_batch* p, long lo) {
+    return clr_batch_leave_one_out(p, at(kinv_diag, lo * N), at(alpha, lo * N), at(loo_logpdf, lo), at(status, lo));
+  });
+}
+
 int clr_sharded_run_timed(clr_sharded* h, int steps, double* shard_ms /* [nshards] or NULL */) {
   // (a timing tool: every shard times its own steps and settles them by its own counts)
   const int st0 = resolve_all(h);

@@ -588,6 +588,23 @@ int clr_batch_predict_var(clr_batch* h, int M, const double* xs, long xs_stride,
  * bounds the automatic choice only: a tile set here is taken as given up to 65535 and M, and clr_batch_predict_var
  * returns the allocation's status if the device cannot hold its buffers. */
 int clr_batch_set_predict_tile(clr_batch* h, int points);
+/* diag(K^-1), K^-1 r and the leave-one-out log predictive density of every problem from the factor of the last
+ * materialising run.  kinv_diag [B][N], alpha [B][N], loo_logpdf [B], status [B]: each may be NULL and is then neither
+ * computed beyond need nor copied down (alpha or loo_logpdf: the batched solve of the residual in force runs); all four
+ * NULL: CLR_INVALID_ARGUMENT.  With c_n = (K^-1)_nn and alpha = K^-1 r (r = y less the mean in force):
+ *     y_n - mu_-n = alpha_n / c_n ,  sigma^2_-n = 1 / c_n ,  log p(y_n | y_-n) = -1/2 log(2 pi / c_n) - 1/2 alpha_n^2 / c_n
+ * and loo_logpdf is the sum over n; the in-sample GP.predict (celerite.py:270-272) is mu_n = y_n - s_n alpha_n,
+ * var_n = s_n - s_n^2 c_n with s_n = diag_n + jitter.  All N entries of c come from ONE backward matrix recurrence on
+ * the factor, O(N J^2) per problem (csrc/clr_binvdiag_kernels.h): widths 1..8 on chunked plans (N >= 128), either factor
+ * layout, the chunk maps shared with clr_batch_solve; widths 9..64 one wave per problem, sequential in n, N >= 512 (else
+ * CLR_UNSUPPORTED, as clr_batch_solve).  loo_logpdf is summed by one workgroup per problem in a fixed order (samples
+ * i, i + 256, ... per thread, then a tree): no atomics, a problem's bits depend on neither the batch nor the sharding.
+ * Statuses are those of the evaluation in force (clr_batch_get_results); rows of problems whose status is not CLR_OK are
+ * NaN in every output. */
+int clr_batch_leave_one_out(clr_batch* h, double* kinv_diag, double* alpha, double* loo_logpdf, int* status);
+/* Device time of the last clr_batch_leave_one_out's three parts (HIP events): the diagonal, the solve, the reduction; a
+ * part that did not run reports 0. */
+int clr_batch_get_leave_one_out_ms(const clr_batch* h, double* diag_ms, double* solve_ms, double* reduce_ms);
 /* CholeskySolver::dot_L (cholesky.h:409-431: y = L z with K = L L^T, what GP.sample draws, celerite.py:422-451) for
  * every problem of the plan from the factor of its last materialising run (either layout): z, y host [B][nrhs][N].
  * Widths 1..8: a chunked diagonal scan on the chunk-interleaved factor, lane = (problem, chunk)
@@ -861,8 +878,8 @@ int clr_sharded_get_coefficients(clr_sharded* h, double* jitter, double* a_real,
 /* The consumers of the factor on a sharded batch (GP.apply_inverse / .sample / .predict for B problems over several
  * GPUs): clr_sharded_materialize runs clr_batch_enqueue(plan, 1) on every shard, settles the evaluation with the
  * batch-wide counts (results as clr_sharded_get_results; any pointer may be NULL) and leaves every shard's factor in
- * its HBM; clr_sharded_solve / _dot_L / _dot / _predict / _predict_var are clr_batch_solve / _dot_L / _dot / _predict / _predict_var on every
- * shard concurrently,
+ * its HBM; clr_sharded_solve / _dot_L / _dot / _predict / _predict_var / _leave_one_out are clr_batch_solve / _dot_L /
+ * _dot / _predict / _predict_var / _leave_one_out on every shard concurrently,
  * each on its contiguous slice of the host arrays ([B][nrhs][N]; xs [B][M] or shared with xs_stride = 0).  No
  * collective: every problem's state is its own (cholesky.h:703-706). */
 int clr_sharded_materialize(clr_sharded* h, double* loglike, double* logdet, double* quad, int* status);
@@ -871,6 +888,7 @@ int clr_sharded_dot_L(clr_sharded* h, int nrhs, const double* z, double* y);
 int clr_sharded_dot(clr_sharded* h, int nrhs, const double* z, double* y);
 int clr_sharded_predict(clr_sharded* h, int M, const double* xs, long xs_stride, double* pred);
 int clr_sharded_predict_var(clr_sharded* h, int M, const double* xs, long xs_stride, double* var);
+int clr_sharded_leave_one_out(clr_sharded* h, double* kinv_diag, double* alpha, double* loo_logpdf, int* status);
 /* `steps` back-to-back evaluations on every shard concurrently (HIP events per shard);
  * shard_ms[s] = that shard's first-to-last event time. */
 int clr_sharded_run_timed(clr_sharded* h, int steps, double* shard_ms);
