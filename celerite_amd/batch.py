@@ -331,6 +331,12 @@ def _loo_args(c, alpha, logpdf, st):
     return [None if a is None else _ptr(a) for a in (c, alpha, logpdf)] + [None if st is None else st.ctypes.data_as(_ip)]
 
 
+def _predict_method(method):
+    """The ``method`` argument of ``predict``: checked before anything touches the device."""
+    if method not in ("solve", "recurrence"):
+        raise ValueError("predict: method is 'solve' or 'recurrence', not %r" % (method,))
+
+
 def leave_one_out_from(kinv_diag, alpha):
     """``(residual, variance, logpdf)`` of the leave-one-out predictive distribution from ``c = diag(K^-1)`` and
     ``alpha = K^-1 r``, both ``(N,)`` or ``(B, N)`` (no GPU):
@@ -736,7 +742,7 @@ class BatchedGP(object):
         _check(lib.clr_batch_solve(self._h, int(nrhs), _ptr(b), _ptr(x)))
         return x
 
-    def predict(self, xs, return_var=False, mean_basis=None):
+    def predict(self, xs, return_var=False, mean_basis=None, method="solve"):
         """The conditional mean ``mu_p + K_p(x*, t_p) K_p^-1 (y_p - mu_p)`` of every problem (``mu_p`` the mean of
         :meth:`set_mean`, zero without one; ``GP.predict``, celerite.py:279) at the prediction points ``xs`` --
         ``(M,)`` shared by all problems or ``(B, M)`` -- from the factor of the last materialising run
@@ -744,7 +750,19 @@ class BatchedGP(object):
         With a linear mean in force (:meth:`set_mean_basis`) ``mean_basis`` is required: the basis at ``xs``, ``(K, M)``
         or ``(B, K, M)``; its product with the weights is added to the conditional mean of the residual.
         ``return_var=True``: ``(mu, var)`` with the conditional variance ``k_p(0) - k*^T K_p^-1 k*`` of every point
-        (``clr_batch_predict_var``; celerite.py:465-470), both ``(B, M)``: only ``xs`` goes up and ``var`` comes down."""
+        (``clr_batch_predict_var``; celerite.py:465-470), both ``(B, M)``: only ``xs`` goes up and ``var`` comes down.
+        ``method`` chooses the variance's route and is ignored for the mean: ``"solve"`` (the default) is one forward
+        substitution per point, O(M N J) per problem, any width; ``"recurrence"`` (``clr_batch_predict_var_recurrence``,
+        narrow plans, widths 1..8) is one forward and one backward matrix recurrence over the series plus O(J^2) per
+        point, O((N + M) J^2).  The two agree to rounding (each within 1e-10 k(0) of the reference), not bit for bit.
+        Which to choose (``profiles/predict_var_recurrence_timing.txt``, device time): on a narrow plan ``"recurrence"``
+        from a handful of points on -- at 256 x 1e4 x width 4 it is the faster one at every measured M >= 1 (0.52 ms
+        against 737 ms at M = N = 1e4), at 1024 x 1e5 x width 8 the two tie at M = 1 (6.5 ms) and it wins from M = 4
+        on (7.2 ms against 25.9 ms; 21.4 ms at M = 1e4).  ``"solve"`` on wide plans (widths 9..64, which the recurrence
+        refuses), for a single point on a long series, and where the phases ``d t`` reach ~1e9: the recurrence evaluates
+        a point's features at the absolute phase ``d x`` and carries its rounding (1e-8 k(0) at t ~ 3e8).  Unsorted
+        points are sorted on the host (150 ms for 256 x 1e4 points): pass them sorted where that matters."""
+        _predict_method(method)
         lib = _load()
         lib.clr_batch_predict.argtypes = [C.c_void_p, C.c_int, _dp, C.c_long, _dp]
         xs = _f64(xs)
@@ -762,9 +780,10 @@ class BatchedGP(object):
             pred = model + pred
         if not return_var:
             return pred
-        lib.clr_batch_predict_var.argtypes = [C.c_void_p, C.c_int, _dp, C.c_long, _dp]
+        entry = lib.clr_batch_predict_var_recurrence if method == "recurrence" else lib.clr_batch_predict_var
+        entry.argtypes = [C.c_void_p, C.c_int, _dp, C.c_long, _dp]
         var = np.empty((self.B, M))
-        _check(lib.clr_batch_predict_var(self._h, int(M), _ptr(xs), stride, _ptr(var)))
+        _check(entry(self._h, int(M), _ptr(xs), stride, _ptr(var)))
         return pred, var
 
     def set_predict_tile(self, points=0):
@@ -1427,10 +1446,11 @@ class ShardedBatchedGP(object):
         self._ok(lib.clr_sharded_dot(self._h, int(nrhs), _ptr(z), _ptr(y)))
         return y
 
-    def predict(self, xs, return_var=False, mean_basis=None):
+    def predict(self, xs, return_var=False, mean_basis=None, method="solve"):
         """The conditional mean of every problem at ``xs`` (``(M,)`` shared or ``(B, M)``) and, with ``return_var=True``,
         the conditional variance beside it, as :meth:`BatchedGP.predict` (``mean_basis``: the linear mean's basis at
-        ``xs``, required while one is in force)."""
+        ``xs``, required while one is in force; ``method``: the variance's route, ``"solve"`` or ``"recurrence"``)."""
+        _predict_method(method)
         lib = _load()
         lib.clr_sharded_predict.argtypes = [C.c_void_p, C.c_int, _dp, C.c_long, _dp]
         xs = _f64(xs)
@@ -1448,9 +1468,10 @@ class ShardedBatchedGP(object):
             pred = model + pred
         if not return_var:
             return pred
-        lib.clr_sharded_predict_var.argtypes = [C.c_void_p, C.c_int, _dp, C.c_long, _dp]
+        entry = lib.clr_sharded_predict_var_recurrence if method == "recurrence" else lib.clr_sharded_predict_var
+        entry.argtypes = [C.c_void_p, C.c_int, _dp, C.c_long, _dp]
         var = np.empty((self.B, M))
-        self._ok(lib.clr_sharded_predict_var(self._h, int(M), _ptr(xs), stride, _ptr(var)))
+        self._ok(entry(self._h, int(M), _ptr(xs), stride, _ptr(var)))
         return pred, var
 
     inverse_diagonal = BatchedGP.inverse_diagonal

@@ -2307,6 +2307,112 @@ int clr_batch_predict_var(clr_batch* h, int M, const double* xs, long xs_stride,
   return CLR_OK;
 }
 
+// The conditional variance of GP.predict for every problem of a narrow plan at M points each in O((N + M) J^2): the
+// factorisation's forward state S and the backward matrix recurrence Q of the leave-one-out diagonal give var(x) in closed
+// form (clr_bpredvar_rec_kernels.h) -- one forward and one backward pass over the series per tile of points, O(J^2) per
+// point.  The kernels want every problem's points ascending: sorted input is detected in O(M), anything else is sorted
+// as an index permutation on the host (NaN last) and the results are scattered back; shared points are sorted once.  The
+// chunks' forward start states (pv_S) and backward start matrices (loo_Q, shared with clr_batch_leave_one_out) depend on
+// the factor only and are formed by the first tile after a materialising run, the chunk maps under clr_batch_solve's rule.
+int clr_batch_predict_var_recurrence(clr_batch* h, int M, const double* xs, long xs_stride, double* var) {
+  int st = require_device(h->device);
+  if (st != CLR_OK) return st;
+  if (M < 0 || (M > 0 && (!xs || !var))) return fail(CLR_INVALID_ARGUMENT, "clr_batch_predict_var_recurrence: M >= 0, the points and an output array");
+  if (xs_stride != 0 && xs_stride != M) return fail(CLR_INVALID_ARGUMENT, "clr_batch_predict_var_recurrence: the points' stride is 0 (shared by all problems) or M");
+  if ((st = require_celerite_width(h, "clr_batch_predict_var_recurrence")) != CLR_OK) return st;
+  if (M == 0) return CLR_OK;
+  if ((st = require_factor(h, true)) != CLR_OK) return st;
+  if (!h->launch)
+    return fail(CLR_UNSUPPORTED, "clr_batch_predict_var_recurrence covers narrow plans (widths 1..8): a wide plan takes clr_batch_predict_var");
+  if (h->nchunk < 2) return fail(CLR_UNSUPPORTED, "clr_batch_predict_var_recurrence needs a chunked plan (N >= 128)");
+  clr::BatchParams P;
+  if ((st = consumer_params(h, false, P)) != CLR_OK) return st;
+  const size_t B = (size_t)h->B, J = (size_t)h->J, Mm = (size_t)M, nsrc = xs_stride == 0 ? 1 : B, nc = (size_t)h->nchunk;
+  const size_t NS = J * (J + 1) / 2;
+  // ascending points per source: as given, or through a permutation
+  std::vector<char> sorted(nsrc, 1);
+  bool all_sorted = true;
+  for (size_t p = 0; p < nsrc; ++p) {
+    const double* x = xs + p * Mm;
+    for (size_t m = 1; m < Mm && sorted[p]; ++m) sorted[p] = x[m - 1] <= x[m];
+    all_sorted = all_sorted && sorted[p];
+  }
+  std::vector<double> xsorted, vtmp;
+  std::vector<int> perm;
+  if (!all_sorted) {
+    xsorted.assign(xs, xs + nsrc * Mm);
+    perm.resize(nsrc * Mm);
+    for (size_t p = 0; p < nsrc; ++p) {
+      int* pp = perm.data() + p * Mm;
+      for (size_t m = 0; m < Mm; ++m) pp[m] = (int)m;
+      if (sorted[p]) continue;
+      const double* x = xs + p * Mm;
+      std::stable_sort(pp, pp + Mm, [x](int a, int b) {
+        const double xa = x[a], xb = x[b];
+        if (xa != xa) return false;   // NaN last
+        if (xb != xb) return true;
+        return xa < xb;
+      });
+      for (size_t m = 0; m < Mm; ++m) xsorted[p * Mm + m] = x[pp[m]];
+    }
+    vtmp.resize(B * Mm);
+  }
+  const double* xup = all_sorted ? xs : xsorted.data();
+  // the phases of the points' features: |d| |x*|, under the plan's own rule
+  double xmax = 0.0;
+  for (size_t k = 0; k < nsrc * Mm; ++k) {
+    const double a = std::fabs(xs[k]);
+    if (a > xmax || a != a) xmax = a;  // (a NaN stays: the library sincos)
+  }
+  const int xfast = (sel_max(h->dmax, h->floor_dmax) * xmax < CLR_FAST_TRIG_LIMIT) ? 1 : 0;
+  // points per tile: the caller's, or the most whose per-point buffers (u(x), e, left) fit in 1 GiB
+  const size_t budget = (size_t)1 << 27, per_point = B * (2 * J + 1);
+  const size_t Rz = std::min<size_t>(h->predict_tile > 0 ? (size_t)h->predict_tile : std::max<size_t>(1, budget / per_point), Mm);
+  const int R = (int)Rz;
+  DevBuf dxs, dvar, dux, de, dleft;
+  if ((st = dxs.reserve(nsrc * Mm)) != CLR_OK) return st;
+  if ((st = dvar.reserve(B * Mm)) != CLR_OK) return st;
+  if ((st = dux.reserve(B * Rz * J)) != CLR_OK) return st;
+  if ((st = de.reserve(B * Rz * J)) != CLR_OK) return st;
+  if ((st = dleft.reserve(B * Rz)) != CLR_OK) return st;
+  if ((st = h->pv_S.reserve(B * nc * NS)) != CLR_OK) return st;
+  if ((st = h->loo_Q.reserve(B * nc * NS)) != CLR_OK) return st;
+  if ((st = h->bs_M.reserve(B * nc * J * J)) != CLR_OK) return st;
+  if ((st = h->bs_off.reserve(B * nc * J)) != CLR_OK) return st;
+  if ((st = h->bs_x.reserve(B * (size_t)h->L * nc)) != CLR_OK) return st;  // (read beside by the solve's summarize when it forms the maps)
+  ConsumerFrame frame{h};
+  HIP_TRY(hipMemcpyAsync(dxs.p, xup, nsrc * Mm * sizeof(double), hipMemcpyHostToDevice, h->stream.get()));
+  HIP_TRY(frame.start());
+  clr::BPredVarRecParams S;
+  S.lean = h->factor_is_lean ? 1 : 0;
+  S.have_S = h->pv_S_valid ? 1 : 0;
+  S.have_Q = h->loo_Q_valid ? 1 : 0;
+  S.Q.lean = S.lean;
+  S.Q.have_M = h->bs_M_valid ? 1 : 0;
+  const bool forms_Q = !S.have_Q;        // ... and with them the chunk maps, unless a solve has formed those
+  if (forms_Q) h->bs_M_valid = false;
+  h->pv_S_valid = h->loo_Q_valid = false;
+  S.Q.cT = h->bs_x.p; S.Q.M = h->bs_M.p; S.Q.Q = h->loo_Q.p; S.Q.off = h->bs_off.p;
+  S.xs_stride = xs_stride; S.t = h->t.p; S.t_stride = h->t_stride;
+  S.S = h->pv_S.p; S.ux = dux.p; S.e = de.p; S.left = dleft.p;
+  S.var_stride = (long)M;
+  for (int m0 = 0; m0 < M; m0 += R) {
+    S.npts = std::min(R, M - m0); S.xs = dxs.p + m0; S.var = dvar.p + m0;
+    h->launch->bpredvar_rec(P, S, xfast, h->stream.get());
+    S.have_S = S.have_Q = 1;
+  }
+  HIP_TRY(frame.stop());
+  if ((st = frame.finish(all_sorted ? var : vtmp.data(), dvar.p, B * Mm)) != CLR_OK) return st;
+  h->pv_S_valid = h->loo_Q_valid = true;
+  if (forms_Q) h->bs_M_valid = true;
+  if (!all_sorted)
+    for (size_t b = 0; b < B; ++b) {
+      const int* pp = perm.data() + (xs_stride == 0 ? 0 : b * Mm);
+      for (size_t m = 0; m < Mm; ++m) var[b * Mm + pp[m]] = vtmp[b * Mm + m];
+    }
+  return CLR_OK;
+}
+
 // ---- clr_batch_leave_one_out: diag(K^-1), K^-1 r and the leave-one-out log predictive density of every problem
 
 // widths 9..64: diag(K^-1) of one problem per wave from the factor in the reference's storage, sequential in n (the
@@ -2441,6 +2547,7 @@ int clr_batch_leave_one_out(clr_batch* h, double* kinv_diag, double* alpha, doub
       //  counted as formed only once this call's kernels have run to completion)
       S.have_M = h->bs_M_valid ? 1 : 0;
       h->bs_M_valid = false;
+      h->loo_Q_valid = false;  // (loo_Q is rewritten: the offsets, then the start matrices -- as clr_batch_predict_var_recurrence reads them)
       S.cT = h->bs_x.p; S.M = h->bs_M.p; S.Q = h->loo_Q.p; S.off = h->bs_off.p;
       h->launch->binvdiag(P, S, s);
       clr::launch_relayout_back(h->bs_x.p, (long)h->L * h->nchunk, h->loo_c.p, (long)N, h->B, h->N, h->L, h->nchunk, s);
@@ -2452,7 +2559,7 @@ int clr_batch_leave_one_out(clr_batch* h, double* kinv_diag, double* alpha, doub
     }
     HIP_TRY(hipEventRecord(h->loo_ev[1].get(), s));
     if ((st = frame.finish(kinv_diag, h->loo_c.p, B * N)) != CLR_OK) return st;
-    if (h->launch) h->bs_M_valid = true;
+    if (h->launch) h->bs_M_valid = h->loo_Q_valid = true;
     HIP_TRY(hipEventElapsedTime(&ms, h->loo_ev[0].get(), h->loo_ev[1].get()));
     h->loo_diag_ms = ms;
   }

@@ -361,6 +361,11 @@ struct clr_batch {
   DevBuf loo_c, loo_Q, loo_out;
   clr::Event loo_ev[4];
   double loo_diag_ms = 0.0, loo_solve_ms = 0.0, loo_reduce_ms = 0.0;
+  // clr_batch_predict_var_recurrence: the chunks' forward start states [B][nchunk][J (J + 1) / 2]; they and the backward
+  // start matrices the leave-one-out diagonal's first two passes leave in loo_Q depend on the factor only, like bs_M, and
+  // follow its validity rule (counted as formed only once the kernels that formed them have run to completion)
+  DevBuf pv_S;
+  bool pv_S_valid = false, loo_Q_valid = false;
   int predict_tile = 0;                         // clr_batch_set_predict_tile: prediction points per tile of clr_batch_predict_var (0: automatic)
   clr::Event bs_ev[2];                          // ... its two timing events, created by the first solve, kept for the plan's life
   int factor_layout = 0;      // clr_batch_set_factor_layout: 0 the reference's four arrays, 1 lean (W, D; phi, u regenerated)
@@ -410,6 +415,7 @@ namespace {
 // a materialising run has queued the writes of the factor, in the lean layout or the reference's
 void factor_written(clr_batch* h, bool lean) {
   h->factor_is_lean = lean; h->factor_inputs_changed = false; h->factor_valid = true; h->bs_M_valid = false;
+  h->pv_S_valid = h->loo_Q_valid = false;
 }
 // the factor's layout in HBM no longer is the one a materialising run would write (chunking, factor layout)
 void factor_dropped(clr_batch* h) { h->have_factor = h->factor_valid = false; }

@@ -1008,6 +1008,7 @@ __global__ void __launch_bounds__(64) warm_check_kernel(const BatchParams P) {
 #include "clr_bdot_kernels.h"
 #include "clr_bpredvar_kernels.h"
 #include "clr_binvdiag_kernels.h"
+#include "clr_bpredvar_rec_kernels.h"
 namespace clr {
 
 // One table entry per (JR, JC): host-callable launchers.
@@ -1034,6 +1035,9 @@ struct BatchLaunchers {
   void (*bpredvar)(const BatchParams&, BPredVarParams S, hipStream_t);
   // diag(K^-1) for all problems from the materialised factor (clr_binvdiag_kernels.h): -> S.cT
   void (*binvdiag)(const BatchParams&, BInvDiagParams S, hipStream_t);
+  // k(0) - k*^T K^-1 k* for all problems at one tile of SORTED prediction points by the two matrix recurrences
+  // (clr_bpredvar_rec_kernels.h): S.xs -> S.var; `xfast`: the points' phases stay below CLR_FAST_TRIG_LIMIT
+  void (*bpredvar_rec)(const BatchParams&, BPredVarRecParams S, int xfast, hipStream_t);
   // lean factor of problem b (replay mode 3) -> the reference's storage, phi and u regenerated (t: the problem's row-major times)
   void (*expand)(const BatchParams&, int b, const double* t, double* phi, double* u, double* W, double* D, hipStream_t);
   int elem_doubles, start_doubles;
@@ -1205,6 +1209,35 @@ struct BatchImpl {
     if (S.lean) { if (P.fast_trig) binvdiag_go<true, true>(P, S, s); else binvdiag_go<true, false>(P, S, s); }
     else binvdiag_go<false, true>(P, S, s);  // (the stored phi, u: no trigonometry)
   }
+  // the predictive variance by recurrence at one tile of sorted points: the points' features; unless formed, the forward
+  // start states (offsets, walk) and the backward start matrices (the chunk maps by the solve's own summarize unless they
+  // are formed, binvdiag's offsets and walk); the forward and the backward replay
+  template <bool LEAN, bool FAST>
+  static void bpredvar_rec_go(const BatchParams& P, const BPredVarRecParams& S, int xfast, hipStream_t s) {
+    const dim3 grid((P.nchunk + 63) / 64, P.B), wgrid((P.B + 63) / 64), fgrid((unsigned)(((long)P.B * S.npts + 255) / 256));
+    if (xfast) hipLaunchKernelGGL((bpvrec_features_kernel<JR, JC, true>), fgrid, dim3(256), 0, s, P, S);
+    else hipLaunchKernelGGL((bpvrec_features_kernel<JR, JC, false>), fgrid, dim3(256), 0, s, P, S);
+    if (!S.have_S) {
+      hipLaunchKernelGGL((bpvrec_forward_kernel<JR, JC, LEAN, FAST, false>), grid, dim3(64), 0, s, P, S);
+      hipLaunchKernelGGL((bpvrec_walk_kernel<JR, JC>), wgrid, dim3(64), 0, s, P, S);
+    }
+    if (!S.have_Q) {
+      if (!S.Q.have_M) {  // (as binvdiag_go: the offsets beside the maps go to Q.off and are not used)
+        BSolveParams Q;
+        Q.nrhs = 1; Q.r = 0; Q.lean = S.lean; Q.have_M = 0;
+        Q.xT = S.Q.cT; Q.M = S.Q.M; Q.off = S.Q.off; Q.starts = nullptr;
+        hipLaunchKernelGGL((bsolve_summarize_kernel<JR, JC, LEAN, FAST, true>), grid, dim3(64), 0, s, P, Q);
+      }
+      hipLaunchKernelGGL((binvdiag_kernel<JR, JC, LEAN, FAST, false>), grid, dim3(64), 0, s, P, S.Q);
+      hipLaunchKernelGGL((binvdiag_walk_kernel<JR + 2 * JC>), wgrid, dim3(64), 0, s, P, S.Q);
+    }
+    hipLaunchKernelGGL((bpvrec_forward_kernel<JR, JC, LEAN, FAST, true>), grid, dim3(64), 0, s, P, S);
+    hipLaunchKernelGGL((bpvrec_backward_kernel<JR, JC, LEAN, FAST>), grid, dim3(64), 0, s, P, S);
+  }
+  static void bpredvar_rec(const BatchParams& P, BPredVarRecParams S, int xfast, hipStream_t s) {
+    if (S.lean) { if (P.fast_trig) bpredvar_rec_go<true, true>(P, S, xfast, s); else bpredvar_rec_go<true, false>(P, S, xfast, s); }
+    else bpredvar_rec_go<false, true>(P, S, xfast, s);  // (the stored phi, u: no trigonometry)
+  }
   static void compose_check(const BatchParams& P, int g, double* coop, double* ref, hipStream_t s) {
     constexpr int J = JR + 2 * JC;
     const int np = (P.nchunk + g - 1) / g;
@@ -1257,7 +1290,7 @@ struct BatchImpl {
   }
   static BatchLaunchers table() {
     return BatchLaunchers{&summarize, &prefix, &correct, &replay, &sequential, &compose_check, &warm, &grad, &grad_reverse,
-                          &bsolve, &bdotl, &bdot, &bpredvar, &binvdiag, &expand, Widths<JR, JC>::ELEM, Widths<JR, JC>::START};
+                          &bsolve, &bdotl, &bdot, &bpredvar, &binvdiag, &bpredvar_rec, &expand, Widths<JR, JC>::ELEM, Widths<JR, JC>::START};
   }
 };
 

@@ -670,6 +670,12 @@ int clr_sharded_predict_var(clr_sharded* h, int M, const double* xs, long xs_str
   });
 }
 
+int clr_sharded_predict_var_recurrence(clr_sharded* h, int M, const double* xs, long xs_stride, double* var) {
+  return on_slices(h, M >= 0 && (M == 0 || (xs && var)) && (xs_stride == 0 || xs_stride == M), [=](clr_batch* p, long lo) {
+    return clr_batch_predict_var_recurrence(p, M, xs + lo * xs_stride, xs_stride, var + lo * (long)M);
+  });
+}
+
 int clr_sharded_leave_one_out(clr_sharded* h, double* kinv_diag, double* alpha, double* loo_logpdf, int* status) {
   const long N = h->N;
   return on_slices(h, kinv_diag || alpha || loo_logpdf || status, [=](clr_batch* p, long lo) {

@@ -588,6 +588,24 @@ int clr_batch_predict_var(clr_batch* h, int M, const double* xs, long xs_stride,
  * bounds the automatic choice only: a tile set here is taken as given up to 65535 and M, and clr_batch_predict_var
  * returns the allocation's status if the device cannot hold its buffers. */
 int clr_batch_set_predict_tile(clr_batch* h, int points);
+/* clr_batch_predict_var -- same arguments, same meaning, same preconditions -- in O((N + M) J^2) per problem instead of
+ * O(M N J): with the factorisation's forward state S (S+_n = S_n + D_n W_n W_n^T, S_{n+1} = Phi S+_n Phi) and the backward
+ * matrix recurrence Q of clr_batch_leave_one_out, for a point x with m samples at or before it
+ *     psi = exp(-c (x - t_{m-1})) ,  w = psi o u(x) ,  e = v(x) - psi o (S+_{m-1} w) ,  e' = exp(-c (t_m - x)) o e
+ *     var(x) = k(0) - w^T S+_{m-1} w - e'^T Q_m e'
+ * (csrc/clr_bpredvar_rec_kernels.h): one forward and one backward pass over the series per tile plus O(J^2) per point.
+ * Narrow plans only (widths 1..8, chunked: N >= 128, either factor layout); a wide plan returns CLR_UNSUPPORTED -- take
+ * clr_batch_predict_var there.  The points need not be sorted: ascending input is detected in O(M), anything else is
+ * sorted as an index permutation on the host (shared points once) and the results are scattered back.  Tiles are runs
+ * of consecutive sorted points: automatic -- the most whose per-point buffers (2 J + 1 doubles per problem) fit in
+ * 1 GiB -- or clr_batch_set_predict_tile's, up to M; a point's result depends on neither the tile, the batch nor the
+ * sharding, bit for bit.  The chunks' start states of both recurrences depend on the factor only and are kept until
+ * the next materialising run (the backward ones shared with clr_batch_leave_one_out, the chunk maps with
+ * clr_batch_solve).  Agrees with clr_batch_predict_var to rounding (both within 1e-10 k(0) of the reference), not bit
+ * for bit; a point's features are evaluated at its absolute phase d x, as the factor's are at d t_n, so where d t
+ * reaches ~1e9 the result carries that phase's rounding (1e-8 k(0) at t ~ 3e8), which clr_batch_predict_var's
+ * cross-covariances of x - t_n do not.  clr_batch_get_solve_ms then reports this call's device time. */
+int clr_batch_predict_var_recurrence(clr_batch* h, int M, const double* xs, long xs_stride, double* var);
 /* diag(K^-1), K^-1 r and the leave-one-out log predictive density of every problem from the factor of the last
  * materialising run.  kinv_diag [B][N], alpha [B][N], loo_logpdf [B], status [B]: each may be NULL and is then neither
  * computed beyond need nor copied down (alpha or loo_logpdf: the batched solve of the residual in force runs); all four
@@ -878,8 +896,8 @@ int clr_sharded_get_coefficients(clr_sharded* h, double* jitter, double* a_real,
 /* The consumers of the factor on a sharded batch (GP.apply_inverse / .sample / .predict for B problems over several
  * GPUs): clr_sharded_materialize runs clr_batch_enqueue(plan, 1) on every shard, settles the evaluation with the
  * batch-wide counts (results as clr_sharded_get_results; any pointer may be NULL) and leaves every shard's factor in
- * its HBM; clr_sharded_solve / _dot_L / _dot / _predict / _predict_var / _leave_one_out are clr_batch_solve / _dot_L /
- * _dot / _predict / _predict_var / _leave_one_out on every shard concurrently,
+ * its HBM; clr_sharded_solve / _dot_L / _dot / _predict / _predict_var / _predict_var_recurrence / _leave_one_out are
+ * clr_batch_solve / _dot_L / _dot / _predict / _predict_var / _predict_var_recurrence / _leave_one_out on every shard concurrently,
  * each on its contiguous slice of the host arrays ([B][nrhs][N]; xs [B][M] or shared with xs_stride = 0).  No
  * collective: every problem's state is its own (cholesky.h:703-706). */
 int clr_sharded_materialize(clr_sharded* h, double* loglike, double* logdet, double* quad, int* status);
@@ -888,6 +906,7 @@ int clr_sharded_dot_L(clr_sharded* h, int nrhs, const double* z, double* y);
 int clr_sharded_dot(clr_sharded* h, int nrhs, const double* z, double* y);
 int clr_sharded_predict(clr_sharded* h, int M, const double* xs, long xs_stride, double* pred);
 int clr_sharded_predict_var(clr_sharded* h, int M, const double* xs, long xs_stride, double* var);
+int clr_sharded_predict_var_recurrence(clr_sharded* h, int M, const double* xs, long xs_stride, double* var);
 int clr_sharded_leave_one_out(clr_sharded* h, double* kinv_diag, double* alpha, double* loo_logpdf, int* status);
 /* `steps` back-to-back evaluations on every shard concurrently (HIP events per shard);
  * shard_ms[s] = that shard's first-to-last event time. */
