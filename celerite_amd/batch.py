@@ -19,7 +19,7 @@ import numpy as np
 
 __all__ = ["BatchedGP", "ShardedBatchedGP", "shard_bounds", "batch_log_likelihood", "batch_grad_log_likelihood",
            "kernel_coefficient_table", "kernel_coefficient_jacobian_table", "chain_gradient", "compile_kernel",
-           "CompiledKernel", "MeanFit", "gram_solve", "LIB_PATH"]
+           "CompiledKernel", "MeanFit", "OneStepAhead", "gram_solve", "LIB_PATH"]
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libcelerite_hip.so")
 
@@ -121,6 +121,10 @@ def _load():
     lib.clr_batch_leave_one_out.argtypes = [C.c_void_p, _dp, _dp, _dp, _ip]
     lib.clr_sharded_leave_one_out.argtypes = [C.c_void_p, _dp, _dp, _dp, _ip]
     lib.clr_batch_get_leave_one_out_ms.argtypes = [C.c_void_p, _dp, _dp, _dp]
+    lib.clr_batch_one_step_ahead.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _ip]
+    lib.clr_sharded_one_step_ahead.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _ip]
+    lib.clr_batch_forecast.argtypes = [C.c_void_p, C.c_int, _dp, C.c_long, _dp, _dp]
+    lib.clr_sharded_forecast.argtypes = [C.c_void_p, C.c_int, _dp, C.c_long, _dp, _dp]
     lib.clr_gram_solve.argtypes = [C.c_int, C.c_int, _dp, _dp, C.c_double] + [_dp] * 4 + [_ip]
     lib.clr_kernel_create.argtypes = [C.c_int, _ip, C.c_int, _dp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
     lib.clr_kernel_destroy.argtypes = [C.c_void_p]
@@ -368,6 +372,61 @@ def leave_one_out_from(kinv_diag, alpha):
     logpdf = part[:, 0].copy()
     residual, variance = a / c, 1.0 / c
     return (residual, variance, logpdf[0]) if single else (residual, variance, logpdf)
+
+
+class OneStepAhead(collections.namedtuple("OneStepAhead", ["innovation", "variance", "status"])):
+    """The one-step-ahead residuals of every sample (``one_step_ahead``): ``innovation[B, N]`` (``[B, nrhs, N]`` for a 3-D
+    ``b``) = ``z = L^-1 b`` with ``K = L diag(D) L^T``, ``variance[B, N]`` = ``D`` and ``status[B]``.  For the residual
+    ``r``: ``E[y_n | y_<n] = y_n - z_n`` with variance ``D_n``.  Rows of problems whose status is not 0 are NaN."""
+    __slots__ = ()
+
+    def _var(self):
+        return self.variance if self.innovation.ndim == 2 else self.variance[:, None, :]
+
+    @property
+    def standardized(self):
+        """``innovation / sqrt(variance)``: white and standard normal under the model."""
+        return self.innovation / np.sqrt(self._var())
+
+    @property
+    def log_density(self):
+        """``-1/2 (log(2 pi variance) + innovation^2 / variance)`` per sample: ``log p(y_n | y_<n)``; its sum over n is
+        the log-likelihood."""
+        v = self._var()
+        return -0.5 * (np.log(2.0 * np.pi * v) + self.innovation * self.innovation / v)
+
+
+def _one_step_ahead(plan, name, check, b):
+    """``one_step_ahead`` of both plan classes: the arguments are checked before the library is touched."""
+    if b is None:
+        nrhs, shape, bp = 1, (plan.B, plan.N), None
+    else:
+        b = _f64(b)
+        if b.ndim not in (2, 3) or b.shape[0] != plan.B or b.shape[-1] != plan.N:
+            raise ValueError("dimension mismatch")
+        nrhs, shape, bp = (1 if b.ndim == 2 else b.shape[1]), b.shape, _ptr(b)
+    z, D, st = np.empty(shape), np.empty((plan.B, plan.N)), np.empty(plan.B, dtype=np.int32)
+    check(getattr(_load(), name)(plan._h, int(nrhs), bp, _ptr(z), _ptr(D), st.ctypes.data_as(_ip)))
+    return OneStepAhead(z, D, st)
+
+
+def _forecast(plan, name, check, xs, return_var, mean_basis):
+    """``forecast`` of both plan classes: the arguments are checked before the library is touched."""
+    xs = _f64(xs)
+    if xs.ndim == 1:
+        stride = 0
+    elif xs.ndim == 2 and xs.shape[0] == plan.B:
+        stride = xs.shape[1]
+    else:
+        raise ValueError("dimension mismatch")
+    M = xs.shape[-1]
+    model = _linear_mean_at(plan, mean_basis, M)
+    mean = np.empty((plan.B, M))
+    var = np.empty((plan.B, M)) if return_var else None
+    check(getattr(_load(), name)(plan._h, int(M), _ptr(xs), stride, _ptr(mean), None if var is None else _ptr(var)))
+    if model is not None:
+        mean = model + mean
+    return (mean, var) if return_var else mean
 
 
 def _exclusive_means(mean, mean_weights):
@@ -792,6 +851,28 @@ class BatchedGP(object):
         lib = _load()
         lib.clr_batch_set_predict_tile.argtypes = [C.c_void_p, C.c_int]
         _check(lib.clr_batch_set_predict_tile(self._h, int(points)))
+
+    def one_step_ahead(self, b=None):
+        """The one-step-ahead residuals (innovations) of every problem, a :class:`OneStepAhead`
+        (``clr_batch_one_step_ahead``), from the factor ``K = L diag(D) L^T`` of the last materialising run:
+        ``innovation = L^-1 b``, undivided, ``variance = D``.  ``b``: ``(B, N)`` or ``(B, nrhs, N)``; ``None``: the
+        residual in force, ``y`` less the mean of :meth:`set_mean` / :meth:`set_mean_weights` (no upload).  Then
+        ``E[y_n | y_<n] = y_n - innovation_n`` with variance ``variance_n`` (``diag_n + jitter`` enters it),
+        ``.standardized`` should be white and standard normal, and ``.log_density`` sums to the log-likelihood.  One
+        forward chunked scan -- the forward half of :meth:`solve`."""
+        return _one_step_ahead(self, "clr_batch_one_step_ahead", _check, b)
+
+    def forecast(self, xs, return_var=False, mean_basis=None):
+        """The causal forecast ``p(f(x) | y_n : t_n < x)`` of every problem at the points ``xs`` -- ``(M,)`` shared by
+        all problems or ``(B, M)``, sorted or not -- given only the samples STRICTLY before each point
+        (``clr_batch_forecast``), from the factor of the last materialising run; narrow plans (widths 1..8).  Returns
+        the mean ``(B, M)``, with ``return_var=True`` ``(mean, var)``: the conditional variance of the latent process
+        (no jitter, no observational variance), as :meth:`predict`'s.  The mean in force is added at the points as
+        :meth:`predict` adds it: a constant mean as is, a linear mean through ``mean_basis`` (required while one is in
+        force).  Before the first sample the result is the prior (the mean model, ``k(0)``); at ``x = t_n`` it is the
+        one-step-ahead prediction of sample n (:meth:`one_step_ahead`: ``y_n - innovation_n``, ``variance_n - diag_n -
+        jitter``).  One forward pass over the series plus O(J^2) per point; tiles follow :meth:`set_predict_tile`."""
+        return _forecast(self, "clr_batch_forecast", _check, xs, return_var, mean_basis)
 
     def inverse_diagonal(self):
         """``diag(K_p^-1)`` of every problem, ``(B, N)``, from the factor of the last materialising run
@@ -1473,6 +1554,14 @@ class ShardedBatchedGP(object):
         var = np.empty((self.B, M))
         self._ok(entry(self._h, int(M), _ptr(xs), stride, _ptr(var)))
         return pred, var
+
+    def one_step_ahead(self, b=None):
+        """The one-step-ahead residuals of every problem (as :meth:`BatchedGP.one_step_ahead`), every shard on its slice."""
+        return _one_step_ahead(self, "clr_sharded_one_step_ahead", lambda st: self._ok(st), b)
+
+    def forecast(self, xs, return_var=False, mean_basis=None):
+        """The causal forecast of every problem at ``xs`` (as :meth:`BatchedGP.forecast`), every shard on its slice."""
+        return _forecast(self, "clr_sharded_forecast", lambda st: self._ok(st), xs, return_var, mean_basis)
 
     inverse_diagonal = BatchedGP.inverse_diagonal
     leave_one_out = BatchedGP.leave_one_out

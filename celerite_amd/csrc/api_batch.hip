@@ -2307,6 +2307,54 @@ int clr_batch_predict_var(clr_batch* h, int M, const double* xs, long xs_stride,
   return CLR_OK;
 }
 
+// Every source's points ascending, for the kernels that walk them with a cursor (clr_batch_predict_var_recurrence,
+// clr_batch_forecast): as given where they already are (detected in O(M)), else through an index permutation (NaN last;
+// shared points once) that scatter() undoes on the results.  xmax: max |x| (a NaN stays), for the points' phase rule.
+struct SortedPoints {
+  bool all_sorted = true;
+  std::vector<double> xsorted;
+  std::vector<int> perm;
+  const double* up = nullptr;  // the points to upload, [nsrc][M]
+  double xmax = 0.0;
+  void sort(const double* xs, size_t nsrc, size_t Mm) {
+    std::vector<char> sorted(nsrc, 1);
+    for (size_t p = 0; p < nsrc; ++p) {
+      const double* x = xs + p * Mm;
+      for (size_t m = 1; m < Mm && sorted[p]; ++m) sorted[p] = x[m - 1] <= x[m];
+      all_sorted = all_sorted && sorted[p];
+    }
+    if (!all_sorted) {
+      xsorted.assign(xs, xs + nsrc * Mm);
+      perm.resize(nsrc * Mm);
+      for (size_t p = 0; p < nsrc; ++p) {
+        int* pp = perm.data() + p * Mm;
+        for (size_t m = 0; m < Mm; ++m) pp[m] = (int)m;
+        if (sorted[p]) continue;
+        const double* x = xs + p * Mm;
+        std::stable_sort(pp, pp + Mm, [x](int a, int b) {
+          const double xa = x[a], xb = x[b];
+          if (xa != xa) return false;   // NaN last
+          if (xb != xb) return true;
+          return xa < xb;
+        });
+        for (size_t m = 0; m < Mm; ++m) xsorted[p * Mm + m] = x[pp[m]];
+      }
+    }
+    up = all_sorted ? xs : xsorted.data();
+    for (size_t k = 0; k < nsrc * Mm; ++k) {
+      const double a = std::fabs(xs[k]);
+      if (a > xmax || a != a) xmax = a;  // (a NaN stays: the library sincos)
+    }
+  }
+  // results in sorted order [B][M] -> the caller's order
+  void scatter(const double* tmp, double* out, size_t B, size_t Mm, bool shared) const {
+    for (size_t b = 0; b < B; ++b) {
+      const int* pp = perm.data() + (shared ? 0 : b * Mm);
+      for (size_t m = 0; m < Mm; ++m) out[b * Mm + pp[m]] = tmp[b * Mm + m];
+    }
+  }
+};
+
 // The conditional variance of GP.predict for every problem of a narrow plan at M points each in O((N + M) J^2): the
 // factorisation's forward state S and the backward matrix recurrence Q of the leave-one-out diagonal give var(x) in closed
 // form (clr_bpredvar_rec_kernels.h) -- one forward and one backward pass over the series per tile of points, O(J^2) per
@@ -2329,42 +2377,13 @@ int clr_batch_predict_var_recurrence(clr_batch* h, int M, const double* xs, long
   if ((st = consumer_params(h, false, P)) != CLR_OK) return st;
   const size_t B = (size_t)h->B, J = (size_t)h->J, Mm = (size_t)M, nsrc = xs_stride == 0 ? 1 : B, nc = (size_t)h->nchunk;
   const size_t NS = J * (J + 1) / 2;
-  // ascending points per source: as given, or through a permutation
-  std::vector<char> sorted(nsrc, 1);
-  bool all_sorted = true;
-  for (size_t p = 0; p < nsrc; ++p) {
-    const double* x = xs + p * Mm;
-    for (size_t m = 1; m < Mm && sorted[p]; ++m) sorted[p] = x[m - 1] <= x[m];
-    all_sorted = all_sorted && sorted[p];
-  }
-  std::vector<double> xsorted, vtmp;
-  std::vector<int> perm;
-  if (!all_sorted) {
-    xsorted.assign(xs, xs + nsrc * Mm);
-    perm.resize(nsrc * Mm);
-    for (size_t p = 0; p < nsrc; ++p) {
-      int* pp = perm.data() + p * Mm;
-      for (size_t m = 0; m < Mm; ++m) pp[m] = (int)m;
-      if (sorted[p]) continue;
-      const double* x = xs + p * Mm;
-      std::stable_sort(pp, pp + Mm, [x](int a, int b) {
-        const double xa = x[a], xb = x[b];
-        if (xa != xa) return false;   // NaN last
-        if (xb != xb) return true;
-        return xa < xb;
-      });
-      for (size_t m = 0; m < Mm; ++m) xsorted[p * Mm + m] = x[pp[m]];
-    }
-    vtmp.resize(B * Mm);
-  }
-  const double* xup = all_sorted ? xs : xsorted.data();
-  // the phases of the points' features: |d| |x*|, under the plan's own rule
-  double xmax = 0.0;
-  for (size_t k = 0; k < nsrc * Mm; ++k) {
-    const double a = std::fabs(xs[k]);
-    if (a > xmax || a != a) xmax = a;  // (a NaN stays: the library sincos)
-  }
-  const int xfast = (sel_max(h->dmax, h->floor_dmax) * xmax < CLR_FAST_TRIG_LIMIT) ? 1 : 0;
+  SortedPoints pts;
+  pts.sort(xs, nsrc, Mm);
+  const bool all_sorted = pts.all_sorted;
+  std::vector<double> vtmp;
+  if (!all_sorted) vtmp.resize(B * Mm);
+  const double* xup = pts.up;
+  const int xfast = (sel_max(h->dmax, h->floor_dmax) * pts.xmax < CLR_FAST_TRIG_LIMIT) ? 1 : 0;
   // points per tile: the caller's, or the most whose per-point buffers (u(x), e, left) fit in 1 GiB
   const size_t budget = (size_t)1 << 27, per_point = B * (2 * J + 1);
   const size_t Rz = std::min<size_t>(h->predict_tile > 0 ? (size_t)h->predict_tile : std::max<size_t>(1, budget / per_point), Mm);
@@ -2405,12 +2424,181 @@ int clr_batch_predict_var_recurrence(clr_batch* h, int M, const double* xs, long
   if ((st = frame.finish(all_sorted ? var : vtmp.data(), dvar.p, B * Mm)) != CLR_OK) return st;
   h->pv_S_valid = h->loo_Q_valid = true;
   if (forms_Q) h->bs_M_valid = true;
-  if (!all_sorted)
-    for (size_t b = 0; b < B; ++b) {
-      const int* pp = perm.data() + (xs_stride == 0 ? 0 : b * Mm);
-      for (size_t m = 0; m < Mm; ++m) var[b * Mm + pp[m]] = vtmp[b * Mm + m];
-    }
+  if (!all_sorted) pts.scatter(vtmp.data(), var, B, Mm, xs_stride == 0);
   return CLR_OK;
+}
+
+// ---- clr_batch_one_step_ahead, clr_batch_forecast: the causal half of the factor (clr_bfilter_kernels.h)
+
+// rows of problems without a factor (or refused by the kernel program) -> NaN; the statuses of the evaluation in force
+static int nan_rows_without_factor(clr_batch* h, std::vector<int>& stat, std::initializer_list<std::pair<double*, size_t>> outs) {
+  const size_t B = (size_t)h->B;
+  stat.resize(B);
+  const int st = clr_batch_get_results(h, nullptr, nullptr, nullptr, stat.data());
+  if (st != CLR_OK) return st;
+  mark_refused(h, nullptr, nullptr, nullptr, stat.data());
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  for (size_t b = 0; b < B; ++b) {
+    if (stat[b] == CLR_OK) continue;
+    for (const auto& o : outs)
+      if (o.first) std::fill(o.first + b * o.second, o.first + (b + 1) * o.second, nan);
+  }
+  return CLR_OK;
+}
+
+// z = L^-1 b and D for every problem from the factor of the last materialising run: the forward half of clr_batch_solve
+// without its division.  Narrow plans: the solve's summarize and forward walk for the chunks' start states, then
+// bfilter_forward_kernel on the chunk-interleaved right-hand sides (the chunk maps under clr_batch_solve's validity rule),
+// D de-interleaved beside.  Wide plans (widths 9..64): the forward sweep of wide_batch_solve (launch_wsweep_scan,
+// backward = 0), whose output is z; D lies row-major in the factor.
+int clr_batch_one_step_ahead(clr_batch* h, int nrhs, const double* b, double* innovation, double* variance, int* status) {
+  int st = require_device(h->device);
+  if (st != CLR_OK) return st;
+  if (nrhs < 1) return fail(CLR_INVALID_ARGUMENT, "clr_batch_one_step_ahead: nrhs >= 1");
+  if (!b && nrhs != 1) return fail(CLR_INVALID_ARGUMENT, "clr_batch_one_step_ahead: b == NULL means the residual in force (one right-hand side)");
+  if (!innovation && !variance && !status) return fail(CLR_INVALID_ARGUMENT, "clr_batch_one_step_ahead: at least one output array");
+  if ((st = require_celerite_width(h, "clr_batch_one_step_ahead")) != CLR_OK) return st;
+  if ((st = require_factor(h, true)) != CLR_OK) return st;
+  if (!h->launch && !clr::wsweep_scan_supported(h->N, h->J))
+    return fail(CLR_UNSUPPORTED, "clr_batch_one_step_ahead on a wide plan needs N >= 512");
+  if (h->launch && h->nchunk < 2) return fail(CLR_UNSUPPORTED, "clr_batch_one_step_ahead needs a chunked plan (N >= 128)");
+  const size_t B = (size_t)h->B, N = (size_t)h->N, R = (size_t)nrhs;
+  DevBuf dD;  // (narrow plans: D row-major)
+  if (innovation || variance) {
+    clr::BatchParams P;
+    clr::SweepParams W;
+    if (h->launch) {
+      if ((st = consumer_params(h, false, P)) != CLR_OK) return st;
+      if (innovation && (st = reserve_narrow_solve(h, R)) != CLR_OK) return st;
+      if (variance && (st = dD.reserve(B * N)) != CLR_OK) return st;
+    } else if (innovation) {
+      W = wide_solve_params(h, nrhs);
+      if ((st = h->bs_M.reserve(B * clr::wsweep_workspace_doubles(h->J, W.nchunk, nrhs))) != CLR_OK) return st;
+      if ((st = h->bs_x.reserve(B * R * N)) != CLR_OK) return st;  // the forward sweep's output
+    }
+    if (innovation && (st = h->bs_rm.reserve(B * R * N)) != CLR_OK) return st;
+    ConsumerFrame frame{h};
+    hipStream_t s = h->stream.get();
+    if (innovation && b) HIP_TRY(hipMemcpyAsync(h->bs_rm.p, b, B * R * N * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(frame.start());
+    const double* zdev = nullptr;
+    bool forms_M = false;
+    if (innovation && h->launch) {
+      const clr::BSolveParams Q = narrow_solve_begin(h, nrhs);  // (clears bs_M_valid: set again once the frame has finished)
+      forms_M = true;
+      clr::BFilterParams S{};
+      S.nrhs = nrhs; S.lean = Q.lean; S.have_M = Q.have_M;
+      S.xT = S.zT = Q.xT; S.M = Q.M; S.off = Q.off; S.starts = Q.starts;
+      narrow_kernels(h, nrhs, b ? h->bs_rm.p : h->y.p, b ? (long)N : h->y_stride, h->bs_x.p, h->bs_x.p,
+                     [&] { h->launch->bfilter(P, S, 0, s); });
+      zdev = h->bs_rm.p;
+    } else if (innovation) {
+      W.nrhs = nrhs;
+      W.stride_out = (long)(R * N);
+      W.stride_ws = (long)clr::wsweep_workspace_doubles(h->J, W.nchunk, nrhs);
+      W.in = b ? h->bs_rm.p : h->y.p; W.stride_in = b ? (long)(R * N) : h->y_stride;
+      W.out = h->bs_x.p;
+      W.backward = 0;
+      clr::launch_wsweep_scan(W, h->bs_M.p, s);
+      zdev = h->bs_x.p;
+    }
+    const double* Ddev = h->D.p;  // (wide plans: the reference's storage, problem after problem)
+    if (variance && h->launch) {
+      clr::launch_relayout_back(h->D.p, (long)h->L * h->nchunk, dD.p, (long)N, h->B, h->N, h->L, h->nchunk, s);
+      Ddev = dD.p;
+    }
+    HIP_TRY(frame.stop());
+    HIP_TRY(hipGetLastError());
+    if (variance) HIP_TRY(hipMemcpyAsync(variance, Ddev, B * N * sizeof(double), hipMemcpyDeviceToHost, s));
+    if ((st = frame.finish(innovation, zdev, innovation ? B * R * N : 0)) != CLR_OK) return st;
+    if (forms_M) h->bs_M_valid = true;
+  }
+  std::vector<int> stat;
+  if ((st = nan_rows_without_factor(h, stat, {{innovation, R * N}, {variance, N}})) != CLR_OK) return st;
+  if (status) std::copy(stat.begin(), stat.end(), status);
+  return CLR_OK;
+}
+
+// The mean and variance at M points per problem given the samples strictly before each (clr_bfilter_kernels.h): the
+// residual in force laid out chunk-interleaved once, the chunks' start states of g by the first tile (they follow the
+// residual: never kept), those of S (pv_S, shared with clr_batch_predict_var_recurrence, only with `var`) unless formed,
+// then one forward pass per tile of sorted points.  Points, sorting and tiles as clr_batch_predict_var_recurrence.
+int clr_batch_forecast(clr_batch* h, int M, const double* xs, long xs_stride, double* mean, double* var) {
+  int st = require_device(h->device);
+  if (st != CLR_OK) return st;
+  if (M < 0 || (M > 0 && !xs)) return fail(CLR_INVALID_ARGUMENT, "clr_batch_forecast: M >= 0 and the points");
+  if (!mean && !var) return fail(CLR_INVALID_ARGUMENT, "clr_batch_forecast: at least one output array");
+  if (xs_stride != 0 && xs_stride != M) return fail(CLR_INVALID_ARGUMENT, "clr_batch_forecast: the points' stride is 0 (shared by all problems) or M");
+  if ((st = require_celerite_width(h, "clr_batch_forecast")) != CLR_OK) return st;
+  if (M == 0) return CLR_OK;
+  if ((st = require_factor(h, true)) != CLR_OK) return st;
+  if (!h->launch)
+    return fail(CLR_UNSUPPORTED, "clr_batch_forecast covers narrow plans (widths 1..8): a wide plan takes clr_batch_predict / clr_batch_predict_var");
+  if (h->nchunk < 2) return fail(CLR_UNSUPPORTED, "clr_batch_forecast needs a chunked plan (N >= 128)");
+  clr::BatchParams P;
+  if ((st = consumer_params(h, false, P)) != CLR_OK) return st;
+  const size_t B = (size_t)h->B, J = (size_t)h->J, Mm = (size_t)M, nsrc = xs_stride == 0 ? 1 : B, nc = (size_t)h->nchunk;
+  const size_t NS = J * (J + 1) / 2, nout = (mean ? 1 : 0) + (var ? 1 : 0);
+  SortedPoints pts;
+  pts.sort(xs, nsrc, Mm);
+  // the phases of the points' features: |d| |x*|, under the plan's own rule
+  const int xfast = (sel_max(h->dmax, h->floor_dmax) * pts.xmax < CLR_FAST_TRIG_LIMIT) ? 1 : 0;
+  // points per tile: the caller's, or the most whose per-point buffer (u(x)) fits in 1 GiB
+  const size_t budget = (size_t)1 << 27, per_point = B * J;
+  const size_t Rz = std::min<size_t>(h->predict_tile > 0 ? (size_t)h->predict_tile : std::max<size_t>(1, budget / per_point), Mm);
+  const int R = (int)Rz;
+  DevBuf dxs, dout, dux;  // dout: mean [B][M] | var [B][M], those asked for
+  if ((st = dxs.reserve(nsrc * Mm)) != CLR_OK) return st;
+  if ((st = dout.reserve(nout * B * Mm)) != CLR_OK) return st;
+  if ((st = dux.reserve(B * Rz * J)) != CLR_OK) return st;
+  if (var && (st = h->pv_S.reserve(B * nc * NS)) != CLR_OK) return st;
+  if ((st = reserve_narrow_solve(h, 1)) != CLR_OK) return st;
+  ConsumerFrame frame{h};
+  hipStream_t s = h->stream.get();
+  HIP_TRY(hipMemcpyAsync(dxs.p, pts.up, nsrc * Mm * sizeof(double), hipMemcpyHostToDevice, s));
+  HIP_TRY(frame.start());
+  const clr::BSolveParams Q = narrow_solve_begin(h, 1);  // (clears bs_M_valid: set again once the frame has finished)
+  clr::BFilterParams S{};
+  S.nrhs = 1; S.lean = Q.lean; S.have_M = Q.have_M;
+  S.have_S = h->pv_S_valid ? 1 : 0;
+  const bool forms_S = var && !h->pv_S_valid;
+  S.xT = Q.xT; S.zT = nullptr; S.M = Q.M; S.off = Q.off; S.starts = Q.starts;
+  S.S = h->pv_S.p; S.t = h->t.p; S.t_stride = h->t_stride;
+  S.xs_stride = xs_stride; S.ux = dux.p; S.out_stride = (long)M;
+  double* dmean = mean ? dout.p : nullptr;
+  double* dvar = var ? dout.p + (mean ? B * Mm : 0) : nullptr;
+  const long cells = (long)h->L * h->nchunk;
+  clr::launch_relayout(h->y.p, h->y_stride, h->bs_x.p, cells, h->B, h->N, h->L, h->nchunk, 0, s);
+  for (int m0 = 0; m0 < M; m0 += R) {
+    S.npts = std::min(R, M - m0); S.xs = dxs.p + m0;
+    S.mean = dmean ? dmean + m0 : nullptr; S.var = dvar ? dvar + m0 : nullptr;
+    h->launch->bfilter(P, S, xfast, s);
+    S.have_g = S.have_M = 1;
+    if (var) S.have_S = 1;
+  }
+  HIP_TRY(frame.stop());
+  std::vector<double> tmp(nout * B * Mm);
+  if ((st = frame.finish(tmp.data(), dout.p, nout * B * Mm)) != CLR_OK) return st;
+  h->bs_M_valid = true;
+  if (forms_S) h->pv_S_valid = true;
+  const double* tmean = tmp.data();
+  const double* tvar = tmp.data() + (mean ? B * Mm : 0);
+  if (pts.all_sorted) {
+    if (mean) std::copy(tmean, tmean + B * Mm, mean);
+    if (var) std::copy(tvar, tvar + B * Mm, var);
+  } else {
+    if (mean) pts.scatter(tmean, mean, B, Mm, xs_stride == 0);
+    if (var) pts.scatter(tvar, var, B, Mm, xs_stride == 0);
+  }
+  // the constant mean plus the conditional mean of the residual, as clr_batch_predict; under a linear mean the residual's
+  // alone -- the basis at the points is the caller's
+  if (mean && h->have_mean)
+    for (size_t p = 0; p < B; ++p) {
+      const double m = h->host_mean[h->mean_stride ? p : 0];
+      for (size_t k = 0; k < Mm; ++k) mean[p * Mm + k] = m + mean[p * Mm + k];
+    }
+  std::vector<int> stat;
+  return nan_rows_without_factor(h, stat, {{mean, Mm}, {var, Mm}});
 }
 
 // ---- clr_batch_leave_one_out: diag(K^-1), K^-1 r and the leave-one-out log predictive density of every problem

@@ -1009,6 +1009,7 @@ __global__ void __launch_bounds__(64) warm_check_kernel(const BatchParams P) {
 #include "clr_bpredvar_kernels.h"
 #include "clr_binvdiag_kernels.h"
 #include "clr_bpredvar_rec_kernels.h"
+#include "clr_bfilter_kernels.h"
 namespace clr {
 
 // One table entry per (JR, JC): host-callable launchers.
@@ -1038,6 +1039,10 @@ struct BatchLaunchers {
   // k(0) - k*^T K^-1 k* for all problems at one tile of SORTED prediction points by the two matrix recurrences
   // (clr_bpredvar_rec_kernels.h): S.xs -> S.var; `xfast`: the points' phases stay below CLR_FAST_TRIG_LIMIT
   void (*bpredvar_rec)(const BatchParams&, BPredVarRecParams S, int xfast, hipStream_t);
+  // L^-1 b for all problems and right-hand sides from the materialised factor (S.xT -> S.zT), and with a tile of SORTED
+  // points (S.npts > 0) the mean (S.mean) and variance (S.var) at each given the samples strictly before it
+  // (clr_bfilter_kernels.h); `xfast`: the points' phases stay below CLR_FAST_TRIG_LIMIT
+  void (*bfilter)(const BatchParams&, BFilterParams S, int xfast, hipStream_t);
   // lean factor of problem b (replay mode 3) -> the reference's storage, phi and u regenerated (t: the problem's row-major times)
   void (*expand)(const BatchParams&, int b, const double* t, double* phi, double* u, double* W, double* D, hipStream_t);
   int elem_doubles, start_doubles;
@@ -1238,6 +1243,46 @@ struct BatchImpl {
     if (S.lean) { if (P.fast_trig) bpredvar_rec_go<true, true>(P, S, xfast, s); else bpredvar_rec_go<true, false>(P, S, xfast, s); }
     else bpredvar_rec_go<false, true>(P, S, xfast, s);  // (the stored phi, u: no trigonometry)
   }
+  // the causal half, forward only: unless an earlier tile of the call has formed them, the chunks' start states of g (the
+  // solve's own summarize -- with the chunk maps unless they are formed -- and forward walk); with S.var, unless formed, the
+  // chunks' start states of S (the recurrence variance's offsets and walk); the points' features; the forward recurrence
+  template <bool LEAN, bool FAST>
+  static void bfilter_go(const BatchParams& P, const BFilterParams& S, int xfast, hipStream_t s) {
+    constexpr int J = JR + 2 * JC;
+    const unsigned lanes = (unsigned)((P.nchunk + 63) / 64), R = (unsigned)S.nrhs;
+    const dim3 grid(lanes, P.B, R), wgrid((P.B + 63) / 64), pgrid((unsigned)(((long)P.B * S.nrhs + 63) / 64));
+    if (!S.have_g) {
+      BSolveParams Q;
+      Q.nrhs = S.nrhs; Q.r = 0; Q.lean = S.lean; Q.have_M = S.have_M;
+      Q.xT = const_cast<double*>(S.xT); Q.M = S.M; Q.off = S.off; Q.starts = S.starts;
+      if (!S.have_M) {
+        hipLaunchKernelGGL((bsolve_summarize_kernel<JR, JC, LEAN, FAST, true>), dim3(lanes, P.B, 1), dim3(64), 0, s, P, Q);
+        Q.r = 1;
+      }
+      if (Q.r < S.nrhs)
+        hipLaunchKernelGGL((bsolve_summarize_kernel<JR, JC, LEAN, FAST, false>), dim3(lanes, P.B, R - Q.r), dim3(64), 0, s, P, Q);
+      hipLaunchKernelGGL((bsolve_prefix_kernel<J, false>), pgrid, dim3(64), 0, s, P, Q);
+    }
+    if (S.var && !S.have_S) {
+      BPredVarRecParams V{};
+      V.lean = S.lean; V.S = S.S; V.t = S.t; V.t_stride = S.t_stride;
+      hipLaunchKernelGGL((bpvrec_forward_kernel<JR, JC, LEAN, FAST, false>), dim3(lanes, P.B), dim3(64), 0, s, P, V);
+      hipLaunchKernelGGL((bpvrec_walk_kernel<JR, JC>), wgrid, dim3(64), 0, s, P, V);
+    }
+    if (S.npts == 0) {
+      hipLaunchKernelGGL((bfilter_forward_kernel<JR, JC, LEAN, FAST, false, false>), grid, dim3(64), 0, s, P, S);
+      return;
+    }
+    const dim3 fgrid((unsigned)(((long)P.B * S.npts + 255) / 256));
+    if (xfast) hipLaunchKernelGGL((bfilter_features_kernel<JR, JC, true>), fgrid, dim3(256), 0, s, P, S);
+    else hipLaunchKernelGGL((bfilter_features_kernel<JR, JC, false>), fgrid, dim3(256), 0, s, P, S);
+    if (S.var) hipLaunchKernelGGL((bfilter_forward_kernel<JR, JC, LEAN, FAST, true, true>), grid, dim3(64), 0, s, P, S);
+    else hipLaunchKernelGGL((bfilter_forward_kernel<JR, JC, LEAN, FAST, true, false>), grid, dim3(64), 0, s, P, S);
+  }
+  static void bfilter(const BatchParams& P, BFilterParams S, int xfast, hipStream_t s) {
+    if (S.lean) { if (P.fast_trig) bfilter_go<true, true>(P, S, xfast, s); else bfilter_go<true, false>(P, S, xfast, s); }
+    else bfilter_go<false, true>(P, S, xfast, s);  // (the stored phi, u: no trigonometry)
+  }
   static void compose_check(const BatchParams& P, int g, double* coop, double* ref, hipStream_t s) {
     constexpr int J = JR + 2 * JC;
     const int np = (P.nchunk + g - 1) / g;
@@ -1290,7 +1335,7 @@ struct BatchImpl {
   }
   static BatchLaunchers table() {
     return BatchLaunchers{&summarize, &prefix, &correct, &replay, &sequential, &compose_check, &warm, &grad, &grad_reverse,
-                          &bsolve, &bdotl, &bdot, &bpredvar, &binvdiag, &bpredvar_rec, &expand, Widths<JR, JC>::ELEM, Widths<JR, JC>::START};
+                          &bsolve, &bdotl, &bdot, &bpredvar, &binvdiag, &bpredvar_rec, &bfilter, &expand, Widths<JR, JC>::ELEM, Widths<JR, JC>::START};
   }
 };
 

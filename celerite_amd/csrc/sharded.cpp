@@ -683,6 +683,19 @@ int clr_sharded_leave_one_out(clr_sharded* h, double* kinv_diag, double* alpha, 
   });
 }
 
+int clr_sharded_one_step_ahead(clr_sharded* h, int nrhs, const double* b, double* innovation, double* variance, int* status) {
+  const long N = h->N, per = (long)nrhs * h->N;
+  return on_slices(h, nrhs >= 1 && (b || nrhs == 1) && (innovation || variance || status), [=](clr_batch* p, long lo) {
+    return clr_batch_one_step_ahead(p, nrhs, b ? b + lo * per : nullptr, at(innovation, lo * per), at(variance, lo * N), at(status, lo));
+  });
+}
+
+int clr_sharded_forecast(clr_sharded* h, int M, const double* xs, long xs_stride, double* mean, double* var) {
+  return on_slices(h, M >= 0 && (M == 0 || (xs && (mean || var))) && (xs_stride == 0 || xs_stride == M), [=](clr_batch* p, long lo) {
+    return clr_batch_forecast(p, M, xs + lo * xs_stride, xs_stride, at(mean, lo * (long)M), at(var, lo * (long)M));
+  });
+}
+
 int clr_sharded_run_timed(clr_sharded* h, int steps, double* shard_ms /* [nshards] or NULL */) {
   // (a timing tool: every shard times its own steps and settles them by its own counts)
   const int st0 = resolve_all(h);

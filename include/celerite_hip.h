@@ -606,6 +606,41 @@ int clr_batch_set_predict_tile(clr_batch* h, int points);
  * reaches ~1e9 the result carries that phase's rounding (1e-8 k(0) at t ~ 3e8), which clr_batch_predict_var's
  * cross-covariances of x - t_n do not.  clr_batch_get_solve_ms then reports this call's device time. */
 int clr_batch_predict_var_recurrence(clr_batch* h, int M, const double* xs, long xs_stride, double* var);
+/* The causal half of the factor of the last materialising run, K = L diag(D) L^T: the one-step-ahead residuals
+ * (innovations) z = L^-1 b and their variances D for every problem.  b host [B][nrhs][N] as for clr_batch_solve; b == NULL
+ * with nrhs == 1: the residual in force (y less the mean of clr_batch_set_mean / _set_mean_weights, already in HBM, no
+ * upload), any other nrhs with b == NULL is CLR_INVALID_ARGUMENT.  innovation [B][nrhs][N] = L^-1 b, undivided;
+ * variance [B][N] = D (diag_n + jitter enters it), shared by all right-hand sides; status [B].  Each may be NULL, not all:
+ * CLR_INVALID_ARGUMENT.  For the residual r:  E[y_n | y_<n] = y_n - z_n with variance D_n, z_n / sqrt(D_n) is white and
+ * standard normal under the model, and sum_n -1/2 (log 2 pi D_n + z_n^2 / D_n) is the log-likelihood.  With
+ *     z_n = b_n - u[n] . g_n ,  g+_n = g_n + W[n] z_n ,  g_{n+1} = phi[n] o g+_n ,  g_0 = 0
+ * this is the forward sweep of clr_batch_solve before its division by D, and none of its backward half: widths 1..8 one
+ * forward chunked scan on chunked plans (N >= 128, either factor layout; csrc/clr_bfilter_kernels.h), the chunk maps shared
+ * with clr_batch_solve under its validity rule; widths 9..64 the forward sweep of clr_batch_solve's wide route, N >= 512
+ * (else CLR_UNSUPPORTED, as clr_batch_solve).  Statuses are those of the evaluation in force (clr_batch_get_results); rows
+ * of problems whose status is not CLR_OK are NaN in every output.  clr_batch_get_solve_ms then reports this call's device
+ * time. */
+int clr_batch_one_step_ahead(clr_batch* h, int nrhs, const double* b, double* innovation, double* variance, int* status);
+/* The causal forecast: mean and variance of every problem's process at M points each given only the samples STRICTLY
+ * before the point, p(f(x) | y_n : t_n < x), from the factor of the last materialising run -- xs, xs_stride, sorting and
+ * tiling exactly as clr_batch_predict_var_recurrence (host [B][M] with xs_stride = M, or M shared points with
+ * xs_stride = 0; unsorted points go through a host index permutation, NaN last, and the results are scattered back; tiles
+ * follow clr_batch_set_predict_tile).  With m = #{n : t_n < x}, g+ the forward state of clr_batch_one_step_ahead on the
+ * residual in force and S+ the factorisation's own state (S+_n = S_n + D_n W_n W_n^T, S_{n+1} = Phi_n S+_n Phi_n, S_0 = 0)
+ *     psi = exp(-c (x - t_{m-1})) ,  w = psi o u(x) ,  mean(x) = w^T g+_{m-1} ,  var(x) = k(0) - w^T S+_{m-1} w
+ * and m = 0 gives the prior: mean 0, var k(0).  mean host [B][M]: the conditional mean of the residual process plus, as
+ * in clr_batch_predict, the constant mean of clr_batch_set_mean; under a linear mean the residual's alone -- the model at
+ * the points is the caller's.  var host [B][M]: the conditional variance of the latent process (no jitter, no
+ * observational variance), as clr_batch_predict_var.  Either may be NULL, not both; with var == NULL the state S is
+ * neither formed nor carried.  Strict < is deliberate: at x = t_n the result is the one-step-ahead prediction of sample n,
+ * y_n - z_n and D_n - diag_n - jitter.  One forward pass over the series per tile plus O(J^2) per point
+ * (csrc/clr_bfilter_kernels.h): narrow plans only (widths 1..8, chunked: N >= 128, either factor layout); a wide plan
+ * returns CLR_UNSUPPORTED -- take clr_batch_predict / clr_batch_predict_var there.  The start states of S are shared with
+ * clr_batch_predict_var_recurrence and kept until the next materialising run; those of g follow the residual and are
+ * formed by every call.  A point's exponentials are the library's: its result depends on neither the tile, the batch nor
+ * the sharding, bit for bit.  A NaN point gives NaN; rows of problems whose status is not CLR_OK are NaN.
+ * clr_batch_get_solve_ms then reports this call's device time. */
+int clr_batch_forecast(clr_batch* h, int M, const double* xs, long xs_stride, double* mean, double* var);
 /* diag(K^-1), K^-1 r and the leave-one-out log predictive density of every problem from the factor of the last
  * materialising run.  kinv_diag [B][N], alpha [B][N], loo_logpdf [B], status [B]: each may be NULL and is then neither
  * computed beyond need nor copied down (alpha or loo_logpdf: the batched solve of the residual in force runs); all four
@@ -896,8 +931,9 @@ int clr_sharded_get_coefficients(clr_sharded* h, double* jitter, double* a_real,
 /* The consumers of the factor on a sharded batch (GP.apply_inverse / .sample / .predict for B problems over several
  * GPUs): clr_sharded_materialize runs clr_batch_enqueue(plan, 1) on every shard, settles the evaluation with the
  * batch-wide counts (results as clr_sharded_get_results; any pointer may be NULL) and leaves every shard's factor in
- * its HBM; clr_sharded_solve / _dot_L / _dot / _predict / _predict_var / _predict_var_recurrence / _leave_one_out are
- * clr_batch_solve / _dot_L / _dot / _predict / _predict_var / _predict_var_recurrence / _leave_one_out on every shard concurrently,
+ * its HBM; clr_sharded_solve / _dot_L / _dot / _predict / _predict_var / _predict_var_recurrence / _leave_one_out /
+ * _one_step_ahead / _forecast are clr_batch_solve / _dot_L / _dot / _predict / _predict_var / _predict_var_recurrence /
+ * _leave_one_out / _one_step_ahead / _forecast on every shard concurrently,
  * each on its contiguous slice of the host arrays ([B][nrhs][N]; xs [B][M] or shared with xs_stride = 0).  No
  * collective: every problem's state is its own (cholesky.h:703-706). */
 int clr_sharded_materialize(clr_sharded* h, double* loglike, double* logdet, double* quad, int* status);
@@ -908,6 +944,8 @@ int clr_sharded_predict(clr_sharded* h, int M, const double* xs, long xs_stride,
 int clr_sharded_predict_var(clr_sharded* h, int M, const double* xs, long xs_stride, double* var);
 int clr_sharded_predict_var_recurrence(clr_sharded* h, int M, const double* xs, long xs_stride, double* var);
 int clr_sharded_leave_one_out(clr_sharded* h, double* kinv_diag, double* alpha, double* loo_logpdf, int* status);
+int clr_sharded_one_step_ahead(clr_sharded* h, int nrhs, const double* b, double* innovation, double* variance, int* status);
+int clr_sharded_forecast(clr_sharded* h, int M, const double* xs, long xs_stride, double* mean, double* var);
 /* `steps` back-to-back evaluations on every shard concurrently (HIP events per shard);
  * shard_ms[s] = that shard's first-to-last event time. */
 int clr_sharded_run_timed(clr_sharded* h, int steps, double* shard_ms);
