@@ -2601,6 +2601,138 @@ int clr_batch_forecast(clr_batch* h, int M, const double* xs, long xs_stride, do
   return nan_rows_without_factor(h, stat, {{mean, Mm}, {var, Mm}});
 }
 
+// ---- clr_batch_predict_terms: the posterior of every group of kernel terms (clr_bterms_kernels.h)
+
+// The mean k_g*^T K^-1 r and the variance k_g(0) - k_g*^T K^-1 k_g* of G groups of coefficient terms at M points per
+// problem.  With `mean`: alpha = K^-1 r by the batched solve (left on the device), laid out chunk-interleaved once, the
+// chunks' start states of p and b by the first tile (they follow the residual: never kept).  With `var`: the start states
+// of S (pv_S) and Q (loo_Q) under the rules of clr_batch_predict_var_recurrence -- a mean-only call touches neither.
+// Points, sorting and tiles as clr_batch_forecast; the per-point buffers grow with G.  No mean is added: it belongs to no
+// term.
+int clr_batch_predict_terms(clr_batch* h, int M, const double* xs, long xs_stride, int G, const unsigned char* groups,
+                            double* mean, double* var) {
+  int st = require_device(h->device);
+  if (st != CLR_OK) return st;
+  if (M < 0 || (M > 0 && !xs)) return fail(CLR_INVALID_ARGUMENT, "clr_batch_predict_terms: M >= 0 and the points");
+  if (G < 1 || !groups) return fail(CLR_INVALID_ARGUMENT, "clr_batch_predict_terms: G >= 1 and the groups");
+  if (!mean && !var) return fail(CLR_INVALID_ARGUMENT, "clr_batch_predict_terms: at least one output array");
+  if (xs_stride != 0 && xs_stride != M) return fail(CLR_INVALID_ARGUMENT, "clr_batch_predict_terms: the points' stride is 0 (shared by all problems) or M");
+  if ((st = require_celerite_width(h, "clr_batch_predict_terms")) != CLR_OK) return st;
+  const int T = h->J_real + h->J_comp;
+  for (size_t k = 0; k < (size_t)G * T; ++k)
+    if (groups[k] > 1) return fail(CLR_INVALID_ARGUMENT, "clr_batch_predict_terms: a group is 0 or 1 per coefficient term");
+  if (M == 0) return CLR_OK;
+  if ((st = require_factor(h, true)) != CLR_OK) return st;
+  if (!h->launch)
+    return fail(CLR_UNSUPPORTED, "clr_batch_predict_terms covers narrow plans (widths 1..8): a wide plan takes clr_batch_predict / clr_batch_predict_var for the full kernel");
+  if (h->nchunk < 2) return fail(CLR_UNSUPPORTED, "clr_batch_predict_terms needs a chunked plan (N >= 128), as clr_batch_predict on a narrow plan does");
+  if (mean && (st = batch_solve_impl(h, 1, nullptr, nullptr)) != CLR_OK) return st;  // alpha = K^-1 r -> bs_rm [B][N]
+  clr::BatchParams P;
+  if ((st = consumer_params(h, false, P)) != CLR_OK) return st;
+  const size_t B = (size_t)h->B, J = (size_t)h->J, Mm = (size_t)M, Gg = (size_t)G, nsrc = xs_stride == 0 ? 1 : B;
+  const size_t nc = (size_t)h->nchunk, NS = J * (J + 1) / 2, nout = (mean ? 1 : 0) + (var ? 1 : 0);
+  const size_t cells = (size_t)h->L * nc;
+  // a group's rows: a real term its one row, a complex term its cos and its sin row
+  std::vector<unsigned> rowmask(Gg, 0u);
+  for (size_t g = 0; g < Gg; ++g)
+    for (int k = 0; k < T; ++k) {
+      if (!groups[g * T + k]) continue;
+      if (k < h->J_real) rowmask[g] |= 1u << k;
+      else rowmask[g] |= 3u << (h->J_real + 2 * (k - h->J_real));
+    }
+  SortedPoints pts;
+  pts.sort(xs, nsrc, Mm);
+  const int xfast = (sel_max(h->dmax, h->floor_dmax) * pts.xmax < CLR_FAST_TRIG_LIMIT) ? 1 : 0;
+  // points per tile: the caller's, or the most whose per-point buffers (u(x), v(x); e and left per group) fit in 1 GiB
+  const size_t budget = (size_t)1 << 27, per_point = B * (2 * J + (var ? Gg * (J + 1) : 0));
+  const size_t Rz = std::min<size_t>(h->predict_tile > 0 ? (size_t)h->predict_tile : std::max<size_t>(1, budget / per_point), Mm);
+  const int R = (int)Rz;
+  DevBuf dxs, dout, dux, dvx, de, dleft, dbstart;  // dout: mean [B][G][M] | var [B][G][M], those asked for
+  clr::Buffer<unsigned> dmask;
+  if ((st = dxs.reserve(nsrc * Mm)) != CLR_OK) return st;
+  if ((st = dout.reserve(nout * B * Gg * Mm)) != CLR_OK) return st;
+  if ((st = dux.reserve(B * Rz * J)) != CLR_OK) return st;
+  if ((st = dvx.reserve(B * Rz * J)) != CLR_OK) return st;
+  if ((st = dmask.reserve(Gg)) != CLR_OK) return st;
+  if (mean) {
+    if ((st = h->bs_x.reserve(B * cells)) != CLR_OK) return st;
+    if ((st = h->bs_decay.reserve(B * nc * J)) != CLR_OK) return st;
+    if ((st = h->bs_off.reserve(B * nc * J)) != CLR_OK) return st;
+    if ((st = h->bs_starts.reserve(B * nc * J)) != CLR_OK) return st;
+    if ((st = dbstart.reserve(B * nc * J)) != CLR_OK) return st;
+  }
+  if (var) {
+    if ((st = de.reserve(B * Rz * Gg * J)) != CLR_OK) return st;
+    if ((st = dleft.reserve(B * Rz * Gg)) != CLR_OK) return st;
+    if ((st = h->pv_S.reserve(B * nc * NS)) != CLR_OK) return st;
+    if ((st = h->loo_Q.reserve(B * nc * NS)) != CLR_OK) return st;
+    if ((st = h->bs_M.reserve(B * nc * J * J)) != CLR_OK) return st;
+    if ((st = h->bs_off.reserve(B * nc * J)) != CLR_OK) return st;
+    if ((st = h->bs_x.reserve(B * cells)) != CLR_OK) return st;  // (read beside by the solve's summarize when it forms the maps)
+  }
+  const double solve_ms = mean ? h->solve_device_ms : 0.0;  // (the solve above: reported with this frame's kernels)
+  ConsumerFrame frame{h};
+  hipStream_t s = h->stream.get();
+  HIP_TRY(hipMemcpyAsync(dxs.p, pts.up, nsrc * Mm * sizeof(double), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(dmask.p, rowmask.data(), Gg * sizeof(unsigned), hipMemcpyHostToDevice, s));
+  HIP_TRY(frame.start());
+  clr::BTermsParams S{};
+  S.G = G; S.lean = h->factor_is_lean ? 1 : 0;
+  S.xs_stride = xs_stride; S.rowmask = dmask.p;
+  S.ux = dux.p; S.vx = dvx.p; S.e = de.p; S.left = dleft.p; S.out_stride = (long)M;
+  if (mean) {  // the series of alpha chunk-interleaved, once per call
+    clr::launch_relayout(h->bs_rm.p, (long)h->N, h->bs_x.p, (long)cells, h->B, h->N, h->L, h->nchunk, 0, s);
+    S.aT = h->bs_x.p;
+    S.pb.nrhs = 1; S.pb.zT = h->bs_x.p; S.pb.yT = h->bs_x.p; S.pb.decay = h->bs_decay.p; S.pb.off = h->bs_off.p;
+    S.pstart = h->bs_starts.p; S.bstart = dbstart.p;
+  }
+  bool forms_Q = false;
+  if (var) {
+    S.have_S = h->pv_S_valid ? 1 : 0;
+    S.have_Q = h->loo_Q_valid ? 1 : 0;
+    S.Q.lean = S.lean;
+    S.Q.have_M = h->bs_M_valid ? 1 : 0;
+    forms_Q = !S.have_Q;  // ... and with them the chunk maps, unless a solve has formed those
+    if (forms_Q) h->bs_M_valid = false;
+    h->pv_S_valid = h->loo_Q_valid = false;
+    // (with `mean` the chunk maps are the solve's and bs_x holds alpha: the summarize beside them is not run)
+    S.Q.cT = h->bs_x.p; S.Q.M = h->bs_M.p; S.Q.Q = h->loo_Q.p; S.Q.off = h->bs_off.p;
+    S.t = h->t.p; S.t_stride = h->t_stride; S.S = h->pv_S.p;
+  }
+  double* dmean = mean ? dout.p : nullptr;
+  double* dvar = var ? dout.p + (mean ? B * Gg * Mm : 0) : nullptr;
+  for (int m0 = 0; m0 < M; m0 += R) {
+    S.npts = std::min(R, M - m0); S.xs = dxs.p + m0;
+    S.mean = dmean ? dmean + m0 : nullptr; S.var = dvar ? dvar + m0 : nullptr;
+    h->launch->bterms(P, S, xfast, s);
+    S.have_pb = 1;
+    if (var) S.have_S = S.have_Q = 1;
+  }
+  HIP_TRY(frame.stop());
+  std::vector<double> tmp(nout * B * Gg * Mm);
+  if ((st = frame.finish(tmp.data(), dout.p, nout * B * Gg * Mm)) != CLR_OK) return st;
+  h->solve_device_ms += solve_ms;
+  if (var) {
+    h->pv_S_valid = h->loo_Q_valid = true;
+    if (forms_Q) h->bs_M_valid = true;
+  }
+  const double* tsrc[2] = {tmp.data(), tmp.data() + (mean ? B * Gg * Mm : 0)};
+  double* tdst[2] = {mean, var};
+  for (int o = 0; o < 2; ++o) {
+    if (!tdst[o]) continue;
+    if (pts.all_sorted) { std::copy(tsrc[o], tsrc[o] + B * Gg * Mm, tdst[o]); continue; }
+    for (size_t b = 0; b < B; ++b) {
+      const int* pp = pts.perm.data() + (xs_stride == 0 ? 0 : b * Mm);
+      for (size_t g = 0; g < Gg; ++g) {
+        const size_t at = (b * Gg + g) * Mm;
+        for (size_t m = 0; m < Mm; ++m) tdst[o][at + pp[m]] = tsrc[o][at + m];
+      }
+    }
+  }
+  std::vector<int> stat;
+  return nan_rows_without_factor(h, stat, {{mean, Gg * Mm}, {var, Gg * Mm}});
+}
+
 // ---- clr_batch_leave_one_out: diag(K^-1), K^-1 r and the leave-one-out log predictive density of every problem
 
 // widths 9..64: diag(K^-1) of one problem per wave from the factor in the reference's storage, sequential in n (the

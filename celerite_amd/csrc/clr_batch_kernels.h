@@ -1010,6 +1010,7 @@ __global__ void __launch_bounds__(64) warm_check_kernel(const BatchParams P) {
 #include "clr_binvdiag_kernels.h"
 #include "clr_bpredvar_rec_kernels.h"
 #include "clr_bfilter_kernels.h"
+#include "clr_bterms_kernels.h"
 namespace clr {
 
 // One table entry per (JR, JC): host-callable launchers.
@@ -1043,6 +1044,9 @@ struct BatchLaunchers {
   // points (S.npts > 0) the mean (S.mean) and variance (S.var) at each given the samples strictly before it
   // (clr_bfilter_kernels.h); `xfast`: the points' phases stay below CLR_FAST_TRIG_LIMIT
   void (*bfilter)(const BatchParams&, BFilterParams S, int xfast, hipStream_t);
+  // the posterior mean (S.mean) and variance (S.var) of every group of kernel terms for all problems at one tile of SORTED
+  // points (clr_bterms_kernels.h); `xfast`: the points' phases stay below CLR_FAST_TRIG_LIMIT
+  void (*bterms)(const BatchParams&, BTermsParams S, int xfast, hipStream_t);
   // lean factor of problem b (replay mode 3) -> the reference's storage, phi and u regenerated (t: the problem's row-major times)
   void (*expand)(const BatchParams&, int b, const double* t, double* phi, double* u, double* W, double* D, hipStream_t);
   int elem_doubles, start_doubles;
@@ -1283,6 +1287,60 @@ struct BatchImpl {
     if (S.lean) { if (P.fast_trig) bfilter_go<true, true>(P, S, xfast, s); else bfilter_go<true, false>(P, S, xfast, s); }
     else bfilter_go<false, true>(P, S, xfast, s);  // (the stored phi, u: no trigonometry)
   }
+  // component separation at one tile of sorted points: the points' features; with S.mean, unless an earlier tile of the
+  // call has formed them, the chunks' start states of b and p (the two passes of the batched dot on alpha, offsets and
+  // walks) and the two mean replays; with S.var, unless formed, the start states of S and Q exactly as bpredvar_rec_go,
+  // and the two variance replays
+  template <bool FAST>
+  static void bterms_mean_go(const BatchParams& P, const BTermsParams& S, hipStream_t s) {
+    constexpr int J = JR + 2 * JC;
+    const dim3 grid((P.nchunk + 63) / 64, P.B), wgrid((P.B + 63) / 64);
+    if (!S.have_pb) {
+      BDotParams D = S.pb;
+      D.starts = S.bstart;
+      hipLaunchKernelGGL((bdot_kernel<JR, JC, FAST, 0, false>), grid, dim3(64), 0, s, P, D);
+      hipLaunchKernelGGL((bdot_prefix_kernel<J, 0>), wgrid, dim3(64), 0, s, P, D);
+      D.starts = S.pstart;
+      hipLaunchKernelGGL((bdot_kernel<JR, JC, FAST, 1, false>), grid, dim3(64), 0, s, P, D);
+      hipLaunchKernelGGL((bdot_prefix_kernel<J, 1>), wgrid, dim3(64), 0, s, P, D);
+    }
+    hipLaunchKernelGGL((bterms_mean_forward_kernel<JR, JC, FAST>), grid, dim3(64), 0, s, P, S);
+    hipLaunchKernelGGL((bterms_mean_backward_kernel<JR, JC, FAST>), grid, dim3(64), 0, s, P, S);
+  }
+  template <bool LEAN, bool FAST>
+  static void bterms_var_go(const BatchParams& P, const BTermsParams& S, hipStream_t s) {
+    const dim3 grid((P.nchunk + 63) / 64, P.B), wgrid((P.B + 63) / 64);
+    if (!S.have_S) {
+      BPredVarRecParams V{};
+      V.lean = S.lean; V.S = S.S; V.t = S.t; V.t_stride = S.t_stride;
+      hipLaunchKernelGGL((bpvrec_forward_kernel<JR, JC, LEAN, FAST, false>), grid, dim3(64), 0, s, P, V);
+      hipLaunchKernelGGL((bpvrec_walk_kernel<JR, JC>), wgrid, dim3(64), 0, s, P, V);
+    }
+    if (!S.have_Q) {
+      if (!S.Q.have_M) {  // (as binvdiag_go: the offsets beside the maps go to Q.off and are not used)
+        BSolveParams Q;
+        Q.nrhs = 1; Q.r = 0; Q.lean = S.lean; Q.have_M = 0;
+        Q.xT = S.Q.cT; Q.M = S.Q.M; Q.off = S.Q.off; Q.starts = nullptr;
+        hipLaunchKernelGGL((bsolve_summarize_kernel<JR, JC, LEAN, FAST, true>), grid, dim3(64), 0, s, P, Q);
+      }
+      hipLaunchKernelGGL((binvdiag_kernel<JR, JC, LEAN, FAST, false>), grid, dim3(64), 0, s, P, S.Q);
+      hipLaunchKernelGGL((binvdiag_walk_kernel<JR + 2 * JC>), wgrid, dim3(64), 0, s, P, S.Q);
+    }
+    hipLaunchKernelGGL((bterms_var_forward_kernel<JR, JC, LEAN, FAST>), grid, dim3(64), 0, s, P, S);
+    hipLaunchKernelGGL((bterms_var_backward_kernel<JR, JC, LEAN, FAST>), grid, dim3(64), 0, s, P, S);
+  }
+  static void bterms(const BatchParams& P, BTermsParams S, int xfast, hipStream_t s) {
+    const dim3 fgrid((unsigned)(((long)P.B * S.npts + 255) / 256));
+    BPredVarRecParams X{};
+    X.npts = S.npts; X.xs = S.xs; X.xs_stride = S.xs_stride; X.ux = S.ux; X.e = S.vx;
+    if (xfast) hipLaunchKernelGGL((bpvrec_features_kernel<JR, JC, true>), fgrid, dim3(256), 0, s, P, X);
+    else hipLaunchKernelGGL((bpvrec_features_kernel<JR, JC, false>), fgrid, dim3(256), 0, s, P, X);
+    if (S.mean) { if (P.fast_trig) bterms_mean_go<true>(P, S, s); else bterms_mean_go<false>(P, S, s); }
+    if (S.var) {
+      if (S.lean) { if (P.fast_trig) bterms_var_go<true, true>(P, S, s); else bterms_var_go<true, false>(P, S, s); }
+      else bterms_var_go<false, true>(P, S, s);  // (the stored phi, u: no trigonometry)
+    }
+  }
   static void compose_check(const BatchParams& P, int g, double* coop, double* ref, hipStream_t s) {
     constexpr int J = JR + 2 * JC;
     const int np = (P.nchunk + g - 1) / g;
@@ -1335,7 +1393,7 @@ struct BatchImpl {
   }
   static BatchLaunchers table() {
     return BatchLaunchers{&summarize, &prefix, &correct, &replay, &sequential, &compose_check, &warm, &grad, &grad_reverse,
-                          &bsolve, &bdotl, &bdot, &bpredvar, &binvdiag, &bpredvar_rec, &bfilter, &expand, Widths<JR, JC>::ELEM, Widths<JR, JC>::START};
+                          &bsolve, &bdotl, &bdot, &bpredvar, &binvdiag, &bpredvar_rec, &bfilter, &bterms, &expand, Widths<JR, JC>::ELEM, Widths<JR, JC>::START};
   }
 };
 

@@ -696,6 +696,15 @@ int clr_sharded_forecast(clr_sharded* h, int M, const double* xs, long xs_stride
   });
 }
 
+int clr_sharded_predict_terms(clr_sharded* h, int M, const double* xs, long xs_stride, int G, const unsigned char* groups,
+                              double* mean, double* var) {
+  const long per = (long)G * M;  // (the groups are the same on every shard)
+  return on_slices(h, M >= 0 && (M == 0 || xs) && G >= 1 && groups && (mean || var) && (xs_stride == 0 || xs_stride == M),
+                   [=](clr_batch* p, long lo) {
+    return clr_batch_predict_terms(p, M, xs + lo * xs_stride, xs_stride, G, groups, at(mean, lo * per), at(var, lo * per));
+  });
+}
+
 int clr_sharded_run_timed(clr_sharded* h, int steps, double* shard_ms /* [nshards] or NULL */) {
   // (a timing tool: every shard times its own steps and settles them by its own counts)
   const int st0 = resolve_all(h);

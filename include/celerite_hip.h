@@ -641,6 +641,27 @@ int clr_batch_one_step_ahead(clr_batch* h, int nrhs, const double* b, double* in
  * the sharding, bit for bit.  A NaN point gives NaN; rows of problems whose status is not CLR_OK are NaN.
  * clr_batch_get_solve_ms then reports this call's device time. */
 int clr_batch_forecast(clr_batch* h, int M, const double* xs, long xs_stride, double* mean, double* var);
+/* Component separation: the posterior of the process of a GROUP of kernel terms, for G groups at M points per problem,
+ * from the factor of the last materialising run:  mean_g(x) = k_g*^T K^-1 r  and  var_g(x) = k_g(0) - k_g*^T K^-1 k_g*,
+ * where k_g is the sum of the group's terms and K the full kernel with its diagonal.  groups host [G][T], T = J_real +
+ * J_comp bytes per group in the order of the coefficients (real terms first, then the complex ones), each 0 or 1 -- any
+ * other byte is CLR_INVALID_ARGUMENT; G >= 1.  mean, var host [B][G][M]; either may be NULL, not both.  xs, xs_stride,
+ * sorting and tiling exactly as clr_batch_forecast (the per-point buffers grow with G: 2 J doubles per problem, and
+ * G (J + 1) more with var).  The group with every term gives clr_batch_predict's conditional mean of the residual and
+ * clr_batch_predict_var_recurrence's variance to rounding; the empty group gives exactly 0 twice.  NO mean is added: the
+ * mean of clr_batch_set_mean / _set_mean_weights belongs to no term, and the residual in force (y less that mean) is what
+ * is decomposed.  The variance of a group is not the sum of its terms' variances, which is why groups are an input.
+ * m = #{n : t_n <= x} as in clr_batch_predict_var_recurrence.  Cost: with mean the batched solve of the residual plus
+ * one forward and one backward pass over the times and alpha alone; with var one forward and one backward pass over the
+ * factor; O(G J^2) per point; whatever G (csrc/clr_bterms_kernels.h).  Narrow plans only (widths 1..8, chunked: N >= 128,
+ * either factor layout): a wide plan returns CLR_UNSUPPORTED -- clr_batch_predict covers the full kernel there -- and so
+ * does an unchunked one, as for clr_batch_predict.  With var the start states of S and Q are shared with clr_batch_predict_var_recurrence / clr_batch_leave_one_out
+ * and kept until the next materialising run; a call without var neither forms nor invalidates them.  A point's
+ * exponentials are the library's: its result depends on neither the tile, the batch nor the sharding, bit for bit.  A NaN
+ * point gives NaN; rows of problems whose status is not CLR_OK are NaN.  clr_batch_get_solve_ms then reports this call's
+ * device time, the solve included. */
+int clr_batch_predict_terms(clr_batch* h, int M, const double* xs, long xs_stride, int G, const unsigned char* groups,
+                            double* mean, double* var);
 /* diag(K^-1), K^-1 r and the leave-one-out log predictive density of every problem from the factor of the last
  * materialising run.  kinv_diag [B][N], alpha [B][N], loo_logpdf [B], status [B]: each may be NULL and is then neither
  * computed beyond need nor copied down (alpha or loo_logpdf: the batched solve of the residual in force runs); all four
@@ -932,8 +953,8 @@ int clr_sharded_get_coefficients(clr_sharded* h, double* jitter, double* a_real,
  * GPUs): clr_sharded_materialize runs clr_batch_enqueue(plan, 1) on every shard, settles the evaluation with the
  * batch-wide counts (results as clr_sharded_get_results; any pointer may be NULL) and leaves every shard's factor in
  * its HBM; clr_sharded_solve / _dot_L / _dot / _predict / _predict_var / _predict_var_recurrence / _leave_one_out /
- * _one_step_ahead / _forecast are clr_batch_solve / _dot_L / _dot / _predict / _predict_var / _predict_var_recurrence /
- * _leave_one_out / _one_step_ahead / _forecast on every shard concurrently,
+ * _one_step_ahead / _forecast / _predict_terms are clr_batch_solve / _dot_L / _dot / _predict / _predict_var / _predict_var_recurrence /
+ * _leave_one_out / _one_step_ahead / _forecast / _predict_terms on every shard concurrently,
  * each on its contiguous slice of the host arrays ([B][nrhs][N]; xs [B][M] or shared with xs_stride = 0).  No
  * collective: every problem's state is its own (cholesky.h:703-706). */
 int clr_sharded_materialize(clr_sharded* h, double* loglike, double* logdet, double* quad, int* status);
@@ -946,6 +967,8 @@ int clr_sharded_predict_var_recurrence(clr_sharded* h, int M, const double* xs, 
 int clr_sharded_leave_one_out(clr_sharded* h, double* kinv_diag, double* alpha, double* loo_logpdf, int* status);
 int clr_sharded_one_step_ahead(clr_sharded* h, int nrhs, const double* b, double* innovation, double* variance, int* status);
 int clr_sharded_forecast(clr_sharded* h, int M, const double* xs, long xs_stride, double* mean, double* var);
+int clr_sharded_predict_terms(clr_sharded* h, int M, const double* xs, long xs_stride, int G, const unsigned char* groups,
+                              double* mean, double* var);
 /* `steps` back-to-back evaluations on every shard concurrently (HIP events per shard);
  * shard_ms[s] = that shard's first-to-last event time. */
 int clr_sharded_run_timed(clr_sharded* h, int steps, double* shard_ms);
