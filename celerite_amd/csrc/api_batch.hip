@@ -1,12 +1,12 @@
 // celerite_amd/csrc/api_batch.hip -- C ABI of the batched plans (clr_batch_*): HBM residency, path selection
-// (scan pipeline, warm-started recurrence, one-launch path, wide kernels, general terms), evaluation and results.
+// (scan pipeline, warm-started recurrence, one-launch path, wide kernels, general terms), evaluation and results.  The
+// consumers of a plan's factor and coefficients: api_batch_consumers.hip.
 #include "api_internal.h"
 #include "clr_options.h"
 #include "clr_group_hooks.h"
 #include "clr_kernel.h"
 #include "clr_bmean_kernels.h"
 
-#include <functional>
 #include <limits>
 
 extern "C" {
@@ -47,7 +47,6 @@ clr_batch* clr_batch_create(int B, int N, int J_real, int J_comp, int device) {
 void clr_batch_destroy(clr_batch* h) { delete h; }
 
 static int warm_plan_chunks(clr_batch* h);
-static int warm_resolve(clr_batch* h, bool* pin_current);
 static int warm_scan_spans(clr_batch* h);
 static void warm_select(clr_batch* h);
 static int plan_general_chunks(clr_batch* h);
@@ -660,7 +659,7 @@ int clr_batch_set_parameters(clr_batch* h, const double* params) {
 }
 
 // draws the program refused (evaluated at their stand-in coefficients): NaN and CLR_INVALID_ARGUMENT
-static void mark_refused(const clr_batch* h, double* a, double* b, double* c, int* status) {
+extern "C++" void mark_refused(const clr_batch* h, double* a, double* b, double* c, int* status) {
   if (!h->kp_in_force) return;
   for (size_t i = 0; i < (size_t)h->B; ++i) {
     if (!h->kp_refused[i]) continue;
@@ -1671,7 +1670,7 @@ static int resolve_finish(clr_batch* h, long pending_total, long eligible_total)
   return CLR_OK;
 }
 
-static int warm_resolve(clr_batch* h, bool* pin_current) {
+extern "C++" int warm_resolve(clr_batch* h, bool* pin_current) {
   if (pin_current) *pin_current = false;
   if (!h->res_open && !h->warm_inflight && !h->small_inflight && !h->rescue_inflight) {
     // (nothing in flight; an evaluation the sharded layer has already resolved left its results in the staging buffer)
@@ -1711,1361 +1710,6 @@ int clr_batch_get_results(clr_batch* h, double* loglike, double* logdet, double*
   if (logdet) memcpy(logdet, h->pin.p + B, B * sizeof(double));
   if (quad) memcpy(quad, h->pin.p + 2 * B, B * sizeof(double));
   if (status) memcpy(status, h->pin.p + 3 * B, B * sizeof(int));
-  return CLR_OK;
-}
-
-// ---- the batched consumers of a plan's factor and coefficients: clr_batch_get_factor, _solve, _dot_L, _dot, _predict
-
-// the factor of the last materialising run, still usable (a lean one is not once its series or coefficients changed);
-// `settle`: settle an evaluation in flight first and require a completed run -- all but clr_batch_get_factor
-static int require_factor(clr_batch* h, bool settle) {
-  int st;
-  if (settle && (st = warm_resolve(h, nullptr)) != CLR_OK) return st;
-  if (!h->have_factor || (settle && !h->factor_valid))
-    return fail(CLR_NOT_COMPUTED, settle ? "no materialising run has been made (clr_batch_enqueue(h, 1))"
-                                         : "no materialising run has been made");
-  if (h->factor_is_lean && h->factor_inputs_changed)
-    return fail(CLR_NOT_COMPUTED, "the lean factor's phi and u are regenerated from the plan's series and coefficients, "
-                                  "which were replaced after the materialising run: materialise again");
-  return CLR_OK;
-}
-
-// the consumers cover celerite terms up to width 64 (`entry`: the refused call)
-static int require_celerite_width(const clr_batch* h, const char* entry) {
-  if (h->J_general > 0 || h->J > clr::wide_max_width())
-    return fail(CLR_UNSUPPORTED, std::string(entry) + " covers celerite-only plans of widths 1..64");
-  return CLR_OK;
-}
-
-// a narrow consumer's parameters, the times read from the row-major series (lean: one time per step and lane) where the
-// evaluation stages them through LDS (solve, dot_L), or always (`row_major`, clr_batch_dot: it must not depend on an
-// evaluation having made the role-split summarize's chunk-interleaved copy)
-static int consumer_params(clr_batch* h, bool row_major, clr::BatchParams& P) {
-  const int st = batch_params(h, 0, P, false);
-  if (st != CLR_OK) return st;
-  if (row_major || P.staged) { P.t = h->t.p; P.t_stride = h->t_stride; P.lane_is = 1; P.lane_cs = h->L; P.staged = 0; }
-  return CLR_OK;
-}
-
-// One consumer call's device work, made before it queues anything: every return waits for the stream, so no kernel or
-// copy outlives the local buffers (declared before the frame) and host arrays it reads.  start() / stop() time the
-// kernels, never the copies, into solve_device_ms; finish() downloads n doubles of `result` into `out` and drains.
-struct ConsumerFrame {
-  clr_batch* h;
-  bool timed = false, drained = false;
-  ~ConsumerFrame() { if (!drained) (void)hipStreamSynchronize(h->stream.get()); }
-  hipError_t start() {
-    hipError_t r;
-    for (clr::Event& e : h->bs_ev)
-      if (!e && (r = clr::create_event(e)) != hipSuccess) return r;
-    timed = true;
-    return hipEventRecord(h->bs_ev[0].get(), h->stream.get());
-  }
-  hipError_t stop() { return hipEventRecord(h->bs_ev[1].get(), h->stream.get()); }
-  int finish(double* out = nullptr, const double* result = nullptr, size_t n = 0) {
-    HIP_TRY(hipGetLastError());
-    if (out) HIP_TRY(hipMemcpyAsync(out, result, n * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
-    drained = true;
-    HIP_TRY(hipStreamSynchronize(h->stream.get()));
-    float ms = 0.f;
-    if (timed) HIP_TRY(hipEventElapsedTime(&ms, h->bs_ev[0].get(), h->bs_ev[1].get()));
-    if (timed) h->solve_device_ms = ms;
-    return CLR_OK;
-  }
-};
-
-// a narrow consumer's kernels on the chunk-interleaved right-hand sides: the B * nrhs rows of `in` laid out into xT,
-// kernels(), and the result they leave in outT back row-major into bs_rm
-static void narrow_kernels(clr_batch* h, int nrhs, const double* in, long stride, double* xT, const double* outT,
-                           const std::function<void()>& kernels) {
-  const long cells = (long)h->L * h->nchunk;
-  const int rows = h->B * nrhs;
-  clr::launch_relayout(in, stride, xT, cells, rows, h->N, h->L, h->nchunk, 0, h->stream.get());
-  kernels();
-  clr::launch_relayout_back(outT, cells, h->bs_rm.p, (long)h->N, rows, h->N, h->L, h->nchunk, h->stream.get());
-}
-
-// problem p of the plan for the object API's kernels (the batched counterpart of generic_view)
-static clr::GenericProblem problem_view(const clr_batch* h, const clr::BatchParams& P, size_t p) {
-  clr::GenericProblem g;
-  g.N = h->N; g.J = h->J; g.J_real = h->J_real; g.J_comp = h->J_comp; g.J_general = 0;
-  g.a_real = P.a_real + p * h->J_real; g.c_real = P.c_real + p * h->J_real;
-  g.a_comp = P.a_comp + p * h->J_comp; g.b_comp = P.b_comp + p * h->J_comp;
-  g.c_comp = P.c_comp + p * h->J_comp; g.d_comp = P.d_comp + p * h->J_comp;
-  g.U = nullptr; g.V = nullptr;
-  g.t = h->t.p + p * (size_t)h->t_stride;
-  return g;
-}
-
-int clr_batch_get_factor(clr_batch* h, int p, double* phi, double* u, double* W, double* D) {
-  int st = require_device(h->device);
-  if (st != CLR_OK) return st;
-  if ((st = require_factor(h, false)) != CLR_OK) return st;
-  if (p < 0 || p >= h->B) return fail(CLR_INVALID_ARGUMENT, "problem index out of range");
-  const size_t N = (size_t)h->N, J = (size_t)h->J, Nm1 = N - 1, cells = (size_t)h->L * h->nchunk;
-  ConsumerFrame frame{h};
-  const double *fphi, *fu, *fW, *fD;
-  if (!h->launch) {  // widths 9..64: already in the reference's storage, problem after problem
-    fphi = h->phi.p + p * J * Nm1; fu = h->u.p + p * J * Nm1; fW = h->W.p + p * J * N; fD = h->D.p + p * N;
-  } else {
-    if ((st = h->fphi.reserve(J * Nm1)) != CLR_OK) return st;
-    if ((st = h->fu.reserve(J * Nm1)) != CLR_OK) return st;
-    if ((st = h->fW.reserve(J * N)) != CLR_OK) return st;
-    if ((st = h->fD.reserve(N)) != CLR_OK) return st;
-    if (h->factor_is_lean) {
-      // the lean layout holds W and D; phi and u are regenerated from the plan's times and the coefficients in force --
-      // which must still be the ones of the materialising run (require_factor)
-      clr::BatchParams P;
-      if ((st = batch_params(h, 0, P, false)) != CLR_OK) return st;
-      h->launch->expand(P, p, h->t.p + (size_t)p * (size_t)h->t_stride, h->fphi.p, h->fu.p, h->fW.p, h->fD.p, h->stream.get());
-    } else {
-      clr::launch_deinterleave_factor(h->phi.p + p * J * cells, h->u.p + p * J * cells,
-                                      h->W.p + p * J * cells, h->D.p + p * cells, h->fphi.p, h->fu.p,
-                                      h->fW.p, h->fD.p, h->N, h->J, h->L, h->nchunk, h->stream.get());
-    }
-    HIP_TRY(hipGetLastError());
-    fphi = h->fphi.p; fu = h->fu.p; fW = h->fW.p; fD = h->fD.p;
-  }
-  if (phi && J * Nm1) HIP_TRY(hipMemcpyAsync(phi, fphi, J * Nm1 * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
-  if (u && J * Nm1) HIP_TRY(hipMemcpyAsync(u, fu, J * Nm1 * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
-  if (W) HIP_TRY(hipMemcpyAsync(W, fW, J * N * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
-  if (D) HIP_TRY(hipMemcpyAsync(D, fD, N * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
-  return frame.finish();
-}
-
-// one launch over every problem of a wide plan (grid.z = problem) on its factor, about `want` chunks per problem
-static clr::SweepParams wide_sweep_params(const clr_batch* h, int nrhs, int want) {
-  clr::SweepParams P;
-  memset(&P, 0, sizeof(P));
-  const long N = h->N, J = h->J;
-  P.N = h->N; P.J = h->J; P.nrhs = nrhs; P.batch = h->B;
-  clr::chunking(h->N - 1, want, &P.L, &P.nchunk);
-  P.phi = h->phi.p; P.u = h->u.p; P.W = h->W.p; P.D = h->D.p;
-  P.stride_phi = J * (N - 1); P.stride_W = J * N; P.stride_D = N;
-  P.stride_in = P.stride_out = nrhs * N;
-  return P;
-}
-
-// the batched solve's sweeps on a wide plan: chunks per problem about two rounds of the chip's SIMDs over the batch
-// (2048 / B, at most the single solver's 1024, at least 2), chunks of at least 64 steps -- shared by clr_batch_solve,
-// clr_batch_predict_var and clr_batch_fit_mean_weights
-static clr::SweepParams wide_solve_params(const clr_batch* h, int nrhs) {
-  int want = std::min(clr::wsweep_chunks(h->N, h->J), std::max(2, 2048 / h->B));
-  if (want > (h->N - 1) / 64) want = std::max(1, (h->N - 1) / 64);
-  return wide_sweep_params(h, nrhs, want);
-}
-
-// the two sweeps of CholeskySolver::solve on `nrhs` right-hand sides per problem, row-major in `in` (problems `stride_in`
-// apart): forward into bs_x (undivided), backward into bs_rm [B][nrhs][N]; the workspace in bs_M.  The caller has
-// reserved the three for at least nrhs right-hand sides.
-static void wide_solve_sweeps(clr_batch* h, clr::SweepParams P, int nrhs, const double* in, long stride_in) {
-  P.nrhs = nrhs;
-  P.stride_out = (long)nrhs * (long)h->N;
-  P.stride_ws = (long)clr::wsweep_workspace_doubles(h->J, P.nchunk, nrhs);
-  P.in = in; P.stride_in = stride_in;
-  P.out = h->bs_x.p;
-  P.backward = 0;
-  clr::launch_wsweep_scan(P, h->bs_M.p, h->stream.get());
-  P.in = h->bs_x.p; P.stride_in = P.stride_out;
-  P.out = h->bs_rm.p;
-  P.backward = 1;
-  clr::launch_wsweep_scan(P, h->bs_M.p, h->stream.get());
-}
-
-// clr_batch_solve on a wide plan (widths 9..64): the factor lies in the reference's storage, problem after problem
-// (wide_scan_kernel, MODE 0), and the two sweeps of CholeskySolver::solve are the object API's chunked affine scans
-// (wsweep_kernels.hip: one wave per chunk, one lane per column of the chunk's map) launched ONCE for the whole batch --
-// grid.z = problem (SweepParams::batch).  Chunks per problem: about two rounds of the chip's SIMDs over the batch
-// (2048 / B, at most the single solver's 1024, at least 2).
-static int wide_batch_solve(clr_batch* h, int nrhs, const double* b, double* x) {
-  int st;
-  if ((st = require_celerite_width(h, "clr_batch_solve")) != CLR_OK) return st;
-  if (!clr::wsweep_scan_supported(h->N, h->J)) return fail(CLR_UNSUPPORTED, "clr_batch_solve on a wide plan needs N >= 512 (shorter series: CholeskySolver.solve)");
-  const size_t B = (size_t)h->B, N = (size_t)h->N, R = (size_t)nrhs;
-  const clr::SweepParams P = wide_solve_params(h, nrhs);
-  const size_t ws = clr::wsweep_workspace_doubles(h->J, P.nchunk, nrhs);
-  if ((st = h->bs_M.reserve(B * ws)) != CLR_OK) return st;
-  if ((st = h->bs_x.reserve(B * R * N)) != CLR_OK) return st;   // the forward sweep's output (undivided)
-  if ((st = h->bs_rm.reserve(B * R * N)) != CLR_OK) return st;  // right-hand sides in, results out
-  ConsumerFrame frame{h};
-  if (b) HIP_TRY(hipMemcpyAsync(h->bs_rm.p, b, B * R * N * sizeof(double), hipMemcpyHostToDevice, h->stream.get()));
-  HIP_TRY(frame.start());
-  wide_solve_sweeps(h, P, nrhs, b ? h->bs_rm.p : h->y.p, b ? (long)(R * N) : h->y_stride);
-  HIP_TRY(frame.stop());
-  return frame.finish(x, h->bs_rm.p, B * R * N);  // (x null: the result stays in bs_rm)
-}
-
-// the narrow batched solve's buffers for R right-hand sides per problem: the chunk-interleaved right-hand sides and
-// solutions, the chunk maps, the offsets and start states -- clr_batch_solve and clr_batch_fit_mean_weights
-static int reserve_narrow_solve(clr_batch* h, size_t R) {
-  const size_t B = (size_t)h->B, J = (size_t)h->J, nc = (size_t)h->nchunk;
-  int st;
-  if ((st = h->bs_x.reserve(B * R * (size_t)h->L * nc)) != CLR_OK) return st;
-  if ((st = h->bs_M.reserve(B * nc * J * J)) != CLR_OK) return st;
-  if ((st = h->bs_off.reserve(B * R * nc * J)) != CLR_OK) return st;
-  return h->bs_starts.reserve(B * R * nc * J);
-}
-
-// ... and its parameters on those buffers.  The chunk maps depend on the factor only: formed by the first solve after a
-// materialising run; they count as formed only once that solve's kernels have run to completion -- a failed launch or
-// copy must not leave the next solve reading uninitialised maps.  So this CLEARS bs_M_valid, and the caller sets it
-// again after its frame has finished.
-static clr::BSolveParams narrow_solve_begin(clr_batch* h, int nrhs) {
-  clr::BSolveParams S;
-  S.nrhs = nrhs; S.r = 0; S.lean = h->factor_is_lean ? 1 : 0;
-  S.have_M = h->bs_M_valid ? 1 : 0;
-  h->bs_M_valid = false;
-  S.xT = h->bs_x.p; S.M = h->bs_M.p; S.off = h->bs_off.p; S.starts = h->bs_starts.p;
-  return S;
-}
-
-// x == null: the result stays on the device, row-major [B][nrhs][N] in bs_rm (clr_batch_predict)
-static int batch_solve_impl(clr_batch* h, int nrhs, const double* b, double* x) {
-  int st = require_device(h->device);
-  if (st != CLR_OK) return st;
-  if (nrhs < 1) return fail(CLR_INVALID_ARGUMENT, "clr_batch_solve: nrhs >= 1");
-  if (!b && nrhs != 1) return fail(CLR_INVALID_ARGUMENT, "clr_batch_solve: b == NULL means the plan's own y (one right-hand side)");
-  if ((st = require_factor(h, true)) != CLR_OK) return st;
-  if (!h->launch) return wide_batch_solve(h, nrhs, b, x);
-  if (h->nchunk < 2) return fail(CLR_UNSUPPORTED, "clr_batch_solve needs a chunked plan (N >= 128)");
-  clr::BatchParams P;
-  if ((st = consumer_params(h, false, P)) != CLR_OK) return st;
-  const size_t B = (size_t)h->B, N = (size_t)h->N, R = (size_t)nrhs;
-  if ((st = reserve_narrow_solve(h, R)) != CLR_OK) return st;
-  if ((st = h->bs_rm.reserve(B * R * N)) != CLR_OK) return st;
-  ConsumerFrame frame{h};
-  if (b) HIP_TRY(hipMemcpyAsync(h->bs_rm.p, b, B * R * N * sizeof(double), hipMemcpyHostToDevice, h->stream.get()));
-  HIP_TRY(frame.start());
-  const clr::BSolveParams S = narrow_solve_begin(h, nrhs);
-  narrow_kernels(h, nrhs, b ? h->bs_rm.p : h->y.p, b ? (long)N : h->y_stride, h->bs_x.p, h->bs_x.p,
-                 [&] { h->launch->bsolve(P, S, h->stream.get()); });
-  HIP_TRY(frame.stop());
-  if ((st = frame.finish(x, h->bs_rm.p, B * R * N)) != CLR_OK) return st;
-  h->bs_M_valid = true;
-  return CLR_OK;
-}
-
-int clr_batch_solve(clr_batch* h, int nrhs, const double* b, double* x) {
-  if (!x) return fail(CLR_INVALID_ARGUMENT, "clr_batch_solve: an output array");
-  return batch_solve_impl(h, nrhs, b, x);
-}
-
-// CholeskySolver::dot_L (cholesky.h:409-431; GP.sample draws L z, celerite.py:422-451) for every problem of the plan from
-// the factor of its last materialising run.  Narrow plans: the chunked diagonal scan of clr_bdotl_kernels.h on the
-// chunk-interleaved factor (either layout), lane = (problem, chunk).  Wide plans (widths 9..64): the factor lies in the
-// reference's storage and the object API's wave-per-chunk scan (wsweep_kernels.hip: wdotl_kernel) runs once for the whole
-// batch, grid.z = problem; series too short for it: the sequential kernel, problem by problem.
-int clr_batch_dot_L(clr_batch* h, int nrhs, const double* z, double* y) {
-  int st = require_device(h->device);
-  if (st != CLR_OK) return st;
-  if (nrhs < 1 || nrhs > 65535 || !z || !y) return fail(CLR_INVALID_ARGUMENT, "clr_batch_dot_L: 1 <= nrhs <= 65535 (grid.z), z and an output array");
-  if ((st = require_factor(h, true)) != CLR_OK) return st;
-  if ((st = require_celerite_width(h, "clr_batch_dot_L")) != CLR_OK) return st;
-  const size_t B = (size_t)h->B, N = (size_t)h->N, J = (size_t)h->J, R = (size_t)nrhs;
-  if ((st = h->bs_rm.reserve(B * R * N)) != CLR_OK) return st;
-  ConsumerFrame frame{h};
-  HIP_TRY(hipMemcpyAsync(h->bs_rm.p, z, B * R * N * sizeof(double), hipMemcpyHostToDevice, h->stream.get()));
-  if (!h->launch) {  // wide plans
-    if ((st = h->bs_x.reserve(B * R * N)) != CLR_OK) return st;
-    HIP_TRY(frame.start());
-    if (clr::wdotl_scan_supported(h->N, h->J)) {
-      // chunks per problem: about two rounds of the chip's SIMDs over the batch (not a function of nrhs: a right-hand
-      // side's result does not depend on how many others ride along)
-      clr::SweepParams P = wide_sweep_params(h, nrhs, std::min(clr::wdotl_chunks(h->N), std::max(2, (int)(2048 / B))));
-      const size_t ws = R * (size_t)P.nchunk * 3 * J;
-      if ((st = h->bs_off.reserve(B * ws)) != CLR_OK) return st;
-      P.stride_ws = (long)ws;
-      P.in = h->bs_rm.p; P.out = h->bs_x.p;
-      clr::launch_wdotl_scan(P, h->bs_off.p, h->stream.get());
-    } else {
-      for (size_t p = 0; p < B; ++p)
-        clr::launch_dot_L(h->N, h->J, nrhs, h->phi.p + p * J * (N - 1), h->u.p + p * J * (N - 1), h->W.p + p * J * N,
-                          h->D.p + p * N, h->bs_rm.p + p * R * N, h->bs_x.p + p * R * N, h->stream.get());
-    }
-    HIP_TRY(frame.stop());
-  } else {
-    clr::BatchParams P;
-    if ((st = consumer_params(h, false, P)) != CLR_OK) return st;
-    const size_t cells = (size_t)h->L * h->nchunk;
-    if ((st = h->bs_x.reserve(B * R * cells)) != CLR_OK) return st;
-    if ((st = h->bs_decay.reserve(B * h->nchunk * J)) != CLR_OK) return st;
-    if ((st = h->bs_off.reserve(B * R * h->nchunk * J)) != CLR_OK) return st;
-    if ((st = h->bs_starts.reserve(B * R * h->nchunk * J)) != CLR_OK) return st;
-    HIP_TRY(frame.start());
-    clr::BDotLParams S;
-    S.nrhs = nrhs; S.lean = h->factor_is_lean ? 1 : 0;
-    S.xT = h->bs_x.p; S.decay = h->bs_decay.p; S.off = h->bs_off.p; S.starts = h->bs_starts.p;
-    narrow_kernels(h, nrhs, h->bs_rm.p, (long)N, h->bs_x.p, h->bs_x.p, [&] { h->launch->bdotl(P, S, h->stream.get()); });
-    HIP_TRY(frame.stop());
-  }
-  return frame.finish(y, h->launch ? h->bs_rm.p : h->bs_x.p, B * R * N);  // (bs_x as reserved above)
-}
-
-// the constant diagonal of one problem's K for dot: sum a_real + sum a_comp + jitter (cholesky.h:483-485), N copies
-__global__ void __launch_bounds__(256) dot_diagonal_kernel(const double* a_real, const double* a_comp, const double* jitter, int JR,
-                                                           int JC, double* dg, int N) {
-  double sr = 0.0, sc = 0.0;
-  for (int j = 0; j < JR; ++j) sr += a_real[j];
-  for (int j = 0; j < JC; ++j) sc += a_comp[j];
-  const double d = (sr + sc) + jitter[0];
-  for (long n = (long)blockIdx.x * blockDim.x + threadIdx.x; n < N; n += (long)gridDim.x * blockDim.x) dg[n] = d;
-}
-
-// CholeskySolver::dot (cholesky.h:441-596; GP.dot, celerite.py:453-489) for every problem of the plan: y_p = K_p z_p with
-// K_p given by the plan's resident times and the coefficients in force (diagonal sum a_real + sum a_comp + jitter: no
-// observational variance, :483-485) -- no factor, no materialising run.  Narrow plans: the two triangles as chunked
-// diagonal scans with the features evaluated on the fly (clr_bdot_kernels.h), lane = (problem, chunk).  Wide plans
-// (widths 9..64): the object API's kernels problem by problem (launch_dot_setup + the wave-per-chunk scans of
-// wsweep_kernels.hip, or the sequential kernel on short series) on the plan's resident arrays.
-int clr_batch_dot(clr_batch* h, int nrhs, const double* z, double* y) {
-  int st = require_device(h->device);
-  if (st != CLR_OK) return st;
-  if (nrhs < 1 || nrhs > 65535 || !z || !y) return fail(CLR_INVALID_ARGUMENT, "clr_batch_dot: 1 <= nrhs <= 65535 (grid.z), z and an output array");
-  if ((st = warm_resolve(h, nullptr)) != CLR_OK) return st;
-  if ((st = require_celerite_width(h, "clr_batch_dot")) != CLR_OK) return st;
-  clr::BatchParams P;  // (wide plans read its coefficients only)
-  if ((st = consumer_params(h, true, P)) != CLR_OK) return st;
-  const size_t B = (size_t)h->B, N = (size_t)h->N, J = (size_t)h->J, R = (size_t)nrhs;
-  if ((st = h->bs_rm.reserve(B * R * N)) != CLR_OK) return st;
-  DevBuf feat, dgb, ws;  // (wide plans: one problem's features, its constant diagonal and the scan's workspace)
-  ConsumerFrame frame{h};
-  HIP_TRY(hipMemcpyAsync(h->bs_rm.p, z, B * R * N * sizeof(double), hipMemcpyHostToDevice, h->stream.get()));
-  if (!h->launch) {  // wide plans: problem by problem
-    if ((st = feat.reserve(3 * J * N)) != CLR_OK) return st;
-    if ((st = dgb.reserve(N)) != CLR_OK) return st;  // (refilled per problem, same stream)
-    if ((st = h->bs_x.reserve(B * R * N)) != CLR_OK) return st;
-    const bool scan = clr::wdotl_scan_supported(h->N, h->J);
-    clr::SweepParams SP;
-    memset(&SP, 0, sizeof(SP));
-    if (scan) {
-      SP.N = h->N; SP.J = h->J; SP.nrhs = nrhs;
-      clr::chunking(h->N - 1, clr::wdotl_chunks(h->N), &SP.L, &SP.nchunk);
-      if ((st = ws.reserve(R * (size_t)SP.nchunk * 3 * J)) != CLR_OK) return st;
-    }
-    HIP_TRY(frame.start());
-    for (size_t p = 0; p < B; ++p) {
-      const clr::GenericProblem g = problem_view(h, P, p);
-      double *phi = feat.p, *u = feat.p + J * N, *v = feat.p + 2 * J * N;
-      clr::launch_dot_setup(g, phi, u, v, h->stream.get());
-      hipLaunchKernelGGL(dot_diagonal_kernel, dim3((unsigned)std::min<size_t>((N + 255) / 256, 1024)), dim3(256), 0, h->stream.get(),
-                         g.a_real, g.a_comp, P.jitter + p, h->J_real, h->J_comp, dgb.p, h->N);
-      if (scan) {
-        SP.phi = phi; SP.u = u;
-        SP.in = h->bs_rm.p + p * R * N; SP.out = h->bs_x.p + p * R * N;
-        clr::launch_wdot_scan(SP, v, dgb.p, ws.p, h->stream.get());
-      } else {
-        clr::launch_dot(h->N, h->J, nrhs, phi, u, v, dgb.p, h->bs_rm.p + p * R * N, h->bs_x.p + p * R * N, h->stream.get());
-      }
-    }
-    HIP_TRY(frame.stop());
-  } else {
-    const size_t cells = (size_t)h->L * h->nchunk;
-    if ((st = h->bs_x.reserve(B * R * cells)) != CLR_OK) return st;
-    if ((st = h->bs_y.reserve(B * R * cells)) != CLR_OK) return st;
-    if ((st = h->bs_decay.reserve(B * h->nchunk * J)) != CLR_OK) return st;
-    if ((st = h->bs_off.reserve(B * R * h->nchunk * J)) != CLR_OK) return st;
-    if ((st = h->bs_starts.reserve(B * R * h->nchunk * J)) != CLR_OK) return st;
-    HIP_TRY(frame.start());
-    clr::BDotParams S;
-    S.nrhs = nrhs; S.zT = h->bs_x.p; S.yT = h->bs_y.p; S.decay = h->bs_decay.p; S.off = h->bs_off.p; S.starts = h->bs_starts.p;
-    narrow_kernels(h, nrhs, h->bs_rm.p, (long)N, h->bs_x.p, h->bs_y.p, [&] { h->launch->bdot(P, S, h->stream.get()); });
-    HIP_TRY(frame.stop());
-  }
-  return frame.finish(y, h->launch ? h->bs_rm.p : h->bs_x.p, B * R * N);  // (bs_x as reserved above)
-}
-
-// CholeskySolver::predict (cholesky.h:599-698; GP.predict's conditional mean, celerite.py:330-420) for every problem of
-// the plan: mu*_p(x*) = K_p(x*, t_p) K_p^-1 y_p at M points per problem.  alpha = K^-1 y is the batched solve on the
-// materialised factor (either layout, any width <= 64), left on the device; the reference's two passes over the sorted
-// prediction points are the object API's chunked diagonal scans (generic_kernels.hip: launch_predict_scan, a parallel
-// prefix over chunks of 16 samples + one thread per point) run problem by problem on the plan's resident times and
-// coefficients -- they need nothing of the factor.  Unsorted points: the sequential walk (launch_predict).
-int clr_batch_predict(clr_batch* h, int M, const double* xs, long xs_stride, double* pred) {
-  int st = require_device(h->device);
-  if (st != CLR_OK) return st;
-  if (M < 0 || (M > 0 && (!xs || !pred))) return fail(CLR_INVALID_ARGUMENT, "clr_batch_predict: M >= 0, the points and an output array");
-  if (xs_stride != 0 && xs_stride != M) return fail(CLR_INVALID_ARGUMENT, "clr_batch_predict: the points' stride is 0 (shared by all problems) or M");
-  if ((st = require_celerite_width(h, "clr_batch_predict")) != CLR_OK) return st;
-  if (M == 0) return CLR_OK;
-  if ((st = batch_solve_impl(h, 1, nullptr, nullptr)) != CLR_OK) return st;  // alpha = K^-1 y -> bs_rm [B][N]
-  clr::BatchParams P;
-  if ((st = batch_params(h, 0, P, false)) != CLR_OK) return st;
-  const size_t B = (size_t)h->B, Mm = (size_t)M, nsrc = xs_stride == 0 ? 1 : B;
-  DevBuf dxs, dpred, ws;
-  if ((st = dxs.reserve(nsrc * Mm)) != CLR_OK) return st;
-  if ((st = dpred.reserve(B * Mm)) != CLR_OK) return st;
-  const bool scan_ok = clr::predict_scan_supported(h->N, h->J_real, h->J_comp);
-  int pchunk = 0, pL = 0;
-  if (scan_ok) {
-    clr::chunking(h->N, std::max(1, std::min(h->N / 16, 8192)), &pL, &pchunk);
-    if ((st = ws.reserve(clr::predict_workspace_doubles(pchunk, h->J))) != CLR_OK) return st;
-  }
-  ConsumerFrame frame{h};  // (untimed: solve_device_ms is the solve's)
-  if (hipMemcpyAsync(dxs.p, xs, nsrc * Mm * sizeof(double), hipMemcpyHostToDevice, h->stream.get()) != hipSuccess ||
-      hipMemsetAsync(dpred.p, 0, B * Mm * sizeof(double), h->stream.get()) != hipSuccess)
-    return fail(CLR_HIP_ERROR, "clr_batch_predict: upload failed");
-  std::vector<char> sorted(nsrc, 1);
-  for (size_t p = 0; p < nsrc; ++p)
-    for (size_t m = 1; m < Mm && sorted[p]; ++m) sorted[p] = xs[p * Mm + m - 1] <= xs[p * Mm + m];
-  for (size_t p = 0; p < B; ++p) {
-    const clr::GenericProblem g = problem_view(h, P, p);
-    const double* alpha = h->bs_rm.p + p * (size_t)h->N;
-    const double* xp = dxs.p + (xs_stride == 0 ? 0 : p * Mm);
-    if (scan_ok && sorted[xs_stride == 0 ? 0 : p]) clr::launch_predict_scan(g, alpha, M, xp, dpred.p + p * Mm, ws.p, pchunk, pL, h->stream.get());
-    else clr::launch_predict(g, alpha, M, xp, dpred.p + p * Mm, h->stream.get());
-  }
-  if (frame.finish(pred, dpred.p, B * Mm) != CLR_OK)
-    return fail(CLR_HIP_ERROR, "clr_batch_predict: kernels or the download failed");
-  // the mean plus the conditional mean of the residual (celerite.py:279); under a linear mean (clr_batch_set_mean_basis) the
-  // conditional mean of the residual alone -- the basis at the prediction points is the caller's
-  if (h->have_mean)
-    for (size_t p = 0; p < B; ++p) {
-      const double m = h->host_mean[h->mean_stride ? p : 0];
-      for (size_t k = 0; k < Mm; ++k) pred[p * Mm + k] = m + pred[p * Mm + k];
-    }
-  return CLR_OK;
-}
-
-// ---- clr_batch_predict_var: the conditional variance of GP.predict for every problem of the plan
-
-// widths 9..64: the tile's cross-covariances k_p(x*_r - t_{p,n}) row-major [problem][rhs][n] (grid: n, rhs, problem);
-// `fast`: the phases stay below CLR_FAST_TRIG_LIMIT (a launch-uniform branch: registers are no concern here)
-__global__ void __launch_bounds__(256) predvar_cross_rowmajor_kernel(const double* a_real, const double* c_real, const double* a_comp,
-                                                                     const double* b_comp, const double* c_comp, const double* d_comp,
-                                                                     int JR, int JC, const double* t, long t_stride, int N,
-                                                                     const double* xs, long xs_stride, int nrhs, int fast, double* out) {
-  const long n = (long)blockIdx.x * 256 + threadIdx.x, r = blockIdx.y, b = blockIdx.z;
-  if (n >= N) return;
-  const double tau = xs[b * xs_stride + r] - t[b * t_stride + n];
-  const double *ar = a_real + b * JR, *cr = c_real + b * JR, *ac = a_comp + b * JC, *bc = b_comp + b * JC, *cc = c_comp + b * JC,
-               *dc = d_comp + b * JC;
-  out[(b * nrhs + r) * N + n] = fast ? clr::cross_covariance<true>(ar, cr, JR, ac, bc, cc, dc, JC, tau)
-                                     : clr::cross_covariance<false>(ar, cr, JR, ac, bc, cc, dc, JC, tau);
-}
-
-// widths 9..64: var = k_p(0) - sum_n x_n^2 / D_n of one (problem, rhs) per workgroup (grid: rhs, problem) in a fixed
-// order -- thread i sums the samples i, i + 256, ... in order, then a fixed tree over the 256 threads
-__global__ void __launch_bounds__(256) predvar_reduce_kernel(const double* x, const double* D, int N, int nrhs, const double* a_real,
-                                                             const double* a_comp, int JR, int JC, double* var, long var_stride) {
-  __shared__ double sh[256];
-  const long r = blockIdx.x, b = blockIdx.y;
-  const double* xp = x + (b * nrhs + r) * N;
-  const double* Dp = D + b * N;
-  double s = 0.0;
-  for (int n = threadIdx.x; n < N; n += 256) s += xp[n] * xp[n] / Dp[n];
-  sh[threadIdx.x] = s;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    double sr = 0.0, sc = 0.0;
-    for (int j = 0; j < JR; ++j) sr += a_real[b * JR + j];
-    for (int j = 0; j < JC; ++j) sc += a_comp[b * JC + j];
-    var[b * var_stride + r] = (sr + sc) - sh[0];
-  }
-}
-
-// d loglike / d w[b][k] = Phi_k^T K_b^-1 r_b: the batched solve of the residual in `y` on the factor in HBM, left row-major
-// in bs_rm, then the projection onto the resident basis (clr_bmean_kernels.h).  The gradient sweeps are not involved: the
-// log-likelihood depends on the weights through r alone, d (-1/2 r^T K^-1 r) / d w_k = Phi_k^T K^-1 r.
-int clr_batch_grad_mean_weights(clr_batch* h, double* dw, int* status) {
-  int st = require_device(h->device);
-  if (st != CLR_OK) return st;
-  if (h->mean_K == 0) return fail(CLR_INVALID_ARGUMENT, "clr_batch_grad_mean_weights: no basis is set (clr_batch_set_mean_basis)");
-  if (!dw) return fail(CLR_INVALID_ARGUMENT, "clr_batch_grad_mean_weights: an output array");
-  if ((st = batch_solve_impl(h, 1, nullptr, nullptr)) != CLR_OK) return st;  // K^-1 r -> bs_rm [B][N]
-  const size_t B = (size_t)h->B, K = (size_t)h->mean_K;
-  if ((st = h->proj_part.reserve(clr::mean_project_workspace(h->B, h->N, h->mean_K))) != CLR_OK) return st;
-  if ((st = h->proj_out.reserve(B * K)) != CLR_OK) return st;
-  for (clr::Event& e : h->proj_ev)
-    if (!e) HIP_TRY(clr::create_event(e));
-  {
-    ConsumerFrame frame{h};  // (untimed: solve_device_ms stays the solve's; the projection has its own events)
-    HIP_TRY(hipEventRecord(h->proj_ev[0].get(), h->stream.get()));
-    if (!clr::launch_mean_project(h->basis_dev.p, h->basis_stride, h->bs_rm.p, h->mean_K, h->B, h->N, h->proj_part.p,
-                                  h->proj_out.p, h->stream.get()))
-      return fail(CLR_UNSUPPORTED, "clr_batch_grad_mean_weights: B x N / 4096 workgroups do not fit one launch");
-    HIP_TRY(hipEventRecord(h->proj_ev[1].get(), h->stream.get()));
-    if ((st = frame.finish(dw, h->proj_out.p, B * K)) != CLR_OK) return st;
-  }
-  float ms = 0.f;
-  HIP_TRY(hipEventElapsedTime(&ms, h->proj_ev[0].get(), h->proj_ev[1].get()));
-  h->project_device_ms = ms;
-  // the statuses of the evaluation in force; a problem without a factor (or refused by the kernel program): zeros
-  std::vector<int> stat(B);
-  if ((st = clr_batch_get_results(h, nullptr, nullptr, nullptr, stat.data())) != CLR_OK) return st;
-  mark_refused(h, nullptr, nullptr, nullptr, stat.data());
-  for (size_t b = 0; b < B; ++b)
-    if (stat[b] != CLR_OK) std::fill(dw + b * K, dw + (b + 1) * K, 0.0);  // (the gradient's quiet semantics)
-  if (status) std::copy(stat.begin(), stat.end(), status);
-  return CLR_OK;
-}
-
-int clr_batch_get_mean_project_ms(const clr_batch* h, double* device_ms) {
-  if (device_ms) *device_ms = h->project_device_ms;
-  return CLR_OK;
-}
-
-int clr_batch_set_predict_tile(clr_batch* h, int points) {
-  h->predict_tile = points > 0 ? points : 0;
-  return CLR_OK;
-}
-
-// points per tile: the caller's (clr_batch_set_predict_tile), or the most whose buffers -- `per_point` doubles each --
-// fit in 1 GiB; never above grid.z's 65535 nor M, at least 1
-static int predict_tile(const clr_batch* h, int M, size_t per_point) {
-  const size_t budget = (size_t)1 << 27;  // doubles
-  size_t R = h->predict_tile > 0 ? (size_t)h->predict_tile : std::max<size_t>(1, budget / std::max<size_t>(1, per_point));
-  return (int)std::min<size_t>(std::min<size_t>(R, 65535), (size_t)M);
-}
-
-// The conditional variance of GP.predict (celerite.py:465-470) for every problem of the plan at M points each:
-// var = k(0) - k*^T K^-1 k* = k(0) - sum_n z_n^2 / D_n with z = L^-1 k* -- the forward half of a solve per point, on
-// right-hand sides formed on the device from the plan's times, the coefficients in force and the points, a tile of
-// points at a time.  Narrow plans: clr_bpredvar_kernels.h on the chunk-interleaved factor (either layout), the chunk maps
-// shared with clr_batch_solve.  Wide plans (widths 9..64): the cross-covariances row-major, the forward sweep of
-// wide_batch_solve (launch_wsweep_scan, backward = 0) and one workgroup per (problem, point) for the quadratic form.
-int clr_batch_predict_var(clr_batch* h, int M, const double* xs, long xs_stride, double* var) {
-  int st = require_device(h->device);
-  if (st != CLR_OK) return st;
-  if (M < 0 || (M > 0 && (!xs || !var))) return fail(CLR_INVALID_ARGUMENT, "clr_batch_predict_var: M >= 0, the points and an output array");
-  if (xs_stride != 0 && xs_stride != M) return fail(CLR_INVALID_ARGUMENT, "clr_batch_predict_var: the points' stride is 0 (shared by all problems) or M");
-  if ((st = require_celerite_width(h, "clr_batch_predict_var")) != CLR_OK) return st;
-  if (M == 0) return CLR_OK;
-  if ((st = require_factor(h, true)) != CLR_OK) return st;
-  if (!h->launch && !clr::wsweep_scan_supported(h->N, h->J))
-    return fail(CLR_UNSUPPORTED, "clr_batch_predict_var on a wide plan needs N >= 512 (shorter series: GP.predict)");
-  if (h->launch && h->nchunk < 2) return fail(CLR_UNSUPPORTED, "clr_batch_predict_var needs a chunked plan (N >= 128)");
-  clr::BatchParams P;  // (wide plans read its coefficients only)
-  if ((st = consumer_params(h, false, P)) != CLR_OK) return st;
-  const size_t B = (size_t)h->B, N = (size_t)h->N, J = (size_t)h->J, Mm = (size_t)M, nsrc = xs_stride == 0 ? 1 : B;
-  // the phases of the cross-covariances: |d| |x* - t| <= max|d| (max|x*| + max|t|), under the plan's own rule
-  double xmax = 0.0;
-  for (size_t k = 0; k < nsrc * Mm; ++k) {
-    const double a = std::fabs(xs[k]);
-    if (a > xmax || a != a) xmax = a;  // (a NaN stays: the library sincos)
-  }
-  const int cross_fast = (sel_max(h->dmax, h->floor_dmax) * (sel_max(h->tmax, h->floor_tmax) + xmax) < CLR_FAST_TRIG_LIMIT) ? 1 : 0;
-  DevBuf dxs, dvar;
-  if ((st = dxs.reserve(nsrc * Mm)) != CLR_OK) return st;
-  if ((st = dvar.reserve(B * Mm)) != CLR_OK) return st;
-  if (!h->launch) {  // wide plans
-    clr::SweepParams W = wide_solve_params(h, 1);
-    const size_t ws_point = clr::wsweep_workspace_doubles(h->J, W.nchunk, 2) - clr::wsweep_workspace_doubles(h->J, W.nchunk, 1);
-    const int R = predict_tile(h, M, B * (2 * N + ws_point));
-    const size_t ws = clr::wsweep_workspace_doubles(h->J, W.nchunk, R);
-    if ((st = h->bs_M.reserve(B * ws)) != CLR_OK) return st;
-    if ((st = h->bs_x.reserve(B * R * N)) != CLR_OK) return st;   // the forward sweep's output (undivided)
-    if ((st = h->bs_rm.reserve(B * R * N)) != CLR_OK) return st;  // the tile's cross-covariances
-    ConsumerFrame frame{h};
-    HIP_TRY(hipMemcpyAsync(dxs.p, xs, nsrc * Mm * sizeof(double), hipMemcpyHostToDevice, h->stream.get()));
-    HIP_TRY(frame.start());
-    for (int m0 = 0; m0 < M; m0 += R) {
-      const int nr = std::min(R, M - m0);
-      const dim3 cgrid((unsigned)((N + 255) / 256), nr, (unsigned)B);
-      hipLaunchKernelGGL(predvar_cross_rowmajor_kernel, cgrid, dim3(256), 0, h->stream.get(), P.a_real, P.c_real, P.a_comp, P.b_comp, P.c_comp, P.d_comp,
-                         h->J_real, h->J_comp, h->t.p, h->t_stride, h->N, dxs.p + m0, xs_stride, nr, cross_fast, h->bs_rm.p);
-      W.nrhs = nr; W.stride_in = W.stride_out = (long)nr * (long)N;
-      W.stride_ws = (long)clr::wsweep_workspace_doubles(h->J, W.nchunk, nr);
-      W.in = h->bs_rm.p; W.out = h->bs_x.p; W.backward = 0;
-      clr::launch_wsweep_scan(W, h->bs_M.p, h->stream.get());
-      hipLaunchKernelGGL(predvar_reduce_kernel, dim3(nr, (unsigned)B), dim3(256), 0, h->stream.get(), h->bs_x.p, h->D.p, h->N, nr,
-                         P.a_real, P.a_comp, h->J_real, h->J_comp, dvar.p + m0, (long)M);
-    }
-    HIP_TRY(frame.stop());
-    return frame.finish(var, dvar.p, B * Mm);
-  }
-  const size_t cells = (size_t)h->L * h->nchunk, nc = (size_t)h->nchunk;
-  const int R = predict_tile(h, M, B * (cells + 2 * nc * J));
-  if ((st = h->bs_x.reserve(B * R * cells)) != CLR_OK) return st;
-  if ((st = h->bs_M.reserve(B * nc * J * J)) != CLR_OK) return st;
-  if ((st = h->bs_off.reserve(B * R * nc * J)) != CLR_OK) return st;
-  if ((st = h->bs_starts.reserve(B * R * nc * J)) != CLR_OK) return st;
-  ConsumerFrame frame{h};
-  HIP_TRY(hipMemcpyAsync(dxs.p, xs, nsrc * Mm * sizeof(double), hipMemcpyHostToDevice, h->stream.get()));
-  HIP_TRY(frame.start());
-  clr::BPredVarParams S;
-  S.lean = h->factor_is_lean ? 1 : 0; S.cross_fast = cross_fast;
-  // (the chunk maps are the batched solve's, under its validity rule: formed by the first tile after a materialising run
-  //  unless a solve has formed them, and counted as formed only once this call's kernels have run to completion)
-  S.have_M = h->bs_M_valid ? 1 : 0;
-  h->bs_M_valid = false;
-  S.xs_stride = xs_stride; S.t = h->t.p; S.t_stride = h->t_stride;
-  S.xT = h->bs_x.p; S.M = h->bs_M.p; S.off = h->bs_off.p; S.starts = h->bs_starts.p;
-  S.part = h->bs_off.p;  // (the walk has consumed the offsets by the time the forward recurrence writes its sums)
-  S.var_stride = (long)M;
-  for (int m0 = 0; m0 < M; m0 += R) {
-    S.nrhs = std::min(R, M - m0); S.xs = dxs.p + m0; S.var = dvar.p + m0;
-    h->launch->bpredvar(P, S, h->stream.get());
-    S.have_M = 1;
-  }
-  HIP_TRY(frame.stop());
-  if ((st = frame.finish(var, dvar.p, B * Mm)) != CLR_OK) return st;
-  h->bs_M_valid = true;
-  return CLR_OK;
-}
-
-// Every source's points ascending, for the kernels that walk them with a cursor (clr_batch_predict_var_recurrence,
-// clr_batch_forecast): as given where they already are (detected in O(M)), else through an index permutation (NaN last;
-// shared points once) that scatter() undoes on the results.  xmax: max |x| (a NaN stays), for the points' phase rule.
-struct SortedPoints {
-  bool all_sorted = true;
-  std::vector<double> xsorted;
-  std::vector<int> perm;
-  const double* up = nullptr;  // the points to upload, [nsrc][M]
-  double xmax = 0.0;
-  void sort(const double* xs, size_t nsrc, size_t Mm) {
-    std::vector<char> sorted(nsrc, 1);
-    for (size_t p = 0; p < nsrc; ++p) {
-      const double* x = xs + p * Mm;
-      for (size_t m = 1; m < Mm && sorted[p]; ++m) sorted[p] = x[m - 1] <= x[m];
-      all_sorted = all_sorted && sorted[p];
-    }
-    if (!all_sorted) {
-      xsorted.assign(xs, xs + nsrc * Mm);
-      perm.resize(nsrc * Mm);
-      for (size_t p = 0; p < nsrc; ++p) {
-        int* pp = perm.data() + p * Mm;
-        for (size_t m = 0; m < Mm; ++m) pp[m] = (int)m;
-        if (sorted[p]) continue;
-        const double* x = xs + p * Mm;
-        std::stable_sort(pp, pp + Mm, [x](int a, int b) {
-          const double xa = x[a], xb = x[b];
-          if (xa != xa) return false;   // NaN last
-          if (xb != xb) return true;
-          return xa < xb;
-        });
-        for (size_t m = 0; m < Mm; ++m) xsorted[p * Mm + m] = x[pp[m]];
-      }
-    }
-    up = all_sorted ? xs : xsorted.data();
-    for (size_t k = 0; k < nsrc * Mm; ++k) {
-      const double a = std::fabs(xs[k]);
-      if (a > xmax || a != a) xmax = a;  // (a NaN stays: the library sincos)
-    }
-  }
-  // results in sorted order [B][M] -> the caller's order
-  void scatter(const double* tmp, double* out, size_t B, size_t Mm, bool shared) const {
-    for (size_t b = 0; b < B; ++b) {
-      const int* pp = perm.data() + (shared ? 0 : b * Mm);
-      for (size_t m = 0; m < Mm; ++m) out[b * Mm + pp[m]] = tmp[b * Mm + m];
-    }
-  }
-};
-
-// The conditional variance of GP.predict for every problem of a narrow plan at M points each in O((N + M) J^2): the
-// factorisation's forward state S and the backward matrix recurrence Q of the leave-one-out diagonal give var(x) in closed
-// form (clr_bpredvar_rec_kernels.h) -- one forward and one backward pass over the series per tile of points, O(J^2) per
-// point.  The kernels want every problem's points ascending: sorted input is detected in O(M), anything else is sorted
-// as an index permutation on the host (NaN last) and the results are scattered back; shared points are sorted once.  The
-// chunks' forward start states (pv_S) and backward start matrices (loo_Q, shared with clr_batch_leave_one_out) depend on
-// the factor only and are formed by the first tile after a materialising run, the chunk maps under clr_batch_solve's rule.
-int clr_batch_predict_var_recurrence(clr_batch* h, int M, const double* xs, long xs_stride, double* var) {
-  int st = require_device(h->device);
-  if (st != CLR_OK) return st;
-  if (M < 0 || (M > 0 && (!xs || !var))) return fail(CLR_INVALID_ARGUMENT, "clr_batch_predict_var_recurrence: M >= 0, the points and an output array");
-  if (xs_stride != 0 && xs_stride != M) return fail(CLR_INVALID_ARGUMENT, "clr_batch_predict_var_recurrence: the points' stride is 0 (shared by all problems) or M");
-  if ((st = require_celerite_width(h, "clr_batch_predict_var_recurrence")) != CLR_OK) return st;
-  if (M == 0) return CLR_OK;
-  if ((st = require_factor(h, true)) != CLR_OK) return st;
-  if (!h->launch)
-    return fail(CLR_UNSUPPORTED, "clr_batch_predict_var_recurrence covers narrow plans (widths 1..8): a wide plan takes clr_batch_predict_var");
-  if (h->nchunk < 2) return fail(CLR_UNSUPPORTED, "clr_batch_predict_var_recurrence needs a chunked plan (N >= 128)");
-  clr::BatchParams P;
-  if ((st = consumer_params(h, false, P)) != CLR_OK) return st;
-  const size_t B = (size_t)h->B, J = (size_t)h->J, Mm = (size_t)M, nsrc = xs_stride == 0 ? 1 : B, nc = (size_t)h->nchunk;
-  const size_t NS = J * (J + 1) / 2;
-  SortedPoints pts;
-  pts.sort(xs, nsrc, Mm);
-  const bool all_sorted = pts.all_sorted;
-  std::vector<double> vtmp;
-  if (!all_sorted) vtmp.resize(B * Mm);
-  const double* xup = pts.up;
-  const int xfast = (sel_max(h->dmax, h->floor_dmax) * pts.xmax < CLR_FAST_TRIG_LIMIT) ? 1 : 0;
-  // points per tile: the caller's, or the most whose per-point buffers (u(x), e, left) fit in 1 GiB
-  const size_t budget = (size_t)1 << 27, per_point = B * (2 * J + 1);
-  const size_t Rz = std::min<size_t>(h->predict_tile > 0 ? (size_t)h->predict_tile : std::max<size_t>(1, budget / per_point), Mm);
-  const int R = (int)Rz;
-  DevBuf dxs, dvar, dux, de, dleft;
-  if ((st = dxs.reserve(nsrc * Mm)) != CLR_OK) return st;
-  if ((st = dvar.reserve(B * Mm)) != CLR_OK) return st;
-  if ((st = dux.reserve(B * Rz * J)) != CLR_OK) return st;
-  if ((st = de.reserve(B * Rz * J)) != CLR_OK) return st;
-  if ((st = dleft.reserve(B * Rz)) != CLR_OK) return st;
-  if ((st = h->pv_S.reserve(B * nc * NS)) != CLR_OK) return st;
-  if ((st = h->loo_Q.reserve(B * nc * NS)) != CLR_OK) return st;
-  if ((st = h->bs_M.reserve(B * nc * J * J)) != CLR_OK) return st;
-  if ((st = h->bs_off.reserve(B * nc * J)) != CLR_OK) return st;
-  if ((st = h->bs_x.reserve(B * (size_t)h->L * nc)) != CLR_OK) return st;  // (read beside by the solve's summarize when it forms the maps)
-  ConsumerFrame frame{h};
-  HIP_TRY(hipMemcpyAsync(dxs.p, xup, nsrc * Mm * sizeof(double), hipMemcpyHostToDevice, h->stream.get()));
-  HIP_TRY(frame.start());
-  clr::BPredVarRecParams S;
-  S.lean = h->factor_is_lean ? 1 : 0;
-  S.have_S = h->pv_S_valid ? 1 : 0;
-  S.have_Q = h->loo_Q_valid ? 1 : 0;
-  S.Q.lean = S.lean;
-  S.Q.have_M = h->bs_M_valid ? 1 : 0;
-  const bool forms_Q = !S.have_Q;        // ... and with them the chunk maps, unless a solve has formed those
-  if (forms_Q) h->bs_M_valid = false;
-  h->pv_S_valid = h->loo_Q_valid = false;
-  S.Q.cT = h->bs_x.p; S.Q.M = h->bs_M.p; S.Q.Q = h->loo_Q.p; S.Q.off = h->bs_off.p;
-  S.xs_stride = xs_stride; S.t = h->t.p; S.t_stride = h->t_stride;
-  S.S = h->pv_S.p; S.ux = dux.p; S.e = de.p; S.left = dleft.p;
-  S.var_stride = (long)M;
-  for (int m0 = 0; m0 < M; m0 += R) {
-    S.npts = std::min(R, M - m0); S.xs = dxs.p + m0; S.var = dvar.p + m0;
-    h->launch->bpredvar_rec(P, S, xfast, h->stream.get());
-    S.have_S = S.have_Q = 1;
-  }
-  HIP_TRY(frame.stop());
-  if ((st = frame.finish(all_sorted ? var : vtmp.data(), dvar.p, B * Mm)) != CLR_OK) return st;
-  h->pv_S_valid = h->loo_Q_valid = true;
-  if (forms_Q) h->bs_M_valid = true;
-  if (!all_sorted) pts.scatter(vtmp.data(), var, B, Mm, xs_stride == 0);
-  return CLR_OK;
-}
-
-// ---- clr_batch_one_step_ahead, clr_batch_forecast: the causal half of the factor (clr_bfilter_kernels.h)
-
-// rows of problems without a factor (or refused by the kernel program) -> NaN; the statuses of the evaluation in force
-static int nan_rows_without_factor(clr_batch* h, std::vector<int>& stat, std::initializer_list<std::pair<double*, size_t>> outs) {
-  const size_t B = (size_t)h->B;
-  stat.resize(B);
-  const int st = clr_batch_get_results(h, nullptr, nullptr, nullptr, stat.data());
-  if (st != CLR_OK) return st;
-  mark_refused(h, nullptr, nullptr, nullptr, stat.data());
-  const double nan = std::numeric_limits<double>::quiet_NaN();
-  for (size_t b = 0; b < B; ++b) {
-    if (stat[b] == CLR_OK) continue;
-    for (const auto& o : outs)
-      if (o.first) std::fill(o.first + b * o.second, o.first + (b + 1) * o.second, nan);
-  }
-  return CLR_OK;
-}
-
-// z = L^-1 b and D for every problem from the factor of the last materialising run: the forward half of clr_batch_solve
-// without its division.  Narrow plans: the solve's summarize and forward walk for the chunks' start states, then
-// bfilter_forward_kernel on the chunk-interleaved right-hand sides (the chunk maps under clr_batch_solve's validity rule),
-// D de-interleaved beside.  Wide plans (widths 9..64): the forward sweep of wide_batch_solve (launch_wsweep_scan,
-// backward = 0), whose output is z; D lies row-major in the factor.
-int clr_batch_one_step_ahead(clr_batch* h, int nrhs, const double* b, double* innovation, double* variance, int* status) {
-  int st = require_device(h->device);
-  if (st != CLR_OK) return st;
-  if (nrhs < 1) return fail(CLR_INVALID_ARGUMENT, "clr_batch_one_step_ahead: nrhs >= 1");
-  if (!b && nrhs != 1) return fail(CLR_INVALID_ARGUMENT, "clr_batch_one_step_ahead: b == NULL means the residual in force (one right-hand side)");
-  if (!innovation && !variance && !status) return fail(CLR_INVALID_ARGUMENT, "clr_batch_one_step_ahead: at least one output array");
-  if ((st = require_celerite_width(h, "clr_batch_one_step_ahead")) != CLR_OK) return st;
-  if ((st = require_factor(h, true)) != CLR_OK) return st;
-  if (!h->launch && !clr::wsweep_scan_supported(h->N, h->J))
-    return fail(CLR_UNSUPPORTED, "clr_batch_one_step_ahead on a wide plan needs N >= 512");
-  if (h->launch && h->nchunk < 2) return fail(CLR_UNSUPPORTED, "clr_batch_one_step_ahead needs a chunked plan (N >= 128)");
-  const size_t B = (size_t)h->B, N = (size_t)h->N, R = (size_t)nrhs;
-  DevBuf dD;  // (narrow plans: D row-major)
-  if (innovation || variance) {
-    clr::BatchParams P;
-    clr::SweepParams W;
-    if (h->launch) {
-      if ((st = consumer_params(h, false, P)) != CLR_OK) return st;
-      if (innovation && (st = reserve_narrow_solve(h, R)) != CLR_OK) return st;
-      if (variance && (st = dD.reserve(B * N)) != CLR_OK) return st;
-    } else if (innovation) {
-      W = wide_solve_params(h, nrhs);
-      if ((st = h->bs_M.reserve(B * clr::wsweep_workspace_doubles(h->J, W.nchunk, nrhs))) != CLR_OK) return st;
-      if ((st = h->bs_x.reserve(B * R * N)) != CLR_OK) return st;  // the forward sweep's output
-    }
-    if (innovation && (st = h->bs_rm.reserve(B * R * N)) != CLR_OK) return st;
-    ConsumerFrame frame{h};
-    hipStream_t s = h->stream.get();
-    if (innovation && b) HIP_TRY(hipMemcpyAsync(h->bs_rm.p, b, B * R * N * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(frame.start());
-    const double* zdev = nullptr;
-    bool forms_M = false;
-    if (innovation && h->launch) {
-      const clr::BSolveParams Q = narrow_solve_begin(h, nrhs);  // (clears bs_M_valid: set again once the frame has finished)
-      forms_M = true;
-      clr::BFilterParams S{};
-      S.nrhs = nrhs; S.lean = Q.lean; S.have_M = Q.have_M;
-      S.xT = S.zT = Q.xT; S.M = Q.M; S.off = Q.off; S.starts = Q.starts;
-      narrow_kernels(h, nrhs, b ? h->bs_rm.p : h->y.p, b ? (long)N : h->y_stride, h->bs_x.p, h->bs_x.p,
-                     [&] { h->launch->bfilter(P, S, 0, s); });
-      zdev = h->bs_rm.p;
-    } else if (innovation) {
-      W.nrhs = nrhs;
-      W.stride_out = (long)(R * N);
-      W.stride_ws = (long)clr::wsweep_workspace_doubles(h->J, W.nchunk, nrhs);
-      W.in = b ? h->bs_rm.p : h->y.p; W.stride_in = b ? (long)(R * N) : h->y_stride;
-      W.out = h->bs_x.p;
-      W.backward = 0;
-      clr::launch_wsweep_scan(W, h->bs_M.p, s);
-      zdev = h->bs_x.p;
-    }
-    const double* Ddev = h->D.p;  // (wide plans: the reference's storage, problem after problem)
-    if (variance && h->launch) {
-      clr::launch_relayout_back(h->D.p, (long)h->L * h->nchunk, dD.p, (long)N, h->B, h->N, h->L, h->nchunk, s);
-      Ddev = dD.p;
-    }
-    HIP_TRY(frame.stop());
-    HIP_TRY(hipGetLastError());
-    if (variance) HIP_TRY(hipMemcpyAsync(variance, Ddev, B * N * sizeof(double), hipMemcpyDeviceToHost, s));
-    if ((st = frame.finish(innovation, zdev, innovation ? B * R * N : 0)) != CLR_OK) return st;
-    if (forms_M) h->bs_M_valid = true;
-  }
-  std::vector<int> stat;
-  if ((st = nan_rows_without_factor(h, stat, {{innovation, R * N}, {variance, N}})) != CLR_OK) return st;
-  if (status) std::copy(stat.begin(), stat.end(), status);
-  return CLR_OK;
-}
-
-// The mean and variance at M points per problem given the samples strictly before each (clr_bfilter_kernels.h): the
-// residual in force laid out chunk-interleaved once, the chunks' start states of g by the first tile (they follow the
-// residual: never kept), those of S (pv_S, shared with clr_batch_predict_var_recurrence, only with `var`) unless formed,
-// then one forward pass per tile of sorted points.  Points, sorting and tiles as clr_batch_predict_var_recurrence.
-int clr_batch_forecast(clr_batch* h, int M, const double* xs, long xs_stride, double* mean, double* var) {
-  int st = require_device(h->device);
-  if (st != CLR_OK) return st;
-  if (M < 0 || (M > 0 && !xs)) return fail(CLR_INVALID_ARGUMENT, "clr_batch_forecast: M >= 0 and the points");
-  if (!mean && !var) return fail(CLR_INVALID_ARGUMENT, "clr_batch_forecast: at least one output array");
-  if (xs_stride != 0 && xs_stride != M) return fail(CLR_INVALID_ARGUMENT, "clr_batch_forecast: the points' stride is 0 (shared by all problems) or M");
-  if ((st = require_celerite_width(h, "clr_batch_forecast")) != CLR_OK) return st;
-  if (M == 0) return CLR_OK;
-  if ((st = require_factor(h, true)) != CLR_OK) return st;
-  if (!h->launch)
-    return fail(CLR_UNSUPPORTED, "clr_batch_forecast covers narrow plans (widths 1..8): a wide plan takes clr_batch_predict / clr_batch_predict_var");
-  if (h->nchunk < 2) return fail(CLR_UNSUPPORTED, "clr_batch_forecast needs a chunked plan (N >= 128)");
-  clr::BatchParams P;
-  if ((st = consumer_params(h, false, P)) != CLR_OK) return st;
-  const size_t B = (size_t)h->B, J = (size_t)h->J, Mm = (size_t)M, nsrc = xs_stride == 0 ? 1 : B, nc = (size_t)h->nchunk;
-  const size_t NS = J * (J + 1) / 2, nout = (mean ? 1 : 0) + (var ? 1 : 0);
-  SortedPoints pts;
-  pts.sort(xs, nsrc, Mm);
-  // the phases of the points' features: |d| |x*|, under the plan's own rule
-  const int xfast = (sel_max(h->dmax, h->floor_dmax) * pts.xmax < CLR_FAST_TRIG_LIMIT) ? 1 : 0;
-  // points per tile: the caller's, or the most whose per-point buffer (u(x)) fits in 1 GiB
-  const size_t budget = (size_t)1 << 27, per_point = B * J;
-  const size_t Rz = std::min<size_t>(h->predict_tile > 0 ? (size_t)h->predict_tile : std::max<size_t>(1, budget / per_point), Mm);
-  const int R = (int)Rz;
-  DevBuf dxs, dout, dux;  // dout: mean [B][M] | var [B][M], those asked for
-  if ((st = dxs.reserve(nsrc * Mm)) != CLR_OK) return st;
-  if ((st = dout.reserve(nout * B * Mm)) != CLR_OK) return st;
-  if ((st = dux.reserve(B * Rz * J)) != CLR_OK) return st;
-  if (var && (st = h->pv_S.reserve(B * nc * NS)) != CLR_OK) return st;
-  if ((st = reserve_narrow_solve(h, 1)) != CLR_OK) return st;
-  ConsumerFrame frame{h};
-  hipStream_t s = h->stream.get();
-  HIP_TRY(hipMemcpyAsync(dxs.p, pts.up, nsrc * Mm * sizeof(double), hipMemcpyHostToDevice, s));
-  HIP_TRY(frame.start());
-  const clr::BSolveParams Q = narrow_solve_begin(h, 1);  // (clears bs_M_valid: set again once the frame has finished)
-  clr::BFilterParams S{};
-  S.nrhs = 1; S.lean = Q.lean; S.have_M = Q.have_M;
-  S.have_S = h->pv_S_valid ? 1 : 0;
-  const bool forms_S = var && !h->pv_S_valid;
-  S.xT = Q.xT; S.zT = nullptr; S.M = Q.M; S.off = Q.off; S.starts = Q.starts;
-  S.S = h->pv_S.p; S.t = h->t.p; S.t_stride = h->t_stride;
-  S.xs_stride = xs_stride; S.ux = dux.p; S.out_stride = (long)M;
-  double* dmean = mean ? dout.p : nullptr;
-  double* dvar = var ? dout.p + (mean ? B * Mm : 0) : nullptr;
-  const long cells = (long)h->L * h->nchunk;
-  clr::launch_relayout(h->y.p, h->y_stride, h->bs_x.p, cells, h->B, h->N, h->L, h->nchunk, 0, s);
-  for (int m0 = 0; m0 < M; m0 += R) {
-    S.npts = std::min(R, M - m0); S.xs = dxs.p + m0;
-    S.mean = dmean ? dmean + m0 : nullptr; S.var = dvar ? dvar + m0 : nullptr;
-    h->launch->bfilter(P, S, xfast, s);
-    S.have_g = S.have_M = 1;
-    if (var) S.have_S = 1;
-  }
-  HIP_TRY(frame.stop());
-  std::vector<double> tmp(nout * B * Mm);
-  if ((st = frame.finish(tmp.data(), dout.p, nout * B * Mm)) != CLR_OK) return st;
-  h->bs_M_valid = true;
-  if (forms_S) h->pv_S_valid = true;
-  const double* tmean = tmp.data();
-  const double* tvar = tmp.data() + (mean ? B * Mm : 0);
-  if (pts.all_sorted) {
-    if (mean) std::copy(tmean, tmean + B * Mm, mean);
-    if (var) std::copy(tvar, tvar + B * Mm, var);
-  } else {
-    if (mean) pts.scatter(tmean, mean, B, Mm, xs_stride == 0);
-    if (var) pts.scatter(tvar, var, B, Mm, xs_stride == 0);
-  }
-  // the constant mean plus the conditional mean of the residual, as clr_batch_predict; under a linear mean the residual's
-  // alone -- the basis at the points is the caller's
-  if (mean && h->have_mean)
-    for (size_t p = 0; p < B; ++p) {
-      const double m = h->host_mean[h->mean_stride ? p : 0];
-      for (size_t k = 0; k < Mm; ++k) mean[p * Mm + k] = m + mean[p * Mm + k];
-    }
-  std::vector<int> stat;
-  return nan_rows_without_factor(h, stat, {{mean, Mm}, {var, Mm}});
-}
-
-// ---- clr_batch_predict_terms: the posterior of every group of kernel terms (clr_bterms_kernels.h)
-
-// The mean k_g*^T K^-1 r and the variance k_g(0) - k_g*^T K^-1 k_g* of G groups of coefficient terms at M points per
-// problem.  With `mean`: alpha = K^-1 r by the batched solve (left on the device), laid out chunk-interleaved once, the
-// chunks' start states of p and b by the first tile (they follow the residual: never kept).  With `var`: the start states
-// of S (pv_S) and Q (loo_Q) under the rules of clr_batch_predict_var_recurrence -- a mean-only call touches neither.
-// Points, sorting and tiles as clr_batch_forecast; the per-point buffers grow with G.  No mean is added: it belongs to no
-// term.
-int clr_batch_predict_terms(clr_batch* h, int M, const double* xs, long xs_stride, int G, const unsigned char* groups,
-                            double* mean, double* var) {
-  int st = require_device(h->device);
-  if (st != CLR_OK) return st;
-  if (M < 0 || (M > 0 && !xs)) return fail(CLR_INVALID_ARGUMENT, "clr_batch_predict_terms: M >= 0 and the points");
-  if (G < 1 || !groups) return fail(CLR_INVALID_ARGUMENT, "clr_batch_predict_terms: G >= 1 and the groups");
-  if (!mean && !var) return fail(CLR_INVALID_ARGUMENT, "clr_batch_predict_terms: at least one output array");
-  if (xs_stride != 0 && xs_stride != M) return fail(CLR_INVALID_ARGUMENT, "clr_batch_predict_terms: the points' stride is 0 (shared by all problems) or M");
-  if ((st = require_celerite_width(h, "clr_batch_predict_terms")) != CLR_OK) return st;
-  const int T = h->J_real + h->J_comp;
-  for (size_t k = 0; k < (size_t)G * T; ++k)
-    if (groups[k] > 1) return fail(CLR_INVALID_ARGUMENT, "clr_batch_predict_terms: a group is 0 or 1 per coefficient term");
-  if (M == 0) return CLR_OK;
-  if ((st = require_factor(h, true)) != CLR_OK) return st;
-  if (!h->launch)
-    return fail(CLR_UNSUPPORTED, "clr_batch_predict_terms covers narrow plans (widths 1..8): a wide plan takes clr_batch_predict / clr_batch_predict_var for the full kernel");
-  if (h->nchunk < 2) return fail(CLR_UNSUPPORTED, "clr_batch_predict_terms needs a chunked plan (N >= 128), as clr_batch_predict on a narrow plan does");
-  if (mean && (st = batch_solve_impl(h, 1, nullptr, nullptr)) != CLR_OK) return st;  // alpha = K^-1 r -> bs_rm [B][N]
-  clr::BatchParams P;
-  if ((st = consumer_params(h, false, P)) != CLR_OK) return st;
-  const size_t B = (size_t)h->B, J = (size_t)h->J, Mm = (size_t)M, Gg = (size_t)G, nsrc = xs_stride == 0 ? 1 : B;
-  const size_t nc = (size_t)h->nchunk, NS = J * (J + 1) / 2, nout = (mean ? 1 : 0) + (var ? 1 : 0);
-  const size_t cells = (size_t)h->L * nc;
-  // a group's rows: a real term its one row, a complex term its cos and its sin row
-  std::vector<unsigned> rowmask(Gg, 0u);
-  for (size_t g = 0; g < Gg; ++g)
-    for (int k = 0; k < T; ++k) {
-      if (!groups[g * T + k]) continue;
-      if (k < h->J_real) rowmask[g] |= 1u << k;
-      else rowmask[g] |= 3u << (h->J_real + 2 * (k - h->J_real));
-    }
-  SortedPoints pts;
-  pts.sort(xs, nsrc, Mm);
-  const int xfast = (sel_max(h->dmax, h->floor_dmax) * pts.xmax < CLR_FAST_TRIG_LIMIT) ? 1 : 0;
-  // points per tile: the caller's, or the most whose per-point buffers (u(x), v(x); e and left per group) fit in 1 GiB
-  const size_t budget = (size_t)1 << 27, per_point = B * (2 * J + (var ? Gg * (J + 1) : 0));
-  const size_t Rz = std::min<size_t>(h->predict_tile > 0 ? (size_t)h->predict_tile : std::max<size_t>(1, budget / per_point), Mm);
-  const int R = (int)Rz;
-  DevBuf dxs, dout, dux, dvx, de, dleft, dbstart;  // dout: mean [B][G][M] | var [B][G][M], those asked for
-  clr::Buffer<unsigned> dmask;
-  if ((st = dxs.reserve(nsrc * Mm)) != CLR_OK) return st;
-  if ((st = dout.reserve(nout * B * Gg * Mm)) != CLR_OK) return st;
-  if ((st = dux.reserve(B * Rz * J)) != CLR_OK) return st;
-  if ((st = dvx.reserve(B * Rz * J)) != CLR_OK) return st;
-  if ((st = dmask.reserve(Gg)) != CLR_OK) return st;
-  if (mean) {
-    if ((st = h->bs_x.reserve(B * cells)) != CLR_OK) return st;
-    if ((st = h->bs_decay.reserve(B * nc * J)) != CLR_OK) return st;
-    if ((st = h->bs_off.reserve(B * nc * J)) != CLR_OK) return st;
-    if ((st = h->bs_starts.reserve(B * nc * J)) != CLR_OK) return st;
-    if ((st = dbstart.reserve(B * nc * J)) != CLR_OK) return st;
-  }
-  if (var) {
-    if ((st = de.reserve(B * Rz * Gg * J)) != CLR_OK) return st;
-    if ((st = dleft.reserve(B * Rz * Gg)) != CLR_OK) return st;
-    if ((st = h->pv_S.reserve(B * nc * NS)) != CLR_OK) return st;
-    if ((st = h->loo_Q.reserve(B * nc * NS)) != CLR_OK) return st;
-    if ((st = h->bs_M.reserve(B * nc * J * J)) != CLR_OK) return st;
-    if ((st = h->bs_off.reserve(B * nc * J)) != CLR_OK) return st;
-    if ((st = h->bs_x.reserve(B * cells)) != CLR_OK) return st;  // (read beside by the solve's summarize when it forms the maps)
-  }
-  const double solve_ms = mean ? h->solve_device_ms : 0.0;  // (the solve above: reported with this frame's kernels)
-  ConsumerFrame frame{h};
-  hipStream_t s = h->stream.get();
-  HIP_TRY(hipMemcpyAsync(dxs.p, pts.up, nsrc * Mm * sizeof(double), hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(dmask.p, rowmask.data(), Gg * sizeof(unsigned), hipMemcpyHostToDevice, s));
-  HIP_TRY(frame.start());
-  clr::BTermsParams S{};
-  S.G = G; S.lean = h->factor_is_lean ? 1 : 0;
-  S.xs_stride = xs_stride; S.rowmask = dmask.p;
-  S.ux = dux.p; S.vx = dvx.p; S.e = de.p; S.left = dleft.p; S.out_stride = (long)M;
-  if (mean) {  // the series of alpha chunk-interleaved, once per call
-    clr::launch_relayout(h->bs_rm.p, (long)h->N, h->bs_x.p, (long)cells, h->B, h->N, h->L, h->nchunk, 0, s);
-    S.aT = h->bs_x.p;
-    S.pb.nrhs = 1; S.pb.zT = h->bs_x.p; S.pb.yT = h->bs_x.p; S.pb.decay = h->bs_decay.p; S.pb.off = h->bs_off.p;
-    S.pstart = h->bs_starts.p; S.bstart = dbstart.p;
-  }
-  bool forms_Q = false;
-  if (var) {
-    S.have_S = h->pv_S_valid ? 1 : 0;
-    S.have_Q = h->loo_Q_valid ? 1 : 0;
-    S.Q.lean = S.lean;
-    S.Q.have_M = h->bs_M_valid ? 1 : 0;
-    forms_Q = !S.have_Q;  // ... and with them the chunk maps, unless a solve has formed those
-    if (forms_Q) h->bs_M_valid = false;
-    h->pv_S_valid = h->loo_Q_valid = false;
-    // (with `mean` the chunk maps are the solve's and bs_x holds alpha: the summarize beside them is not run)
-    S.Q.cT = h->bs_x.p; S.Q.M = h->bs_M.p; S.Q.Q = h->loo_Q.p; S.Q.off = h->bs_off.p;
-    S.t = h->t.p; S.t_stride = h->t_stride; S.S = h->pv_S.p;
-  }
-  double* dmean = mean ? dout.p : nullptr;
-  double* dvar = var ? dout.p + (mean ? B * Gg * Mm : 0) : nullptr;
-  for (int m0 = 0; m0 < M; m0 += R) {
-    S.npts = std::min(R, M - m0); S.xs = dxs.p + m0;
-    S.mean = dmean ? dmean + m0 : nullptr; S.var = dvar ? dvar + m0 : nullptr;
-    h->launch->bterms(P, S, xfast, s);
-    S.have_pb = 1;
-    if (var) S.have_S = S.have_Q = 1;
-  }
-  HIP_TRY(frame.stop());
-  std::vector<double> tmp(nout * B * Gg * Mm);
-  if ((st = frame.finish(tmp.data(), dout.p, nout * B * Gg * Mm)) != CLR_OK) return st;
-  h->solve_device_ms += solve_ms;
-  if (var) {
-    h->pv_S_valid = h->loo_Q_valid = true;
-    if (forms_Q) h->bs_M_valid = true;
-  }
-  const double* tsrc[2] = {tmp.data(), tmp.data() + (mean ? B * Gg * Mm : 0)};
-  double* tdst[2] = {mean, var};
-  for (int o = 0; o < 2; ++o) {
-    if (!tdst[o]) continue;
-    if (pts.all_sorted) { std::copy(tsrc[o], tsrc[o] + B * Gg * Mm, tdst[o]); continue; }
-    for (size_t b = 0; b < B; ++b) {
-      const int* pp = pts.perm.data() + (xs_stride == 0 ? 0 : b * Mm);
-      for (size_t g = 0; g < Gg; ++g) {
-        const size_t at = (b * Gg + g) * Mm;
-        for (size_t m = 0; m < Mm; ++m) tdst[o][at + pp[m]] = tsrc[o][at + m];
-      }
-    }
-  }
-  std::vector<int> stat;
-  return nan_rows_without_factor(h, stat, {{mean, Gg * Mm}, {var, Gg * Mm}});
-}
-
-// ---- clr_batch_leave_one_out: diag(K^-1), K^-1 r and the leave-one-out log predictive density of every problem
-
-// widths 9..64: diag(K^-1) of one problem per wave from the factor in the reference's storage, sequential in n (the
-// recurrence of clr_binvdiag_kernels.h: Q_n = P - u v^T - v u^T + c_n u u^T, c_n = 1 / D_n + g^T Q_{n+1} g).  Lane k holds
-// column k of Q (JP doubles, the width padded with zeros); (Q g)_k is lane-local by symmetry, s one wave reduction; the
-// steps' phi, g = phi o W and u are staged through LDS a tile of TILE samples at a time, v per step.
-extern "C++" {
-template <int JP>
-__global__ void __launch_bounds__(64) wide_invdiag_kernel(const double* __restrict__ phi, const double* __restrict__ u,
-                                                          const double* __restrict__ W, const double* __restrict__ D, int N, int J,
-                                                          double* __restrict__ out) {
-  constexpr int TILE = 16;
-  __shared__ double s_phi[TILE][JP], s_g[TILE][JP], s_u[TILE][JP], s_v[2][JP], s_d[TILE];
-  const long b = blockIdx.x;
-  const int lane = threadIdx.x;
-  const bool live = lane < JP;
-  const int k = live ? lane : 0;
-  const double *php = phi + b * (long)J * (N - 1), *up = u + b * (long)J * (N - 1), *Wp = W + b * (long)J * N, *Dp = D + b * (long)N;
-  double* op = out + b * (long)N;
-  double Q[JP];
-#pragma unroll
-  for (int j = 0; j < JP; ++j) Q[j] = 0.0;
-  for (int hi = N; hi > 0; hi -= TILE) {
-    const int lo = hi > TILE ? hi - TILE : 0, cnt = hi - lo;
-    __syncthreads();  // (the previous tile has been read)
-    for (int e = lane; e < cnt * JP; e += 64) {
-      const int i = e / JP, j = e % JP, n = lo + i;
-      double ph = 0.0, ww = 0.0, uu = 0.0;
-      if (j < J) {
-        ww = Wp[(long)n * J + j];
-        if (n < N - 1) ph = php[(long)n * J + j];   // (the last sample's transition is 0)
-        if (n >= 1) uu = up[(long)(n - 1) * J + j];  // (u_(:, n-1) = U~(t_n); U~(t_0) enters no entry)
-      }
-      s_phi[i][j] = ph; s_g[i][j] = ph * ww; s_u[i][j] = uu;
-    }
-    if (lane < cnt) s_d[lane] = Dp[lo + lane];
-    __syncthreads();
-    for (int i = cnt - 1; i >= 0; --i) {
-      double qg = 0.0;
-#pragma unroll
-      for (int j = 0; j < JP; ++j) qg = fma(Q[j], s_g[i][j], qg);
-      const double phk = s_phi[i][k], uk = s_u[i][k];
-      double s = live ? s_g[i][k] * qg : 0.0;
-      const double vk = phk * qg;
-      if (live) s_v[i & 1][k] = vk;
-#pragma unroll
-      for (int w = 32; w > 0; w >>= 1) s += __shfl_xor(s, w, 64);
-      const double cn = 1.0 / s_d[i] + s;
-      if (lane == 0) op[lo + i] = cn;
-      __syncthreads();
-      {
-#pragma clang fp contract(off)  // (entries (j, k) and (k, j) round alike: Q stays symmetric to the bit)
-#pragma unroll
-        for (int j = 0; j < JP; ++j) {
-          const double pj = s_phi[i][j], uj = s_u[i][j], vj = s_v[i & 1][j];
-          Q[j] = (pj * phk) * Q[j] - (uj * vk + vj * uk) + cn * (uj * uk);
-        }
-      }
-    }
-  }
-}
-}  // extern "C++"
-
-// sum_n -1/2 log(2 pi / c_n) - 1/2 alpha_n^2 / c_n of one problem per workgroup in a fixed order -- thread i sums the
-// samples i, i + 256, ... in order, then a fixed tree over the 256 threads (batch.leave_one_out_from does the same on the host)
-__global__ void __launch_bounds__(256) loo_reduce_kernel(const double* __restrict__ c, const double* __restrict__ alpha, int N,
-                                                         double* __restrict__ out) {
-#pragma clang fp contract(off)
-  __shared__ double sh[256];
-  const long b = blockIdx.x;
-  const double *cp = c + b * N, *ap = alpha + b * N;
-  double s = 0.0;
-  for (int n = threadIdx.x; n < N; n += 256) {
-    const double cn = cp[n], an = ap[n];
-    s += -0.5 * log(6.283185307179586 / cn) - 0.5 * an * an / cn;
-  }
-  sh[threadIdx.x] = s;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[b] = sh[0];
-}
-
-int clr_batch_get_leave_one_out_ms(const clr_batch* h, double* diag_ms, double* solve_ms, double* reduce_ms) {
-  if (diag_ms) *diag_ms = h->loo_diag_ms;
-  if (solve_ms) *solve_ms = h->loo_solve_ms;
-  if (reduce_ms) *reduce_ms = h->loo_reduce_ms;
-  return CLR_OK;
-}
-
-// c = diag(K^-1), alpha = K^-1 r and sum_n log p(y_n | y_-n) = sum_n -1/2 log(2 pi / c_n) - 1/2 alpha_n^2 / c_n for every
-// problem from the factor of the last materialising run.  c: narrow plans, the backward matrix recurrence of
-// clr_binvdiag_kernels.h on the chunk-interleaved factor (either layout), the chunk maps shared with clr_batch_solve under
-// its validity rule; wide plans (widths 9..64), one wave per problem, sequential in n (wide_invdiag_kernel).  alpha: the
-// batched solve of the residual in force, left row-major in bs_rm.  The sum: one workgroup per problem, no atomics.
-int clr_batch_leave_one_out(clr_batch* h, double* kinv_diag, double* alpha, double* loo_logpdf, int* status) {
-  int st = require_device(h->device);
-  if (st != CLR_OK) return st;
-  if (!kinv_diag && !alpha && !loo_logpdf && !status)
-    return fail(CLR_INVALID_ARGUMENT, "clr_batch_leave_one_out: at least one output array");
-  if ((st = require_celerite_width(h, "clr_batch_leave_one_out")) != CLR_OK) return st;
-  if ((st = require_factor(h, true)) != CLR_OK) return st;
-  if (!h->launch && !clr::wsweep_scan_supported(h->N, h->J))
-    return fail(CLR_UNSUPPORTED, "clr_batch_leave_one_out on a wide plan needs N >= 512");
-  if (h->launch && h->nchunk < 2) return fail(CLR_UNSUPPORTED, "clr_batch_leave_one_out needs a chunked plan (N >= 128)");
-  const size_t B = (size_t)h->B, N = (size_t)h->N, J = (size_t)h->J;
-  const bool need_c = kinv_diag || loo_logpdf, need_alpha = alpha || loo_logpdf;
-  for (clr::Event& e : h->loo_ev)
-    if (!e) HIP_TRY(clr::create_event(e));
-  h->loo_diag_ms = h->loo_solve_ms = h->loo_reduce_ms = 0.0;
-  float ms = 0.f;
-  if (need_c) {
-    if ((st = h->loo_c.reserve(B * N)) != CLR_OK) return st;
-    clr::BatchParams P;
-    if (h->launch) {
-      if ((st = consumer_params(h, false, P)) != CLR_OK) return st;
-      const size_t nc = (size_t)h->nchunk;
-      if ((st = h->bs_x.reserve(B * (size_t)h->L * nc)) != CLR_OK) return st;
-      if ((st = h->bs_M.reserve(B * nc * J * J)) != CLR_OK) return st;
-      if ((st = h->bs_off.reserve(B * nc * J)) != CLR_OK) return st;
-      if ((st = h->loo_Q.reserve(B * nc * (J * (J + 1) / 2))) != CLR_OK) return st;
-    }
-    ConsumerFrame frame{h};  // (untimed: the parts have their own events)
-    hipStream_t s = h->stream.get();
-    HIP_TRY(hipEventRecord(h->loo_ev[0].get(), s));
-    if (h->launch) {
-      clr::BInvDiagParams S;
-      S.lean = h->factor_is_lean ? 1 : 0;
-      // (the chunk maps are the batched solve's, under its validity rule: formed here unless a solve has formed them, and
-      //  counted as formed only once this call's kernels have run to completion)
-      S.have_M = h->bs_M_valid ? 1 : 0;
-      h->bs_M_valid = false;
-      h->loo_Q_valid = false;  // (loo_Q is rewritten: the offsets, then the start matrices -- as clr_batch_predict_var_recurrence reads them)
-      S.cT = h->bs_x.p; S.M = h->bs_M.p; S.Q = h->loo_Q.p; S.off = h->bs_off.p;
-      h->launch->binvdiag(P, S, s);
-      clr::launch_relayout_back(h->bs_x.p, (long)h->L * h->nchunk, h->loo_c.p, (long)N, h->B, h->N, h->L, h->nchunk, s);
-    } else {
-      const int JP = clr::wide_padded_width(h->J);
-#define CLR_GO(WIDTH) hipLaunchKernelGGL((wide_invdiag_kernel<WIDTH>), dim3((unsigned)B), dim3(64), 0, s, h->phi.p, h->u.p, h->W.p, h->D.p, h->N, h->J, h->loo_c.p)
-      if (JP == 16) CLR_GO(16); else if (JP == 32) CLR_GO(32); else CLR_GO(64);
-#undef CLR_GO
-    }
-    HIP_TRY(hipEventRecord(h->loo_ev[1].get(), s));
-    if ((st = frame.finish(kinv_diag, h->loo_c.p, B * N)) != CLR_OK) return st;
-    if (h->launch) h->bs_M_valid = h->loo_Q_valid = true;
-    HIP_TRY(hipEventElapsedTime(&ms, h->loo_ev[0].get(), h->loo_ev[1].get()));
-    h->loo_diag_ms = ms;
-  }
-  if (need_alpha) {
-    if ((st = batch_solve_impl(h, 1, nullptr, nullptr)) != CLR_OK) return st;  // alpha = K^-1 r -> bs_rm [B][N]
-    h->loo_solve_ms = h->solve_device_ms;
-    if (loo_logpdf && (st = h->loo_out.reserve(B)) != CLR_OK) return st;
-    ConsumerFrame frame{h};  // (untimed)
-    hipStream_t s = h->stream.get();
-    if (loo_logpdf) {
-      HIP_TRY(hipEventRecord(h->loo_ev[2].get(), s));
-      hipLaunchKernelGGL(loo_reduce_kernel, dim3((unsigned)B), dim3(256), 0, s, h->loo_c.p, h->bs_rm.p, h->N, h->loo_out.p);
-      HIP_TRY(hipEventRecord(h->loo_ev[3].get(), s));
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(hipMemcpyAsync(loo_logpdf, h->loo_out.p, B * sizeof(double), hipMemcpyDeviceToHost, s));
-    }
-    if ((st = frame.finish(alpha, h->bs_rm.p, B * N)) != CLR_OK) return st;
-    if (loo_logpdf) {
-      HIP_TRY(hipEventElapsedTime(&ms, h->loo_ev[2].get(), h->loo_ev[3].get()));
-      h->loo_reduce_ms = ms;
-    }
-  }
-  // the statuses of the evaluation in force; a problem without a factor (or refused by the kernel program): NaN everywhere
-  std::vector<int> stat(B);
-  if ((st = clr_batch_get_results(h, nullptr, nullptr, nullptr, stat.data())) != CLR_OK) return st;
-  mark_refused(h, nullptr, nullptr, nullptr, stat.data());
-  const double nan = std::numeric_limits<double>::quiet_NaN();
-  for (size_t b = 0; b < B; ++b) {
-    if (stat[b] == CLR_OK) continue;
-    if (kinv_diag) std::fill(kinv_diag + b * N, kinv_diag + (b + 1) * N, nan);
-    if (alpha) std::fill(alpha + b * N, alpha + (b + 1) * N, nan);
-    if (loo_logpdf) loo_logpdf[b] = nan;
-  }
-  if (status) std::copy(stat.begin(), stat.end(), status);
-  return CLR_OK;
-}
-
-// ---- clr_batch_fit_mean_weights: the generalised-least-squares fit of a linear mean's weights
-
-int clr_batch_set_mean_fit_tile(clr_batch* h, int rhs) {
-  h->mean_fit_tile = rhs > 0 ? rhs : 0;
-  return CLR_OK;
-}
-
-int clr_batch_get_mean_fit_ms(const clr_batch* h, double* solve_ms, double* gram_ms, double* small_ms) {
-  if (solve_ms) *solve_ms = h->fit_solve_ms;
-  if (gram_ms) *gram_ms = h->fit_gram_ms;
-  if (small_ms) *small_ms = h->fit_small_ms;
-  return CLR_OK;
-}
-
-// right-hand sides per tile: the caller's (clr_batch_set_mean_fit_tile), or the most whose buffers -- `per_rhs` doubles
-// each -- fit in predict_tile's 1 GiB; never above `most` (the K + 1 there are, or what a grid axis takes), at least 1
-static int fit_tile(const clr_batch* h, size_t most, size_t per_rhs) {
-  const size_t budget = (size_t)1 << 27;  // doubles
-  const size_t R = h->mean_fit_tile > 0 ? (size_t)h->mean_fit_tile : std::max<size_t>(1, budget / std::max<size_t>(1, per_rhs));
-  return (int)std::max<size_t>(1, std::min(R, most));
-}
-
-// For every problem of a plan with a linear mean: the weights that maximise the log-likelihood at the coefficients in
-// force, w = w0 + G^-1 d with G = Phi^T K^-1 Phi, d = Phi^T K^-1 r, r the residual at the weights w0 in force -- the
-// log-likelihood is exactly quadratic in the weights, so this one Newton step from any w0 is the optimum.  The K + 1
-// right-hand sides (Phi_0 .. Phi_K-1, r) are formed on the device from the resident basis and residual, a tile of columns
-// at a time, and solved on the factor in HBM by the batched solve's kernels (narrow plans: launch->bsolve on the
-// chunk-interleaved factor, either layout, the chunk maps under clr_batch_solve's validity rule; wide plans: the two
-// sweeps of wide_batch_solve); every tile's solutions go through the bordered Gram pass (clr_bmean_kernels.h), and one
-// thread per problem runs the small solve (clr_gram_solve.h).  The weights in force stay as they are.
-int clr_batch_fit_mean_weights(clr_batch* h, double min_pivot, double* w_hat, double* cov, double* gram, double* quad_profiled,
-                               double* logdet_gram, int* status) {
-  int st = require_device(h->device);
-  if (st != CLR_OK) return st;
-  if (!std::isfinite(min_pivot) || min_pivot < 0.0 || min_pivot >= 1.0)
-    return fail(CLR_INVALID_ARGUMENT, "clr_batch_fit_mean_weights: min_pivot is finite and in [0, 1)");
-  if (h->have_mean)
-    return fail(CLR_INVALID_ARGUMENT, "clr_batch_fit_mean_weights: a constant mean is in force (clr_batch_set_mean): the fit is "
-                                      "the linear mean's -- make the constant a basis function");
-  if (h->mean_K == 0) return fail(CLR_INVALID_ARGUMENT, "clr_batch_fit_mean_weights: no basis is set (clr_batch_set_mean_basis)");
-  if ((st = require_celerite_width(h, "clr_batch_fit_mean_weights")) != CLR_OK) return st;
-  if ((st = require_factor(h, true)) != CLR_OK) return st;
-  if (h->B > 65535) return fail(CLR_UNSUPPORTED, "clr_batch_fit_mean_weights: at most 65535 problems per plan (a grid axis): shard the batch");
-  if (!h->launch && !clr::wsweep_scan_supported(h->N, h->J))
-    return fail(CLR_UNSUPPORTED, "clr_batch_fit_mean_weights on a wide plan needs N >= 512");
-  if (h->launch && h->nchunk < 2) return fail(CLR_UNSUPPORTED, "clr_batch_fit_mean_weights needs a chunked plan (N >= 128)");
-  const size_t B = (size_t)h->B, N = (size_t)h->N, J = (size_t)h->J, K = (size_t)h->mean_K, K1 = K + 1;
-  const size_t nout = clr::gram_solve_out_doubles(h->mean_K);
-  clr::BatchParams P;  // (wide plans do not read it)
-  clr::SweepParams W;
-  int R;
-  if (h->launch) {
-    if ((st = consumer_params(h, false, P)) != CLR_OK) return st;
-    const size_t cells = (size_t)h->L * h->nchunk, nc = (size_t)h->nchunk;
-    // (rows of the relayouts ride on grid.z: B * R <= 65535; a column's buffers: its chunk-interleaved cells, its
-    //  row-major solution in bs_rm, offsets and start states)
-    R = fit_tile(h, std::min<size_t>(K1, 65535 / B), B * (cells + N + 2 * nc * J));
-    if ((st = reserve_narrow_solve(h, (size_t)R)) != CLR_OK) return st;
-  } else {
-    W = wide_solve_params(h, 1);
-    const size_t ws_rhs = clr::wsweep_workspace_doubles(h->J, W.nchunk, 2) - clr::wsweep_workspace_doubles(h->J, W.nchunk, 1);
-    R = fit_tile(h, K1, B * (2 * N + ws_rhs));
-    if ((st = h->bs_M.reserve(B * clr::wsweep_workspace_doubles(h->J, W.nchunk, R))) != CLR_OK) return st;
-    if ((st = h->bs_x.reserve(B * R * N)) != CLR_OK) return st;  // the forward sweep's output (undivided)
-  }
-  if ((st = h->bs_rm.reserve(B * R * N)) != CLR_OK) return st;  // the tile's solutions, row-major
-  if ((st = h->fit_part.reserve(clr::mean_gram_workspace(h->B, h->N, h->mean_K))) != CLR_OK) return st;
-  if ((st = h->fit_gram.reserve(B * K1 * K1)) != CLR_OK) return st;
-  if ((st = h->fit_w0.reserve(B * K)) != CLR_OK) return st;
-  if ((st = h->fit_out.reserve(B * nout)) != CLR_OK) return st;
-  if ((st = h->fit_work.reserve(clr::gram_solve_workspace(h->B, h->mean_K))) != CLR_OK) return st;
-  if ((st = h->fit_status.reserve(B)) != CLR_OK) return st;
-  const int ntile = ((int)K1 + R - 1) / R;
-  if (h->fit_ev.size() < (size_t)(2 * ntile + 3)) h->fit_ev.resize(2 * ntile + 3);
-  for (int i = 0; i < 2 * ntile + 3; ++i)
-    if (!h->fit_ev[i]) HIP_TRY(clr::create_event(h->fit_ev[i]));
-  const std::vector<double> w0 = h->host_weights;  // (the copy below is drained before this call returns)
-  std::vector<double> out(B * nout);
-  std::vector<int> solve_status(B);
-  const clr::FitRhs rhs{h->basis_dev.p, h->basis_stride, h->y.p, h->y_stride, h->mean_K, h->N};
-  {
-    ConsumerFrame frame{h};  // (untimed: the three parts have their own events)
-    hipStream_t s = h->stream.get();
-    HIP_TRY(hipMemcpyAsync(h->fit_w0.p, w0.data(), B * K * sizeof(double), hipMemcpyHostToDevice, s));
-    clr::BSolveParams S;  // (narrow plans: the chunk maps are the batched solve's, formed by the first tile unless a solve left them)
-    if (h->launch) S = narrow_solve_begin(h, R);
-    HIP_TRY(hipEventRecord(h->fit_ev[0].get(), s));
-    for (int t = 0, c0 = 0; t < ntile; ++t, c0 += R) {
-      const int nr = std::min(R, (int)K1 - c0);
-      if (h->launch) {
-        const long cells = (long)h->L * h->nchunk;
-        clr::launch_fit_rhs_interleaved(rhs, c0, nr, h->B, h->L, h->nchunk, h->bs_x.p, cells, s);
-        S.nrhs = nr;
-        h->launch->bsolve(P, S, s);
-        S.have_M = 1;
-        clr::launch_relayout_back(h->bs_x.p, cells, h->bs_rm.p, (long)h->N, h->B * nr, h->N, h->L, h->nchunk, s);
-      } else {
-        clr::launch_fit_rhs_rowmajor(rhs, c0, nr, h->B, h->bs_rm.p, s);
-        wide_solve_sweeps(h, W, nr, h->bs_rm.p, (long)nr * (long)N);
-      }
-      HIP_TRY(hipEventRecord(h->fit_ev[2 * t + 1].get(), s));
-      clr::launch_mean_gram(rhs, h->bs_rm.p, c0, nr, h->B, h->fit_part.p, s);
-      HIP_TRY(hipEventRecord(h->fit_ev[2 * t + 2].get(), s));
-    }
-    clr::launch_mean_gram_finish(h->fit_part.p, h->mean_K, h->B, h->N, h->fit_gram.p, s);
-    HIP_TRY(hipEventRecord(h->fit_ev[2 * ntile + 1].get(), s));
-    clr::launch_gram_solve(h->fit_gram.p, h->fit_w0.p, min_pivot, h->mean_K, h->B, h->fit_out.p, h->fit_status.p, h->fit_work.p, s);
-    HIP_TRY(hipEventRecord(h->fit_ev[2 * ntile + 2].get(), s));
-    HIP_TRY(hipGetLastError());
-    if (gram) HIP_TRY(hipMemcpyAsync(gram, h->fit_gram.p, B * K1 * K1 * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(solve_status.data(), h->fit_status.p, B * sizeof(int), hipMemcpyDeviceToHost, s));
-    if ((st = frame.finish(out.data(), h->fit_out.p, B * nout)) != CLR_OK) return st;
-  }
-  if (h->launch) h->bs_M_valid = true;
-  double ms_solve = 0.0, ms_gram = 0.0;
-  float ms = 0.f;
-  for (int t = 0; t < ntile; ++t) {
-    HIP_TRY(hipEventElapsedTime(&ms, h->fit_ev[2 * t].get(), h->fit_ev[2 * t + 1].get()));
-    ms_solve += ms;
-    HIP_TRY(hipEventElapsedTime(&ms, h->fit_ev[2 * t + 1].get(), h->fit_ev[2 * t + 2].get()));
-    ms_gram += ms;
-  }
-  HIP_TRY(hipEventElapsedTime(&ms, h->fit_ev[2 * ntile].get(), h->fit_ev[2 * ntile + 1].get()));
-  ms_gram += ms;
-  HIP_TRY(hipEventElapsedTime(&ms, h->fit_ev[2 * ntile + 1].get(), h->fit_ev[2 * ntile + 2].get()));
-  h->fit_solve_ms = ms_solve; h->fit_gram_ms = ms_gram; h->fit_small_ms = ms;
-  // the statuses of the evaluation in force come first: a problem without a factor (or refused by the kernel program)
-  // keeps its weights, and everything else of it is NaN
-  std::vector<int> stat(B);
-  if ((st = clr_batch_get_results(h, nullptr, nullptr, nullptr, stat.data())) != CLR_OK) return st;
-  mark_refused(h, nullptr, nullptr, nullptr, stat.data());
-  const double nan = std::numeric_limits<double>::quiet_NaN();
-  for (size_t b = 0; b < B; ++b) {
-    const double* o = out.data() + b * nout;
-    const bool evaluated = stat[b] == CLR_OK;
-    const double* w = evaluated ? o : w0.data() + b * K;  // (a refused small solve has written w0 there itself)
-    if (w_hat) std::copy(w, w + K, w_hat + b * K);
-    if (cov && evaluated) std::copy(o + K, o + K + K * K, cov + b * K * K);
-    if (cov && !evaluated) std::fill(cov + b * K * K, cov + (b + 1) * K * K, nan);
-    if (gram && !evaluated) std::fill(gram + b * K1 * K1, gram + (b + 1) * K1 * K1, nan);
-    if (quad_profiled) quad_profiled[b] = evaluated ? o[K + K * K] : nan;
-    if (logdet_gram) logdet_gram[b] = evaluated ? o[K + K * K + 1] : nan;
-    if (status) status[b] = evaluated ? solve_status[b] : stat[b];
-  }
-  return CLR_OK;
-}
-
-int clr_batch_get_solve_ms(const clr_batch* h, double* device_ms) {
-  if (device_ms) *device_ms = h->solve_device_ms;
   return CLR_OK;
 }
 

@@ -2,6 +2,7 @@
 //   api_misc.hip    library / device entries, the CARMA handle
 //   api_solver.hip  clr_solver_*: the object API (one problem per handle)
 //   api_batch.hip   clr_batch_*: plans, HBM residency, path selection, evaluation, results
+//   api_batch_consumers.hip  clr_batch_*: the consumers of a plan's factor and coefficients (solve .. fit_mean_weights)
 //   api_grad.hip    clr_batch_grad*: the gradient entry points
 //   api_kernels.hip the small kernels the plans launch themselves (finalize, relayouts, factor de-interleave)
 // Here: error reporting, the device buffer types, the two handle structs, and the functions that turn a plan's state into
@@ -366,7 +367,7 @@ struct clr_batch {
   // follow its validity rule (counted as formed only once the kernels that formed them have run to completion)
   DevBuf pv_S;
   bool pv_S_valid = false, loo_Q_valid = false;
-  int predict_tile = 0;                         // clr_batch_set_predict_tile: prediction points per tile of clr_batch_predict_var (0: automatic)
+  int predict_tile = 0;                         // clr_batch_set_predict_tile: prediction points per tile of the point consumers (predict_tile; 0: automatic)
   clr::Event bs_ev[2];                          // ... its two timing events, created by the first solve, kept for the plan's life
   int factor_layout = 0;      // clr_batch_set_factor_layout: 0 the reference's four arrays, 1 lean (W, D; phi, u regenerated)
   bool factor_is_lean = false;  // what the factor in HBM holds (set by the materialising run that wrote it)
@@ -409,6 +410,13 @@ struct clr_batch {
 };
 
 
+
+// ---- defined in api_batch.hip, called by the consumers too (api_batch_consumers.hip) ---------------------------
+// settles the evaluation in flight (pending problems of a warm, one-launch or re-planned evaluation); `pin_current`: set
+// when that left the final results in the pinned staging buffer
+int warm_resolve(clr_batch* h, bool* pin_current);
+// draws the kernel program refused: NaN and CLR_INVALID_ARGUMENT in the arrays given
+void mark_refused(const clr_batch* h, double* a, double* b, double* c, int* status);
 
 // ---- what a replaced input of a plan leaves stale: one function per cause, called by the entry points ----------
 namespace {

@@ -21,6 +21,7 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "clr_core.h"
 
@@ -1117,6 +1118,56 @@ struct BatchImpl {
     if (P.fast_trig) hipLaunchKernelGGL((expand_lean_factor_kernel<JR, JC, true>), dim3(blocks), dim3(256), 0, s, P, b, t_rowmajor, phi, u, W, D);
     else hipLaunchKernelGGL((expand_lean_factor_kernel<JR, JC, false>), dim3(blocks), dim3(256), 0, s, P, b, t_rowmajor, phi, u, W, D);
   }
+  // A factor consumer's kernels are compiled per factor layout and trig flavour: go(LEAN, FAST) with the two as
+  // std::true_type / std::false_type.  The stored phi, u of the reference layout involve no trigonometry.
+  template <class Go>
+  static void lean_fast(int lean, const BatchParams& P, Go&& go) {
+    if (!lean) go(std::false_type{}, std::true_type{});
+    else if (P.fast_trig) go(std::true_type{}, std::true_type{});
+    else go(std::true_type{}, std::false_type{});
+  }
+  // the chunks' forward start states of g for Q.nrhs right-hand sides on grid.z: the solve's summarize -- split at the first
+  // right-hand side, which alone forms the chunk maps unless they are formed -- and its forward walk
+  template <bool LEAN, bool FAST>
+  static void form_g_starts(const BatchParams& P, BSolveParams Q, hipStream_t s) {
+    constexpr int J = JR + 2 * JC;
+    const unsigned lanes = (unsigned)((P.nchunk + 63) / 64), R = (unsigned)Q.nrhs;
+    const dim3 pgrid((unsigned)(((long)P.B * Q.nrhs + 63) / 64));
+    if (!Q.have_M) {
+      hipLaunchKernelGGL((bsolve_summarize_kernel<JR, JC, LEAN, FAST, true>), dim3(lanes, P.B, 1), dim3(64), 0, s, P, Q);
+      Q.r = 1;
+    }
+    if (Q.r < Q.nrhs)
+      hipLaunchKernelGGL((bsolve_summarize_kernel<JR, JC, LEAN, FAST, false>), dim3(lanes, P.B, R - Q.r), dim3(64), 0, s, P, Q);
+    hipLaunchKernelGGL((bsolve_prefix_kernel<J, false>), pgrid, dim3(64), 0, s, P, Q);
+  }
+  // the chunks' backward start matrices Q: the chunk maps by the solve's own summarize unless they are formed (the
+  // right-hand side it reads beside is whatever cT holds: its offsets go to S.off and are not used), the chunks' offsets,
+  // the walk
+  template <bool LEAN, bool FAST>
+  static void form_Q_starts(const BatchParams& P, const BInvDiagParams& S, hipStream_t s) {
+    const dim3 grid((P.nchunk + 63) / 64, P.B);
+    if (!S.have_M) {
+      BSolveParams Q;
+      Q.nrhs = 1; Q.r = 0; Q.lean = S.lean; Q.have_M = 0;
+      Q.xT = S.cT; Q.M = S.M; Q.off = S.off; Q.starts = nullptr;
+      hipLaunchKernelGGL((bsolve_summarize_kernel<JR, JC, LEAN, FAST, true>), grid, dim3(64), 0, s, P, Q);
+    }
+    hipLaunchKernelGGL((binvdiag_kernel<JR, JC, LEAN, FAST, false>), grid, dim3(64), 0, s, P, S);
+    hipLaunchKernelGGL((binvdiag_walk_kernel<JR + 2 * JC>), dim3((P.B + 63) / 64), dim3(64), 0, s, P, S);
+  }
+  // the chunks' forward start states of S: the recurrence variance's offsets and walk.  They read V.lean, V.S, V.t and
+  // V.t_stride alone (S_starts_params: a consumer with a parameter struct of its own)
+  template <bool LEAN, bool FAST>
+  static void form_S_starts(const BatchParams& P, const BPredVarRecParams& V, hipStream_t s) {
+    hipLaunchKernelGGL((bpvrec_forward_kernel<JR, JC, LEAN, FAST, false>), dim3((P.nchunk + 63) / 64, P.B), dim3(64), 0, s, P, V);
+    hipLaunchKernelGGL((bpvrec_walk_kernel<JR, JC>), dim3((P.B + 63) / 64), dim3(64), 0, s, P, V);
+  }
+  static BPredVarRecParams S_starts_params(int lean, double* S, const double* t, long t_stride) {
+    BPredVarRecParams V{};
+    V.lean = lean; V.S = S; V.t = t; V.t_stride = t_stride;
+    return V;
+  }
   // the batched solve: chunk maps once, then per right-hand side the forward and the backward chunked affine scans
   template <bool LEAN, bool FAST>
   static void bsolve_go(const BatchParams& P, BSolveParams S, hipStream_t s) {
@@ -1143,8 +1194,7 @@ struct BatchImpl {
     }
   }
   static void bsolve(const BatchParams& P, BSolveParams S, hipStream_t s) {
-    if (S.lean) { if (P.fast_trig) bsolve_go<true, true>(P, S, s); else bsolve_go<true, false>(P, S, s); }
-    else bsolve_go<false, true>(P, S, s);  // (the stored phi, u: no trigonometry)
+    lean_fast(S.lean, P, [&](auto L, auto F) { bsolve_go<L(), F()>(P, S, s); });
   }
   // the batched dot_L: chunk offsets and decay products, the walk over the chunks, the recurrence from the start states
   template <bool LEAN, bool FAST>
@@ -1155,8 +1205,7 @@ struct BatchImpl {
     hipLaunchKernelGGL((bdotl_kernel<JR, JC, LEAN, FAST, true>), grid, dim3(64), 0, s, P, S);
   }
   static void bdotl(const BatchParams& P, BDotLParams S, hipStream_t s) {
-    if (S.lean) { if (P.fast_trig) bdotl_go<true, true>(P, S, s); else bdotl_go<true, false>(P, S, s); }
-    else bdotl_go<false, true>(P, S, s);  // (the stored phi, u: no trigonometry)
+    lean_fast(S.lean, P, [&](auto L, auto F) { bdotl_go<L(), F()>(P, S, s); });
   }
   // the batched dot: per triangle the chunk offsets (and, once, the decay products), the walk, the recurrence
   template <bool FAST>
@@ -1185,94 +1234,52 @@ struct BatchImpl {
     BSolveParams Q;
     Q.nrhs = S.nrhs; Q.r = 0; Q.lean = S.lean; Q.have_M = S.have_M;
     Q.xT = S.xT; Q.M = S.M; Q.off = S.off; Q.starts = S.starts;
-    if (!S.have_M) {
-      hipLaunchKernelGGL((bsolve_summarize_kernel<JR, JC, LEAN, FAST, true>), dim3(lanes, P.B, 1), dim3(64), 0, s, P, Q);
-      Q.r = 1;
-    }
-    if (Q.r < S.nrhs)
-      hipLaunchKernelGGL((bsolve_summarize_kernel<JR, JC, LEAN, FAST, false>), dim3(lanes, P.B, R - Q.r), dim3(64), 0, s, P, Q);
-    hipLaunchKernelGGL((bsolve_prefix_kernel<J, false>), pgrid, dim3(64), 0, s, P, Q);
+    form_g_starts<LEAN, FAST>(P, Q, s);
     hipLaunchKernelGGL((bpredvar_forward_kernel<JR, JC, LEAN, FAST, RPL>), dim3(lanes, P.B, (R + RPL - 1) / RPL), dim3(64), 0, s, P, S);
     hipLaunchKernelGGL((bpredvar_finish_kernel<JR, JC>), pgrid, dim3(64), 0, s, P, S);
   }
   static void bpredvar(const BatchParams& P, BPredVarParams S, hipStream_t s) {
-    if (S.lean) { if (P.fast_trig) bpredvar_go<true, true>(P, S, s); else bpredvar_go<true, false>(P, S, s); }
-    else bpredvar_go<false, true>(P, S, s);  // (the stored phi, u: no trigonometry)
+    lean_fast(S.lean, P, [&](auto L, auto F) { bpredvar_go<L(), F()>(P, S, s); });
   }
   // diag(K^-1): the chunk maps by the solve's own summarize unless they are formed, the chunks' offsets, the walk, the
   // recurrence from the start matrices
   template <bool LEAN, bool FAST>
   static void binvdiag_go(const BatchParams& P, const BInvDiagParams& S, hipStream_t s) {
-    const dim3 grid((P.nchunk + 63) / 64, P.B);
-    if (!S.have_M) {  // (the right-hand side it reads beside is whatever cT holds: its offsets go to S.off and are not used)
-      BSolveParams Q;
-      Q.nrhs = 1; Q.r = 0; Q.lean = S.lean; Q.have_M = 0;
-      Q.xT = S.cT; Q.M = S.M; Q.off = S.off; Q.starts = nullptr;
-      hipLaunchKernelGGL((bsolve_summarize_kernel<JR, JC, LEAN, FAST, true>), grid, dim3(64), 0, s, P, Q);
-    }
-    hipLaunchKernelGGL((binvdiag_kernel<JR, JC, LEAN, FAST, false>), grid, dim3(64), 0, s, P, S);
-    hipLaunchKernelGGL((binvdiag_walk_kernel<JR + 2 * JC>), dim3((P.B + 63) / 64), dim3(64), 0, s, P, S);
-    hipLaunchKernelGGL((binvdiag_kernel<JR, JC, LEAN, FAST, true>), grid, dim3(64), 0, s, P, S);
+    form_Q_starts<LEAN, FAST>(P, S, s);
+    hipLaunchKernelGGL((binvdiag_kernel<JR, JC, LEAN, FAST, true>), dim3((P.nchunk + 63) / 64, P.B), dim3(64), 0, s, P, S);
   }
   static void binvdiag(const BatchParams& P, BInvDiagParams S, hipStream_t s) {
-    if (S.lean) { if (P.fast_trig) binvdiag_go<true, true>(P, S, s); else binvdiag_go<true, false>(P, S, s); }
-    else binvdiag_go<false, true>(P, S, s);  // (the stored phi, u: no trigonometry)
+    lean_fast(S.lean, P, [&](auto L, auto F) { binvdiag_go<L(), F()>(P, S, s); });
   }
   // the predictive variance by recurrence at one tile of sorted points: the points' features; unless formed, the forward
   // start states (offsets, walk) and the backward start matrices (the chunk maps by the solve's own summarize unless they
   // are formed, binvdiag's offsets and walk); the forward and the backward replay
   template <bool LEAN, bool FAST>
   static void bpredvar_rec_go(const BatchParams& P, const BPredVarRecParams& S, int xfast, hipStream_t s) {
-    const dim3 grid((P.nchunk + 63) / 64, P.B), wgrid((P.B + 63) / 64), fgrid((unsigned)(((long)P.B * S.npts + 255) / 256));
+    const dim3 grid((P.nchunk + 63) / 64, P.B), fgrid((unsigned)(((long)P.B * S.npts + 255) / 256));
     if (xfast) hipLaunchKernelGGL((bpvrec_features_kernel<JR, JC, true>), fgrid, dim3(256), 0, s, P, S);
     else hipLaunchKernelGGL((bpvrec_features_kernel<JR, JC, false>), fgrid, dim3(256), 0, s, P, S);
-    if (!S.have_S) {
-      hipLaunchKernelGGL((bpvrec_forward_kernel<JR, JC, LEAN, FAST, false>), grid, dim3(64), 0, s, P, S);
-      hipLaunchKernelGGL((bpvrec_walk_kernel<JR, JC>), wgrid, dim3(64), 0, s, P, S);
-    }
-    if (!S.have_Q) {
-      if (!S.Q.have_M) {  // (as binvdiag_go: the offsets beside the maps go to Q.off and are not used)
-        BSolveParams Q;
-        Q.nrhs = 1; Q.r = 0; Q.lean = S.lean; Q.have_M = 0;
-        Q.xT = S.Q.cT; Q.M = S.Q.M; Q.off = S.Q.off; Q.starts = nullptr;
-        hipLaunchKernelGGL((bsolve_summarize_kernel<JR, JC, LEAN, FAST, true>), grid, dim3(64), 0, s, P, Q);
-      }
-      hipLaunchKernelGGL((binvdiag_kernel<JR, JC, LEAN, FAST, false>), grid, dim3(64), 0, s, P, S.Q);
-      hipLaunchKernelGGL((binvdiag_walk_kernel<JR + 2 * JC>), wgrid, dim3(64), 0, s, P, S.Q);
-    }
+    if (!S.have_S) form_S_starts<LEAN, FAST>(P, S, s);
+    if (!S.have_Q) form_Q_starts<LEAN, FAST>(P, S.Q, s);
     hipLaunchKernelGGL((bpvrec_forward_kernel<JR, JC, LEAN, FAST, true>), grid, dim3(64), 0, s, P, S);
     hipLaunchKernelGGL((bpvrec_backward_kernel<JR, JC, LEAN, FAST>), grid, dim3(64), 0, s, P, S);
   }
   static void bpredvar_rec(const BatchParams& P, BPredVarRecParams S, int xfast, hipStream_t s) {
-    if (S.lean) { if (P.fast_trig) bpredvar_rec_go<true, true>(P, S, xfast, s); else bpredvar_rec_go<true, false>(P, S, xfast, s); }
-    else bpredvar_rec_go<false, true>(P, S, xfast, s);  // (the stored phi, u: no trigonometry)
+    lean_fast(S.lean, P, [&](auto L, auto F) { bpredvar_rec_go<L(), F()>(P, S, xfast, s); });
   }
   // the causal half, forward only: unless an earlier tile of the call has formed them, the chunks' start states of g (the
   // solve's own summarize -- with the chunk maps unless they are formed -- and forward walk); with S.var, unless formed, the
   // chunks' start states of S (the recurrence variance's offsets and walk); the points' features; the forward recurrence
   template <bool LEAN, bool FAST>
   static void bfilter_go(const BatchParams& P, const BFilterParams& S, int xfast, hipStream_t s) {
-    constexpr int J = JR + 2 * JC;
-    const unsigned lanes = (unsigned)((P.nchunk + 63) / 64), R = (unsigned)S.nrhs;
-    const dim3 grid(lanes, P.B, R), wgrid((P.B + 63) / 64), pgrid((unsigned)(((long)P.B * S.nrhs + 63) / 64));
+    const dim3 grid((P.nchunk + 63) / 64, P.B, S.nrhs);
     if (!S.have_g) {
       BSolveParams Q;
       Q.nrhs = S.nrhs; Q.r = 0; Q.lean = S.lean; Q.have_M = S.have_M;
       Q.xT = const_cast<double*>(S.xT); Q.M = S.M; Q.off = S.off; Q.starts = S.starts;
-      if (!S.have_M) {
-        hipLaunchKernelGGL((bsolve_summarize_kernel<JR, JC, LEAN, FAST, true>), dim3(lanes, P.B, 1), dim3(64), 0, s, P, Q);
-        Q.r = 1;
-      }
-      if (Q.r < S.nrhs)
-        hipLaunchKernelGGL((bsolve_summarize_kernel<JR, JC, LEAN, FAST, false>), dim3(lanes, P.B, R - Q.r), dim3(64), 0, s, P, Q);
-      hipLaunchKernelGGL((bsolve_prefix_kernel<J, false>), pgrid, dim3(64), 0, s, P, Q);
+      form_g_starts<LEAN, FAST>(P, Q, s);
     }
-    if (S.var && !S.have_S) {
-      BPredVarRecParams V{};
-      V.lean = S.lean; V.S = S.S; V.t = S.t; V.t_stride = S.t_stride;
-      hipLaunchKernelGGL((bpvrec_forward_kernel<JR, JC, LEAN, FAST, false>), dim3(lanes, P.B), dim3(64), 0, s, P, V);
-      hipLaunchKernelGGL((bpvrec_walk_kernel<JR, JC>), wgrid, dim3(64), 0, s, P, V);
-    }
+    if (S.var && !S.have_S) form_S_starts<LEAN, FAST>(P, S_starts_params(S.lean, S.S, S.t, S.t_stride), s);
     if (S.npts == 0) {
       hipLaunchKernelGGL((bfilter_forward_kernel<JR, JC, LEAN, FAST, false, false>), grid, dim3(64), 0, s, P, S);
       return;
@@ -1284,8 +1291,7 @@ struct BatchImpl {
     else hipLaunchKernelGGL((bfilter_forward_kernel<JR, JC, LEAN, FAST, true, false>), grid, dim3(64), 0, s, P, S);
   }
   static void bfilter(const BatchParams& P, BFilterParams S, int xfast, hipStream_t s) {
-    if (S.lean) { if (P.fast_trig) bfilter_go<true, true>(P, S, xfast, s); else bfilter_go<true, false>(P, S, xfast, s); }
-    else bfilter_go<false, true>(P, S, xfast, s);  // (the stored phi, u: no trigonometry)
+    lean_fast(S.lean, P, [&](auto L, auto F) { bfilter_go<L(), F()>(P, S, xfast, s); });
   }
   // component separation at one tile of sorted points: the points' features; with S.mean, unless an earlier tile of the
   // call has formed them, the chunks' start states of b and p (the two passes of the batched dot on alpha, offsets and
@@ -1309,23 +1315,9 @@ struct BatchImpl {
   }
   template <bool LEAN, bool FAST>
   static void bterms_var_go(const BatchParams& P, const BTermsParams& S, hipStream_t s) {
-    const dim3 grid((P.nchunk + 63) / 64, P.B), wgrid((P.B + 63) / 64);
-    if (!S.have_S) {
-      BPredVarRecParams V{};
-      V.lean = S.lean; V.S = S.S; V.t = S.t; V.t_stride = S.t_stride;
-      hipLaunchKernelGGL((bpvrec_forward_kernel<JR, JC, LEAN, FAST, false>), grid, dim3(64), 0, s, P, V);
-      hipLaunchKernelGGL((bpvrec_walk_kernel<JR, JC>), wgrid, dim3(64), 0, s, P, V);
-    }
-    if (!S.have_Q) {
-      if (!S.Q.have_M) {  // (as binvdiag_go: the offsets beside the maps go to Q.off and are not used)
-        BSolveParams Q;
-        Q.nrhs = 1; Q.r = 0; Q.lean = S.lean; Q.have_M = 0;
-        Q.xT = S.Q.cT; Q.M = S.Q.M; Q.off = S.Q.off; Q.starts = nullptr;
-        hipLaunchKernelGGL((bsolve_summarize_kernel<JR, JC, LEAN, FAST, true>), grid, dim3(64), 0, s, P, Q);
-      }
-      hipLaunchKernelGGL((binvdiag_kernel<JR, JC, LEAN, FAST, false>), grid, dim3(64), 0, s, P, S.Q);
-      hipLaunchKernelGGL((binvdiag_walk_kernel<JR + 2 * JC>), wgrid, dim3(64), 0, s, P, S.Q);
-    }
+    const dim3 grid((P.nchunk + 63) / 64, P.B);
+    if (!S.have_S) form_S_starts<LEAN, FAST>(P, S_starts_params(S.lean, S.S, S.t, S.t_stride), s);
+    if (!S.have_Q) form_Q_starts<LEAN, FAST>(P, S.Q, s);
     hipLaunchKernelGGL((bterms_var_forward_kernel<JR, JC, LEAN, FAST>), grid, dim3(64), 0, s, P, S);
     hipLaunchKernelGGL((bterms_var_backward_kernel<JR, JC, LEAN, FAST>), grid, dim3(64), 0, s, P, S);
   }
@@ -1336,10 +1328,7 @@ struct BatchImpl {
     if (xfast) hipLaunchKernelGGL((bpvrec_features_kernel<JR, JC, true>), fgrid, dim3(256), 0, s, P, X);
     else hipLaunchKernelGGL((bpvrec_features_kernel<JR, JC, false>), fgrid, dim3(256), 0, s, P, X);
     if (S.mean) { if (P.fast_trig) bterms_mean_go<true>(P, S, s); else bterms_mean_go<false>(P, S, s); }
-    if (S.var) {
-      if (S.lean) { if (P.fast_trig) bterms_var_go<true, true>(P, S, s); else bterms_var_go<true, false>(P, S, s); }
-      else bterms_var_go<false, true>(P, S, s);  // (the stored phi, u: no trigonometry)
-    }
+    if (S.var) lean_fast(S.lean, P, [&](auto L, auto F) { bterms_var_go<L(), F()>(P, S, s); });
   }
   static void compose_check(const BatchParams& P, int g, double* coop, double* ref, hipStream_t s) {
     constexpr int J = JR + 2 * JC;

@@ -54,7 +54,7 @@ struct FitRhs {
 };
 // columns c0 .. c0 + nr of every problem chunk-interleaved, row b * nr + r of dst ([row][i][chunk], rows `cells` apart;
 // cells past the series: zeros) -- the narrow plans' batched solve reads this.  The rows ride on grid.z: the caller keeps
-// B * nr <= 65535 (api_batch.hip: clr_batch_fit_mean_weights sizes its tile so).
+// B * nr <= 65535 (api_batch_consumers.hip: clr_batch_fit_mean_weights sizes its tile so).
 void launch_fit_rhs_interleaved(const FitRhs& R, int c0, int nr, int B, int L, int nchunk, double* dst, long cells, hipStream_t s);
 // ... row-major, dst[(b * nr + r) * N + n] -- the wide plans' sweeps read this
 void launch_fit_rhs_rowmajor(const FitRhs& R, int c0, int nr, int B, double* dst, hipStream_t s);

@@ -97,6 +97,27 @@ def coeffs_of(case, p=None):
     return tuple(case[k][p] for k in keys)
 
 
+def edge_points(case, rng, extra=6, own=10, L=32):
+    """For a series cut into chunks of ``L`` samples (the consumer tests' 700 samples in 22 chunks of 32, the last one
+    ragged).  Shared sorted points -- one before t_0, x = t_0 (m = 0), the chunk edges t[31], the midpoint of
+    t[31] | t[32], t[32] and t[64], one inside the ragged last chunk, t[N-1] and 5 % past the end, a few random ones --,
+    per-problem points, and an unsorted permutation of the shared ones.  The data times are problem 0's: exact there,
+    interior elsewhere."""
+    t = case["t"]
+    B, N = t.shape
+    lo, hi = t.min(), t.max()
+    pad = 0.05 * (hi - lo)
+    t0 = t[0]
+    shared = np.sort(np.concatenate([[lo - pad, t0[0], t0[L - 1], 0.5 * (t0[L - 1] + t0[L]), t0[L], t0[2 * L],
+                                      0.5 * (t0[21 * L + 9] + t0[21 * L + 10]), t0[N - 1], hi + pad],
+                                     rng.uniform(lo - pad, hi + pad, extra)]))
+    mine = np.stack([np.sort(np.concatenate([[t[p, 0] - pad, t[p, 0], t[p, L - 1], t[p, L], t[p, N - 1], t[p, N - 1] + pad],
+                                             rng.uniform(lo - pad, hi + pad, own - 6)])) for p in range(B)])
+    perm = rng.permutation(len(shared))
+    assert np.any(np.diff(shared[perm]) < 0)
+    return shared, mine, perm
+
+
 ALL_WIDTH_SHAPES = [(jr, jc) for jc in range(5) for jr in range(9) if 1 <= jr + 2 * jc <= 8]
 
 # one wide shape per summarize / prefix instantiation bucket of launch_wsweep_scan (csrc/wsweep_kernels.hip): the batched

@@ -14,7 +14,7 @@ import pytest
 
 from celerite_amd import batch
 from oracle import ref
-from _cases import ALL_WIDTH_SHAPES, CONSUMER_WIDE_SHAPES, synthetic, coeffs_of, within
+from _cases import ALL_WIDTH_SHAPES, CONSUMER_WIDE_SHAPES, synthetic, coeffs_of, within, edge_points
 
 pytestmark = pytest.mark.gpu
 
@@ -235,6 +235,86 @@ def test_narrow_consumers_on_the_library_trig_kernels(JR, JC):
         else:
             within("narrow consumers, library trig: lean vs reference layout of the same plan, of the largest entry",
                    of_largest(outs["lean"][key], outs["reference"][key]), DOT, key)
+
+
+# the entries that claim a plan's cached factor state (the chunk maps, the start states of S, the start matrices Q), each
+# as the FIRST call after a materialising run; `x`, `phi`: per-problem unsorted points and the mean's basis there
+FIRST_CALLS = {
+    "solve": lambda plan, x, phi: plan.solve(),
+    "predict var (solve route)": lambda plan, x, phi: plan.predict(x, return_var=True, mean_basis=phi),
+    "predict var (recurrence)": lambda plan, x, phi: plan.predict(x, return_var=True, mean_basis=phi, method="recurrence"),
+    "inverse_diagonal": lambda plan, x, phi: plan.inverse_diagonal(),
+    "one_step_ahead": lambda plan, x, phi: plan.one_step_ahead(),
+    "forecast var": lambda plan, x, phi: plan.forecast(x, return_var=True, mean_basis=phi),
+    "predict_terms var": lambda plan, x, phi: plan.predict_terms(x, return_var=True),
+    "fit_mean_weights": lambda plan, x, phi: plan.fit_mean_weights(),
+}
+# ... and what runs after it on the same plan, in this order
+FOLLOWERS = [
+    ("solve", FIRST_CALLS["solve"]),
+    ("predict var (recurrence)", FIRST_CALLS["predict var (recurrence)"]),
+    ("forecast var", FIRST_CALLS["forecast var"]),
+    ("leave_one_out", lambda plan, x, phi: plan.leave_one_out()),
+    ("predict_terms var", FIRST_CALLS["predict_terms var"]),
+]
+_CALL_ORDER = {}
+
+
+def call_order_case(layout):
+    """The case, its points and -- computed once per layout -- what a fresh plan returns for each follower alone."""
+    if layout not in _CALL_ORDER:
+        JR, JC = 2, 3
+        case = synthetic(NARROW_B, NARROW_N, JR, JC, "bench", seed=613)
+        rng = np.random.RandomState(29)
+        own = edge_points(case, rng, own=12)[1]
+        own = own[:, rng.permutation(own.shape[1])]          # before t_0, at samples and past t_{N-1}, unsorted
+        assert np.any(np.diff(own, axis=1) < 0) and (own.min(axis=1) < case["t"][:, 0]).all()
+        assert (own.max(axis=1) > case["t"][:, -1]).all() and all(case["t"][p, 0] in own[p] for p in range(NARROW_B))
+        phi = np.ones((1, own.shape[1]))
+        alone = {}
+        for name, call in FOLLOWERS:
+            plan = call_order_plan(case, layout)
+            try:
+                alone[name] = arrays_of(call(plan, own, phi))
+            finally:
+                plan.close()
+        _CALL_ORDER[layout] = (case, own, phi, alone)
+    return _CALL_ORDER[layout]
+
+
+def call_order_plan(case, layout):
+    """A materialised plan under a one-column basis with weights zero: the residual is y exactly, and the fit can run."""
+    plan = narrow_plan(case, 2, 3, layout)
+    plan.set_mean_basis(np.ones((1, NARROW_N)))
+    st = plan.log_likelihood(materialize=True)[3]
+    assert (st == 0).all(), st
+    return plan
+
+
+def arrays_of(out):
+    return [out] if isinstance(out, np.ndarray) else [np.asarray(a) for a in out]
+
+
+@pytest.mark.parametrize("first", sorted(FIRST_CALLS))
+@pytest.mark.parametrize("layout", ["reference", "lean"])
+def test_cached_factor_state_whoever_claims_it_first(layout, first):
+    """The chunk maps, the forward start states of S and the backward start matrices Q depend on the factor only and are
+    shared by eight entries: whichever runs first after a materialising run forms what it needs, and the others must find
+    exactly what they would have formed themselves.  Every claimant in turn is the first call; then ``solve``, the
+    recurrence variance, ``forecast`` with its variance, ``leave_one_out`` and ``predict_terms`` with its variance run on
+    the same plan, and each equals, bit for bit, what a fresh plan returns for that call alone.  22 chunks with a ragged
+    last one (a stale start state shows there), widths (2, 3), a dozen unsorted points per problem."""
+    case, own, phi, alone = call_order_case(layout)
+    plan = call_order_plan(case, layout)
+    try:
+        FIRST_CALLS[first](plan, own, phi)
+        for name, call in FOLLOWERS:
+            got = arrays_of(call(plan, own, phi))
+            assert len(got) == len(alone[name])
+            for k, (a, b) in enumerate(zip(got, alone[name])):
+                assert np.array_equal(a, b), (first, name, k, float(np.max(np.abs(a - b))))
+    finally:
+        plan.close()
 
 
 # ---------------------------------------------------------------------------------------------------------------------

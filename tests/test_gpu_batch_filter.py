@@ -25,7 +25,7 @@ import pytest
 
 from celerite_amd import batch
 from oracle import ref
-from _cases import ALL_WIDTH_SHAPES, synthetic, coeffs_of, within, grad_family_long_gap
+from _cases import ALL_WIDTH_SHAPES, synthetic, coeffs_of, within, grad_family_long_gap, edge_points
 
 pytestmark = pytest.mark.gpu
 
@@ -131,25 +131,6 @@ def check_innovations(tag, case, osa, rhs=None, bar=NARROW_SOLVE, skip=()):
         within(tag + ": innovation vs oracle forward substitution, of the largest entry", dz, bar, p)
         within(tag + ": variance vs oracle D (relative)", dD, D_BAR, p)
     print("%s: innovation %.3e of the largest entry, variance %.3e relative" % (tag, worst[0], worst[1]))
-
-
-def edge_points(case, rng, extra=6, own=10):
-    """Shared sorted points -- one before t_0, x = t_0 (m = 0), the chunk edges t[31], the midpoint of t[31] | t[32], t[32]
-    and t[64], one inside the ragged last chunk, t[N-1] and 5 % past the end, a few random ones --, per-problem points,
-    and an unsorted permutation of the shared ones.  The data times are problem 0's: exact there, interior elsewhere."""
-    t = case["t"]
-    B, N = t.shape
-    lo, hi = t.min(), t.max()
-    pad = 0.05 * (hi - lo)
-    t0 = t[0]
-    shared = np.sort(np.concatenate([[lo - pad, t0[0], t0[L - 1], 0.5 * (t0[L - 1] + t0[L]), t0[L], t0[2 * L],
-                                      0.5 * (t0[21 * L + 9] + t0[21 * L + 10]), t0[N - 1], hi + pad],
-                                     rng.uniform(lo - pad, hi + pad, extra)]))
-    mine = np.stack([np.sort(np.concatenate([[t[p, 0] - pad, t[p, 0], t[p, L - 1], t[p, L], t[p, N - 1], t[p, N - 1] + pad],
-                                             rng.uniform(lo - pad, hi + pad, own - 6)])) for p in range(B)])
-    perm = rng.permutation(len(shared))
-    assert np.any(np.diff(shared[perm]) < 0)
-    return shared, mine, perm
 
 
 def narrow_plan(case, JR, JC, layout, chunks=24, expect=NARROW_CHUNKS, cls=batch.BatchedGP, **kw):
