@@ -127,6 +127,12 @@ def _load():
     lib.clr_sharded_forecast.argtypes = [C.c_void_p, C.c_int, _dp, C.c_long, _dp, _dp]
     lib.clr_batch_predict_terms.argtypes = [C.c_void_p, C.c_int, _dp, C.c_long, C.c_int, C.c_void_p, _dp, _dp]
     lib.clr_sharded_predict_terms.argtypes = [C.c_void_p, C.c_int, _dp, C.c_long, C.c_int, C.c_void_p, _dp, _dp]
+    lib.clr_batch_predict_cov.argtypes = [C.c_void_p, C.c_int, _dp, C.c_long, _dp]
+    lib.clr_sharded_predict_cov.argtypes = [C.c_void_p, C.c_int, _dp, C.c_long, _dp]
+    lib.clr_batch_sample_conditional.argtypes = [C.c_void_p, C.c_int, _dp, C.c_long, C.c_int, _dp, C.c_double, C.c_double, _dp, _ip]
+    lib.clr_sharded_sample_conditional.argtypes = [C.c_void_p, C.c_int, _dp, C.c_long, C.c_int, _dp, C.c_double, C.c_double, _dp, _ip]
+    lib.clr_batch_set_conditional_tile.argtypes = [C.c_void_p, C.c_int]
+    lib.clr_sharded_set_conditional_tile.argtypes = [C.c_void_p, C.c_int]
     lib.clr_gram_solve.argtypes = [C.c_int, C.c_int, _dp, _dp, C.c_double] + [_dp] * 4 + [_ip]
     lib.clr_kernel_create.argtypes = [C.c_int, _ip, C.c_int, _dp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
     lib.clr_kernel_destroy.argtypes = [C.c_void_p]
@@ -476,6 +482,72 @@ def _predict_terms(plan, name, check, xs, groups, return_var):
     check(getattr(_load(), name)(plan._h, int(M), _ptr(xs), stride, int(G), masks.ctypes.data_as(C.c_void_p), _ptr(mean),
                                  None if var is None else _ptr(var)))
     return (mean, var) if return_var else mean
+
+
+def _points_arg(plan, xs):
+    xs = _f64(xs)
+    if xs.ndim == 1:
+        return xs, 0
+    if xs.ndim == 2 and xs.shape[0] == plan.B:
+        return xs, xs.shape[1]
+    raise ValueError("dimension mismatch")
+
+
+def _predict_cov(plan, name, check, xs):
+    """``predict_cov`` of both plan classes: the arguments are checked before the library is touched."""
+    xs, stride = _points_arg(plan, xs)
+    M = xs.shape[-1]
+    cov = np.empty((plan.B, M, M))
+    check(getattr(_load(), name)(plan._h, int(M), _ptr(xs), stride, _ptr(cov)))
+    return cov
+
+
+def _predict_any_order(plan, xs, mean_basis):
+    """``plan.predict(xs, mean_basis=mean_basis)`` for points in any order: ``predict`` walks its points as the reference
+    does, ascending, so unsorted ones go in sorted (ties in the given order) and the means come back in the caller's order."""
+    if xs.shape[-1] < 2 or not np.any(np.diff(xs, axis=-1) < 0):
+        return plan.predict(xs, mean_basis=mean_basis)
+    order = np.argsort(xs, axis=-1, kind="stable")
+    basis = None
+    if mean_basis is not None:
+        a = _f64(mean_basis)
+        if xs.ndim == 1:
+            basis = np.ascontiguousarray(a[..., order])
+        else:
+            a = np.broadcast_to(a, (plan.B,) + a.shape[-2:]) if a.ndim in (2, 3) else a
+            basis = np.ascontiguousarray(np.take_along_axis(a, order[:, None, :], axis=-1))
+    got = plan.predict(np.ascontiguousarray(np.take_along_axis(xs, order, axis=-1)), mean_basis=basis)
+    mean = np.empty_like(got)
+    np.put_along_axis(mean, np.broadcast_to(order, got.shape), got, axis=-1)
+    return mean
+
+
+def _sample_conditional(plan, name, check, xs, size, regularize, min_pivot, mean_basis, random, normals, return_status):
+    """``sample_conditional`` of both plan classes: the arguments are checked before the library is touched."""
+    xs, stride = _points_arg(plan, xs)
+    M = xs.shape[-1]
+    if size is not None and (isinstance(size, (bool, np.bool_)) or int(size) != size or int(size) < 1):
+        raise ValueError("size is None or an integer >= 1")
+    n = 1 if size is None else int(size)
+    p = _check_min_pivot(min_pivot)
+    reg = float(regularize)
+    if not (np.isfinite(reg) and reg >= 0.0):
+        raise ValueError("regularize must be finite and not negative")
+    if normals is not None:
+        z = _f64(normals)
+        if z.shape != ((plan.B, M) if size is None else (plan.B, n, M)):
+            raise ValueError("dimension mismatch")
+    else:
+        rng = np.random if random is None else random
+        z = _f64(rng.standard_normal((plan.B, M) if size is None else (plan.B, n, M)))
+    _linear_mean_at(plan, mean_basis, M)      # (its checks, before the device works)
+    draws = np.empty((plan.B, n, M))
+    st = np.empty(plan.B, dtype=np.int32)
+    check(getattr(_load(), name)(plan._h, int(M), _ptr(xs), stride, n, _ptr(z), reg, p, _ptr(draws), st.ctypes.data_as(_ip)))
+    out = _predict_any_order(plan, xs, mean_basis)[:, None, :] + draws
+    if size is None:
+        out = out[:, 0, :]
+    return (out, st) if return_status else out
 
 
 def _exclusive_means(mean, mean_weights):
@@ -941,6 +1013,38 @@ class BatchedGP(object):
         M = 1e4, where G times the numbers come down and the points go in 5 tiles, 171 ms beside 247 ms and 334 ms
         beside 277 ms.  At 256 x 1e4 x width 4: 1.20 / 1.32 ms beside 19.3 / 19.6 ms at M = 1."""
         return _predict_terms(self, "clr_batch_predict_terms", _check, xs, groups, return_var)
+
+    def predict_cov(self, xs):
+        """The posterior covariance of the latent process between the points ``xs`` -- ``(M,)`` shared by all problems or
+        ``(B, M)``, sorted or not -- of every problem, ``(B, M, M)`` (``clr_batch_predict_cov``; ``GP.predict(...,
+        return_cov=True)``, celerite.py:283-291, for B problems): ``k(x_i - x_j) - k*_i^T K^-1 k*_j`` from the factor of the
+        last materialising run -- no jitter, no observational variance, as :meth:`predict`'s variance, which is its
+        diagonal.  Full, symmetric to the bit.  No N x M block is solved: one forward and two backward passes over the
+        factor, O(J^3) per point and O(J^2) per pair of points (``csrc/clr_bcond_kernels.h``).  Narrow plans (widths
+        1..8, N >= 128); problems go through in tiles (:meth:`set_conditional_tile`)."""
+        return _predict_cov(self, "clr_batch_predict_cov", _check, xs)
+
+    def sample_conditional(self, xs, size=None, regularize=0.0, min_pivot=1e-10, mean_basis=None, random=None, normals=None,
+                           return_status=False):
+        """Joint draws of the latent process at the points ``xs`` given the data (``GP.sample_conditional``,
+        celerite.py:327-332, for B problems): :meth:`predict`'s conditional mean (``mean_basis`` as there) plus
+        ``L diag(d)^1/2 n`` with ``C + regularize I = L diag(d) L^T``, ``C`` the covariance of :meth:`predict_cov`
+        (``clr_batch_sample_conditional``).  ``size=None``: ``(B, M)``; else ``(B, size, M)``.  The standard normals
+        ``n`` come from ``random`` (default ``np.random``) as in :meth:`sample`, or are ``normals`` of the result's
+        shape; ``normals[..., r]`` belongs to point ``xs[..., r]``, the factor is taken in ascending order of the points.
+        The factor follows from the celerite recurrence over the points -- O(J^3) per point, O(J^2) per point and draw,
+        no M x M matrix.  A pivot within ``min_pivot k(0)`` of zero (1e-10: the bar on a predictive variance) marks a
+        point that is a function of the earlier ones -- a repeated point, a point on a sample without noise -- and its
+        normal does not enter; a pivot below ``-min_pivot k(0)`` refuses the problem: its rows are NaN and its status
+        ``CLR_NOT_POSITIVE_DEFINITE`` (``return_status=True``: ``(draws, status[B])``).  Narrow plans (widths 1..8,
+        N >= 128); problems go through in tiles (:meth:`set_conditional_tile`)."""
+        return _sample_conditional(self, "clr_batch_sample_conditional", _check, xs, size, regularize, min_pivot, mean_basis,
+                                   random, normals, return_status)
+
+    def set_conditional_tile(self, problems=0):
+        """Problems per tile of :meth:`predict_cov` and :meth:`sample_conditional` (``clr_batch_set_conditional_tile``);
+        0: automatic, as many as fit 1 GiB of device scratch.  The results do not depend on it."""
+        _check(_load().clr_batch_set_conditional_tile(self._h, int(problems)))
 
     def inverse_diagonal(self):
         """``diag(K_p^-1)`` of every problem, ``(B, N)``, from the factor of the last materialising run
@@ -1635,6 +1739,22 @@ class ShardedBatchedGP(object):
         """The posterior of each group of kernel terms at ``xs`` (as :meth:`BatchedGP.predict_terms`), every shard on
         its slice."""
         return _predict_terms(self, "clr_sharded_predict_terms", lambda st: self._ok(st), xs, groups, return_var)
+
+    def predict_cov(self, xs):
+        """The posterior covariance between the points ``xs`` of every problem (as :meth:`BatchedGP.predict_cov`), every
+        shard on its slice."""
+        return _predict_cov(self, "clr_sharded_predict_cov", lambda st: self._ok(st), xs)
+
+    def sample_conditional(self, xs, size=None, regularize=0.0, min_pivot=1e-10, mean_basis=None, random=None, normals=None,
+                           return_status=False):
+        """Joint draws at the points ``xs`` given the data (as :meth:`BatchedGP.sample_conditional`), every shard on its
+        slice."""
+        return _sample_conditional(self, "clr_sharded_sample_conditional", lambda st: self._ok(st), xs, size, regularize,
+                                   min_pivot, mean_basis, random, normals, return_status)
+
+    def set_conditional_tile(self, problems=0):
+        """Problems per tile of :meth:`predict_cov` and :meth:`sample_conditional` on every shard."""
+        self._ok(_load().clr_sharded_set_conditional_tile(self._h, int(problems)))
 
     inverse_diagonal = BatchedGP.inverse_diagonal
     leave_one_out = BatchedGP.leave_one_out

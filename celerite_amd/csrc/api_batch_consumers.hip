@@ -1,6 +1,7 @@
 // celerite_amd/csrc/api_batch_consumers.hip -- C ABI of the batched plans, second part: the consumers of a plan's factor
 // and coefficients (clr_batch_get_factor, _solve, _dot_L, _dot, _predict, _predict_var, _predict_var_recurrence,
-// _one_step_ahead, _forecast, _predict_terms, _leave_one_out, _grad_mean_weights, _fit_mean_weights) and the helpers they
+// _one_step_ahead, _forecast, _predict_terms, _predict_cov, _sample_conditional, _leave_one_out, _grad_mean_weights,
+// _fit_mean_weights) and the helpers they
 // share: the factor and route checks, the frame of one call's device work, prediction points and tiles.
 #include "api_internal.h"
 #include "clr_bmean_kernels.h"
@@ -1027,6 +1028,190 @@ int clr_batch_predict_terms(clr_batch* h, int M, const double* xs, long xs_strid
   h->solve_device_ms += solve_ms;
   pts.deliver(tmp.data(), B, Gg, {mean, var});
   return nan_rows_without_factor(h, {{mean, Gg * Mm}, {var, Gg * Mm}});
+}
+
+// ---- clr_batch_predict_cov, clr_batch_sample_conditional: the joint posterior at the points (clr_bcond_kernels.h)
+
+int clr_batch_set_conditional_tile(clr_batch* h, int problems) {
+  h->conditional_tile = problems > 0 ? problems : 0;
+  return CLR_OK;
+}
+
+// problems b0 .. b0 + nb - 1 of a narrow plan as a plan of their own for a factor consumer's kernels: the factor, the
+// times and the coefficients of the slice (what make_slots, the lanes' times and load_problem read)
+static clr::BatchParams problem_slice(const clr_batch* h, clr::BatchParams P, size_t b0, int nb) {
+  const size_t J = (size_t)h->J, cells = (size_t)h->L * h->nchunk, JR = (size_t)h->J_real, JC = (size_t)h->J_comp;
+  P.B = nb;
+  P.W += b0 * J * cells; P.D += b0 * cells;
+  if (P.phi) P.phi += b0 * J * cells;
+  if (P.u) P.u += b0 * J * cells;
+  P.t += b0 * (size_t)P.t_stride;
+  P.a_real += b0 * JR; P.c_real += b0 * JR;
+  P.a_comp += b0 * JC; P.b_comp += b0 * JC; P.c_comp += b0 * JC; P.d_comp += b0 * JC;
+  P.jitter += b0;
+  return P;
+}
+
+// Both entries: `cov` [B][M][M] (clr_batch_predict_cov) or `draws` [B][size][M] from `normals` (clr_batch_sample_conditional).
+// The points ascending through SortedPoints; the start states of S (pv_S) and Q (loo_Q) under the rules of
+// clr_batch_predict_var_recurrence, the solve's chunk maps read where they are formed; then a tile of PROBLEMS at a time --
+// a problem needs all its points at once: about M (J^2 + 4 J) doubles of generators and transports plus M^2 (the
+// covariance) or 2 size M (normals, draws) each, as many problems per tile as fit the 1 GiB of predict_tile's automatic
+// choice (clr_batch_set_conditional_tile: the caller's).  A single problem that does not fit: the allocation's status.
+// The device time is the kernels' of every tile, never the copies'.
+static int conditional_impl(clr_batch* h, const char* entry, int M, const double* xs, long xs_stride, int size, const double* normals,
+                            double regularize, double min_pivot, double* cov, double* draws, int* status) {
+  int st;
+  const std::string e(entry);
+  Route route;
+  route.wide_instead = "clr_batch_predict / clr_batch_predict_var, point by point";
+  bool none;
+  if ((st = require_points(h, entry, cov ? "M >= 0, the points and an output array" : "M >= 0, the points, the normals and an output array", M,
+                           xs && (cov || (normals && draws)), xs_stride, &route, &none)) != CLR_OK || none)
+    return st;
+  clr::BatchParams P;
+  if ((st = consumer_params(h, false, P)) != CLR_OK) return st;
+  const size_t B = (size_t)h->B, J = (size_t)h->J, Mm = (size_t)M, nsrc = xs_stride == 0 ? 1 : B, nc = (size_t)h->nchunk;
+  const size_t NS = J * (J + 1) / 2, Sz = (size_t)size, out_pp = cov ? Mm * Mm : Sz * Mm;
+  SortedPoints pts;
+  pts.sort(xs, nsrc, Mm);
+  if (pts.xmax != pts.xmax) return fail(CLR_INVALID_ARGUMENT, e + ": a point is NaN");
+  const int xfast = pts.xfast(h);
+  // per problem: u(x) / r, e, left, var, T, the chunks' transports and counts; omega, sqrt(d); the output (and the normals)
+  const size_t per_problem = Mm * (J * J + 3 * J + 3) + nc * (J * J + 1) + (cov ? Mm * Mm : 2 * Sz * Mm);
+  const size_t budget = (size_t)1 << 27;  // doubles (predict_tile's)
+  const size_t want = h->conditional_tile > 0 ? (size_t)h->conditional_tile : std::max<size_t>(1, budget / per_problem);
+  const size_t Bt = std::min<size_t>(std::min<size_t>(want, B), 65535);  // (the problems ride on grid.y)
+  DevBuf dxs, dr, de, dleft, dvar, dT, dE, dout, dsd, dom, dnorm;
+  clr::Buffer<int> down, dstat;
+  if ((st = dr.reserve(Bt * Mm * J)) != CLR_OK) return st;
+  if ((st = de.reserve(Bt * Mm * J)) != CLR_OK) return st;
+  if ((st = dleft.reserve(Bt * Mm)) != CLR_OK) return st;
+  if ((st = dvar.reserve(Bt * Mm)) != CLR_OK) return st;
+  if ((st = dT.reserve(Bt * Mm * J * J)) != CLR_OK) return st;
+  if ((st = dE.reserve(Bt * nc * J * J)) != CLR_OK) return st;
+  if ((st = down.reserve(Bt * nc)) != CLR_OK) return st;
+  if ((st = dout.reserve(Bt * out_pp)) != CLR_OK) return st;
+  if (!cov) {
+    if ((st = dsd.reserve(Bt * Mm)) != CLR_OK) return st;
+    if ((st = dom.reserve(Bt * Mm * J)) != CLR_OK) return st;
+    if ((st = dnorm.reserve(Bt * Sz * Mm)) != CLR_OK) return st;
+    if ((st = dstat.reserve(B)) != CLR_OK) return st;
+  }
+  if ((st = reserve_recurrence_state(h)) != CLR_OK) return st;
+  // the normals in the points' ascending order
+  std::vector<double> nsorted, block;
+  if (!cov && !pts.all_sorted) {
+    nsorted.resize(B * Sz * Mm);
+    for (size_t b = 0; b < B; ++b) {
+      const int* pp = pts.perm.data() + (nsrc == 1 ? 0 : b * Mm);
+      for (size_t s = 0; s < Sz; ++s) {
+        const size_t at = (b * Sz + s) * Mm;
+        for (size_t m = 0; m < Mm; ++m) nsorted[at + m] = normals[at + pp[m]];
+      }
+    }
+    normals = nsorted.data();
+  }
+  if (!pts.all_sorted) block.resize(cov ? Bt * out_pp : B * out_pp);
+  std::vector<int> fstat(B, 0);
+  double total_ms = 0.0;
+  {
+    ConsumerFrame frame{h};
+    hipStream_t s = h->stream.get();
+    if ((st = pts.upload(dxs, s)) != CLR_OK) return st;
+    clr::BPredVarRecParams V{};
+    V.lean = h->factor_is_lean ? 1 : 0;
+    const int have_M_before = h->bs_M_valid ? 1 : 0;
+    claim_recurrence_state(h, frame, V.lean, V.have_S, V.have_Q, V.Q);
+    clr::BCondParams S{};
+    S.have_M = V.have_Q ? have_M_before : 1;  // (formed beside Q unless a consumer had formed them)
+    V.npts = M; V.xs_stride = xs_stride; V.t_stride = h->t_stride; V.ux = dr.p; V.e = de.p; V.left = dleft.p; V.var = dvar.p; V.var_stride = (long)M;
+    S.npts = M; S.lean = V.lean; S.size = size; S.xs_stride = xs_stride; S.t_stride = h->t_stride;
+    S.r = dr.p; S.e = de.p; S.T = dT.p; S.E = dE.p; S.own = down.p;
+    S.cov = cov ? dout.p : nullptr; S.draws = cov ? nullptr : dout.p;
+    S.regularize = regularize; S.min_pivot = min_pivot; S.sd = dsd.p; S.omega = dom.p; S.normals = dnorm.p;
+    for (size_t b0 = 0; b0 < B; b0 += Bt) {
+      const size_t nb = std::min(Bt, B - b0);
+      const clr::BatchParams Pt = problem_slice(h, P, b0, (int)nb);
+      V.xs = S.xs = dxs.p + (xs_stride == 0 ? 0 : b0 * Mm);
+      V.t = S.t = h->t.p + b0 * (size_t)h->t_stride;
+      V.S = h->pv_S.p + b0 * nc * NS;
+      S.Q = h->loo_Q.p + b0 * nc * NS;
+      S.M = h->bs_M.p + b0 * nc * J * J;
+      S.status = cov ? nullptr : dstat.p + b0;
+      if (!cov) HIP_TRY(hipMemcpyAsync(dnorm.p, normals + b0 * out_pp, nb * out_pp * sizeof(double), hipMemcpyHostToDevice, s));
+      if (b0 == 0) {  // the start states of the whole plan, unless formed
+        HIP_TRY(frame.start());
+        clr::BPredVarRecParams V0 = V;
+        V0.t = h->t.p; V0.S = h->pv_S.p;
+        h->launch->bcond(P, V0, S, 0, xfast, s);
+        V.have_S = V.have_Q = 1;
+      } else {
+        HIP_TRY(hipEventRecord(h->bs_ev[0].get(), s));
+      }
+      h->launch->bcond(Pt, V, S, cov ? 1 : 2, xfast, s);
+      HIP_TRY(frame.stop());
+      HIP_TRY(hipGetLastError());
+      double* dst = pts.all_sorted ? (cov ? cov : draws) + b0 * out_pp : block.data() + (cov ? 0 : b0 * out_pp);
+      HIP_TRY(hipMemcpyAsync(dst, dout.p, nb * out_pp * sizeof(double), hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipStreamSynchronize(s));
+      float ms = 0.f;
+      HIP_TRY(hipEventElapsedTime(&ms, h->bs_ev[0].get(), h->bs_ev[1].get()));
+      total_ms += ms;
+      if (cov && !pts.all_sorted) {  // both axes back to the caller's order
+        for (size_t b = 0; b < nb; ++b) {
+          const int* pp = pts.perm.data() + (nsrc == 1 ? 0 : (b0 + b) * Mm);
+          const double* src = block.data() + b * out_pp;
+          double* out = cov + (b0 + b) * out_pp;
+          for (size_t i = 0; i < Mm; ++i)
+            for (size_t j = 0; j < Mm; ++j) out[(size_t)pp[i] * Mm + pp[j]] = src[i * Mm + j];
+        }
+      }
+    }
+    if (!cov) HIP_TRY(hipMemcpyAsync(fstat.data(), dstat.p, B * sizeof(int), hipMemcpyDeviceToHost, s));
+    if ((st = frame.finish()) != CLR_OK) return st;
+    h->solve_device_ms = total_ms;
+  }
+  if (!cov && !pts.all_sorted) pts.deliver(block.data(), B, Sz, {draws});
+  std::vector<int> estat(B, 0);
+  if ((st = nan_rows_without_factor(h, {{cov ? cov : draws, out_pp}}, estat.data())) != CLR_OK) return st;
+  if (!cov) {
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    for (size_t b = 0; b < B; ++b) {
+      if (estat[b] == CLR_OK && fstat[b] != 0) {  // refused by the pivot rule
+        estat[b] = CLR_NOT_POSITIVE_DEFINITE;
+        std::fill(draws + b * out_pp, draws + (b + 1) * out_pp, nan);
+      }
+    }
+    if (status) std::copy(estat.begin(), estat.end(), status);
+  }
+  return CLR_OK;
+}
+
+// The posterior covariance of the latent process between M points per problem (GP.predict(..., return_cov=True),
+// celerite.py:283-291, without its N x M solve): C_ij = r_j^T T_{j-1} ... T_i e_i from the factor's two matrix
+// recurrences and the transports between the points, O((N + M J) J^2 + M^2 J^2) per problem.
+int clr_batch_predict_cov(clr_batch* h, int M, const double* xs, long xs_stride, double* cov) {
+  int st = require_device(h->device);
+  if (st != CLR_OK) return st;
+  return conditional_impl(h, "clr_batch_predict_cov", M, xs, xs_stride, 0, nullptr, 0.0, 0.0, cov, nullptr, nullptr);
+}
+
+// Joint draws of the latent process at M points per problem given the data, the zero-mean part (GP.sample_conditional,
+// celerite.py:327-332, without its dense covariance and its O(M^3) factorisation): draws = L diag(d)^1/2 n with
+// C + regularize I = L diag(d) L^T by the celerite recurrence over the points, O((N + M J) J^2) per problem plus
+// O(M J^2) per draw.  The mean is clr_batch_predict's and is the caller's to add.
+int clr_batch_sample_conditional(clr_batch* h, int M, const double* xs, long xs_stride, int size, const double* normals,
+                                 double regularize, double min_pivot, double* draws, int* status) {
+  int st = require_device(h->device);
+  if (st != CLR_OK) return st;
+  if (size < 1) return fail(CLR_INVALID_ARGUMENT, "clr_batch_sample_conditional: size >= 1");
+  if (!std::isfinite(min_pivot) || min_pivot < 0.0 || min_pivot >= 1.0)
+    return fail(CLR_INVALID_ARGUMENT, "clr_batch_sample_conditional: min_pivot is finite and in [0, 1)");
+  if (!std::isfinite(regularize) || regularize < 0.0)
+    return fail(CLR_INVALID_ARGUMENT, "clr_batch_sample_conditional: regularize is finite and not negative");
+  if (M > 0 && !draws) return fail(CLR_INVALID_ARGUMENT, "clr_batch_sample_conditional: M >= 0, the points, the normals and an output array");
+  return conditional_impl(h, "clr_batch_sample_conditional", M, xs, xs_stride, size, normals, regularize, min_pivot, nullptr, draws, status);
 }
 
 // ---- clr_batch_leave_one_out: diag(K^-1), K^-1 r and the leave-one-out log predictive density of every problem

@@ -1012,6 +1012,7 @@ __global__ void __launch_bounds__(64) warm_check_kernel(const BatchParams P) {
 #include "clr_bpredvar_rec_kernels.h"
 #include "clr_bfilter_kernels.h"
 #include "clr_bterms_kernels.h"
+#include "clr_bcond_kernels.h"
 namespace clr {
 
 // One table entry per (JR, JC): host-callable launchers.
@@ -1048,6 +1049,11 @@ struct BatchLaunchers {
   // the posterior mean (S.mean) and variance (S.var) of every group of kernel terms for all problems at one tile of SORTED
   // points (clr_bterms_kernels.h); `xfast`: the points' phases stay below CLR_FAST_TRIG_LIMIT
   void (*bterms)(const BatchParams&, BTermsParams S, int xfast, hipStream_t);
+  // the joint posterior at SORTED points (clr_bcond_kernels.h).  what = 0: unless formed, the start states of S and Q of the
+  // whole plan (V.have_S, V.have_Q, V.S, V.Q) -- nothing else; what = 1, 2: for the problems of P (a slice of the plan, V
+  // and S its buffers) the points' generators and transports, then the covariance S.cov (1) or the factor and the draws
+  // S.draws (2); `xfast`: the points' phases stay below CLR_FAST_TRIG_LIMIT
+  void (*bcond)(const BatchParams&, const BPredVarRecParams& V, const BCondParams& S, int what, int xfast, hipStream_t);
   // lean factor of problem b (replay mode 3) -> the reference's storage, phi and u regenerated (t: the problem's row-major times)
   void (*expand)(const BatchParams&, int b, const double* t, double* phi, double* u, double* W, double* D, hipStream_t);
   int elem_doubles, start_doubles;
@@ -1330,6 +1336,34 @@ struct BatchImpl {
     if (S.mean) { if (P.fast_trig) bterms_mean_go<true>(P, S, s); else bterms_mean_go<false>(P, S, s); }
     if (S.var) lean_fast(S.lean, P, [&](auto L, auto F) { bterms_var_go<L(), F()>(P, S, s); });
   }
+  // the joint posterior at sorted points: the start states exactly as bpredvar_rec_go (what = 0); per slice of problems the
+  // features and the forward replay of the recurrence variance (u(x), e), r, the transports and their stitch, then the pair
+  // phase or the factor and the draws
+  template <bool LEAN, bool FAST>
+  static void bcond_go(const BatchParams& P, const BPredVarRecParams& V, const BCondParams& S, int what, int xfast, hipStream_t s) {
+    constexpr int J = JR + 2 * JC;
+    if (what == 0) {
+      if (!V.have_S) form_S_starts<LEAN, FAST>(P, V, s);
+      if (!V.have_Q) form_Q_starts<LEAN, FAST>(P, V.Q, s);
+      return;
+    }
+    const dim3 grid((P.nchunk + 63) / 64, P.B), fgrid((unsigned)(((long)P.B * V.npts + 255) / 256));
+    if (xfast) hipLaunchKernelGGL((bpvrec_features_kernel<JR, JC, true>), fgrid, dim3(256), 0, s, P, V);
+    else hipLaunchKernelGGL((bpvrec_features_kernel<JR, JC, false>), fgrid, dim3(256), 0, s, P, V);
+    hipLaunchKernelGGL((bpvrec_forward_kernel<JR, JC, LEAN, FAST, true>), grid, dim3(64), 0, s, P, V);
+    hipLaunchKernelGGL((bcond_backward_kernel<JR, JC, LEAN, FAST>), grid, dim3(64), 0, s, P, S);
+    hipLaunchKernelGGL((bcond_transport_kernel<JR, JC, LEAN, FAST>), grid, dim3(64), 0, s, P, S);
+    hipLaunchKernelGGL((bcond_stitch_kernel<J>), dim3(P.B), dim3(64), 0, s, P, S);
+    if (what == 1) {
+      hipLaunchKernelGGL((bcond_pair_kernel<J>), dim3((S.npts + 63) / 64, P.B), dim3(64), 0, s, P, S);
+    } else {
+      hipLaunchKernelGGL((bcond_factor_kernel<JR, JC>), dim3(P.B), dim3(64), 0, s, P, S);
+      hipLaunchKernelGGL((bcond_draw_kernel<J>), dim3((S.size + 63) / 64, P.B), dim3(64), 0, s, P, S);
+    }
+  }
+  static void bcond(const BatchParams& P, const BPredVarRecParams& V, const BCondParams& S, int what, int xfast, hipStream_t s) {
+    lean_fast(V.lean, P, [&](auto L, auto F) { bcond_go<L(), F()>(P, V, S, what, xfast, s); });
+  }
   static void compose_check(const BatchParams& P, int g, double* coop, double* ref, hipStream_t s) {
     constexpr int J = JR + 2 * JC;
     const int np = (P.nchunk + g - 1) / g;
@@ -1382,7 +1416,7 @@ struct BatchImpl {
   }
   static BatchLaunchers table() {
     return BatchLaunchers{&summarize, &prefix, &correct, &replay, &sequential, &compose_check, &warm, &grad, &grad_reverse,
-                          &bsolve, &bdotl, &bdot, &bpredvar, &binvdiag, &bpredvar_rec, &bfilter, &bterms, &expand, Widths<JR, JC>::ELEM, Widths<JR, JC>::START};
+                          &bsolve, &bdotl, &bdot, &bpredvar, &binvdiag, &bpredvar_rec, &bfilter, &bterms, &bcond, &expand, Widths<JR, JC>::ELEM, Widths<JR, JC>::START};
   }
 };
 

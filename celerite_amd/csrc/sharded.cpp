@@ -705,6 +705,29 @@ int clr_sharded_predict_terms(clr_sharded* h, int M, const double* xs, long xs_s
   });
 }
 
+int clr_sharded_predict_cov(clr_sharded* h, int M, const double* xs, long xs_stride, double* cov) {
+  const long per = (long)M * M;
+  return on_slices(h, M >= 0 && (M == 0 || (xs && cov)) && (xs_stride == 0 || xs_stride == M), [=](clr_batch* p, long lo) {
+    return clr_batch_predict_cov(p, M, xs + lo * xs_stride, xs_stride, at(cov, lo * per));
+  });
+}
+
+int clr_sharded_sample_conditional(clr_sharded* h, int M, const double* xs, long xs_stride, int size, const double* normals,
+                                   double regularize, double min_pivot, double* draws, int* status) {
+  const long per = (long)size * M;
+  return on_slices(h, M >= 0 && size >= 1 && (M == 0 || (xs && normals && draws)) && (xs_stride == 0 || xs_stride == M) &&
+                          std::isfinite(min_pivot) && min_pivot >= 0.0 && min_pivot < 1.0 && std::isfinite(regularize) && regularize >= 0.0,
+                   [=](clr_batch* p, long lo) {
+    return clr_batch_sample_conditional(p, M, xs + lo * xs_stride, xs_stride, size, at(normals, lo * per), regularize, min_pivot,
+                                        at(draws, lo * per), at(status, lo));
+  });
+}
+
+int clr_sharded_set_conditional_tile(clr_sharded* h, int problems) {
+  for (clr_batch* p : h->plan) clr_batch_set_conditional_tile(p, problems);
+  return CLR_OK;
+}
+
 int clr_sharded_run_timed(clr_sharded* h, int steps, double* shard_ms /* [nshards] or NULL */) {
   // (a timing tool: every shard times its own steps and settles them by its own counts)
   const int st0 = resolve_all(h);

@@ -662,6 +662,36 @@ int clr_batch_forecast(clr_batch* h, int M, const double* xs, long xs_stride, do
  * device time, the solve included. */
 int clr_batch_predict_terms(clr_batch* h, int M, const double* xs, long xs_stride, int G, const unsigned char* groups,
                             double* mean, double* var);
+/* The posterior covariance of the latent process between M points per problem (GP.predict(..., return_cov = True),
+ * celerite.py:283-291, for B problems, without its dense N x M solve), from the factor of the last materialising run:
+ * cov host [B][M][M], cov[b][i][j] = k(x_i - x_j) - k*_i^T K^-1 k*_j -- no jitter, no observational variance, as
+ * clr_batch_predict_var, whose value is the diagonal -- full and symmetric to the bit.  xs, xs_stride and unsorted input as
+ * clr_batch_forecast (both axes of cov come back in the caller's order); a NaN point is CLR_INVALID_ARGUMENT.  With the
+ * per-point vectors e_j, r_j and the J x J transports T_j of the forward substitution's state between consecutive sorted
+ * points (csrc/clr_bcond_kernels.h) cov_ij = r_j^T T_{j-1} ... T_i e_i for i <= j: one forward and two backward passes
+ * over the factor, O(J^3) per point and chunk, O(J^2) per pair.  Device scratch is bounded by tiling over PROBLEMS -- a
+ * problem needs all its points at once: about M (J^2 + 4 J) + M^2 doubles each, as many problems per tile as fit 1 GiB
+ * (clr_batch_set_conditional_tile: the caller's; 0: automatic); a single problem that does not fit returns the
+ * allocation's status.  A problem's bits depend on neither the tile, the batch nor the sharding.  Narrow plans only
+ * (widths 1..8, chunked: N >= 128, either factor layout): CLR_UNSUPPORTED otherwise.  The start states of S and Q are
+ * shared with clr_batch_predict_var_recurrence / clr_batch_leave_one_out.  Rows of problems whose status is not CLR_OK are
+ * NaN.  clr_batch_get_solve_ms then reports this call's device time (the kernels of every tile). */
+int clr_batch_predict_cov(clr_batch* h, int M, const double* xs, long xs_stride, double* cov);
+int clr_batch_set_conditional_tile(clr_batch* h, int problems);
+/* Joint draws of the latent process at M points per problem given the data (GP.sample_conditional, celerite.py:327-332,
+ * for B problems, without its dense covariance and its O(M^3) factorisation): normals and draws host [B][size][M],
+ * size >= 1; draws = L diag(d)^1/2 n with C + regularize I = L diag(d) L^T, C the covariance of clr_batch_predict_cov --
+ * the ZERO-MEAN part: the mean is clr_batch_predict's and the caller's to add.  normals[..][r] belongs to the caller's point
+ * r; the factor is taken in ascending order of the points (ties in the caller's order).  L and d follow from the celerite
+ * recurrence over the points with the transports in place of the diagonal decay: O(J^3) per point, O(J^2) per point and
+ * draw; no M x M matrix is formed.  The rule for a pivot d_j, k(0) the problem's own:  d_j < -min_pivot k(0) or not finite
+ * -- the problem is refused, status[b] = CLR_NOT_POSITIVE_DEFINITE, its rows NaN;  |d_j| <= min_pivot k(0) -- the point
+ * is a function of the earlier ones (a repeated point, a point on a sample without noise): its own normal does not enter.
+ * min_pivot finite in [0, 1), regularize finite and >= 0, else CLR_INVALID_ARGUMENT.  status [B] or NULL: the
+ * evaluation's status where that is not CLR_OK (rows NaN), else the factorisation's.  Points, tiles (2 size M doubles in
+ * place of M^2), coverage, shared state and timing as clr_batch_predict_cov. */
+int clr_batch_sample_conditional(clr_batch* h, int M, const double* xs, long xs_stride, int size, const double* normals,
+                                 double regularize, double min_pivot, double* draws, int* status);
 /* diag(K^-1), K^-1 r and the leave-one-out log predictive density of every problem from the factor of the last
  * materialising run.  kinv_diag [B][N], alpha [B][N], loo_logpdf [B], status [B]: each may be NULL and is then neither
  * computed beyond need nor copied down (alpha or loo_logpdf: the batched solve of the residual in force runs); all four
@@ -953,8 +983,8 @@ int clr_sharded_get_coefficients(clr_sharded* h, double* jitter, double* a_real,
  * GPUs): clr_sharded_materialize runs clr_batch_enqueue(plan, 1) on every shard, settles the evaluation with the
  * batch-wide counts (results as clr_sharded_get_results; any pointer may be NULL) and leaves every shard's factor in
  * its HBM; clr_sharded_solve / _dot_L / _dot / _predict / _predict_var / _predict_var_recurrence / _leave_one_out /
- * _one_step_ahead / _forecast / _predict_terms are clr_batch_solve / _dot_L / _dot / _predict / _predict_var / _predict_var_recurrence /
- * _leave_one_out / _one_step_ahead / _forecast / _predict_terms on every shard concurrently,
+ * _one_step_ahead / _forecast / _predict_terms / _predict_cov / _sample_conditional are clr_batch_solve / _dot_L / _dot / _predict / _predict_var / _predict_var_recurrence /
+ * _leave_one_out / _one_step_ahead / _forecast / _predict_terms / _predict_cov / _sample_conditional on every shard concurrently,
  * each on its contiguous slice of the host arrays ([B][nrhs][N]; xs [B][M] or shared with xs_stride = 0).  No
  * collective: every problem's state is its own (cholesky.h:703-706). */
 int clr_sharded_materialize(clr_sharded* h, double* loglike, double* logdet, double* quad, int* status);
@@ -969,6 +999,10 @@ int clr_sharded_one_step_ahead(clr_sharded* h, int nrhs, const double* b, double
 int clr_sharded_forecast(clr_sharded* h, int M, const double* xs, long xs_stride, double* mean, double* var);
 int clr_sharded_predict_terms(clr_sharded* h, int M, const double* xs, long xs_stride, int G, const unsigned char* groups,
                               double* mean, double* var);
+int clr_sharded_predict_cov(clr_sharded* h, int M, const double* xs, long xs_stride, double* cov);
+int clr_sharded_sample_conditional(clr_sharded* h, int M, const double* xs, long xs_stride, int size, const double* normals,
+                                   double regularize, double min_pivot, double* draws, int* status);
+int clr_sharded_set_conditional_tile(clr_sharded* h, int problems);
 /* `steps` back-to-back evaluations on every shard concurrently (HIP events per shard);
  * shard_ms[s] = that shard's first-to-last event time. */
 int clr_sharded_run_timed(clr_sharded* h, int steps, double* shard_ms);
