@@ -257,6 +257,26 @@ def _mean_arg(mu, B):
     return np.ascontiguousarray(m), 1
 
 
+def _lengths_arg(lengths, B, N):
+    """Per-problem series lengths for ``clr_*_set_series_ragged``: ``None`` (every problem has ``N`` samples) or ``B``
+    integers in ``[1, N]``, returned as a contiguous ``int32`` array.  Checked without a device: a wrong shape is
+    ``ValueError("dimension mismatch")``, a non-integral or out-of-range entry a ``ValueError`` that names it."""
+    if lengths is None:
+        return None
+    a = np.asarray(lengths)
+    if a.shape != (B,):
+        raise ValueError("dimension mismatch")
+    if a.dtype == np.bool_ or not (np.issubdtype(a.dtype, np.integer) or np.issubdtype(a.dtype, np.floating)):
+        raise ValueError("lengths must be integers")
+    if np.issubdtype(a.dtype, np.floating):
+        if not np.all(np.isfinite(a)) or np.any(a != np.floor(a)):
+            raise ValueError("lengths must be integers")
+    bad = np.flatnonzero((a < 1) | (a > N))
+    if bad.size:
+        raise ValueError("length %s of problem %d is outside [1, N = %d]" % (a[bad[0]], bad[0], N))
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
 MAX_MEAN_BASIS = 16      # CLR_MAX_MEAN_BASIS of include/celerite_hip.h
 
 
@@ -610,12 +630,19 @@ class BatchedGP(object):
             pass
 
     # -- inputs -------------------------------------------------------------
-    def set_series(self, t, diag, y):
+    def set_series(self, t, diag, y, lengths=None):
         """``t``, ``diag`` (= yerr**2), ``y``: each ``(B, N)`` or ``(N,)`` for one
         series shared by all problems.  ``t`` must be sorted along the last axis
         (checked: GP.compute does the same, celerite.py:126-129).  A mean set by
         :meth:`set_mean` stays in force and is subtracted from the new ``y`` on
-        the device; without one ``y`` is taken as it is (mean zero)."""
+        the device; without one ``y`` is taken as it is (mean zero).
+
+        ``lengths`` (``(B,)`` integers in ``[1, N]``; ``clr_batch_set_series_ragged``): problem ``b`` is the first
+        ``lengths[b]`` samples of its rows, which must then be ``(B, N)`` each.  The rest of a row is never read -- it
+        may be NaN or unsorted -- and every result is that of the problem's own samples.  Narrow plans (widths 1..8)
+        evaluate and differentiate such a batch; the materialised factor and its consumers (:meth:`solve`,
+        :meth:`predict`, ...) refuse it.  Without ``lengths`` the plan is uniform again."""
+        lens = _lengths_arg(lengths, self.B, self.N)
         arrs, strides = [], []
         for a in (t, diag, y):
             a = _f64(a)
@@ -627,8 +654,13 @@ class BatchedGP(object):
                 raise ValueError("dimension mismatch")
             arrs.append(a)
         lib = _load()
-        _check(lib.clr_batch_set_series(self._h, _ptr(arrs[0]), strides[0], _ptr(arrs[1]),
-                                        strides[1], _ptr(arrs[2]), strides[2]))
+        if lens is None:
+            _check(lib.clr_batch_set_series(self._h, _ptr(arrs[0]), strides[0], _ptr(arrs[1]),
+                                            strides[1], _ptr(arrs[2]), strides[2]))
+        else:
+            lib.clr_batch_set_series_ragged.argtypes = [C.c_void_p, _dp, C.c_long, _dp, C.c_long, _dp, C.c_long, _ip]
+            _check(lib.clr_batch_set_series_ragged(self._h, _ptr(arrs[0]), strides[0], _ptr(arrs[1]), strides[1],
+                                                   _ptr(arrs[2]), strides[2], lens.ctypes.data_as(_ip)))
         # sortedness from the device-side scan of the uploaded t (np.diff over 0.8 GB of times costs more than the
         # whole transfer): an unsorted batch is dropped again
         dtmin = C.c_double()
@@ -638,6 +670,16 @@ class BatchedGP(object):
             lib.clr_batch_clear_series.argtypes = [C.c_void_p]
             _check(lib.clr_batch_clear_series(self._h))
             raise ValueError("the input coordinates must be sorted")
+
+    @property
+    def lengths(self):
+        """The series lengths in force, ``(B,)`` (``N`` for every problem of a uniform plan; a series must be set)."""
+        out = np.empty(self.B, dtype=np.int32)
+        lib = _load()
+        lib.clr_batch_get_lengths.argtypes = [C.c_void_p, _ip]
+        _check(lib.clr_batch_get_lengths(self._h, out.ctypes.data_as(_ip)))
+        out.flags.writeable = False
+        return out
 
     def set_mean(self, mu):
         """A constant mean per problem (``clr_batch_set_mean``): a scalar for all problems, ``(B,)``, or ``None`` to
@@ -1498,7 +1540,9 @@ class ShardedBatchedGP(object):
         self._ok(_load().clr_sharded_get_summarize_kernel(self._h, C.byref(k)))
         return ("single wave", "role split", "role split, lazy decay")[k.value] if k.value >= 0 else "shards disagree"
 
-    def set_series(self, t, diag, y):
+    def set_series(self, t, diag, y, lengths=None):
+        """``BatchedGP.set_series`` over the shards; ``lengths`` is ``(B,)`` for the whole batch."""
+        lens = _lengths_arg(lengths, self.B, self.N)
         arrs, strides = [], []
         for a in (t, diag, y):
             a = _f64(a)
@@ -1510,8 +1554,13 @@ class ShardedBatchedGP(object):
                 raise ValueError("dimension mismatch")
             arrs.append(a)
         lib = _load()
-        self._ok(lib.clr_sharded_set_series(self._h, _ptr(arrs[0]), strides[0], _ptr(arrs[1]),
-                                            strides[1], _ptr(arrs[2]), strides[2]))
+        if lens is None:
+            self._ok(lib.clr_sharded_set_series(self._h, _ptr(arrs[0]), strides[0], _ptr(arrs[1]),
+                                                strides[1], _ptr(arrs[2]), strides[2]))
+        else:
+            lib.clr_sharded_set_series_ragged.argtypes = [C.c_void_p, _dp, C.c_long, _dp, C.c_long, _dp, C.c_long, _ip]
+            self._ok(lib.clr_sharded_set_series_ragged(self._h, _ptr(arrs[0]), strides[0], _ptr(arrs[1]), strides[1],
+                                                       _ptr(arrs[2]), strides[2], lens.ctypes.data_as(_ip)))
         dtmin = C.c_double()
         lib.clr_sharded_get_series_order.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
         self._ok(lib.clr_sharded_get_series_order(self._h, C.byref(dtmin)))
@@ -1519,6 +1568,16 @@ class ShardedBatchedGP(object):
             lib.clr_sharded_clear_series.argtypes = [C.c_void_p]
             self._ok(lib.clr_sharded_clear_series(self._h))
             raise ValueError("the input coordinates must be sorted")
+
+    @property
+    def lengths(self):
+        """The series lengths in force over the whole batch, ``(B,)``."""
+        out = np.empty(self.B, dtype=np.int32)
+        lib = _load()
+        lib.clr_sharded_get_lengths.argtypes = [C.c_void_p, _ip]
+        self._ok(lib.clr_sharded_get_lengths(self._h, out.ctypes.data_as(_ip)))
+        out.flags.writeable = False
+        return out
 
     def _coeff_blocks(self, a_real, c_real, a_comp, b_comp, c_comp, d_comp, jitter):
         try:

@@ -230,6 +230,7 @@ static void warm_select(clr_batch* h) {
   h->warm_eligible = 0;
   h->warm_eligible_total = -1;
   if (h->warm_mode == 0 || h->wnchunk < 2 || !h->have_series || h->warm_span.empty() || h->host_cmin.size() != B) return;
+  if (h->ragged) return;  // (per-problem lengths: the warm kernel's copy and boundary check know one length -- the scan takes the plan)
   h->warm_K.assign(B, 0);
   size_t eligible = 0;
   const bool shared = h->t_stride == 0;
@@ -285,6 +286,8 @@ static int apply_mean(clr_batch* h) {
                                 (int)N, h->y.p, h->stream.get());
   else
     clr::launch_residual(h->y_src.p, h->y_src_stride, h->mean_dev.p, h->mean_stride, nout, (int)N, h->y.p, h->stream.get());
+  // (per-problem lengths: the residual's tail stays the padding y = 0, not -mu -- the basis there is never looked at)
+  if (h->ragged) clr::launch_pad_tail(h->y.p, h->B, (int)N, h->len_dev.p, 0, h->stream.get());
   HIP_TRY(hipGetLastError());
   residual_replaced(h, per_problem ? N : 0);
   return CLR_OK;
@@ -393,15 +396,36 @@ int clr_batch_set_mean_weights(clr_batch* h, const double* w) {
   return CLR_OK;
 }
 
-int clr_batch_set_series(clr_batch* h, const double* t, long t_stride, const double* diag,
-                         long diag_stride, const double* y, long y_stride) {
+// clr_batch_set_series and clr_batch_set_series_ragged.  `lengths` (host, [B], may be null): problem b is the first
+// lengths[b] entries of its rows; `ragged`: lengths are in force -- some length of the WHOLE batch differs from N (a
+// slice of a larger batch is told so: clr_group::set_series_lengths).  Everything is checked before the plan changes.
+static int set_series_impl(clr_batch* h, const double* t, long t_stride, const double* diag, long diag_stride,
+                           const double* y, long y_stride, const int* lengths, bool ragged) {
   int st = require_device(h->device);
   if (st != CLR_OK) return st;
   const long N = h->N;
   for (long sd : {t_stride, diag_stride, y_stride})
     if (sd != 0 && sd != N)
       return fail(CLR_INVALID_ARGUMENT, "series stride must be 0 (shared) or N");
+  if (lengths)
+    for (int b = 0; b < h->B; ++b)
+      if (lengths[b] < 1 || lengths[b] > N)
+        return fail(CLR_INVALID_ARGUMENT, "clr_batch_set_series_ragged: length " + std::to_string(lengths[b]) + " of problem " +
+                                          std::to_string(b) + " is outside [1, N = " + std::to_string(N) + "]");
+  if (ragged) {
+    if (t_stride == 0 || diag_stride == 0 || y_stride == 0)
+      return fail(CLR_INVALID_ARGUMENT, "clr_batch_set_series_ragged: with lengths t, diag and y are each [B][N] (stride N) -- "
+                                        "the padded device copy is per problem");
+    if (!h->launch || h->J_general > 0)
+      return fail(CLR_UNSUPPORTED, "clr_batch_set_series_ragged: per-problem lengths cover narrow plans (widths 1..8) without "
+                                   "general terms");
+    if (h->warm_mode == 1 || h->small_mode == 1 || h->summarize_mode > 0)
+      return fail(CLR_UNSUPPORTED, "clr_batch_set_series_ragged: the forced warm start, one-launch mode and role-split summarize "
+                                   "(clr_batch_set_summarize_mode 1, 2) do not carry per-problem lengths: switch them back to "
+                                   "automatic first");
+  }
   if ((st = warm_resolve(h, nullptr)) != CLR_OK) return st;  // (an evaluation in flight is settled on ITS series)
+  if (ragged && (st = h->len_dev.reserve((size_t)h->B)) != CLR_OK) return st;
   auto count = [&](long sd) { return (size_t)(sd == 0 ? N : N * (long)h->B); };
   const auto host_t0 = std::chrono::steady_clock::now();
   if ((st = h->t.reserve(count(t_stride))) != CLR_OK) return st;
@@ -413,6 +437,13 @@ int clr_batch_set_series(clr_batch* h, const double* t, long t_stride, const dou
   // the old one -- interleaved copies, warm-up spans and their selection -- survives
   h->have_series = false;
   series_replaced(h);
+  if (h->ragged != ragged) {  // (a factor and a rescue side plan belong to the other kind of plan)
+    factor_dropped(h);
+    h->rescue.reset();
+    h->rescue_plan_key = -1;
+  }
+  h->ragged = ragged;
+  if (ragged) h->host_len.assign(lengths, lengths + h->B); else h->host_len.clear();
   const clr::CopyJob jobs[3] = {{h->t.p, t, count(t_stride)}, {h->diag.p, diag, count(diag_stride)}, {h->y.p, y, count(y_stride)}};
   const size_t total = (jobs[0].n + jobs[1].n + jobs[2].n) * sizeof(double);
   bool staged = false;
@@ -436,12 +467,21 @@ int clr_batch_set_series(clr_batch* h, const double* t, long t_stride, const dou
   h->t_stride = t_stride;
   h->diag_stride = diag_stride;
   h->y_stride = y_stride;
+  if (ragged) {
+    // the tails become padding IN the resident arrays, before anything looks at them: t held, diagonal 1e300, y = 0 --
+    // every scan below, every copy and every kernel then sees rows whose entries past len[b] a recurrence step ignores
+    HIP_TRY(hipMemcpyAsync(h->len_dev.p, h->host_len.data(), (size_t)h->B * sizeof(int), hipMemcpyHostToDevice, h->stream.get()));
+    clr::launch_pad_tail(h->t.p, h->B, (int)N, h->len_dev.p, 1, h->stream.get());
+    clr::launch_pad_tail(h->diag.p, h->B, (int)N, h->len_dev.p, 2, h->stream.get());
+    clr::launch_pad_tail(h->y.p, h->B, (int)N, h->len_dev.p, 0, h->stream.get());
+    HIP_TRY(hipGetLastError());
+  }
   // one pass over t ON THE DEVICE: max |t| over every sample (sortedness is not assumed), the largest and the smallest
   // step, NaN times; then the warm path's spans
   {
     const int nb = t_stride == 0 ? 1 : h->B;
     if ((st = h->scan.reserve((size_t)nb * std::max(4, (int)clr_batch::WARM_NK))) != CLR_OK) return st;
-    clr::launch_series_stats(h->t.p, t_stride, nb, (int)N, h->scan.p, h->stream.get());
+    clr::launch_series_stats(h->t.p, t_stride, nb, (int)N, ragged ? h->len_dev.p : nullptr, h->scan.p, h->stream.get());
     std::vector<double> stats((size_t)nb * 4);
     HIP_TRY(hipMemcpyAsync(stats.data(), h->scan.p, stats.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
     HIP_TRY(hipStreamSynchronize(h->stream.get()));
@@ -457,7 +497,7 @@ int clr_batch_set_series(clr_batch* h, const double* t, long t_stride, const dou
     // the smallest step over the finite differences (the device's fmin skips NaN); a negative one means "not sorted"
     // whatever else the series holds -- the reference's np.any(np.diff(t) < 0), celerite.py:126-129 -- and only a
     // series without a negative step reports its NaN times as NaN
-    const double finite_min = N > 1 ? dmin : 0.0;
+    const double finite_min = (N > 1 && dmin != INFINITY) ? dmin : 0.0;  // (no step at all: one-sample series)
     h->dtmin = (finite_min < 0.0) ? finite_min : (nan ? NAN : finite_min);
   }
   h->have_series = true;
@@ -474,6 +514,26 @@ int clr_batch_set_series(clr_batch* h, const double* t, long t_stride, const dou
   return CLR_OK;
 }
 
+int clr_batch_set_series(clr_batch* h, const double* t, long t_stride, const double* diag,
+                         long diag_stride, const double* y, long y_stride) {
+  return set_series_impl(h, t, t_stride, diag, diag_stride, y, y_stride, nullptr, false);
+}
+
+int clr_batch_set_series_ragged(clr_batch* h, const double* t, long t_stride, const double* diag, long diag_stride,
+                                const double* y, long y_stride, const int* lengths) {
+  bool ragged = false;  // (lengths that all equal N are the uniform plan)
+  if (lengths)
+    for (int b = 0; b < h->B; ++b) ragged = ragged || lengths[b] != h->N;
+  return set_series_impl(h, t, t_stride, diag, diag_stride, y, y_stride, lengths, ragged);
+}
+
+int clr_batch_get_lengths(const clr_batch* h, int* lengths) {
+  if (!lengths) return fail(CLR_INVALID_ARGUMENT, "clr_batch_get_lengths: lengths is null");
+  if (!h->have_series) return fail(CLR_INVALID_ARGUMENT, "no series set");
+  for (int b = 0; b < h->B; ++b) lengths[b] = h->ragged ? h->host_len[b] : h->N;
+  return CLR_OK;
+}
+
 int clr_batch_get_series_order(const clr_batch* h, double* dtmin) {
   if (!h->have_series) return fail(CLR_INVALID_ARGUMENT, "no series set");
   if (dtmin) *dtmin = h->dtmin;
@@ -486,6 +546,8 @@ int clr_batch_clear_series(clr_batch* h) {
   h->have_series = false;
   h->warm_active = false;
   h->warm_span.clear();
+  h->ragged = false;  // (the lengths belonged to the series)
+  h->host_len.clear();
   return CLR_OK;
 }
 
@@ -969,6 +1031,7 @@ int clr_batch_debug_compose_check(clr_batch* h, int group, double* max_abs_diff,
 
 int clr_batch_set_summarize_mode(clr_batch* h, int mode) {
   if (mode < -1 || mode > 2) return fail(CLR_INVALID_ARGUMENT, "summarize mode must be -1, 0, 1 or 2");
+  if (mode > 0 && h->ragged) return refuse_ragged(h, "the forced role-split summarize");
   if (mode != h->summarize_mode) scan_reader_changed(h);
   h->summarize_mode = mode;
   if (mode >= 0) h->pipeline_pinned = true;
@@ -1050,6 +1113,7 @@ int clr_batch_set_general(clr_batch* h, int J_general, const double* A, long A_s
     return CLR_OK;
   }
   if (!A || !U || !V) return fail(CLR_INVALID_ARGUMENT, "general terms need A, U and V");
+  if ((st = refuse_ragged(h, "clr_batch_set_general")) != CLR_OK) return st;
   if (h->J + J_general > CLR_MAX_WIDTH) return fail(CLR_UNSUPPORTED, "width above CLR_MAX_WIDTH");
   const long N = h->N, UV = (long)J_general * N;
   if ((A_stride != 0 && A_stride != N) || (U_stride != 0 && U_stride != UV) || (V_stride != 0 && V_stride != UV))
@@ -1076,6 +1140,7 @@ int clr_batch_set_general_route(clr_batch* h, int route) {
 
 int clr_batch_set_small_mode(clr_batch* h, int mode) {
   if (mode < -1 || mode > 1) return fail(CLR_INVALID_ARGUMENT, "small mode: -1 (auto), 0 (off) or 1 (whenever supported)");
+  if (mode == 1 && h->ragged) return refuse_ragged(h, "the forced one-launch mode");
   int st = warm_resolve(h, nullptr);
   if (st != CLR_OK) return st;
   h->small_mode = mode;
@@ -1090,6 +1155,7 @@ int clr_batch_get_small_mode(const clr_batch* h, int* active) {
 int clr_batch_set_warm_start(clr_batch* h, int mode, int forced_warmup) {
   if (mode < -1 || mode > 1 || (mode == 1 && forced_warmup < 1))
     return fail(CLR_INVALID_ARGUMENT, "warm start: mode -1 (auto), 0 (off) or 1 (forced, with a warm-up length >= 1)");
+  if (mode == 1 && h->ragged) return refuse_ragged(h, "the forced warm start");
   int st = warm_resolve(h, nullptr);
   if (st != CLR_OK) return st;
   h->warm_mode = mode;
@@ -1167,7 +1233,7 @@ static int fallback_params(clr_batch* h, clr::BatchParams& P) { return batch_par
 // a batch of short, narrow problems: the whole fused evaluation in ONE launch, one workgroup per problem
 // (small_batch_kernel, small_kernels.hip); problems it cannot certify stay pending for the scan pipeline
 static bool small_runs(const clr_batch* h, int materialize) {
-  if (h->grad_scan_only || h->small_mode == 0) return false;
+  if (h->grad_scan_only || h->small_mode == 0 || h->ragged) return false;  // (ragged: the kernel knows one length)
   if (!h->launch || materialize || h->force_exact || !h->wints.p || h->J_general > 0) return false;
   if (!clr::small_batch_supported(h->J_real, h->J_comp, h->N)) return false;
   // (automatic: while a workgroup per problem still fits one round of the chip -- above that the scan pipeline's
@@ -1563,6 +1629,14 @@ static int rescue_run(clr_batch* h, const std::vector<int>& idx, long n_total) {
   }
   r->have_series = true;
   series_replaced(r);
+  r->ragged = h->ragged;  // the re-planned problems' lengths travel with them (their gathered rows are padded already)
+  r->host_len.clear();
+  if (h->ragged) {
+    for (int b : idx) r->host_len.push_back(h->host_len[(size_t)b]);
+    if ((st = r->len_dev.reserve((size_t)n)) != CLR_OK) return st;
+    HIP_TRY(hipMemcpyAsync(r->len_dev.p, r->host_len.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, r->stream.get()));
+    HIP_TRY(hipStreamSynchronize(r->stream.get()));  // (pageable source)
+  }
   const size_t total = (size_t)n * (2 * h->J_real + 4 * h->J_comp + 1);
   if ((st = r->coeffs.reserve(total)) != CLR_OK) return st;
   clr::launch_gather_coeffs(h->coeffs.p, r->coeffs.p, h->rescue_idx.p, h->B, n, h->J_real, h->J_comp, r->stream.get());
@@ -1819,6 +1893,11 @@ int clr_batch_log_likelihood(int B, int N, int J_real, int J_comp, const double*
 // ---- hooks of the sharded layer (clr_group_hooks.h; not part of the C ABI) ----------------------------------------
 namespace clr_group {
 
+int set_series_lengths(clr_batch* h, const double* t, long t_stride, const double* diag, long diag_stride, const double* y,
+                       long y_stride, const int* lengths, bool batch_ragged) {
+  return set_series_impl(h, t, t_stride, diag, diag_stride, y, y_stride, lengths, batch_ragged);
+}
+
 void set_batch_context(clr_batch* h, int B_total) {
   h->group_B = B_total > h->B ? B_total : 0;  // (a single shard IS the whole batch)
 }
@@ -1827,7 +1906,7 @@ long warm_eligible(const clr_batch* h) { return h->warm_eligible; }
 
 void set_warm_eligible_total(clr_batch* h, long eligible_total) {
   if (h->group_B <= 0) return;
-  const bool selectable = h->warm_mode != 0 && h->wnchunk >= 2 && h->have_series && !h->warm_span.empty() &&
+  const bool selectable = !h->ragged && h->warm_mode != 0 && h->wnchunk >= 2 && h->have_series && !h->warm_span.empty() &&
                           h->host_cmin.size() == (size_t)h->B && h->warm_K.size() == (size_t)h->B;
   h->warm_eligible_total = eligible_total;
   h->warm_active = selectable && eligible_total * 2 >= (long)h->group_B;

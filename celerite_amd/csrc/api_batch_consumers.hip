@@ -17,6 +17,7 @@ extern "C" {
 // `settle`: settle an evaluation in flight first and require a completed run -- all but clr_batch_get_factor
 static int require_factor(clr_batch* h, bool settle) {
   int st;
+  if ((st = refuse_ragged(h, "the materialised factor and its consumers")) != CLR_OK) return st;
   if (settle && (st = warm_resolve(h, nullptr)) != CLR_OK) return st;
   if (!h->have_factor || (settle && !h->factor_valid))
     return fail(CLR_NOT_COMPUTED, settle ? "no materialising run has been made (clr_batch_enqueue(h, 1))"
@@ -29,6 +30,7 @@ static int require_factor(clr_batch* h, bool settle) {
 
 // the consumers cover celerite terms up to width 64 (`entry`: the refused call)
 static int require_celerite_width(const clr_batch* h, const char* entry) {
+  if (h->ragged) return refuse_ragged(h, entry);
   if (h->J_general > 0 || h->J > clr::wide_max_width())
     return fail(CLR_UNSUPPORTED, std::string(entry) + " covers celerite-only plans of widths 1..64");
   return CLR_OK;

@@ -338,6 +338,7 @@ int clr_batch_grad(clr_batch* h, double* value, double* grad, int* status) {
     G.B = h->B;
     G.fast_trig = P.fast_trig;
     G.only_level = scan_grad ? P.need_exact : nullptr;
+    G.len = P.len;
     G.out_value = h->g_res.p + B * NG; G.out_grad = G.out_value + B;
     G.out_status = reinterpret_cast<int*>(G.out_grad + B * NG);
     clr::launch_grad(G, h->stream.get());
@@ -346,8 +347,9 @@ int clr_batch_grad(clr_batch* h, double* value, double* grad, int* status) {
     HIP_TRY(hipMemcpyAsync(fb.data(), G.out_grad, B * NG * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
     HIP_TRY(hipStreamSynchronize(h->stream.get()));
   }
-  const double cst = 3.14159265358979323846 * log((double)h->N);  // the reference's constant (solver.cpp:415)
   for (size_t b = 0; b < B; ++b) {
+    // the reference's constant (solver.cpp:415), of the problem's own samples
+    const double cst = 3.14159265358979323846 * log((double)(h->ragged ? h->host_len[b] : h->N));
     const bool bad = stt[b] != CLR_OK;
     const bool from_fb = !bad && (lvl[b] >= 2 || !scan_grad);
     if (status) status[b] = stt[b];
@@ -496,6 +498,7 @@ int clr_batch_grad_mean(clr_batch* h, double* value, double* grad, double* dmean
   G.t_stride = h->t_stride; G.diag_stride = h->diag_stride; G.y_stride = h->y_stride;
   G.A = h->gA.p; G.U = h->gU.p; G.V = h->gV.p;
   G.A_stride = h->gA_stride; G.U_stride = h->gU_stride; G.V_stride = h->gV_stride;
+  G.len = P.len;
   clr::launch_mean_partial_batch(G, didx, (int)rest.size(), h->mean_out.p, h->stream.get());
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(dmean, h->mean_out.p, B * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));

@@ -245,6 +245,14 @@ struct clr_batch {
   clr::PinnedBuffer<double> pin;      // pinned host staging: coefficient uploads, result downloads
   SeriesCopy scan_series;             // the chunk-interleaved copy the scan's kernels read (scan_reads_copy)
   long t_stride = 0, diag_stride = 0, y_stride = 0;
+  // clr_batch_set_series_ragged: problem b holds host_len[b] <= N samples.  `ragged` says that lengths are in force: the
+  // rows of t, diag, y (and of the residual) are padded in place past each problem's length, every narrow kernel takes
+  // its n_b from len_dev (BatchParams::len), the warm-started and the one-launch routes stay off, and the materialising
+  // runs with every consumer of their factor are refused.  A slice of a larger batch is ragged when the WHOLE batch is
+  // (clr_group::set_series_lengths), whatever its own lengths: the route decisions must not depend on the sharding.
+  bool ragged = false;
+  std::vector<int> host_len;          // [B]; empty: uniform
+  DevArray<int> len_dev;              // [B]
   // clr_batch_set_mean: with a mean in force `y` holds the residual y - mu that every route reads, and `y_src` the
   // caller's series as uploaded (y_src_stride: its stride)
   bool have_mean = false;
@@ -511,6 +519,11 @@ bool split_active(const clr_batch* h, bool behind_fast_path) {
   //    fewer complex terms at width 8 its trajectory wave spills ((8,0), (6,1): 4.1-4.2 against 3.7): single wave.
   if (!(h->launch && h->nchunk > 1 && clr::have_summarize_split(h->J_real, h->J_comp))) return false;
   if (behind_fast_path) return false;
+  // per-problem lengths: the single-wave kernel (forcing mode 1 or 2 is refused: clr_batch_set_summarize_mode).  The
+  // role-split kernels sit at their register and scheduling limits: with the per-problem length in place of the kernel
+  // argument N the UNIFORM headline plan ran 2 % slower, all of it in the summarize (profiles/ragged_timing.txt, second
+  // part), and uniform plans must not pay
+  if (h->ragged) return false;
   if (h->summarize_mode > 0) return true;
   if (h->summarize_mode < 0 && h->J >= 7 && lazy_eligible(h)) return true;
   return h->summarize_mode < 0 && (h->J == 7 || (h->J == 8 && h->J_comp >= 2));
@@ -560,10 +573,19 @@ bool scan_reads_copy(const clr_batch* h) {
   return h->launch && (h->layout == 1 || split_active(h, false)) && h->nchunk > 1;
 }
 
+// what a plan with per-problem lengths refuses (`what`: the refused call or run)
+int refuse_ragged(const clr_batch* h, const char* what) {
+  if (!h->ragged) return CLR_OK;
+  return fail(CLR_UNSUPPORTED, std::string(what) + ": the plan has per-problem lengths (clr_batch_set_series_ragged), which the "
+                               "fused evaluation and the gradient of narrow plans carry -- set the series without lengths, or "
+                               "one plan per length, for the materialised factor and its consumers");
+}
+
 int batch_params(clr_batch* h, int materialize, clr::BatchParams& P, bool behind_fast_path) {
   if (!h->have_series || !h->have_coeffs)
     return fail(CLR_INVALID_ARGUMENT, "set_series and set_coefficients must be called first");
   int st = CLR_OK;
+  if (materialize && (st = refuse_ragged(h, "a materialising run")) != CLR_OK) return st;
   if (materialize && !h->have_factor) {
     // widths 1..8: chunk-interleaved device layout (replay_chunk, MATERIALIZE == 2); widths 9..64: the wide kernels
     // write the reference's own storage per problem (wide_scan_kernel, MODE 0: phi, u [N-1][J], W [N][J], D [N])
@@ -578,6 +600,7 @@ int batch_params(clr_batch* h, int materialize, clr::BatchParams& P, bool behind
   memset(&P, 0, sizeof(P));
   const size_t B = (size_t)h->B, nr = B * h->J_real, nc = B * h->J_comp;
   P.B = h->B; P.N = h->N; P.nchunk = h->nchunk; P.L = h->L; P.L0 = h->L0;
+  P.len = h->ragged ? h->len_dev.p : nullptr;
   P.fast_trig = (sel_max(h->dmax, h->floor_dmax) * sel_max(h->tmax, h->floor_tmax) < CLR_FAST_TRIG_LIMIT) ? 1 : 0;
   P.coop_prefix = h->coop_prefix;
   P.plan = h->plan;

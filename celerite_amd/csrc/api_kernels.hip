@@ -73,7 +73,7 @@ __global__ void __launch_bounds__(64) finalize_kernel(const BatchParams P) {
   P.out_status[b] = CLR_OK;
   P.out_logdet[b] = ld;
   P.out_quad[b] = qd;
-  P.out_ll[b] = combine_loglike(ld, qd, P.N);
+  P.out_ll[b] = combine_loglike(ld, qd, series_len(P, b));
 }
 
 void launch_finalize(const BatchParams& P, hipStream_t s) {
@@ -159,6 +159,25 @@ __global__ void __launch_bounds__(256) relayout_warm_kernel(const double* __rest
   for (int q = threadIdx.y; q < 32; q += 8) {
     const int r = r0 + q, c = c0 + threadIdx.x;
     if (r < rows && c < nchunk) out[(long)r * nchunk + c] = tile[threadIdx.x][q];
+  }
+}
+
+// Per-problem lengths (clr_batch_set_series_ragged): the tail n >= len[b] of row b of a resident row-major array [B][N]
+// becomes padding in place -- pad_kind as relayout_kernel's: 1 repeats the series' last value a[len[b] - 1] (t: dx = 0),
+// 2 writes 1e300 (the diagonal), 0 zeros (y).  Whatever the caller left there is never read.  1 <= len[b] <= N (checked
+// on the host): the value read, a[len[b] - 1], lies in front of every cell written.
+__global__ void __launch_bounds__(256) pad_tail_kernel(double* __restrict__ a, int N, const int* __restrict__ len, int pad_kind) {
+  double* row = a + (long)blockIdx.y * N;
+  const int nb = len[blockIdx.y];
+  const double pad = pad_kind == 1 ? row[nb - 1] : (pad_kind == 2 ? 1e300 : 0.0);
+  for (long n = (long)nb + (long)blockIdx.x * 256 + threadIdx.x; n < N; n += (long)gridDim.x * 256) row[n] = pad;
+}
+
+void launch_pad_tail(double* a, int B, int N, const int* len, int pad_kind, hipStream_t s) {
+  const int bx = std::min((N + 255) / 256, 64);
+  for (int b0 = 0; b0 < B; b0 += 65535) {  // (grid.y limit)
+    const int nb = std::min(B - b0, 65535);
+    hipLaunchKernelGGL(pad_tail_kernel, dim3(bx, nb), dim3(256), 0, s, a + (long)b0 * N, N, len + b0, pad_kind);
   }
 }
 

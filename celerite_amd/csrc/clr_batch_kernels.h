@@ -156,7 +156,15 @@ struct BatchParams {
   // factor, only for materialising runs (replay mode 1: reference storage per
   // problem; mode 2: chunk-interleaved [problem][i][j][chunk], see replay_chunk)
   double *phi, *u, *W, *D;
+  // per-problem series lengths (clr_batch_set_series_ragged): problem b holds len[b] <= N samples, the rest of its row is
+  // padding a recurrence step ignores (t held, diagonal 1e300, y = 0 -- in the resident row-major arrays themselves, so
+  // every reader and every copy sees it); null: every problem has N samples
+  const int* len;
 };
+
+// samples of problem b: what the chunk functions take as their N (the samples that count -- log-determinant, quadratic
+// form, flags, riders); the readers stay bounded by the allocation, P.N.  One load per lane or kernel, never per sample.
+__device__ __forceinline__ int series_len(const BatchParams& P, int b) { return P.len ? P.len[b] : P.N; }
 
 template <int JR, int JC>
 __device__ __forceinline__ void load_problem(const BatchParams& P, int b, Problem<JR, JC>& p) {
@@ -284,13 +292,14 @@ __global__ void __launch_bounds__(64) summarize_kernel(const BatchParams P) {
   const long slot = (long)b * P.nchunk + (store ? c : 0);
   double ld0 = 0.0, q0 = 0.0, gamma = 0.0;
   int flag0 = 0;
+  const int nb = series_len(P, b);
   if (STAGED) {
     StagedSeries src = make_staged(P, b, c, tiles);
-    summarize_chunk<JR, JC, FAST>(p, src, P.L, c * P.L, P.N, store, P.elems + slot * Wd::ELEM, &ld0,
+    summarize_chunk<JR, JC, FAST>(p, src, P.L, c * P.L, nb, store, P.elems + slot * Wd::ELEM, &ld0,
                                   &q0, &flag0, &gamma);
   } else {
     DirectSeries src = make_direct(P, b, c);
-    summarize_chunk<JR, JC, FAST>(p, src, P.L, c * P.L, P.N, store, P.elems + slot * Wd::ELEM, &ld0,
+    summarize_chunk<JR, JC, FAST>(p, src, P.L, c * P.L, nb, store, P.elems + slot * Wd::ELEM, &ld0,
                                   &q0, &flag0, &gamma);
   }
   if (!store) return;
@@ -552,7 +561,10 @@ __global__ void __launch_bounds__(64) correct_kernel(const BatchParams P) {
   const int b = (int)(slot / P.nchunk), c = (int)(slot % P.nchunk);
   if (P.only_pending && P.need_scan[b] == 0) return;  // (settled by the warm path: its workspace holds nothing)
   if (P.flags[slot]) atomicOr(P.need_exact + b, 2);  // a zero-start pivot <= 0 (summarize)
-  if (c == 0) {  // the first chunk starts from the zero state: nothing to correct
+  // the first chunk starts from the zero state: nothing to correct.  Nor has a chunk wholly past the problem's last sample
+  // (per-problem lengths): its Jm and eta are zero -- the correction is log det(I) = 0 exactly -- and the certificate's
+  // factorisation of -Jm + delta I = 0 would break down on it (summarize left mu = 1 in the record)
+  if (c == 0 || (long)c * P.L >= series_len(P, b)) {
     if (P.egerr) P.egerr[slot] = 0.0;
     return;
   }
@@ -606,7 +618,7 @@ __global__ void __launch_bounds__(64) replay_kernel(const BatchParams P) {
   // (fix-up pass: lanes that only keep a staged wave's tile loads company -- chunk 0, lanes past the last chunk -- see an
   //  empty series: no sample of theirs is "valid", nothing is stored)
   const int steps = fixup ? (P.fixup_steps < P.L ? P.fixup_steps : P.L) : P.L;
-  const int N_eff = (fixup && (c == 0 || !mine)) ? 0 : P.N;
+  const int N_eff = (fixup && (c == 0 || !mine)) ? 0 : series_len(P, b);
   double *phi_o = nullptr, *u_o = nullptr, *W_o = nullptr, *D_o = nullptr;
   long fstride = 0;
   if (MATERIALIZE == 1) {  // reference storage, one problem after the other
@@ -733,13 +745,16 @@ __global__ void __launch_bounds__(256) decide_kernel(const BatchParams P) {
   // the corrections' rounding-error estimates (chunk_update: J eps / mu, times |w.G w| for the quadratic form) summed
   // over the chunks, against the problem's own log det and quadratic form
   double err_ld = 0.0, err_q = 0.0, sum_ld = 0.0, sum_q = 0.0;
+  // (a chunk wholly past the problem's last sample is padding: its element is the identity on the sums, its correction
+  //  exactly zero -- it adds nothing to the error budget)
+  const long nb = series_len(P, b);
   for (int c = tid; c < P.nchunk; c += NT) {
     const long slot = (long)b * P.nchunk + c;
     g = nmax(g, P.cond[slot * 3]);
     const double mu = P.cond[slot * 3 + 1];
     m = nmin(m, mu);
     if (P.egerr) e = nmax(e, P.egerr[slot]);
-    if (c > 0) err_ld += J * 2.2e-16 / mu;
+    if (c > 0 && (long)c * P.L < nb) err_ld += J * 2.2e-16 / mu;
     err_q += P.cond[slot * 3 + 2];
     P.cond[slot * 3 + 2] = 0.0;  // (from here on: the replay's end-state residual)
     sum_ld += P.part[slot * 2 + 0];
@@ -836,6 +851,7 @@ __global__ void __launch_bounds__(64) sequential_kernel(const BatchParams P) {
   load_problem<JR, JC>(P, b, p);
   double state[Wd::START];
   const long Nm1 = P.N - 1;
+  const int nb = series_len(P, b);
   for (int c = 0; c < P.nchunk; ++c) {
     DirectSeries src = make_direct(P, b, c);
     double ld, qd;
@@ -857,7 +873,7 @@ __global__ void __launch_bounds__(64) sequential_kernel(const BatchParams P) {
       W_o = P.W + (long)b * J * cells + c;
       D_o = P.D + (long)b * cells + c;
     }
-    replay_chunk<JR, JC, MATERIALIZE, FAST>(p, src, P.L, P.N, c * P.L, c > 0 ? state : nullptr, &ld, &qd, &flag,
+    replay_chunk<JR, JC, MATERIALIZE, FAST>(p, src, P.L, nb, c * P.L, c > 0 ? state : nullptr, &ld, &qd, &flag,
                                             phi_o, u_o, W_o, D_o, fstride, state);
     const long slot = (long)b * P.nchunk + c;
     P.partx[slot * 2 + 0] = ld;
@@ -998,7 +1014,7 @@ __global__ void __launch_bounds__(64) warm_check_kernel(const BatchParams P) {
   P.out_status[b] = CLR_OK_STATUS;
   P.out_logdet[b] = ld;
   P.out_quad[b] = qd;
-  P.out_ll[b] = combine_loglike(ld, qd, P.N);
+  P.out_ll[b] = combine_loglike(ld, qd, series_len(P, b));
 }
 
 }  // namespace clr
@@ -1449,6 +1465,9 @@ void launch_relayout(const double* src, long src_stride, double* dst, long dst_s
 // [problem][n] -> the warm kernel's [problem][row][chunk], row r of chunk c = sample c L - Kpad + r (api_kernels.hip)
 void launch_relayout_warm(const double* src, long src_stride, double* dst, long dst_stride, int nsrc, int N, int L,
                           int nchunk, int Kpad, int rows, int pad_kind, hipStream_t s);
+
+// rows of a[B][N] past their problem's length len[b] -> padding, in place (api_kernels.hip; pad_kind as launch_relayout)
+void launch_pad_tail(double* a, int B, int N, const int* len, int pad_kind, hipStream_t s);
 
 // a few problems of a plan re-planned as a small plan of their own (api_kernels.hip; api_batch.hip: rescue_run)
 void launch_gather_series(const double* src, long src_stride, double* dst, const int* idx, int n, int N, hipStream_t s);

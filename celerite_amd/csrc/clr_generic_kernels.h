@@ -37,6 +37,7 @@ struct GenericBatch {
   long A_stride, U_stride, V_stride;     // per problem (0: shared)
   double *out_ll, *out_logdet, *out_quad;
   int* out_status;
+  const int* len;  // may be null: problem b has len[b] <= N samples (celerite terms only; the strides stay N)
 };
 void launch_generic_loglike_batch(const GenericBatch& G, hipStream_t s);
 // d loglike / d mu = 1^T K^-1 r for the problems idx[0..count) of G (idx == nullptr: problems 0..count; G.y: the
@@ -116,6 +117,7 @@ struct GradParams {
   const double* jitter_b;
   long t_stride, diag_stride, y_stride;
   const int* only_level;  // batched, may be null: only the problems with only_level[b] >= 2 are computed
+  const int* len;         // batched sequential form, may be null: problem b has len[b] <= N samples (no general terms)
   // CHUNKED mode (the gradient parallel in n at widths 9..32 and with general terms, wide_grad_kernels.hip):
   // blockIdx.z = chunk c.  The wave runs samples [chunk c) only, from the TRUE base state at the chunk's first sample
   // (starts: [B][nchunk][JP (JP + 1) / 2 + JP] from the wide scan, packed upper triangle at the padded width JP | f)

@@ -18,6 +18,12 @@ namespace clr_group {
 // this plan holds a contiguous slice of a batch of `B_total` problems (<= the plan's own size: it is the whole batch)
 void set_batch_context(clr_batch* h, int B_total);
 
+// clr_batch_set_series_ragged for a slice: `lengths` is the slice's own part of the batch's lengths, `batch_ragged` whether
+// ANY length of the whole batch differs from N.  A slice whose own lengths all equal N is still a plan with lengths in
+// force then -- the routes that plans with lengths leave out (warm start, one-launch mode) are a decision of the batch.
+int set_series_lengths(clr_batch* h, const double* t, long t_stride, const double* diag, long diag_stride, const double* y,
+                       long y_stride, const int* lengths, bool batch_ragged);
+
 // warm-started recurrence: problems of this plan that could start warm at the series / coefficients in force, and the
 // count over the whole batch (activation: at least half of the batch)
 long warm_eligible(const clr_batch* h);

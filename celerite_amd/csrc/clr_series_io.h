@@ -32,8 +32,8 @@ int staging_create(UploadStaging& s, int device);  // 0 on success, else a hipEr
 int upload_parallel(UploadStaging& s, const CopyJob* jobs, int njobs);
 
 // per source series (nsrc = 1 for a shared series): max |t|, largest |step|, smallest step (negative: not sorted),
-// NaN seen (0 / 1) -> out[nsrc][4]
-void launch_series_stats(const double* t, long stride, int nsrc, int N, double* out, hipStream_t s);
+// NaN seen (0 / 1) -> out[nsrc][4]; `len` (device, [nsrc], may be null): series b is the first len[b] <= N entries of its row
+void launch_series_stats(const double* t, long stride, int nsrc, int N, const int* len, double* out, hipStream_t s);
 // per source series and candidate k: the shortest time the cand[k] samples in front of a warm-path chunk boundary
 // (samples c wL, c = 1 .. wnchunk - 1) span; 0 for candidates above wL / 2 -> out[nsrc][nk]
 struct WarmCands { int K[16]; int nk; };

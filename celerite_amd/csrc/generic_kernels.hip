@@ -140,7 +140,8 @@ template <bool MEAN>
 __global__ void __launch_bounds__(256) generic_loglike_batch_kernel(const GenericBatch G, double* dmean,
                                                                     const int* idx) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int b = (MEAN && idx) ? idx[blockIdx.x] : (int)blockIdx.x, N = G.N, tid = threadIdx.x, nt = blockDim.x;
+  const int b = (MEAN && idx) ? idx[blockIdx.x] : (int)blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
+  const int N = (G.len && G.J_general == 0) ? G.len[b] : G.N;  // (a plan with per-problem lengths: the problem's own samples)
   GenericProblem g;
   g.N = N;
   g.J_real = G.J_real; g.J_comp = G.J_comp; g.J_general = G.J_general;

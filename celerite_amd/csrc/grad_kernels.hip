@@ -46,6 +46,7 @@ __global__ void __launch_bounds__(64) wide_grad_kernel(const GradParams Pin) {
     P.jitter = Pin.jitter_b[b];
     P.t += b * Pin.t_stride; P.diag += b * Pin.diag_stride; P.y += b * Pin.y_stride;
     P.out_value += b; P.out_grad += b * NG; P.out_status += b;
+    if (!CHUNKED && Pin.len) P.N = Pin.len[b];  // (a plan with per-problem lengths: the problem's own samples alone)
   }
   using G = WideGeom<WMAX>;
   constexpr int LPR = G::LPR, COLS = G::COLS;

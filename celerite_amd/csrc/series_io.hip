@@ -75,8 +75,9 @@ int upload_parallel(UploadStaging& s, const CopyJob* jobs, int njobs) {
 // ---- scans of t on the device ----------------------------------------------------------------------------------
 namespace {
 
-__global__ void __launch_bounds__(256) series_stats_kernel(const double* t, long stride, int N, double* out) {
+__global__ void __launch_bounds__(256) series_stats_kernel(const double* t, long stride, int N, const int* len, double* out) {
   const double* tb = t + (long)blockIdx.x * stride;
+  if (len) N = len[blockIdx.x];  // (per-problem lengths: the row's first len[b] entries are the series, the rest is not looked at)
   double tm = 0.0, dm = 0.0, dmin = INFINITY;
   int nan = 0;
   for (int n = threadIdx.x; n < N; n += 256) {
@@ -127,8 +128,8 @@ __global__ void warm_spans_kernel(const double* t, long stride, int nsrc, int wL
 
 }  // namespace
 
-void launch_series_stats(const double* t, long stride, int nsrc, int N, double* out, hipStream_t s) {
-  hipLaunchKernelGGL(series_stats_kernel, dim3(nsrc), dim3(256), 0, s, t, stride, N, out);
+void launch_series_stats(const double* t, long stride, int nsrc, int N, const int* len, double* out, hipStream_t s) {
+  hipLaunchKernelGGL(series_stats_kernel, dim3(nsrc), dim3(256), 0, s, t, stride, N, len, out);
 }
 
 void launch_warm_spans(const double* t, long stride, int nsrc, int wL, int wnchunk, WarmCands cands, double* out,

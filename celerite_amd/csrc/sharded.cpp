@@ -387,6 +387,51 @@ int clr_sharded_set_series(clr_sharded* h, const double* t, long t_stride, const
   return CLR_OK;
 }
 
+int clr_sharded_set_series_ragged(clr_sharded* h, const double* t, long t_stride, const double* diag, long diag_stride,
+                                  const double* y, long y_stride, const int* lengths) {
+  if (!lengths) return clr_sharded_set_series(h, t, t_stride, diag, diag_stride, y, y_stride);
+  // whether lengths are in force is decided once, over the WHOLE batch; a bad length is refused before any shard changes
+  bool ragged = false;
+  for (int b = 0; b < h->B; ++b) {
+    if (lengths[b] < 1 || lengths[b] > h->N) {
+      g_sharded_error = "clr_sharded_set_series_ragged: length " + std::to_string(lengths[b]) + " of problem " +
+                        std::to_string(b) + " is outside [1, N]";
+      return CLR_INVALID_ARGUMENT;
+    }
+    ragged = ragged || lengths[b] != h->N;
+  }
+  if (ragged && (t_stride == 0 || diag_stride == 0 || y_stride == 0)) {
+    g_sharded_error = "clr_sharded_set_series_ragged: with lengths t, diag and y are each [B][N] (stride N)";
+    return CLR_INVALID_ARGUMENT;
+  }
+  int st = resolve_all(h);
+  if (st != CLR_OK) return st;
+  st = h->all([=](int s) {
+    const long lo = h->lo[s];
+    return clr_group::set_series_lengths(h->plan[s], t + lo * t_stride, t_stride, diag + lo * diag_stride, diag_stride,
+                                         y + lo * y_stride, y_stride, lengths + lo, ragged);
+  });
+  if (st != CLR_OK) return st;
+  spread_maxima(h, true);
+  reselect_all(h);
+  return CLR_OK;
+}
+
+int clr_sharded_get_lengths(const clr_sharded* h, int* lengths) {
+  if (!lengths) {
+    g_sharded_error = "clr_sharded_get_lengths: lengths is null";
+    return CLR_INVALID_ARGUMENT;
+  }
+  for (size_t s = 0; s < h->plan.size(); ++s) {
+    const int st = clr_batch_get_lengths(h->plan[s], lengths + h->lo[s]);
+    if (st != CLR_OK) {
+      g_sharded_error = "shard " + std::to_string(s) + ": " + clr_last_error();
+      return st;
+    }
+  }
+  return CLR_OK;
+}
+
 int clr_sharded_get_series_order(const clr_sharded* h, double* dtmin) {
   // the smallest step over the shards' finite values; a negative one ("not sorted") wins over a NaN time in any
   // shard, and only a batch without a negative step reports NaN (clr_batch_get_series_order has the same rule)

@@ -248,6 +248,40 @@ int clr_batch_set_series(clr_batch* h,
                          const double* t, long t_stride,
                          const double* diag, long diag_stride,
                          const double* y, long y_stride);
+/* Per-problem series lengths (ragged batches): problem b is the first lengths[b] samples of its rows, 1 <= lengths[b]
+ * <= N (host, [B]).  NULL is exactly clr_batch_set_series, lengths that all equal N are the uniform plan, and a later
+ * clr_batch_set_series returns the plan to uniform.  With lengths in force t, diag and y are each [B][N] (stride N): a
+ * shared array (stride 0) is CLR_INVALID_ARGUMENT -- the padded device copy is per problem -- and so is a length outside
+ * [1, N]; both leave the plan as it was.
+ *   The tail is never read: entries n >= lengths[b] of a row may be NaN, unsorted, anything.  After the upload a small
+ *   kernel rewrites them IN the resident arrays to the padding a recurrence step ignores -- t held at t[lengths[b] - 1],
+ *   diagonal 1e300, y = 0 -- before any scan looks at them, so clr_batch_get_series_order, the selection bounds and
+ *   every copy of the series see the first lengths[b] entries alone.  A padded step changes no state above rounding; the
+ *   kernels leave it out of the log-determinant, the quadratic form, the flags and the riders by a select on n < n_b,
+ *   with n_b loaded once per lane (BatchParams::len).  A mean (clr_batch_set_mean, _set_mean_basis) leaves the residual's
+ *   tail at 0, not -mu.
+ *   What carries n_b: the fused evaluation of narrow plans (widths 1..8, no general terms) on every layout, prefix
+ *   mode and route -- the replay-free route, the checked replay, the sequential recurrence, the re-planned
+ *   side plan (clr_batch_set_rescue), clr_batch_set_exact -- and the gradient (reverse, forward, the sequential
+ *   fallback, the mean's partial); loglike, logdet, quad, gradient, status and the gradient value's pi log n_b are those
+ *   of the problem's own samples.
+ *   What stays off: the warm-started recurrence and the one-launch small mode do not run while lengths are in force
+ *   (clr_batch_get_warm_start and clr_batch_get_small_mode report inactive; forcing either is CLR_UNSUPPORTED, as is
+ *   setting lengths while one is forced).  Nor do the role-split summarize kernels of widths 7 and 8: such a plan runs
+ *   the single-wave summarize under the modes -1 and 0 (clr_batch_get_summarize_kernel reports 0), and
+ *   clr_batch_set_summarize_mode(h, 1 or 2) -- or lengths on a plan where one of them is set -- is CLR_UNSUPPORTED.  The
+ *   role-split kernels are exactly what uniform plans ran before; a ragged batch of width 7 or 8 costs about 1.5 x the
+ *   uniform plan of its shape (profiles/ragged_timing.txt).  clr_batch_clear_series drops the lengths with the series.
+ *   What refuses (CLR_UNSUPPORTED, "the plan has per-problem lengths"; the plan still evaluates afterwards): wide plans
+ *   (widths above 8) and plans with general terms, every materialising run, and every consumer of the materialised
+ *   factor or of the padded rows: clr_batch_get_factor, _solve, _dot_L, _dot, _predict*, _one_step_ahead, _forecast,
+ *   _predict_terms, _predict_cov, _sample_conditional, _leave_one_out, _grad_mean_weights, _fit_mean_weights.
+ * clr_batch_get_lengths: the lengths in force (N for every problem of a uniform plan). */
+int clr_batch_set_series_ragged(clr_batch* h,
+                                const double* t, long t_stride,
+                                const double* diag, long diag_stride,
+                                const double* y, long y_stride, const int* lengths);
+int clr_batch_get_lengths(const clr_batch* h, int* lengths);
 /* Short narrow problems (widths 1..4, 512 <= N <= 32768; BASELINE configs[1]: 256 x 1e4 x width 4): the whole fused
  * evaluation in ONE launch, one workgroup per problem -- chunk elements composed by a Kogge-Stone scan in LDS, the
  * reference recurrence per chunk from the scanned states, every chunk boundary checked; a problem that fails the check
@@ -940,6 +974,12 @@ int clr_sharded_get_series_order(const clr_sharded* h, double* dtmin);
 int clr_sharded_clear_series(clr_sharded* h);
 int clr_sharded_set_series(clr_sharded* h, const double* t, long t_stride, const double* diag,
                            long diag_stride, const double* y, long y_stride);
+/* clr_batch_set_series_ragged / clr_batch_get_lengths over all shards: `lengths` is [B] for the whole batch, each shard
+ * takes its slice.  Whether lengths are in force is decided once for the batch (a shard whose own lengths all equal N is
+ * still a plan with lengths then), so results are the same bits under any sharding. */
+int clr_sharded_set_series_ragged(clr_sharded* h, const double* t, long t_stride, const double* diag, long diag_stride,
+                                  const double* y, long y_stride, const int* lengths);
+int clr_sharded_get_lengths(const clr_sharded* h, int* lengths);
 int clr_sharded_set_coefficients(clr_sharded* h, const double* jitter, const double* a_real,
                                  const double* c_real, const double* a_comp, const double* b_comp,
                                  const double* c_comp, const double* d_comp);
