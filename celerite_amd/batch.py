@@ -115,6 +115,14 @@ def _load():
     lib.clr_sharded_set_mean_weights.argtypes = [C.c_void_p, _dp]
     lib.clr_sharded_grad_mean_weights.argtypes = [C.c_void_p, _dp, _ip]
     lib.clr_batch_fit_mean_weights.argtypes = [C.c_void_p, C.c_double] + [_dp] * 5 + [_ip]
+    lib.clr_batch_set_noise_basis.argtypes = [C.c_void_p, C.c_int, _dp, C.c_long]
+    lib.clr_batch_set_noise_weights.argtypes = [C.c_void_p, _dp]
+    lib.clr_batch_grad_noise_weights.argtypes = [C.c_void_p, _dp, _ip]
+    lib.clr_batch_get_noise_project_ms.argtypes = [C.c_void_p, _dp]
+    lib.clr_sharded_set_noise_basis.argtypes = [C.c_void_p, C.c_int, _dp, C.c_long]
+    lib.clr_sharded_set_noise_weights.argtypes = [C.c_void_p, _dp]
+    lib.clr_sharded_grad_noise_weights.argtypes = [C.c_void_p, _dp, _ip]
+    lib.clr_sharded_get_noise_project_ms.argtypes = [C.c_void_p, _dp]
     lib.clr_sharded_fit_mean_weights.argtypes = [C.c_void_p, C.c_double] + [_dp] * 5 + [_ip]
     lib.clr_batch_set_mean_fit_tile.argtypes = [C.c_void_p, C.c_int]
     lib.clr_batch_get_mean_fit_ms.argtypes = [C.c_void_p, _dp, _dp, _dp]
@@ -305,6 +313,37 @@ def _weights_arg(w, B, K):
     if K < 1 or a.shape not in ((K,), (B, K)):
         raise ValueError("dimension mismatch")
     return np.ascontiguousarray(np.broadcast_to(a, (B, K)))
+
+
+MAX_NOISE_BASIS = 16     # CLR_MAX_NOISE_BASIS of include/celerite_hip.h
+
+
+def _noise_basis_arg(Psi, B, N, lengths=None):
+    """:func:`_basis_arg` for a linear noise model's basis (``clr_*_set_noise_basis``; the same shapes and limit), with
+    the entries checked: all finite -- with per-problem ``lengths`` in force, within each problem's length (of a shared
+    basis: the longest problem's), for the rest of a row is never looked at."""
+    a, stride, K = _basis_arg(Psi, B, N)
+    if a is None:
+        return a, stride, K
+    if lengths is None:
+        ok = np.all(np.isfinite(a))
+    else:
+        lens = np.asarray(lengths)
+        live = np.arange(N) < (lens[:, None, None] if a.ndim == 3 else lens.max())
+        ok = np.all(np.isfinite(a) | ~live)
+    if not ok:
+        raise ValueError("a non-finite noise basis entry")
+    return a, stride, K
+
+
+def _noise_weights_arg(s, B, K):
+    """:func:`_weights_arg` for the weights of a linear noise model, which must be finite."""
+    if K < 1:
+        raise ValueError("dimension mismatch: no noise basis is set (set_noise_basis)")
+    a = _weights_arg(s, B, K)
+    if not np.all(np.isfinite(a)):
+        raise ValueError("a non-finite noise weight")
+    return a
 
 
 MeanFit = collections.namedtuple("MeanFit", ["weights", "covariance", "gram", "quad", "logdet_gram", "loglike",
@@ -653,6 +692,7 @@ class BatchedGP(object):
             else:
                 raise ValueError("dimension mismatch")
             arrs.append(a)
+        self._series_lengths = lens      # (set_noise_basis: the part of a row its finiteness check covers)
         lib = _load()
         if lens is None:
             _check(lib.clr_batch_set_series(self._h, _ptr(arrs[0]), strides[0], _ptr(arrs[1]),
@@ -768,6 +808,66 @@ class BatchedGP(object):
         _check(_load().clr_batch_get_mean_project_ms(self._h, C.byref(ms)))
         return ms.value
 
+    def set_noise_basis(self, Psi):
+        """A noise model that is linear in its parameters (``clr_batch_set_noise_basis``): the variances every route
+        reads become
+
+            ``diag_eff[b, n] = diag[b, n] + sum_k s[b, k] Psi_k[b, n]``
+
+        with the plan's scalar ``jitter`` added on top as before.  ``Psi`` is the basis at the plan's samples, ``(K, N)``
+        for all problems or ``(B, K, N)``, ``K <= 16`` -- a jitter per instrument (``diag = sigma^2``, ``Psi_g`` the
+        indicator of instrument g, ``s_g`` its jitter squared), an error-bar inflation ``f^2 sigma^2`` (``Psi_0 =
+        sigma^2``, ``s_0 = f^2 - 1``), a noise level per observing season.  It is uploaded once and stays on the device;
+        the weights start at zero, so the plan is the plain plan until :meth:`set_noise_weights`.  ``None`` removes the
+        noise model.  The entries must be finite (with ``lengths=`` in force: within each problem's length) and need be
+        nothing else: a variance that comes out non-positive shows in the problem's status."""
+        a, stride, K = _noise_basis_arg(Psi, self.B, self.N, getattr(self, "_series_lengths", None))
+        self._set_noise_basis(K, a, stride)
+        self._noise_K = K
+
+    def _set_noise_basis(self, K, a, stride):
+        _check(_load().clr_batch_set_noise_basis(self._h, K, None if a is None else _ptr(a), stride))
+
+    def set_noise_weights(self, s):
+        """The weights of the linear noise model, ``(B, K)`` or ``(K,)`` for all problems
+        (``clr_batch_set_noise_weights``): every route that reads the diagonal then sees ``diag + (s[b, 0] Psi_0 +
+        s[b, 1] Psi_1 + ...)`` -- the bits of that NumPy expression -- formed on the device from the uploaded ``diag``:
+        B x K numbers go up per optimiser or sampler step, not a new ``(B, N)`` diagonal through :meth:`set_series`, and
+        nothing derived from ``t`` is rebuilt.  The factor of an earlier materialising run is that of the earlier
+        variances: materialise again before :meth:`solve`, :meth:`predict`, ... or :meth:`grad_noise_weights`."""
+        self._set_noise_weights(_noise_weights_arg(s, self.B, getattr(self, "_noise_K", 0)))
+
+    def _set_noise_weights(self, a):
+        _check(_load().clr_batch_set_noise_weights(self._h, _ptr(a)))
+
+    def grad_noise_weights(self):
+        """``(ds[B, K], status[B])``: the gradient with respect to the noise weights in force,
+
+            ``d loglike_b / d s[b, k] = 1/2 sum_n Psi_k[b, n] (alpha_n^2 - c_n)``,  ``alpha = K_b^-1 r_b``,  ``c = diag(K_b^-1)``
+
+        (``clr_batch_grad_noise_weights``): :meth:`leave_one_out`'s diagonal recurrence and solve, then one projection
+        pass on the device.  It needs a materialising run (``enqueue(materialize=True)``) made AFTER the weights -- and
+        the basis and the series -- were set: the factor must be that of the variances in force, and a change of any of
+        them since is refused with ``CLR_NOT_COMPUTED`` until the plan is materialised again.  :meth:`leave_one_out`'s
+        domain: celerite-only plans of widths 1..64 without ``lengths=``.  A problem whose status is not 0 has a row of
+        zeros."""
+        K = getattr(self, "_noise_K", 0)
+        if not K:
+            raise RuntimeError("no noise basis is set: call set_noise_basis first")
+        ds, st = np.empty((self.B, K)), np.empty(self.B, dtype=np.int32)
+        self._grad_noise_weights(ds, st)
+        return ds, st
+
+    def _grad_noise_weights(self, ds, st):
+        _check(_load().clr_batch_grad_noise_weights(self._h, _ptr(ds), st.ctypes.data_as(_ip)))
+
+    def noise_project_ms(self):
+        """Device time of the projection pass of the last :meth:`grad_noise_weights` (its diagonal and solve:
+        :meth:`leave_one_out_ms`)."""
+        ms = C.c_double()
+        _check(_load().clr_batch_get_noise_project_ms(self._h, C.byref(ms)))
+        return ms.value
+
     def set_coefficients(self, a_real, c_real, a_comp, b_comp, c_comp, d_comp, jitter=0.0):
         """Coefficient tables ``(B, J_real)`` / ``(B, J_comp)``; ``jitter`` scalar or ``(B,)``."""
         try:
@@ -833,16 +933,20 @@ class BatchedGP(object):
                                              st.ctypes.data_as(_ip)))
         return ll, ld, q, st
 
-    def evaluate(self, a_real, c_real, a_comp, b_comp, c_comp, d_comp, jitter=0.0, mean=None, mean_weights=None):
+    def evaluate(self, a_real, c_real, a_comp, b_comp, c_comp, d_comp, jitter=0.0, mean=None, mean_weights=None,
+                 noise_weights=None):
         """One optimiser / MCMC evaluation in ONE library call (``clr_batch_evaluate``): new coefficient tables in,
         ``(loglike, logdet, quad, status)`` of all B problems out -- ``set_coefficients`` + ``enqueue`` + ``results``
         without two of the three trips through ctypes.  Arrays that already are C-contiguous float64 of the right shape
         are passed as they are.  ``mean`` (a scalar or ``(B,)``): :meth:`set_mean` in the same call
         (``clr_batch_evaluate_mean``); ``None`` leaves the mean in force as it is.  ``mean_weights``:
-        :meth:`set_mean_weights` first (a linear mean, :meth:`set_mean_basis`); not together with ``mean``."""
+        :meth:`set_mean_weights` first (a linear mean, :meth:`set_mean_basis`); not together with ``mean``.
+        ``noise_weights``: :meth:`set_noise_weights` first (a linear noise model, :meth:`set_noise_basis`)."""
         _exclusive_means(mean, mean_weights)
         if mean_weights is not None:
             self.set_mean_weights(mean_weights)
+        if noise_weights is not None:
+            self.set_noise_weights(noise_weights)
         B, JR, JC = self.B, self.J_real, self.J_comp
         tabs = []
         for a, w in ((a_real, JR), (c_real, JR), (a_comp, JC), (b_comp, JC), (c_comp, JC), (d_comp, JC)):
@@ -895,15 +999,17 @@ class BatchedGP(object):
             raise ValueError("dimension mismatch")
         return p
 
-    def evaluate_parameters(self, params, mean=None, mean_weights=None):
+    def evaluate_parameters(self, params, mean=None, mean_weights=None, noise_weights=None):
         """One optimiser / MCMC evaluation from kernel parameters (``clr_batch_evaluate_params``): ``params`` is
-        ``(B, kernel.vector_size)`` in ``get_parameter_vector()`` order, ``mean`` and ``mean_weights`` as in
-        :meth:`evaluate`.  The coefficients are formed on the device and never leave it.  Returns ``(loglike, logdet,
+        ``(B, kernel.vector_size)`` in ``get_parameter_vector()`` order, ``mean``, ``mean_weights`` and
+        ``noise_weights`` as in :meth:`evaluate`.  The coefficients are formed on the device and never leave it.  Returns ``(loglike, logdet,
         quad, status)``; a draw the program refuses (an SHO term across Q = 1/2, a non-finite parameter or coefficient)
         has status ``CLR_INVALID_ARGUMENT`` and NaN results, the other problems are not affected."""
         _exclusive_means(mean, mean_weights)
         if mean_weights is not None:
             self.set_mean_weights(mean_weights)
+        if noise_weights is not None:
+            self.set_noise_weights(noise_weights)
         p = self._params_arg(params)
         ll, ld, q, st = np.empty(self.B), np.empty(self.B), np.empty(self.B), np.empty(self.B, dtype=np.int32)
         m, stride = _mean_arg(mean, self.B)
@@ -1091,7 +1197,8 @@ class BatchedGP(object):
     def inverse_diagonal(self):
         """``diag(K_p^-1)`` of every problem, ``(B, N)``, from the factor of the last materialising run
         (``clr_batch_leave_one_out``): all N entries by one backward matrix recurrence, O(N J^2) per problem.  With
-        ``c = diag(K^-1)``, ``alpha = K^-1 r`` (:meth:`solve`) and ``s_n = diag_n + jitter`` the in-sample answer of
+        ``c = diag(K^-1)``, ``alpha = K^-1 r`` (:meth:`solve`) and ``s_n = diag_eff_n + jitter`` (``diag_eff``: ``diag`` plus the noise model of
+        :meth:`set_noise_weights`) the in-sample answer of
         ``GP.predict(y)`` (celerite.py:270-272) is ``mu_n = y_n - s_n alpha_n``, ``var_n = s_n - s_n^2 c_n`` -- no O(N^2)
         work.  Rows of problems whose status is not 0 are NaN."""
         c = np.empty((self.B, self.N))
@@ -1108,7 +1215,8 @@ class BatchedGP(object):
 
         (``residual`` and ``variance`` are formed on the host from the two downloaded arrays; see
         :func:`leave_one_out_from`).  The in-sample ``GP.predict(y)`` (celerite.py:270-272) follows without O(N^2) work:
-        ``mu_n = y_n - s_n alpha_n``, ``var_n = s_n - s_n^2 c_n`` with ``s_n = diag_n + jitter``.
+        ``mu_n = y_n - s_n alpha_n``, ``var_n = s_n - s_n^2 c_n`` with ``s_n = diag_eff_n + jitter`` (``diag_eff``: ``diag`` plus the noise model of
+        :meth:`set_noise_weights`).
         ``arrays=False`` downloads ``logpdf[B]`` and ``status[B]`` only -- the step of a leave-one-out cross-validation
         model comparison; the array fields are then ``None``.  Rows of problems whose status is not 0 are NaN."""
         logpdf, st = np.empty(self.B), np.empty(self.B, dtype=np.int32)
@@ -1553,6 +1661,7 @@ class ShardedBatchedGP(object):
             else:
                 raise ValueError("dimension mismatch")
             arrs.append(a)
+        self._series_lengths = lens      # (set_noise_basis: the part of a row its finiteness check covers)
         lib = _load()
         if lens is None:
             self._ok(lib.clr_sharded_set_series(self._h, _ptr(arrs[0]), strides[0], _ptr(arrs[1]),
@@ -1607,6 +1716,26 @@ class ShardedBatchedGP(object):
     #  stream, and the sharded C ABI has no entry point for them -- every shard sizes its tile automatically, which no
     #  result depends on)
 
+    set_noise_basis = BatchedGP.set_noise_basis
+    set_noise_weights = BatchedGP.set_noise_weights
+    grad_noise_weights = BatchedGP.grad_noise_weights
+
+    def _set_noise_basis(self, K, a, stride):
+        self._ok(_load().clr_sharded_set_noise_basis(self._h, K, None if a is None else _ptr(a), stride))
+
+    def _set_noise_weights(self, a):
+        self._ok(_load().clr_sharded_set_noise_weights(self._h, _ptr(a)))
+
+    def _grad_noise_weights(self, ds, st):
+        self._ok(_load().clr_sharded_grad_noise_weights(self._h, _ptr(ds), st.ctypes.data_as(_ip)))
+
+    def noise_project_ms(self):
+        """Device time of the projection pass of the last :meth:`grad_noise_weights`: the largest over the shards, which
+        run concurrently (``clr_sharded_get_noise_project_ms``)."""
+        ms = C.c_double()
+        self._ok(_load().clr_sharded_get_noise_project_ms(self._h, C.byref(ms)))
+        return ms.value
+
     def _fit_mean_weights(self, p, w, cov, gram, quad, ld, st):
         self._ok(_load().clr_sharded_fit_mean_weights(self._h, p, _ptr(w), _ptr(cov), _ptr(gram), _ptr(quad), _ptr(ld),
                                                       st.ctypes.data_as(_ip)))
@@ -1657,13 +1786,17 @@ class ShardedBatchedGP(object):
         self.enqueue()
         return self.results()
 
-    def evaluate(self, a_real, c_real, a_comp, b_comp, c_comp, d_comp, jitter=0.0, mean=None, mean_weights=None):
+    def evaluate(self, a_real, c_real, a_comp, b_comp, c_comp, d_comp, jitter=0.0, mean=None, mean_weights=None,
+                 noise_weights=None):
         """One optimiser / MCMC evaluation: new coefficients in, ``(loglike, logdet,
-        quad, status)`` of all B problems out.  ``mean``, ``mean_weights``: as :meth:`BatchedGP.evaluate`
-        (``clr_sharded_evaluate_mean``; :meth:`set_mean_weights` first)."""
+        quad, status)`` of all B problems out.  ``mean``, ``mean_weights``, ``noise_weights``: as
+        :meth:`BatchedGP.evaluate` (``clr_sharded_evaluate_mean``; :meth:`set_mean_weights` / :meth:`set_noise_weights`
+        first)."""
         _exclusive_means(mean, mean_weights)
         if mean_weights is not None:
             self.set_mean_weights(mean_weights)
+        if noise_weights is not None:
+            self.set_noise_weights(noise_weights)
         jit, blocks = self._coeff_blocks(a_real, c_real, a_comp, b_comp, c_comp, d_comp, jitter)
         ll, ld, q, st = self._out()
         if mean is not None:
@@ -1681,12 +1814,14 @@ class ShardedBatchedGP(object):
     def _set_kernel_handle(self, prog):
         self._ok(_load().clr_sharded_set_kernel(self._h, prog._k))
 
-    def evaluate_parameters(self, params, mean=None, mean_weights=None):
+    def evaluate_parameters(self, params, mean=None, mean_weights=None, noise_weights=None):
         """:meth:`BatchedGP.evaluate_parameters` over the shards (``clr_sharded_evaluate_params``): every shard forms the
         coefficients of its slice of ``params`` on its own device."""
         _exclusive_means(mean, mean_weights)
         if mean_weights is not None:
             self.set_mean_weights(mean_weights)
+        if noise_weights is not None:
+            self.set_noise_weights(noise_weights)
         p = self._params_arg(params)
         ll, ld, q, st = self._out()
         m, stride = _mean_arg(mean, self.B)

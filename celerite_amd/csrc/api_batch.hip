@@ -6,6 +6,7 @@
 #include "clr_group_hooks.h"
 #include "clr_kernel.h"
 #include "clr_bmean_kernels.h"
+#include "clr_bnoise_kernels.h"
 
 #include <limits>
 
@@ -396,6 +397,99 @@ int clr_batch_set_mean_weights(clr_batch* h, const double* w) {
   return CLR_OK;
 }
 
+/* ---- a noise model linear in its parameters: clr_batch_set_noise_basis / _set_noise_weights ------------------------ */
+// The variances diag + sum_k s_k Psi_k of clr_batch_set_noise_weights from the caller's diagonal in `diag_src`: one
+// elementwise pass into `diag`, where every route reads its variances (apply_mean's pattern for y); what is derived from
+// `diag` is then stale (variance_replaced).  The weights are per problem, so a shared diagonal becomes B x N variances.
+static int apply_noise(clr_batch* h) {
+  const long N = h->N;
+  int st;
+  if ((st = h->diag.reserve((size_t)h->B * N)) != CLR_OK) return st;
+  const size_t nw = h->host_noise.size();
+  if ((st = h->noise_dev.reserve(nw)) != CLR_OK) return st;
+  // through pinned staging: the copy is asynchronous, and only the previous upload -- not the stream -- is waited for
+  // before the staging is rewritten
+  if (h->noise_ev) HIP_TRY(hipEventSynchronize(h->noise_ev.get()));
+  else HIP_TRY(clr::create_event(h->noise_ev, hipEventDisableTiming));
+  if ((st = h->noise_pin.reserve(nw)) != CLR_OK) return st;
+  std::copy(h->host_noise.begin(), h->host_noise.end(), h->noise_pin.p);
+  HIP_TRY(hipMemcpyAsync(h->noise_dev.p, h->noise_pin.p, nw * sizeof(double), hipMemcpyHostToDevice, h->stream.get()));
+  HIP_TRY(hipEventRecord(h->noise_ev.get(), h->stream.get()));
+  clr::launch_noise_form(h->diag_src.p, h->diag_src_stride, h->noise_basis.p, h->noise_stride, h->noise_dev.p, h->noise_K, h->B,
+                         (int)N, h->diag.p, h->stream.get());
+  // (per-problem lengths: the variances' tail stays the padding 1e300 -- the basis there is never looked at)
+  if (h->ragged) clr::launch_pad_tail(h->diag.p, h->B, (int)N, h->len_dev.p, 2, h->stream.get());
+  HIP_TRY(hipGetLastError());
+  variance_replaced(h, N);
+  return CLR_OK;
+}
+
+int clr_batch_set_noise_basis(clr_batch* h, int K, const double* psi, long psi_stride) {
+  int st = require_device(h->device);
+  if (st != CLR_OK) return st;
+  if (K <= 0 || !psi) {  // remove the noise model: the caller's diagonal is the pipeline's again
+    if (K < 0) return fail(CLR_INVALID_ARGUMENT, "clr_batch_set_noise_basis: K >= 0");
+    if (h->noise_K == 0) return CLR_OK;
+    if ((st = warm_resolve(h, nullptr)) != CLR_OK) return st;  // (an evaluation in flight is settled on ITS variances)
+    h->noise_K = 0;
+    h->host_noise.clear();
+    if (h->have_series) {
+      std::swap(h->diag, h->diag_src);
+      variance_replaced(h, h->diag_src_stride);
+    }
+    return CLR_OK;
+  }
+  if (K > CLR_MAX_NOISE_BASIS) return fail(CLR_INVALID_ARGUMENT, "clr_batch_set_noise_basis: at most CLR_MAX_NOISE_BASIS = 16 basis functions");
+  const size_t per = (size_t)K * (size_t)h->N;
+  if (psi_stride != 0 && psi_stride != (long)per)
+    return fail(CLR_INVALID_ARGUMENT, "clr_batch_set_noise_basis: psi_stride is 0 (psi[K][N], shared) or K * N (psi[B][K][N])");
+  const size_t n = psi_stride ? per * (size_t)h->B : per;
+  // (per-problem lengths in force: a row's tail is never looked at and may hold anything -- of a shared basis the tail past
+  //  the longest problem)
+  const size_t longest = h->ragged ? (size_t)*std::max_element(h->host_len.begin(), h->host_len.end()) : (size_t)h->N;
+  for (size_t r = 0; r < n / (size_t)h->N; ++r) {
+    const size_t len = (h->ragged && psi_stride) ? (size_t)h->host_len[r / (size_t)K] : longest;
+    for (size_t i = 0; i < len; ++i)
+      if (!std::isfinite(psi[r * (size_t)h->N + i])) return fail(CLR_INVALID_ARGUMENT, "clr_batch_set_noise_basis: a non-finite basis entry");
+  }
+  if ((st = warm_resolve(h, nullptr)) != CLR_OK) return st;
+  HIP_TRY(hipStreamSynchronize(h->stream.get()));  // (a forming pass in flight may still read the previous basis)
+  if ((st = h->noise_basis.reserve(n)) != CLR_OK) return st;
+  HIP_TRY(hipMemcpy(h->noise_basis.p, psi, n * sizeof(double), hipMemcpyHostToDevice));
+  if (h->noise_K == 0 && h->have_series) {  // the caller's diagonal moves aside, `diag` will hold the variances
+    std::swap(h->diag, h->diag_src);
+    h->diag_src_stride = h->diag_stride;
+  }
+  h->noise_K = K;
+  h->noise_stride = psi_stride;
+  h->host_noise.assign((size_t)h->B * K, 0.0);  // (a new basis starts from zero weights: the variances are diag)
+  if (!h->have_series) return CLR_OK;  // (clr_batch_set_series applies it)
+  if ((st = apply_noise(h)) != CLR_OK) {
+    h->have_series = false;  // (no half-formed diagonal is ever evaluated: set the series again)
+    return st;
+  }
+  return CLR_OK;
+}
+
+int clr_batch_set_noise_weights(clr_batch* h, const double* w) {
+  int st = require_device(h->device);
+  if (st != CLR_OK) return st;
+  if (h->noise_K == 0) return fail(CLR_INVALID_ARGUMENT, "clr_batch_set_noise_weights: no basis is set (clr_batch_set_noise_basis)");
+  if (!w) return fail(CLR_INVALID_ARGUMENT, "clr_batch_set_noise_weights: s is null");
+  const size_t n = (size_t)h->B * h->noise_K;
+  for (size_t i = 0; i < n; ++i)
+    if (!std::isfinite(w[i])) return fail(CLR_INVALID_ARGUMENT, "clr_batch_set_noise_weights: a non-finite weight");
+  if (memcmp(h->host_noise.data(), w, n * sizeof(double)) == 0) return CLR_OK;  // (the variances in force are these weights')
+  if ((st = warm_resolve(h, nullptr)) != CLR_OK) return st;  // (an evaluation in flight is settled on ITS variances)
+  h->host_noise.assign(w, w + n);
+  if (!h->have_series) return CLR_OK;  // (clr_batch_set_series applies them)
+  if ((st = apply_noise(h)) != CLR_OK) {
+    h->have_series = false;
+    return st;
+  }
+  return CLR_OK;
+}
+
 // clr_batch_set_series and clr_batch_set_series_ragged.  `lengths` (host, [B], may be null): problem b is the first
 // lengths[b] entries of its rows; `ragged`: lengths are in force -- some length of the WHOLE batch differs from N (a
 // slice of a larger batch is told so: clr_group::set_series_lengths).  Everything is checked before the plan changes.
@@ -505,6 +599,11 @@ static int set_series_impl(clr_batch* h, const double* t, long t_stride, const d
     std::swap(h->y, h->y_src);
     h->y_src_stride = y_stride;
     if ((st = apply_mean(h)) != CLR_OK) { h->have_series = false; return st; }
+  }
+  if (h->noise_K > 0) {  // (the upload went to `diag`: it becomes the caller's diagonal, `diag` the variances)
+    std::swap(h->diag, h->diag_src);
+    h->diag_src_stride = diag_stride;
+    if ((st = apply_noise(h)) != CLR_OK) { h->have_series = false; return st; }
   }
   if ((st = warm_scan_spans(h)) != CLR_OK) { h->have_series = false; return st; }
   h->set_series_host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - host_t0).count();

@@ -1,10 +1,11 @@
 // celerite_amd/csrc/api_batch_consumers.hip -- C ABI of the batched plans, second part: the consumers of a plan's factor
 // and coefficients (clr_batch_get_factor, _solve, _dot_L, _dot, _predict, _predict_var, _predict_var_recurrence,
 // _one_step_ahead, _forecast, _predict_terms, _predict_cov, _sample_conditional, _leave_one_out, _grad_mean_weights,
-// _fit_mean_weights) and the helpers they
+// _fit_mean_weights, _grad_noise_weights) and the helpers they
 // share: the factor and route checks, the frame of one call's device work, prediction points and tiles.
 #include "api_internal.h"
 #include "clr_bmean_kernels.h"
+#include "clr_bnoise_kernels.h"
 
 #include <functional>
 #include <limits>
@@ -1313,16 +1314,12 @@ int clr_batch_get_leave_one_out_ms(const clr_batch* h, double* diag_ms, double* 
 // clr_binvdiag_kernels.h on the chunk-interleaved factor (either layout), the chunk maps shared with clr_batch_solve under
 // its validity rule; wide plans (widths 9..64), one wave per problem, sequential in n (wide_invdiag_kernel).  alpha: the
 // batched solve of the residual in force, left row-major in bs_rm.  The sum: one workgroup per problem, no atomics.
-int clr_batch_leave_one_out(clr_batch* h, double* kinv_diag, double* alpha, double* loo_logpdf, int* status) {
-  int st = require_device(h->device);
-  if (st != CLR_OK) return st;
-  if (!kinv_diag && !alpha && !loo_logpdf && !status)
-    return fail(CLR_INVALID_ARGUMENT, "clr_batch_leave_one_out: at least one output array");
-  if ((st = require_celerite_width(h, "clr_batch_leave_one_out")) != CLR_OK) return st;
-  if ((st = require_factor(h, true)) != CLR_OK) return st;
-  if ((st = require_route(h, "clr_batch_leave_one_out")) != CLR_OK) return st;
+// The device parts, behind the caller's checks: c into loo_c (`need_c`) and alpha into bs_rm (`need_alpha`), both row-major
+// [B][N] and left on the device -- clr_batch_grad_noise_weights projects them there; the host arrays that are not null
+// are filled, the sum only when loo_logpdf is asked for.
+static int leave_one_out_device(clr_batch* h, bool need_c, bool need_alpha, double* kinv_diag, double* alpha, double* loo_logpdf) {
+  int st;
   const size_t B = (size_t)h->B, N = (size_t)h->N, J = (size_t)h->J;
-  const bool need_c = kinv_diag || loo_logpdf, need_alpha = alpha || loo_logpdf;
   for (clr::Event& e : h->loo_ev)
     if (!e) HIP_TRY(clr::create_event(e));
   h->loo_diag_ms = h->loo_solve_ms = h->loo_reduce_ms = 0.0;
@@ -1379,7 +1376,71 @@ int clr_batch_leave_one_out(clr_batch* h, double* kinv_diag, double* alpha, doub
       h->loo_reduce_ms = ms;
     }
   }
+  return CLR_OK;
+}
+
+int clr_batch_leave_one_out(clr_batch* h, double* kinv_diag, double* alpha, double* loo_logpdf, int* status) {
+  int st = require_device(h->device);
+  if (st != CLR_OK) return st;
+  if (!kinv_diag && !alpha && !loo_logpdf && !status)
+    return fail(CLR_INVALID_ARGUMENT, "clr_batch_leave_one_out: at least one output array");
+  if ((st = require_celerite_width(h, "clr_batch_leave_one_out")) != CLR_OK) return st;
+  if ((st = require_factor(h, true)) != CLR_OK) return st;
+  if ((st = require_route(h, "clr_batch_leave_one_out")) != CLR_OK) return st;
+  if ((st = leave_one_out_device(h, kinv_diag || loo_logpdf, alpha || loo_logpdf, kinv_diag, alpha, loo_logpdf)) != CLR_OK) return st;
+  const size_t N = (size_t)h->N;
   return nan_rows_without_factor(h, {{kinv_diag, N}, {alpha, N}, {loo_logpdf, 1}}, status);
+}
+
+// ---- clr_batch_grad_noise_weights: the gradient with respect to the weights of a linear noise model
+
+// d loglike / d s[b][k] = 1/2 sum_n Psi_k[b][n] (alpha_n^2 - c_n), alpha = K_b^-1 r_b and c = diag(K_b^-1): d K / d s_k is
+// the diagonal matrix Psi_k, so the partial is 1/2 alpha^T Psi_k alpha - 1/2 tr(K^-1 Psi_k).  Leave-one-out's two device
+// parts (the diagonal's recurrence, the solve of the residual) leave c and alpha row-major in HBM; one projection pass
+// onto the resident basis follows (clr_bnoise_kernels.h).  The gradient sweeps are not involved.
+int clr_batch_grad_noise_weights(clr_batch* h, double* ds, int* status) {
+  static const char* entry = "clr_batch_grad_noise_weights";
+  int st = require_device(h->device);
+  if (st != CLR_OK) return st;
+  if (h->noise_K == 0) return fail(CLR_INVALID_ARGUMENT, std::string(entry) + ": no basis is set (clr_batch_set_noise_basis)");
+  if (!ds) return fail(CLR_INVALID_ARGUMENT, std::string(entry) + ": an output array");
+  if ((st = require_celerite_width(h, entry)) != CLR_OK) return st;
+  if ((st = require_factor(h, true)) != CLR_OK) return fail(st, std::string(entry) + ": " + g_last_error);
+  if (h->variance_changed)
+    return fail(CLR_NOT_COMPUTED, std::string(entry) + ": the noise basis, the noise weights or the series were replaced after the "
+                                  "materialising run whose factor is in HBM -- that factor is another matrix': materialise again "
+                                  "(clr_batch_enqueue(h, 1))");
+  if ((st = require_route(h, entry)) != CLR_OK) return st;
+  if ((st = leave_one_out_device(h, true, true, nullptr, nullptr, nullptr)) != CLR_OK) return fail(st, std::string(entry) + ": " + g_last_error);
+  const size_t B = (size_t)h->B, K = (size_t)h->noise_K;
+  if ((st = h->proj_part.reserve(clr::mean_project_workspace(h->B, h->N, h->noise_K))) != CLR_OK) return st;
+  if ((st = h->proj_out.reserve(B * K)) != CLR_OK) return st;
+  for (clr::Event& e : h->proj_ev)
+    if (!e) HIP_TRY(clr::create_event(e));
+  {
+    ConsumerFrame frame{h};  // (untimed: the projection has its own events)
+    HIP_TRY(hipEventRecord(h->proj_ev[0].get(), h->stream.get()));
+    if (!clr::launch_noise_project(h->noise_basis.p, h->noise_stride, h->bs_rm.p, h->loo_c.p, h->noise_K, h->B, h->N,
+                                   h->proj_part.p, h->proj_out.p, h->stream.get()))
+      return fail(CLR_UNSUPPORTED, std::string(entry) + ": B x N / 4096 workgroups do not fit one launch");
+    HIP_TRY(hipEventRecord(h->proj_ev[1].get(), h->stream.get()));
+    if ((st = frame.finish(ds, h->proj_out.p, B * K)) != CLR_OK) return st;
+  }
+  float ms = 0.f;
+  HIP_TRY(hipEventElapsedTime(&ms, h->proj_ev[0].get(), h->proj_ev[1].get()));
+  h->noise_project_ms = ms;
+  // the statuses of the evaluation in force; a problem without a factor (or refused by the kernel program): zeros
+  std::vector<int> stat;
+  if ((st = evaluation_statuses(h, stat)) != CLR_OK) return st;
+  for (size_t b = 0; b < B; ++b)
+    if (stat[b] != CLR_OK) std::fill(ds + b * K, ds + (b + 1) * K, 0.0);  // (the gradient's quiet semantics)
+  if (status) std::copy(stat.begin(), stat.end(), status);
+  return CLR_OK;
+}
+
+int clr_batch_get_noise_project_ms(const clr_batch* h, double* device_ms) {
+  if (device_ms) *device_ms = h->noise_project_ms;
+  return CLR_OK;
 }
 
 // ---- clr_batch_fit_mean_weights: the generalised-least-squares fit of a linear mean's weights

@@ -2,7 +2,7 @@
 //   api_misc.hip    library / device entries, the CARMA handle
 //   api_solver.hip  clr_solver_*: the object API (one problem per handle)
 //   api_batch.hip   clr_batch_*: plans, HBM residency, path selection, evaluation, results
-//   api_batch_consumers.hip  clr_batch_*: the consumers of a plan's factor and coefficients (solve .. fit_mean_weights)
+//   api_batch_consumers.hip  clr_batch_*: the consumers of a plan's factor and coefficients (solve .. grad_noise_weights)
 //   api_grad.hip    clr_batch_grad*: the gradient entry points
 //   api_kernels.hip the small kernels the plans launch themselves (finalize, relayouts, factor de-interleave)
 // Here: error reporting, the device buffer types, the two handle structs, and the functions that turn a plan's state into
@@ -222,6 +222,7 @@ struct SeriesCopy {
   DevBuf T, D, Y;
   bool stale = true;     // the arrays, or the chunking the copy follows, changed since it was built (or it never was)
   bool y_stale = false;  // the scan's copy only: the residual y alone changed -- Y alone is rebuilt
+  bool d_stale = false;  // ... the variances alone changed (variance_replaced) -- D alone is rebuilt
 };
 
 struct clr_batch {
@@ -286,6 +287,20 @@ struct clr_batch {
   std::vector<char> kp_refused;       // [B] draws of the last clr_batch_set_parameters the program refused
   clr::PinnedBuffer<double> mean_pin; // pinned staging of the mean's upload ...
   clr::Event mean_ev;                 // ... recorded behind it: the staging is rewritten only once the copy has run
+  // clr_batch_set_noise_basis / _set_noise_weights: a noise model linear in its parameters, diag_eff = diag + sum_k s[b][k]
+  // Psi_k (noise_K > 0).  `diag` holds diag_eff, which every route reads, and `diag_src` the caller's diagonal as uploaded
+  // (diag_src_stride: its stride) -- the y / y_src pattern of the mean; the weights go up through noise_pin into
+  // noise_dev; the basis stays resident.  clr_batch_grad_noise_weights shares proj_part / proj_out / proj_ev with the mean's
+  // projection (one call at a time uses them)
+  int noise_K = 0;
+  long noise_stride = 0;              // 0: one basis [K][N] for all problems, K * N: [B][K][N]
+  std::vector<double> host_noise;     // [B][K] (zero until clr_batch_set_noise_weights)
+  DevBuf noise_basis, noise_dev, diag_src;
+  long diag_src_stride = 0;
+  clr::PinnedBuffer<double> noise_pin;
+  clr::Event noise_ev;
+  double noise_project_ms = 0.0;      // device time of the last clr_batch_grad_noise_weights' projection
+  bool variance_changed = false;      // the variances in `diag` were replaced since the last materialising run (its factor is another matrix')
   // clr_batch_grad_mean: the narrow reverse sweep sums the adjoint of y per chunk (BatchParams::g_ysum) and reduces it
   // into mean_out; grad_mean_done[b] says which problems it settled (the rest take mean_partial_batch)
   bool grad_want_mean = false;
@@ -433,6 +448,7 @@ namespace {
 void factor_written(clr_batch* h, bool lean) {
   h->factor_is_lean = lean; h->factor_inputs_changed = false; h->factor_valid = true; h->bs_M_valid = false;
   h->pv_S_valid = h->loo_Q_valid = false;
+  h->variance_changed = false;
 }
 // the factor's layout in HBM no longer is the one a materialising run would write (chunking, factor layout)
 void factor_dropped(clr_batch* h) { h->have_factor = h->factor_valid = false; }
@@ -452,6 +468,19 @@ void residual_replaced(clr_batch* h, long y_stride) {
   h->y_stride = y_stride;
   h->scan_series.y_stale = true;
   h->warm_series.stale = h->small_series.stale = true;
+}
+// `diag` holds other variances, of stride `diag_stride` (noise weights or a noise basis set, changed or removed): of the
+// scan's copy D alone is rebuilt unless the stride changed (a shared diagonal became per-problem variances, or back); the
+// warm and the one-launch copies are rebuilt whole; the factor in HBM is another matrix' (a lean one can no longer be
+// expanded, clr_batch_grad_noise_weights asks for a new run).  Nothing derived from t alone -- the series' statistics and
+// selection bounds, the warm path's spans and selection, the gradient's spans -- reads `diag`, and all of it stays.
+void variance_replaced(clr_batch* h, long diag_stride) {
+  if (diag_stride != h->diag_stride) h->scan_series.stale = true;
+  h->diag_stride = diag_stride;
+  h->scan_series.d_stale = true;
+  h->warm_series.stale = h->small_series.stale = true;
+  h->factor_inputs_changed = true;
+  h->variance_changed = true;
 }
 // nchunk and L changed: the scan's copy, the gradient's spans and the factor's layout follow them
 void chunking_replaced(clr_batch* h) {
@@ -691,18 +720,19 @@ int batch_params(clr_batch* h, int materialize, clr::BatchParams& P, bool behind
 }
 
 // Row-major API layout -> the chunk-interleaved copy the scan reads (sized by batch_params), if it is stale or
-// `regardless`: 3 tiled transposes, Y alone when only the residual changed.  Returns whether the rebuild was queued: a
-// copy that no route reads is not built and STAYS stale -- the need for it can appear later (a new coefficient draw can
-// switch the summarize kernel, another evaluation can take another route) with the series unchanged.
+// `regardless`: 3 tiled transposes, Y alone when only the residual changed, D alone when only the variances did.  Returns
+// whether the rebuild was queued: a copy that no route reads is not built and STAYS stale -- the need for it can appear
+// later (a new coefficient draw can switch the summarize kernel, another evaluation can take another route) with the
+// series unchanged.
 bool build_scan_series(clr_batch* h, bool regardless) {
   SeriesCopy& c = h->scan_series;
-  if (!(regardless || c.stale || c.y_stale) || !scan_reads_copy(h)) return false;
-  const bool y_only = !regardless && !c.stale;
+  if (!(regardless || c.stale || c.y_stale || c.d_stale) || !scan_reads_copy(h)) return false;
+  const bool all = regardless || c.stale;
   const SeriesJobs jobs(h, c, (size_t)h->nchunk * h->L);
   for (auto& j : jobs.job)
-    if (!y_only || j.dst == &c.Y)
+    if (all || (c.y_stale && j.dst == &c.Y) || (c.d_stale && j.dst == &c.D))
       clr::launch_relayout(j.src, j.stride, j.dst->p, j.dst_stride, j.nsrc, h->N, h->L, h->nchunk, j.pad, h->stream.get());
-  c.stale = c.y_stale = false;
+  c.stale = c.y_stale = c.d_stale = false;
   return true;
 }
 

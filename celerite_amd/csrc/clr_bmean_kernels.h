@@ -27,7 +27,7 @@
 namespace clr {
 
 constexpr int CLR_MAX_MEAN_RHS = 17;  // CLR_MAX_MEAN_BASIS basis functions and the residual
-constexpr int CLR_MEAN_SLAB = 4096;  // samples per workgroup of mean_project_kernel (fixed: see above)
+constexpr int CLR_MEAN_SLAB = 4096;  // samples per workgroup of slab_project_kernel (fixed: see above)
 
 // slabs per problem, and the doubles of `partial` launch_mean_project needs
 inline long mean_project_slabs(int N) { return ((long)N + CLR_MEAN_SLAB - 1) / CLR_MEAN_SLAB; }
@@ -41,6 +41,62 @@ void launch_linear_residual(const double* y, long y_stride, const double* phi, l
 // B x slabs does not fit a grid.
 bool launch_mean_project(const double* phi, long phi_stride, const double* z, int K, int B, int N, double* partial,
                          double* g, hipStream_t s);
+
+// The projection's reduction, shared by every pass of the shape g[b][k] = sum_n phi_k[b][n] f(b N + n): mean_project takes
+// f = z (mean_kernels.hip), the noise model's gradient f = 1/2 (alpha^2 - c) (noise_kernels.hip).  One workgroup per
+// (problem, slab): thread i takes the samples i, i + 256, ... of the slab in order, K running sums in registers (KT: the
+// instantiation's register count, K <= KT); then the shuffle tree of each wave, the four waves in order through LDS.  A
+// ragged last slab adds nothing for n >= N.
+template <int KT, class Factor>
+__global__ void __launch_bounds__(256) slab_project_kernel(const double* __restrict__ phi, long phi_stride, const Factor f,
+                                                           int K, int N, long nslab, double* __restrict__ partial) {
+  __shared__ double sh[4][KT];
+  const long b = blockIdx.x / nslab, slab = blockIdx.x % nslab;
+  const long row = b * (long)N;
+  const double* pb = phi + b * phi_stride;
+  double acc[KT];
+#pragma unroll
+  for (int k = 0; k < KT; ++k) acc[k] = 0.0;
+  const long n0 = slab * CLR_MEAN_SLAB + threadIdx.x;
+#pragma unroll 4
+  for (int i = 0; i < CLR_MEAN_SLAB / 256; ++i) {
+    const long n = n0 + i * 256;
+    if (n < N) {
+      const double zn = f(row + n);
+#pragma unroll
+      for (int k = 0; k < KT; ++k)
+        if (k < K) acc[k] = fma(pb[(long)k * N + n], zn, acc[k]);
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < KT; ++k)
+    if (k < K)
+      for (int off = 32; off > 0; off >>= 1) acc[k] += __shfl_down(acc[k], off, 64);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < KT; ++k)
+      if (k < K) sh[wave][k] = acc[k];
+  }
+  __syncthreads();
+  const int k = threadIdx.x;
+  if (k < K) partial[((long)blockIdx.x) * K + k] = ((sh[0][k] + sh[1][k]) + sh[2][k]) + sh[3][k];
+}
+// g[b][k] = the slabs' partials [B][slabs][K] added in slab order (mean_kernels.hip: mean_project_finish_kernel)
+void launch_slab_project_finish(const double* partial, int K, int B, int N, double* g, hipStream_t s);
+// the two launches; false (nothing launched) when B x slabs does not fit a grid
+template <class Factor>
+bool launch_slab_project(const double* phi, long phi_stride, const Factor& f, int K, int B, int N, double* partial, double* g,
+                         hipStream_t s) {
+  const long nslab = mean_project_slabs(N), blocks = (long)B * nslab;
+  if (blocks > 2147483647L) return false;
+  const dim3 grid((unsigned)blocks), block(256);
+  if (K <= 4) hipLaunchKernelGGL((slab_project_kernel<4, Factor>), grid, block, 0, s, phi, phi_stride, f, K, N, nslab, partial);
+  else if (K <= 8) hipLaunchKernelGGL((slab_project_kernel<8, Factor>), grid, block, 0, s, phi, phi_stride, f, K, N, nslab, partial);
+  else hipLaunchKernelGGL((slab_project_kernel<16, Factor>), grid, block, 0, s, phi, phi_stride, f, K, N, nslab, partial);
+  launch_slab_project_finish(partial, K, B, N, g, s);
+  return true;
+}
 
 
 // ---- clr_batch_fit_mean_weights

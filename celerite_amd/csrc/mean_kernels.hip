@@ -32,45 +32,11 @@ __global__ void __launch_bounds__(256) linear_residual_kernel(const double* __re
   }
 }
 
-// One workgroup per (problem, slab): thread i takes the samples i, i + 256, ... of the slab in order, K running sums in
-// registers (KT: the instantiation's register count, K <= KT); then the shuffle tree of each wave, the four waves in
-// order through LDS.  A ragged last slab adds nothing for n >= N.
-template <int KT>
-__global__ void __launch_bounds__(256) mean_project_kernel(const double* __restrict__ phi, long phi_stride,
-                                                           const double* __restrict__ z, int K, int N, long nslab,
-                                                           double* __restrict__ partial) {
-  __shared__ double sh[4][KT];
-  const long b = blockIdx.x / nslab, slab = blockIdx.x % nslab;
-  const double* zb = z + b * (long)N;
-  const double* pb = phi + b * phi_stride;
-  double acc[KT];
-#pragma unroll
-  for (int k = 0; k < KT; ++k) acc[k] = 0.0;
-  const long n0 = slab * CLR_MEAN_SLAB + threadIdx.x;
-#pragma unroll 4
-  for (int i = 0; i < CLR_MEAN_SLAB / 256; ++i) {
-    const long n = n0 + i * 256;
-    if (n < N) {
-      const double zn = zb[n];
-#pragma unroll
-      for (int k = 0; k < KT; ++k)
-        if (k < K) acc[k] = fma(pb[(long)k * N + n], zn, acc[k]);
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < KT; ++k)
-    if (k < K)
-      for (int off = 32; off > 0; off >>= 1) acc[k] += __shfl_down(acc[k], off, 64);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < KT; ++k)
-      if (k < K) sh[wave][k] = acc[k];
-  }
-  __syncthreads();
-  const int k = threadIdx.x;
-  if (k < K) partial[((long)blockIdx.x) * K + k] = ((sh[0][k] + sh[1][k]) + sh[2][k]) + sh[3][k];
-}
+// the per-sample factor of clr_batch_grad_mean_weights' projection (slab_project_kernel, clr_bmean_kernels.h): z = K^-1 r
+struct SolveFactor {
+  const double* z;
+  __device__ double operator()(long i) const { return z[i]; }
+};
 
 // g[b][k] = the slabs' partials added in slab order: one thread per (problem, k)
 __global__ void __launch_bounds__(256) mean_project_finish_kernel(const double* __restrict__ partial, long nslab, int K,
@@ -117,7 +83,7 @@ __global__ void __launch_bounds__(256) fit_rhs_rowmajor_kernel(FitRhs R, int c0,
   for (long n = (long)blockIdx.x * 256 + threadIdx.x; n < R.N; n += (long)gridDim.x * 256) out[n] = in[n];
 }
 
-// mean_project_kernel with the K + 1 right-hand sides in the place of the basis: the workgroup (slab, column k, problem
+// slab_project_kernel (clr_bmean_kernels.h) with the K + 1 right-hand sides in the place of the basis: the workgroup (slab, column k, problem
 // b) sums R_j Z_k over its slab for j = 0 .. K (KT: the instantiation's register count, K + 1 <= KT).  partial:
 // [b][slab][k][j].
 template <int KT>
@@ -227,14 +193,13 @@ void launch_linear_residual(const double* y, long y_stride, const double* phi, l
 
 bool launch_mean_project(const double* phi, long phi_stride, const double* z, int K, int B, int N, double* partial,
                          double* g, hipStream_t s) {
-  const long nslab = mean_project_slabs(N), blocks = (long)B * nslab, BK = (long)B * K;
-  if (blocks > 2147483647L) return false;
-  const dim3 grid((unsigned)blocks), block(256);
-  if (K <= 4) hipLaunchKernelGGL(mean_project_kernel<4>, grid, block, 0, s, phi, phi_stride, z, K, N, nslab, partial);
-  else if (K <= 8) hipLaunchKernelGGL(mean_project_kernel<8>, grid, block, 0, s, phi, phi_stride, z, K, N, nslab, partial);
-  else hipLaunchKernelGGL(mean_project_kernel<16>, grid, block, 0, s, phi, phi_stride, z, K, N, nslab, partial);
-  hipLaunchKernelGGL(mean_project_finish_kernel, dim3((unsigned)((BK + 255) / 256)), block, 0, s, partial, nslab, K, BK, g);
-  return true;
+  return launch_slab_project(phi, phi_stride, SolveFactor{z}, K, B, N, partial, g, s);
+}
+
+void launch_slab_project_finish(const double* partial, int K, int B, int N, double* g, hipStream_t s) {
+  const long BK = (long)B * K;
+  hipLaunchKernelGGL(mean_project_finish_kernel, dim3((unsigned)((BK + 255) / 256)), dim3(256), 0, s, partial,
+                     mean_project_slabs(N), K, BK, g);
 }
 
 }  // namespace clr

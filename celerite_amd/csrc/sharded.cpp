@@ -26,6 +26,7 @@
 // A device may be listed more than once: the shards then share that GPU.  That is how the
 // sharding is tested on a one-GPU box (tests/test_gpu_batch.py: 1, 2, 3, 8 shards must give
 // bit-identical results).
+#include <algorithm>
 #include <cmath>
 #include <condition_variable>
 #include <functional>
@@ -104,6 +105,7 @@ struct clr_sharded {
   int B = 0, N = 0, J_real = 0, J_comp = 0;
   int n_params = 0;  // of the kernel set by clr_sharded_set_kernel
   int mean_K = 0;    // of the basis set by clr_sharded_set_mean_basis
+  int noise_K = 0;   // of the basis set by clr_sharded_set_noise_basis
   std::vector<int> device, lo, hi;
   std::vector<clr_batch*> plan;
   std::vector<std::unique_ptr<Worker>> worker;
@@ -610,6 +612,65 @@ int clr_sharded_grad_mean_weights(clr_sharded* h, double* dw, int* status) {
   return on_slices(h, K > 0 && dw, [=](clr_batch* p, long lo) {
     return clr_batch_grad_mean_weights(p, dw + lo * K, status ? status + lo : nullptr);
   });
+}
+
+/* ---- a linear noise model: clr_batch_set_noise_basis / _set_noise_weights / _grad_noise_weights over the shards ---- */
+int clr_sharded_set_noise_basis(clr_sharded* h, int K, const double* psi, long psi_stride) {
+  const bool remove = K == 0 || !psi;
+  const long per = (long)K * h->N;
+  if (!remove) {  // (checked here: an invalid basis leaves EVERY shard unchanged)
+    g_sharded_error = "clr_sharded_set_noise_basis: 1 <= K <= CLR_MAX_NOISE_BASIS = 16, psi_stride 0 or K * N, finite entries";
+    if (K < 0 || K > CLR_MAX_NOISE_BASIS || (psi_stride != 0 && psi_stride != per)) return CLR_INVALID_ARGUMENT;
+    // the lengths in force (N for every problem of a uniform batch, or before a series is set): a row's tail is never
+    // looked at -- of the one shared basis the tail past the longest problem OF THE BATCH
+    std::vector<int> len((size_t)h->B, h->N);
+    for (size_t s = 0; s < h->plan.size(); ++s) (void)clr_batch_get_lengths(h->plan[s], len.data() + h->lo[s]);
+    const int longest = *std::max_element(len.begin(), len.end());
+    const long rows = psi_stride ? (long)K * h->B : K;
+    for (long r = 0; r < rows; ++r) {
+      const int upto = psi_stride ? len[(size_t)(r / K)] : longest;
+      for (int i = 0; i < upto; ++i)
+        if (!std::isfinite(psi[r * h->N + i])) return CLR_INVALID_ARGUMENT;
+    }
+  }
+  int st = resolve_all(h);  // (an evaluation in flight is settled on ITS variances)
+  if (st != CLR_OK) return st;
+  st = h->all([=](int s) {
+    return clr_batch_set_noise_basis(h->plan[s], remove ? 0 : K, remove ? nullptr : psi + h->lo[s] * psi_stride, psi_stride);
+  });
+  if (st == CLR_OK) h->noise_K = remove ? 0 : K;
+  return st;
+}
+
+int clr_sharded_set_noise_weights(clr_sharded* h, const double* w) {
+  const long K = h->noise_K;
+  g_sharded_error = "clr_sharded_set_noise_weights: a basis must be set (clr_sharded_set_noise_basis) and the weights finite";
+  if (K == 0 || !w) return CLR_INVALID_ARGUMENT;
+  for (long i = 0; i < K * h->B; ++i)
+    if (!std::isfinite(w[i])) return CLR_INVALID_ARGUMENT;
+  const int st = resolve_all(h);
+  if (st != CLR_OK) return st;
+  return h->all([=](int s) { return clr_batch_set_noise_weights(h->plan[s], w + h->lo[s] * K); });
+}
+
+int clr_sharded_grad_noise_weights(clr_sharded* h, double* ds, int* status) {
+  const long K = h->noise_K;
+  g_sharded_error = "clr_sharded_grad_noise_weights: a basis must be set (clr_sharded_set_noise_basis), and an output array";
+  return on_slices(h, K > 0 && ds, [=](clr_batch* p, long lo) {
+    return clr_batch_grad_noise_weights(p, ds + lo * K, status ? status + lo : nullptr);
+  });
+}
+
+// the projection's device time: the largest over the shards, which run concurrently
+int clr_sharded_get_noise_project_ms(const clr_sharded* h, double* device_ms) {
+  double m = 0.0;
+  for (clr_batch* p : h->plan) {
+    double v = 0.0;
+    (void)clr_batch_get_noise_project_ms(p, &v);
+    m = std::max(m, v);
+  }
+  if (device_ms) *device_ms = m;
+  return CLR_OK;
 }
 
 // clr_batch_fit_mean_weights, every shard on its slice (a problem's fit does not depend on the sharding)

@@ -275,7 +275,8 @@ int clr_batch_set_series(clr_batch* h,
  *   What refuses (CLR_UNSUPPORTED, "the plan has per-problem lengths"; the plan still evaluates afterwards): wide plans
  *   (widths above 8) and plans with general terms, every materialising run, and every consumer of the materialised
  *   factor or of the padded rows: clr_batch_get_factor, _solve, _dot_L, _dot, _predict*, _one_step_ahead, _forecast,
- *   _predict_terms, _predict_cov, _sample_conditional, _leave_one_out, _grad_mean_weights, _fit_mean_weights.
+ *   _predict_terms, _predict_cov, _sample_conditional, _leave_one_out, _grad_mean_weights, _fit_mean_weights,
+ *   _grad_noise_weights.
  * clr_batch_get_lengths: the lengths in force (N for every problem of a uniform plan). */
 int clr_batch_set_series_ragged(clr_batch* h,
                                 const double* t, long t_stride,
@@ -546,6 +547,47 @@ int clr_batch_set_mean_basis(clr_batch* h, int K, const double* phi, long phi_st
 int clr_batch_set_mean_weights(clr_batch* h, const double* w);
 int clr_batch_grad_mean_weights(clr_batch* h, double* dw, int* status);
 int clr_batch_get_mean_project_ms(const clr_batch* h, double* device_ms);
+/* A noise model that is LINEAR IN ITS PARAMETERS: the variances every route reads become
+ *     diag_eff[p][n] = diag[p][n] + sum_k s[p][k] Psi_k[p][n] ,   K <= CLR_MAX_NOISE_BASIS basis functions,
+ * with the plan's scalar jitter added on top as before -- a jitter per instrument (diag = sigma^2, Psi_g the indicator of
+ * instrument g, s_g its jitter^2), an error-bar inflation f^2 sigma^2 (Psi_0 = sigma^2, s_0 = f^2 - 1), a noise level per
+ * observing season.  The caller evaluates the basis once; the plan keeps it in HBM, and an optimiser or sampler step sends
+ * B x K weights instead of a new diagonal through clr_batch_set_series.
+ *
+ * clr_batch_set_noise_basis -- psi is host [K][N] with psi_stride == 0 (one basis for all problems) or [B][K][N] with
+ * psi_stride == K * N; uploaded once.  The weights start at zero (the plan is the plain plan), also when a basis replaces
+ * another.  K == 0 or psi == NULL removes the noise model and restores the caller's diagonal.  CLR_INVALID_ARGUMENT, the
+ * plan unchanged: a non-finite entry (with per-problem lengths in force: within a problem's length), K >
+ * CLR_MAX_NOISE_BASIS, another stride.  Before or after clr_batch_set_series: a later clr_batch_set_series /
+ * _set_series_ragged keeps basis and weights in force and applies them to the new diagonal.
+ *
+ * clr_batch_set_noise_weights -- s is host [B][K].  Every route that reads the diagonal -- the evaluation on each of its
+ * routes, the materialising runs, the gradient, the rescue side plan -- then sees
+ *     diag_eff = diag + m ,   m = s[p][0] Psi_0[n] ,  m = m + s[p][k] Psi_k[n]  (k = 1 .. K - 1, in this order),
+ * every product and sum rounded on its own (no FMA): the bits of NumPy's diag + (s_0 * Psi_0 + s_1 * Psi_1 + ...).  It is
+ * formed on the device by one elementwise pass over the caller's diagonal, which stays in HBM untouched (a shared
+ * diagonal becomes B x N variances); with per-problem lengths the tail of a row stays padding and Psi's tail is never
+ * looked at.  Nothing derived from t alone is rebuilt.  The weights and the basis need only be finite: a variance that
+ * comes out non-positive shows in the problem's status, as for a bad diag.  The factor of an earlier materialising run
+ * is that of the earlier variances.  Weights equal to the ones in force: nothing is done.  CLR_INVALID_ARGUMENT: a
+ * non-finite weight, or no basis set.
+ *
+ * clr_batch_grad_noise_weights -- ds host [B][K],
+ *     ds[p][k] = d loglike_p / d s[p][k] = 1/2 sum_n Psi_k[p][n] (alpha_n^2 - c_n) ,  alpha = K_p^-1 r_p ,  c = diag(K_p^-1),
+ * from the factor of a materialising run MADE AFTER the weights (and the basis, and the series) were set: CLR_NOT_COMPUTED
+ * without one, or when any of them changed since -- materialise again.  It runs clr_batch_leave_one_out's two device
+ * parts (the diagonal's recurrence, the solve of the residual) and one projection pass onto the resident basis --
+ * workgroups over fixed slabs of 4096 samples, their partials added in order, no atomics: the same bits on every run, for
+ * any batch size and any sharding.  status (may be NULL) receives the statuses of the evaluation in force; a problem whose
+ * status is not CLR_OK gets a row of zeros.  clr_batch_leave_one_out's domain (its refusals otherwise, naming this
+ * entry): celerite-only plans of widths 1..64, narrow plans chunked, wide plans N >= 512, no per-problem lengths.
+ * clr_batch_get_leave_one_out_ms then reports the device time of the diagonal and the solve,
+ * clr_batch_get_noise_project_ms the projection's. */
+#define CLR_MAX_NOISE_BASIS 16
+int clr_batch_set_noise_basis(clr_batch* h, int K, const double* psi, long psi_stride);
+int clr_batch_set_noise_weights(clr_batch* h, const double* s);
+int clr_batch_grad_noise_weights(clr_batch* h, double* ds, int* status);
+int clr_batch_get_noise_project_ms(const clr_batch* h, double* device_ms);
 /* clr_batch_fit_mean_weights -- the weights that MAXIMISE the log-likelihood of every problem at the coefficients in
  * force.  The log-likelihood is exactly quadratic in the weights, so they need no optimiser: with r = y - Phi w0 the
  * residual at the weights w0 in force,
@@ -1008,6 +1050,13 @@ int clr_sharded_grad_mean(clr_sharded* h, double* value, double* grad, double* d
 int clr_sharded_set_mean_basis(clr_sharded* h, int K, const double* phi, long phi_stride);
 int clr_sharded_set_mean_weights(clr_sharded* h, const double* w);
 int clr_sharded_grad_mean_weights(clr_sharded* h, double* dw, int* status);
+/* The linear noise model over the shards (clr_batch_set_noise_basis / _set_noise_weights / _grad_noise_weights): every
+ * shard takes its slice of psi (psi_stride K * N) or the one basis (0), of s[B][K] and of ds[B][K]; an invalid basis or
+ * weight leaves every shard unchanged.  The results are those of the unsharded plan, bit for bit. */
+int clr_sharded_set_noise_basis(clr_sharded* h, int K, const double* psi, long psi_stride);
+int clr_sharded_set_noise_weights(clr_sharded* h, const double* s);
+int clr_sharded_grad_noise_weights(clr_sharded* h, double* ds, int* status);
+int clr_sharded_get_noise_project_ms(const clr_sharded* h, double* device_ms);  /* the largest over the shards */
 /* clr_batch_fit_mean_weights over the whole batch: every shard fits its slice; the same bits as the unsharded plan */
 int clr_sharded_fit_mean_weights(clr_sharded* h, double min_pivot, double* w_hat, double* cov, double* gram,
                                  double* quad_profiled, double* logdet_gram, int* status);
