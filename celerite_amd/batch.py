@@ -58,6 +58,7 @@ def _load():
     lib.clr_batch_set_layout.argtypes = [C.c_void_p, C.c_int]
     lib.clr_batch_set_summarize_mode.argtypes = [C.c_void_p, C.c_int]
     lib.clr_batch_get_summarize_kernel.argtypes = [C.c_void_p, _ip]
+    lib.clr_batch_get_split_variant.argtypes = [C.c_void_p, _ip]
     lib.clr_batch_fp32_probe.argtypes = [C.c_void_p, _dp, _dp, _dp]
     lib.clr_batch_set_profiling.argtypes = [C.c_void_p, C.c_int]
     lib.clr_batch_get_profile.argtypes = [C.c_void_p, _dp, _ip]
@@ -1510,6 +1511,14 @@ class BatchedGP(object):
         k = C.c_int()
         _check(_load().clr_batch_get_summarize_kernel(self._h, C.byref(k)))
         return ("single wave", "role split", "role split, lazy decay")[k.value]
+
+    def split_variant(self):
+        """The variant of the lazy role-split summarize the next evaluation runs: ``dict(b_zero=...)``, true for the
+        kernel without the ``b_comp`` terms, false for the general one and any other kernel
+        (``clr_batch_get_split_variant``)."""
+        v = C.c_int()
+        _check(_load().clr_batch_get_split_variant(self._h, C.byref(v)))
+        return dict(b_zero=bool(v.value & 1))
 
     def fp32_probe(self):
         """``(logdet, quad, ms)`` of the sequential sweep with a float state (widths 9..32;

@@ -714,10 +714,12 @@ int clr_batch_set_coefficients(clr_batch* h, const double* jitter, const double*
   const size_t B = (size_t)h->B, nr = B * h->J_real, nc = B * h->J_comp;
   h->dmax = 0.0;
   h->cmax = 0.0;
+  h->b_zero = true;
   for (size_t i = 0; i < nc; ++i) {
     const double m = fabs(d_comp[i]), c = fabs(c_comp[i]);
     if (!(m <= h->dmax)) h->dmax = m;
     if (!(c <= h->cmax)) h->cmax = c;
+    if (!(b_comp[i] == 0.0)) h->b_zero = false;
   }
   for (size_t i = 0; i < nr; ++i) {
     const double c = fabs(c_real[i]);
@@ -803,6 +805,7 @@ int clr_batch_set_parameters(clr_batch* h, const double* params) {
   HIP_TRY(hipStreamSynchronize(h->stream.get()));
   h->dmax = 0.0;
   h->cmax = 0.0;
+  h->b_zero = false;  // (the program's statistics do not say: the general features)
   for (size_t b = 0; b < B; ++b) {
     const double m = s[clr::KP_STAT_DMAX * B + b], c = s[clr::KP_STAT_CMAX * B + b];
     if (!(m <= h->dmax)) h->dmax = m;
@@ -1143,6 +1146,12 @@ int clr_batch_get_summarize_kernel(const clr_batch* h, int* kind) {
   if (!h->launch)  // wide plans: plain or lazy flavour of the one-wave-per-chunk summarize
     *kind = (h->nchunk > 1 && (h->summarize_mode < 0 || h->summarize_mode == 2) &&
              (h->J_general > 0 ? lazy_eligible(h) : lazy_eligible_wide(h))) ? 2 : 0;
+  return CLR_OK;
+}
+
+int clr_batch_get_split_variant(const clr_batch* h, int* variant) {
+  if (!variant) return fail(CLR_INVALID_ARGUMENT, "variant is null");
+  *variant = (split_active(h, false) && h->summarize_mode != 1 && lazy_eligible(h)) ? (split_lazy_bzero(h) ? 1 : 0) : 0;
   return CLR_OK;
 }
 

@@ -311,6 +311,7 @@ struct clr_batch {
   // floors for the four maxima above (clr_batch_set_selection_bounds): a sharded plan hands every shard the maxima
   // of the WHOLE batch, so that all shards pick the same kernels whatever the sharding
   double floor_tmax = 0.0, floor_dxmax = 0.0, floor_dmax = 0.0, floor_cmax = 0.0;
+  bool b_zero = false;                // every b_comp of the current coefficients is exactly zero (clr_batch_set_coefficients)
   double set_series_host_ms = 0.0;    // host time of the last clr_batch_set_series (scan + uploads)
   double dtmin = 0.0;                 // smallest step of t over the plan's series (negative: not sorted; NaN: a NaN time)
   clr::UploadStaging staging;         // pinned staging + copy streams of clr_batch_set_series (large series only)
@@ -525,6 +526,13 @@ bool lazy_eligible(const clr_batch* h) {
   return h->have_series && h->have_coeffs && cmax * dxmax < 0.0078125 && dmax * dxmax < 0.03125 && lazy_phases_ok(h);
 }
 
+// Whether the lazy role-split summarize runs its b_comp == 0 variant on this plan (clr_split_kernels.h:
+// split_trajectory_lazy); CLR_SPLIT_GENERIC=1: the general kernel for every batch.
+bool split_lazy_bzero(const clr_batch* h) {
+  const char* g = clr::option("CLR_SPLIT_GENERIC");
+  return h->J_comp > 0 && h->b_zero && !(g && g[0] == '1');
+}
+
 // Wide plans (wave per (problem, chunk), widths 9..64): the lazy flavour of the summarize takes any series since round 5 --
 // a lane whose own interval is too long for the Taylor steps sends its wave through the full sincos / exp for that batch
 // (wide_scan_body, feature_batch) -- as long as the decay accumulated between two renormalisations (64 steps) stays far
@@ -648,6 +656,7 @@ int batch_params(clr_batch* h, int materialize, clr::BatchParams& P, bool behind
   const bool split = split_active(h, behind_fast_path);
   P.split = split ? 1 : 0;
   P.split_lazy = (split && h->summarize_mode != 1 && lazy_eligible(h)) ? 1 : 0;
+  P.split_bzero = (P.split_lazy && split_lazy_bzero(h)) ? 1 : 0;
   // wide plans: the lazy-decay flavour of the wide summarize on dense series (mode 0 / 1 switch it off)
   // (1: dense everywhere -- the strict rule; 2: only the relaxed one: the flavour with the per-batch range test)
   if (!h->launch && h->nchunk > 1 && (h->summarize_mode < 0 || h->summarize_mode == 2) && lazy_eligible_wide(h))

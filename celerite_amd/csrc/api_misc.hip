@@ -13,6 +13,7 @@ namespace {
 const char* const k_option_keys[] = {
     "CLR_GRAD_SEQUENTIAL", "CLR_GRAD_ANY_WIDTH", "CLR_GRAD_REBUILD_SPAN", "CLR_WIDE_WALK", "CLR_WIDE_NO_PAIRED",
     "CLR_NO_ROWS_KERNEL", "CLR_NO_BIG_SWEEP", "CLR_OUTPUT_CHECK_CAP", "CLR_OUTPUT_CHECK_TOL",
+    "CLR_SPLIT_GENERIC",
 };
 bool known_option(const char* key) {
   for (const char* k : k_option_keys)

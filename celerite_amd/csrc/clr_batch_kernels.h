@@ -160,6 +160,9 @@ struct BatchParams {
   // padding a recurrence step ignores (t held, diagonal 1e300, y = 0 -- in the resident row-major arrays themselves, so
   // every reader and every copy sees it); null: every problem has N samples
   const int* len;
+  // lazy role-split summarize (clr_split_kernels.h: split_trajectory_lazy): every b_comp of the current coefficients is
+  // exactly zero (host: batch_params; off under CLR_SPLIT_GENERIC)
+  int split_bzero;
 };
 
 // samples of problem b: what the chunk functions take as their N (the samples that count -- log-determinant, quadratic

@@ -289,16 +289,35 @@ struct SplitLinkLazy {
   static constexpr int RENORM = CLR_SPLIT_RENORM;
 };
 
-// phi = exp(-c dx) and 1/phi = exp(+c dx) of the distinct decays, sharing the even / odd parts
+// a wave-uniform double, moved into a scalar register pair (a uniform fp64 result otherwise stays in vector registers)
+__device__ __forceinline__ double wave_uniform(double v) {
+  const int lo = __builtin_amdgcn_readfirstlane(__double2loint(v)), hi = __builtin_amdgcn_readfirstlane(__double2hiint(v));
+  return __hiloint2double(hi, lo);
+}
+
+// largest |decay rate| of the problem: what features_phi_pair tests its ranges with
 template <int JR, int JC>
-__device__ __forceinline__ void features_phi_pair(const Problem<JR, JC>& p, double dx, double* phid, double* phinv) {
+__device__ __forceinline__ double max_decay_rate(const Problem<JR, JC>& p) {
+  double cm = 0.0;
+#pragma unroll
+  for (int j = 0; j < JR; ++j) cm = fmax(cm, fabs(p.cr[j]));
+#pragma unroll
+  for (int j = 0; j < JC; ++j) cm = fmax(cm, fabs(p.cc[j]));
+  return wave_uniform(cm);
+}
+
+// phi = exp(-c dx) and 1/phi = exp(+c dx) of the distinct decays, sharing the even / odd parts.  The range test looks at
+// amax = max_j |c_j dx|; rounding is monotone, so that is fl(cmax |dx|) with the wave-uniform cmax = max_j |c_j|
+// (max_decay_rate): one multiply instead of a chain of maxima, the same predicate.
+template <int JR, int JC>
+__device__ __forceinline__ void features_phi_pair(const Problem<JR, JC>& p, double cmax, double dx, double* phid, double* phinv) {
   constexpr int M = JR + JC;
   double x[nz(M)];
-  double amax = 0.0;
+  const double amax = cmax * fabs(dx);
 #pragma unroll
-  for (int j = 0; j < JR; ++j) { x[j] = -p.cr[j] * dx; amax = fmax(amax, fabs(x[j])); }
+  for (int j = 0; j < JR; ++j) x[j] = -p.cr[j] * dx;
 #pragma unroll
-  for (int j = 0; j < JC; ++j) { x[JR + j] = -p.cc[j] * dx; amax = fmax(amax, fabs(x[JR + j])); }
+  for (int j = 0; j < JC; ++j) x[JR + j] = -p.cc[j] * dx;
   if (CLR_WAVE_ALL(amax < 0.0009765625)) {  // 2^-10: even part to x^4, odd part to x^3 (next terms < 7.4e-18)
 #pragma unroll
     for (int j = 0; j < M; ++j) {
@@ -323,8 +342,12 @@ __device__ __forceinline__ void features_phi_pair(const Problem<JR, JC>& p, doub
   }
 }
 
-template <int JR, int JC, bool FAST>
-__device__ __forceinline__ void split_trajectory_lazy(const Problem<JR, JC>& p, DirectSeries& src, int L, int n0,
+// BZERO: every b_comp of the plan is exactly zero (host: clr_batch_set_coefficients) -- u of a complex pair is
+// (a cd, a sd), one multiply each.
+template <int JR, int JC, bool FAST, bool BZERO>
+__device__ __forceinline__ void split_trajectory_lazy(const Problem<JR, JC>& p, DirectSeries& src /* of chunk 0 */,
+                                                      unsigned lane_bytes, int L, int n0,
+                                                      int xblk /* the wave's block of 64 chunks */,
                                                       int N, bool store, double* slot0 /* + lane */,
                                                       double* psi_area /* + lane */, double* elem_out,
                                                       double* ld0_out, int* flag0_out, double* gamma_out, int dbg) {
@@ -343,7 +366,6 @@ __device__ __forceinline__ void split_trajectory_lazy(const Problem<JR, JC>& p, 
   double gamma = 0.0;
   LogProduct lp0;
   lp0.init();
-  int flag0 = 0;
   constexpr int PF = 3;
   double tq[PF + 1], dq[PF], yq[PF];
   // Steps past the end of the series (the tail of a problem's last chunk) are HARMLESS instead of masked: the
@@ -353,9 +375,13 @@ __device__ __forceinline__ void split_trajectory_lazy(const Problem<JR, JC>& p, 
   // loads (the sums of this wave are still restricted to n < N below; reads past the chunk's end land in the next
   // chunk or, for the last chunk, in rows 1..5 of the copy: only the state after the last step sees them, and the
   // last chunk's end state is not used).  Dead lanes (no chunk of their own) read chunk 0's samples.
-  auto tt = [&](int i) { return src.tp[src.off(i)]; };
-  auto dd = [&](int i) { return src.dp[src.off(i)]; };
-  auto yy = [&](int i) { return src.yp[src.off(i)]; };
+  // A load's address is (series base + sample offset), wave-uniform and kept in scalar registers, plus the lane's own
+  // 32-bit byte offset `lane_bytes` to its chunk: the form a global load takes as it is, without per-lane 64-bit
+  // address arithmetic (three vector additions per step) or the address registers they need.
+  auto at = [&](const double* base, long o) { return *reinterpret_cast<const double*>(reinterpret_cast<const char*>(base + o) + lane_bytes); };
+  auto tt = [&](int i) { return at(src.tp, src.off(i)); };
+  auto dd = [&](int i) { return at(src.dp, src.off(i)); };
+  auto yy = [&](int i) { return at(src.yp, src.off(i)); };
   double tn = tt(0);
   double cdv[nz(JC)], sdv[nz(JC)];  // cos / sin of d t at the current sample
 #pragma unroll
@@ -367,6 +393,9 @@ __device__ __forceinline__ void split_trajectory_lazy(const Problem<JR, JC>& p, 
   // per-step 64-bit multiplies)
   long od = src.off(PF), ot = src.off(PF + 1);
   int id = PF;  // the index od stands for
+  const double cmax = max_decay_rate<JR, JC>(p);
+  const int nleft = N - n0;  // steps of this lane that are samples of the series
+  unsigned long long bad = 0;  // lanes that met a pivot which is not > 0 (NaN included) at some n >= 1
   for (int i0 = 0; i0 < L; i0 += Lk::RENORM) {
     const int i1 = (i0 + Lk::RENORM < L) ? i0 + Lk::RENORM : L;
     // anchor: the full sincos of the absolute phase at the block's first sample (cholesky.h:137); at
@@ -387,8 +416,13 @@ __device__ __forceinline__ void split_trajectory_lazy(const Problem<JR, JC>& p, 
 #pragma unroll
       for (int j = 0; j < JC; ++j) {
         const int k = JR + 2 * j;
-        u[k] = p.ac[j] * cdv[j] + p.bc[j] * sdv[j];
-        u[k + 1] = p.ac[j] * sdv[j] - p.bc[j] * cdv[j];
+        if (BZERO) {
+          u[k] = p.ac[j] * cdv[j];
+          u[k + 1] = p.ac[j] * sdv[j];
+        } else {
+          u[k] = p.ac[j] * cdv[j] + p.bc[j] * sdv[j];
+          u[k + 1] = p.ac[j] * sdv[j] - p.bc[j] * cdv[j];
+        }
         v[k] = cdv[j];
         v[k + 1] = sdv[j];
       }
@@ -412,7 +446,7 @@ __device__ __forceinline__ void split_trajectory_lazy(const Problem<JR, JC>& p, 
       }
       {  // Psi for the NEXT step (this step's decay included); the old one is no longer needed
         double phid[nz(M)], phinv[nz(M)];
-        features_phi_pair<JR, JC>(p, t_cur_next - tn, phid, phinv);
+        features_phi_pair<JR, JC>(p, cmax, t_cur_next - tn, phid, phinv);
 #pragma unroll
         for (int m = 0; m < M; ++m) { psi[m] *= phid[m]; psinv[m] *= phinv[m]; }
       }
@@ -431,9 +465,10 @@ __device__ __forceinline__ void split_trajectory_lazy(const Problem<JR, JC>& p, 
       const double D = a_n - s;
       const double invD = recip_fast(D);
       {  // (a padded step has D ~ 1e300 > 0 and a_n / D = 1: only the log-determinant has to leave it out)
-        const int n = n0 + i;
-        flag0 |= (n >= 1 && !(D > 0.0)) ? 1 : 0;
-        lp0.mul_window(n < N ? D : 1.0);
+        // The pivot test skips n = n0 + i = 0, which is lane 0 of the problem's first wave at i = 0 only: every step
+        // tests all lanes, collects the lane mask in a scalar pair and clears that one bit there (i is wave-uniform).
+        bad |= __builtin_amdgcn_ballot_w64(!(D > 0.0)) & ((xblk == 0 && i == 0) ? ~1ull : ~0ull);
+        lp0.mul_window(i < nleft ? D : 1.0);
         gamma = fmax(gamma, fabs(a_n * invD));
       }
       double z[J], W[J];
@@ -465,9 +500,12 @@ __device__ __forceinline__ void split_trajectory_lazy(const Problem<JR, JC>& p, 
       tn = t_cur_next;
     };
     auto refill = [&](int k) __attribute__((always_inline)) {  // entry k of the queue <- the sample PF steps ahead
-      tq[k] = src.tp[ot];
-      dq[k] = src.dp[od];
-      yq[k] = src.yp[od];
+      // (opaque per step: otherwise the compiler folds the loop-invariant lane offset into three per-lane 64-bit
+      //  pointers and is back to adding the running offsets to them with vector instructions)
+      asm volatile("" : "+v"(lane_bytes));
+      tq[k] = at(src.tp, ot);
+      dq[k] = at(src.dp, od);
+      yq[k] = at(src.yp, od);
       ++id;
       od = (id == L) ? src.cs : od + src.is;
       ot = (id + 1 == L) ? src.cs : ot + src.is;
@@ -510,7 +548,7 @@ __device__ __forceinline__ void split_trajectory_lazy(const Problem<JR, JC>& p, 
   }
   if (!store) return;
   *ld0_out = lp0.log_value();
-  *flag0_out = flag0;
+  *flag0_out = (int)((bad >> (threadIdx.x & 63)) & 1);
   *gamma_out = gamma;
   double* o = elem_out + J * J + J;
 #pragma unroll
@@ -645,7 +683,7 @@ __device__ __forceinline__ void split_riders_lazy(int L, int n0, int N, bool sto
 // SETS == 4: 8 waves = 4 sets (problem b, block x of 64 chunks), one T and one R wave per set, the per-step barrier
 // spans all 8 waves.  SETS == 1 (round 4 A/B, profiles/r04g_split_wg_ab.txt): one set per 128-thread workgroup -- the
 // barrier couples only the T and R wave that actually exchange data; four workgroups per CU.
-template <int JR, int JC, bool FAST, bool LAZY, int SETS = 4>
+template <int JR, int JC, bool FAST, bool LAZY, int SETS = 4, bool BZERO = false>
 __global__ void __launch_bounds__(128 * SETS) __attribute__((amdgpu_waves_per_eu(2, 2)))
 summarize_split_kernel(const BatchParams P) {
   using Wd = Widths<JR, JC>;
@@ -694,13 +732,17 @@ summarize_split_kernel(const BatchParams P) {
   // run: 3.08 ms default, 3.08 ms with T prioritised, 2.85 ms with R prioritised (profiles/r02b_split_notes.txt).
   if (role == 1) __builtin_amdgcn_s_setprio(3);
   if (role == 0) {
-    DirectSeries src = make_direct(P, b, store ? c : 0);
+    // (lazy: the wave-uniform origin of chunk 0 and the lane's byte offset from it, see split_trajectory_lazy)
+    DirectSeries src = make_direct(P, b, LAZY ? 0 : (store ? c : 0));
+    // (32 bits: the split kernels only ever read the chunk-interleaved copy, lane_cs == 1 -- BatchParams::split,
+    //  scan_reads_copy on the host -- so the offset is c x 8 bytes, c < nchunk)
+    const unsigned lane_bytes = (unsigned)(store ? c : 0) * 8u;
     if (!store) src.nleft = 0;  // lanes past the last chunk / dead sets: padding only
     double ld0 = 0.0, q0 = 0.0, gamma = 0.0;
     int flag0 = 0;
     if (LAZY)
-      split_trajectory_lazy<JR, JC, FAST>(p, src, P.L, c * P.L, P.N, store, slot, psibuf[LAZY ? set : 0] + lane, elem,
-                                          &ld0, &flag0, &gamma, P.split);
+      split_trajectory_lazy<JR, JC, FAST, BZERO>(p, src, lane_bytes, P.L, c * P.L, xblk, P.N, store, slot,
+                                                        psibuf[LAZY ? set : 0] + lane, elem, &ld0, &flag0, &gamma, P.split);
     else
       split_trajectory<JR, JC, FAST>(p, src, P.L, c * P.L, P.N, store, slot, elem, &ld0, &q0, &flag0, &gamma, P.split);
     if (store) {
@@ -730,8 +772,14 @@ inline void launch_split_shape(const BatchParams& P, hipStream_t s) {
 #endif
   const dim3 grid((unsigned)((sets + CLR_SPLIT_SETS - 1) / CLR_SPLIT_SETS)), block(128 * CLR_SPLIT_SETS);
 #define CLR_GO(F, Z) hipLaunchKernelGGL((summarize_split_kernel<JR, JC, F, Z, CLR_SPLIT_SETS>), grid, block, 0, s, P)
-  if (P.split_lazy) { if (P.fast_trig) CLR_GO(true, true); else CLR_GO(false, true); }
-  else              { if (P.fast_trig) CLR_GO(true, false); else CLR_GO(false, false); }
+#define CLR_GO_LAZY(F, BZ) hipLaunchKernelGGL((summarize_split_kernel<JR, JC, F, true, CLR_SPLIT_SETS, BZ>), grid, block, 0, s, P)
+  if (P.split_lazy) {
+    constexpr bool HC = JC > 0;  // (a shape without complex terms has no b_comp: one variant)
+    const bool bz = HC && P.split_bzero;
+    if (P.fast_trig) { if (bz) CLR_GO_LAZY(true, HC); else CLR_GO_LAZY(true, false); }
+    else             { if (bz) CLR_GO_LAZY(false, HC); else CLR_GO_LAZY(false, false); }
+  } else { if (P.fast_trig) CLR_GO(true, false); else CLR_GO(false, false); }
+#undef CLR_GO_LAZY
 #undef CLR_GO
 }
 #define CLR_SPLIT_SHAPE(R, C) if (JR == R && JC == C) { launch_split_shape<R, C>(P, s); return true; }

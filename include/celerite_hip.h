@@ -95,6 +95,8 @@ int clr_device_memory(size_t* free_bytes, size_t* total_bytes);
  *   CLR_NO_ROWS_KERNEL       CholeskySolver above width 64 / general terms above 32: the one-workgroup kernels (S in LDS / L2)
  *                            instead of the row-distributed one (cross-checks)
  *   CLR_NO_BIG_SWEEP         dot_solve / solve above width 64: the sequential sweeps instead of the chunked affine scans
+ *   CLR_SPLIT_GENERIC        lazy role-split summarize (widths 7, 8): "1" the general kernel for every batch, also where
+ *                            every b_comp is zero (cross-checks, A/B runs; clr_batch_get_split_variant)
  * Any other key is refused with CLR_INVALID_ARGUMENT.
  * clr_get_option: the value in force (NULL: not set); the pointer is valid until the calling thread's next call. */
 int clr_set_option(const char* key, const char* value);
@@ -364,6 +366,10 @@ int clr_batch_get_warm_start(const clr_batch* h, int* active, int* nchunk, int* 
                              int* warmup_max, int* settled, int* fallbacks);
 /* Which one the next evaluation will run (0, 1 or 2 as above), given the series and coefficients set. */
 int clr_batch_get_summarize_kernel(const clr_batch* h, int* kind);
+/* The variant of the lazy role-split summarize (kind 2, widths 7 and 8) the next evaluation runs: 1 the one without the
+ * b_comp terms of the features (every b_comp of the current coefficients is exactly zero), 0 the general one -- and 0 for
+ * any other kernel and under CLR_SPLIT_GENERIC=1.  Results do not depend on it (the sign of an exact zero apart). */
+int clr_batch_get_split_variant(const clr_batch* h, int* variant);
 /* Prefix phase of the scan (widths 1..8): how the chunk elements are turned into chunk start states.
  *   2 (default) multi-level: groups of consecutive elements are composed in parallel (element o element, the
  *       associative operator of the scan; csrc/clr_prefix_kernels.h), the few composed elements are walked, and the
