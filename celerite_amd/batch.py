@@ -124,6 +124,12 @@ def _load():
     lib.clr_sharded_set_noise_weights.argtypes = [C.c_void_p, _dp]
     lib.clr_sharded_grad_noise_weights.argtypes = [C.c_void_p, _dp, _ip]
     lib.clr_sharded_get_noise_project_ms.argtypes = [C.c_void_p, _dp]
+    for pre in ("clr_batch", "clr_sharded"):
+        getattr(lib, pre + "_set_amplitude_basis").argtypes = [C.c_void_p, C.c_int, _dp, C.c_long]
+        getattr(lib, pre + "_set_amplitudes").argtypes = [C.c_void_p, _dp]
+        getattr(lib, pre + "_get_log_amplitude_sum").argtypes = [C.c_void_p, _dp]
+        getattr(lib, pre + "_grad_amplitudes").argtypes = [C.c_void_p, _dp, _ip]
+        getattr(lib, pre + "_get_amplitude_project_ms").argtypes = [C.c_void_p, _dp]
     lib.clr_sharded_fit_mean_weights.argtypes = [C.c_void_p, C.c_double] + [_dp] * 5 + [_ip]
     lib.clr_batch_set_mean_fit_tile.argtypes = [C.c_void_p, C.c_int]
     lib.clr_batch_get_mean_fit_ms.argtypes = [C.c_void_p, _dp, _dp, _dp]
@@ -344,6 +350,29 @@ def _noise_weights_arg(s, B, K):
     a = _weights_arg(s, B, K)
     if not np.all(np.isfinite(a)):
         raise ValueError("a non-finite noise weight")
+    return a
+
+
+MAX_AMPLITUDE_BASIS = 16     # CLR_MAX_AMPLITUDE_BASIS of include/celerite_hip.h
+
+
+def _amplitude_basis_arg(Gamma, B, N, lengths=None):
+    """:func:`_noise_basis_arg` for the basis of a per-sample amplitude model (``clr_*_set_amplitude_basis``): the same
+    shapes, the limit ``MAX_AMPLITUDE_BASIS``, and the same rule for the entries -- all finite, with per-problem
+    ``lengths`` in force within each problem's length (of a shared basis: the longest problem's)."""
+    try:
+        return _noise_basis_arg(Gamma, B, N, lengths)
+    except ValueError as e:
+        raise ValueError(str(e).replace("noise basis", "amplitude basis").replace("a linear mean", "an amplitude model"))
+
+
+def _amplitudes_arg(a, B, K):
+    """:func:`_weights_arg` for the amplitudes of an amplitude model, which must be finite."""
+    if K < 1:
+        raise ValueError("dimension mismatch: no amplitude basis is set (set_amplitude_basis)")
+    a = _weights_arg(a, B, K)
+    if not np.all(np.isfinite(a)):
+        raise ValueError("a non-finite amplitude")
     return a
 
 
@@ -867,6 +896,78 @@ class BatchedGP(object):
         :meth:`leave_one_out_ms`)."""
         ms = C.c_double()
         _check(_load().clr_batch_get_noise_project_ms(self._h, C.byref(ms)))
+        return ms.value
+
+    def set_amplitude_basis(self, Gamma):
+        """A per-sample amplitude model (``clr_batch_set_amplitude_basis``): the same latent process ``f`` seen with
+        another amplitude per band,
+
+            ``y_n = s_n f(t_n) + eps_n``,  ``s[b, n] = sum_k a[b, k] Gamma_k[b, n]``
+
+        -- multi-colour photometry of one variable source (``Gamma_k`` the indicator of band k), a radial velocity next
+        to an activity indicator, a chromatic amplitude law (``Gamma`` a polynomial in wavelength).  ``Gamma`` is the basis
+        at the plan's samples, ``(K, N)`` for all problems or ``(B, K, N)``, ``K <= 16``, uploaded once.  A basis alone
+        changes nothing: zero amplitudes are no neutral start, so the plan stays the plain plan until
+        :meth:`set_amplitudes`; a new basis drops the amplitudes in force.  ``None`` removes the model and restores the
+        plain plan.  The entries must be finite (with ``lengths=`` in force: within each problem's length).  Not together
+        with a constant mean (:meth:`set_mean`): a constant in data units is the mean-basis function 1."""
+        a, stride, K = _amplitude_basis_arg(Gamma, self.B, self.N, getattr(self, "_series_lengths", None))
+        self._set_amplitude_basis(K, a, stride)
+        self._amplitude_K = K
+
+    def _set_amplitude_basis(self, K, a, stride):
+        _check(_load().clr_batch_set_amplitude_basis(self._h, K, None if a is None else _ptr(a), stride))
+
+    def set_amplitudes(self, a):
+        """The amplitudes of the amplitude model, ``(B, K)`` or ``(K,)`` for all problems (``clr_batch_set_amplitudes``).
+        With ``S = diag(s)``, ``K_y = S K S + D = S (K + S^-1 D S^-1) S``, so the device rewrites the series every route
+        reads -- ``y' = r / s`` and ``d' = d / (s * s)``, ``r`` and ``d`` the residual and the variances in force, the
+        bits of those NumPy expressions with ``s = a[:, 0, None] * Gamma[0] + ...`` summed in the order of k -- and
+        ``evaluate`` / ``evaluate_parameters`` / ``results`` / the gradient's value report ``logdet = logdet' + (L + L)``,
+        ``loglike = loglike' - L``, ``quad = quad'`` with ``L =`` :meth:`log_amplitude_sum`.  B x K numbers go up per step.
+        A problem with a zero or non-finite ``s_n`` reports NaN and ``CLR_INVALID_ARGUMENT``.  The factor's consumers run
+        on the scaled system: :meth:`predict` and its relatives return the posterior of the LATENT process ``f`` (a band's
+        curve is ``a_band * f``), :meth:`solve` is ``K'^-1 b``, :meth:`leave_one_out` is that of the scaled samples.  The
+        factor of an earlier materialising run is that of the earlier amplitudes: materialise again before them."""
+        self._set_amplitudes(_amplitudes_arg(a, self.B, getattr(self, "_amplitude_K", 0)))
+
+    def _set_amplitudes(self, a):
+        _check(_load().clr_batch_set_amplitudes(self._h, _ptr(a)))
+
+    def log_amplitude_sum(self):
+        """``L[B] = sum_n log|s[b, n]|`` of the amplitudes in force over each problem's length
+        (``clr_batch_get_log_amplitude_sum``); zeros while none are."""
+        L = np.empty(self.B)
+        self._log_amplitude_sum(L)
+        return L
+
+    def _log_amplitude_sum(self, L):
+        _check(_load().clr_batch_get_log_amplitude_sum(self._h, _ptr(L)))
+
+    def grad_amplitudes(self):
+        """``(da[B, K], status[B])``: the gradient with respect to the amplitudes in force,
+
+            ``d loglike_b / d a[b, k] = sum_n Gamma_k[b, n] (alpha'_n y'_n + d'_n (c'_n - alpha'_n^2) - 1) / s_n``
+
+        with ``alpha' = K'^-1 y'`` and ``c' = diag(K'^-1)`` of the scaled system (``clr_batch_grad_amplitudes``):
+        :meth:`grad_noise_weights`' steps and rules -- it needs a materialising run made AFTER the amplitudes, the basis,
+        the noise weights and the series were set (``CLR_NOT_COMPUTED`` otherwise), :meth:`leave_one_out`'s domain, and a
+        problem whose status is not 0 has a row of zeros."""
+        K = getattr(self, "_amplitude_K", 0)
+        if not K:
+            raise RuntimeError("no amplitude basis is set: call set_amplitude_basis first")
+        da, st = np.empty((self.B, K)), np.empty(self.B, dtype=np.int32)
+        self._grad_amplitudes(da, st)
+        return da, st
+
+    def _grad_amplitudes(self, da, st):
+        _check(_load().clr_batch_grad_amplitudes(self._h, _ptr(da), st.ctypes.data_as(_ip)))
+
+    def amplitude_project_ms(self):
+        """Device time of the projection pass of the last :meth:`grad_amplitudes` (its diagonal and solve:
+        :meth:`leave_one_out_ms`)."""
+        ms = C.c_double()
+        _check(_load().clr_batch_get_amplitude_project_ms(self._h, C.byref(ms)))
         return ms.value
 
     def set_coefficients(self, a_real, c_real, a_comp, b_comp, c_comp, d_comp, jitter=0.0):
@@ -1743,6 +1844,30 @@ class ShardedBatchedGP(object):
         run concurrently (``clr_sharded_get_noise_project_ms``)."""
         ms = C.c_double()
         self._ok(_load().clr_sharded_get_noise_project_ms(self._h, C.byref(ms)))
+        return ms.value
+
+    set_amplitude_basis = BatchedGP.set_amplitude_basis
+    set_amplitudes = BatchedGP.set_amplitudes
+    log_amplitude_sum = BatchedGP.log_amplitude_sum
+    grad_amplitudes = BatchedGP.grad_amplitudes
+
+    def _set_amplitude_basis(self, K, a, stride):
+        self._ok(_load().clr_sharded_set_amplitude_basis(self._h, K, None if a is None else _ptr(a), stride))
+
+    def _set_amplitudes(self, a):
+        self._ok(_load().clr_sharded_set_amplitudes(self._h, _ptr(a)))
+
+    def _log_amplitude_sum(self, L):
+        self._ok(_load().clr_sharded_get_log_amplitude_sum(self._h, _ptr(L)))
+
+    def _grad_amplitudes(self, da, st):
+        self._ok(_load().clr_sharded_grad_amplitudes(self._h, _ptr(da), st.ctypes.data_as(_ip)))
+
+    def amplitude_project_ms(self):
+        """Device time of the projection pass of the last :meth:`grad_amplitudes`: the largest over the shards, which
+        run concurrently (``clr_sharded_get_amplitude_project_ms``)."""
+        ms = C.c_double()
+        self._ok(_load().clr_sharded_get_amplitude_project_ms(self._h, C.byref(ms)))
         return ms.value
 
     def _fit_mean_weights(self, p, w, cov, gram, quad, ld, st):

@@ -7,6 +7,7 @@
 #include "clr_kernel.h"
 #include "clr_bmean_kernels.h"
 #include "clr_bnoise_kernels.h"
+#include "clr_bamplitude_kernels.h"
 
 #include <limits>
 
@@ -260,11 +261,35 @@ static void warm_select(clr_batch* h) {
   h->warm_K_dirty = h->warm_active;  // (uploaded behind the next coefficients, or by the next enqueue)
 }
 
+// With amplitudes in force (clr_batch_set_amplitudes) every route reads y' = r / s and d' = d / (s * s): one elementwise pass
+// over the resident scale `amp_s`, behind whatever formed r and d.  r is the residual of the linear mean in force, which
+// apply_mean has just left in `y` (divided in place), or the caller's series in `y_src`; d is the noise model's variances
+// that apply_noise has just left in `diag`, or the caller's diagonal in `diag_src`.  A second in-place pass, not a divisor
+// fused into the forming kernels: those keep their bits and their registers, and a plan without amplitudes runs no other
+// code.  An in-place division is never run twice on the same array: every caller forms r (or d) again first.
+static int amplitude_divide(clr_batch* h, bool do_y, bool do_d) {
+  const long N = h->N;
+  int st;
+  if (do_y && (st = h->y.reserve((size_t)h->B * N)) != CLR_OK) return st;
+  if (do_d && (st = h->diag.reserve((size_t)h->B * N)) != CLR_OK) return st;
+  const bool y_inplace = h->mean_K > 0, d_inplace = h->noise_K > 0;
+  clr::launch_amplitude_divide(y_inplace ? h->y.p : h->y_src.p, y_inplace ? N : h->y_src_stride, do_y ? h->y.p : nullptr,
+                               d_inplace ? h->diag.p : h->diag_src.p, d_inplace ? N : h->diag_src_stride,
+                               do_d ? h->diag.p : nullptr, h->amp_s.p, h->B, (int)N, h->stream.get());
+  // (per-problem lengths: the tails stay the padding y = 0 and 1e300)
+  if (h->ragged && do_y) clr::launch_pad_tail(h->y.p, h->B, (int)N, h->len_dev.p, 0, h->stream.get());
+  if (h->ragged && do_d) clr::launch_pad_tail(h->diag.p, h->B, (int)N, h->len_dev.p, 2, h->stream.get());
+  HIP_TRY(hipGetLastError());
+  if (do_y) residual_replaced(h, N);
+  if (do_d) variance_replaced(h, N);
+  return CLR_OK;
+}
+
 // The residual y - mu of clr_batch_set_mean -- or y - sum_k w_k Phi_k of clr_batch_set_mean_weights -- from the caller's
 // series in `y_src`: one elementwise pass into `y`, where every route reads its series; the copies derived from `y` are
 // then stale (a shared series with a per-problem mean becomes a per-problem residual: the copies are re-sized by the
 // launches that rebuild them).  The factor of a materialising run does not depend on y and stays.
-static int apply_mean(clr_batch* h) {
+static int apply_mean(clr_batch* h, bool divide = true) {
   const long N = h->N;
   const bool linear = h->mean_K > 0;  // (its weights are per problem)
   const bool per_problem = linear || h->y_src_stride != 0 || h->mean_stride != 0;
@@ -291,6 +316,7 @@ static int apply_mean(clr_batch* h) {
   if (h->ragged) clr::launch_pad_tail(h->y.p, h->B, (int)N, h->len_dev.p, 0, h->stream.get());
   HIP_TRY(hipGetLastError());
   residual_replaced(h, per_problem ? N : 0);
+  if (divide && h->amp_active) return amplitude_divide(h, true, false);  // (every route reads r / s)
   return CLR_OK;
 }
 
@@ -304,6 +330,10 @@ int clr_batch_set_mean(clr_batch* h, const double* mu, long mu_stride) {
   if (mu && h->mean_K > 0)
     return fail(CLR_INVALID_ARGUMENT, "clr_batch_set_mean: a linear mean is in force (clr_batch_set_mean_basis) -- the two means "
                                       "are mutually exclusive: remove it first, or make the constant a basis function");
+  if (mu && h->amp_K > 0)
+    return fail(CLR_INVALID_ARGUMENT, "clr_batch_set_mean: an amplitude basis is set (clr_batch_set_amplitude_basis) -- the constant "
+                                      "mean and the amplitude model are mutually exclusive: a constant in data units is the "
+                                      "mean-basis function 1 (clr_batch_set_mean_basis)");
   if (mu && h->have_mean && h->have_series && h->mean_stride == mu_stride && h->host_mean.size() == n &&
       memcmp(h->host_mean.data(), mu, n * sizeof(double)) == 0)
     return CLR_OK;  // (the residual in HBM is this mean's)
@@ -343,6 +373,10 @@ int clr_batch_set_mean_basis(clr_batch* h, int K, const double* phi, long phi_st
     if ((st = warm_resolve(h, nullptr)) != CLR_OK) return st;  // (an evaluation in flight is settled on ITS residual)
     h->mean_K = 0;
     h->host_weights.clear();
+    if (h->have_series && h->amp_active) {  // (the amplitudes stay: y' = y / s from the caller's series)
+      if ((st = amplitude_divide(h, true, false)) != CLR_OK) h->have_series = false;
+      return st;
+    }
     if (h->have_series) {
       std::swap(h->y, h->y_src);
       residual_replaced(h, h->y_src_stride);
@@ -363,7 +397,7 @@ int clr_batch_set_mean_basis(clr_batch* h, int K, const double* phi, long phi_st
   HIP_TRY(hipStreamSynchronize(h->stream.get()));  // (a residual pass in flight may still read the previous basis)
   if ((st = h->basis_dev.reserve(n)) != CLR_OK) return st;
   HIP_TRY(hipMemcpy(h->basis_dev.p, phi, n * sizeof(double), hipMemcpyHostToDevice));
-  if (h->mean_K == 0 && h->have_series) {  // the caller's series moves aside, `y` will hold the residual
+  if (h->mean_K == 0 && h->have_series && !h->amp_active) {  // the caller's series moves aside, `y` will hold the residual
     std::swap(h->y, h->y_src);
     h->y_src_stride = h->y_stride;
   }
@@ -401,7 +435,7 @@ int clr_batch_set_mean_weights(clr_batch* h, const double* w) {
 // The variances diag + sum_k s_k Psi_k of clr_batch_set_noise_weights from the caller's diagonal in `diag_src`: one
 // elementwise pass into `diag`, where every route reads its variances (apply_mean's pattern for y); what is derived from
 // `diag` is then stale (variance_replaced).  The weights are per problem, so a shared diagonal becomes B x N variances.
-static int apply_noise(clr_batch* h) {
+static int apply_noise(clr_batch* h, bool divide = true) {
   const long N = h->N;
   int st;
   if ((st = h->diag.reserve((size_t)h->B * N)) != CLR_OK) return st;
@@ -421,6 +455,7 @@ static int apply_noise(clr_batch* h) {
   if (h->ragged) clr::launch_pad_tail(h->diag.p, h->B, (int)N, h->len_dev.p, 2, h->stream.get());
   HIP_TRY(hipGetLastError());
   variance_replaced(h, N);
+  if (divide && h->amp_active) return amplitude_divide(h, false, true);  // (every route reads diag_eff / (s * s))
   return CLR_OK;
 }
 
@@ -433,6 +468,10 @@ int clr_batch_set_noise_basis(clr_batch* h, int K, const double* psi, long psi_s
     if ((st = warm_resolve(h, nullptr)) != CLR_OK) return st;  // (an evaluation in flight is settled on ITS variances)
     h->noise_K = 0;
     h->host_noise.clear();
+    if (h->have_series && h->amp_active) {  // (the amplitudes stay: d' = diag / (s * s) from the caller's diagonal)
+      if ((st = amplitude_divide(h, false, true)) != CLR_OK) h->have_series = false;
+      return st;
+    }
     if (h->have_series) {
       std::swap(h->diag, h->diag_src);
       variance_replaced(h, h->diag_src_stride);
@@ -456,7 +495,7 @@ int clr_batch_set_noise_basis(clr_batch* h, int K, const double* psi, long psi_s
   HIP_TRY(hipStreamSynchronize(h->stream.get()));  // (a forming pass in flight may still read the previous basis)
   if ((st = h->noise_basis.reserve(n)) != CLR_OK) return st;
   HIP_TRY(hipMemcpy(h->noise_basis.p, psi, n * sizeof(double), hipMemcpyHostToDevice));
-  if (h->noise_K == 0 && h->have_series) {  // the caller's diagonal moves aside, `diag` will hold the variances
+  if (h->noise_K == 0 && h->have_series && !h->amp_active) {  // the caller's diagonal moves aside, `diag` will hold the variances
     std::swap(h->diag, h->diag_src);
     h->diag_src_stride = h->diag_stride;
   }
@@ -486,6 +525,164 @@ int clr_batch_set_noise_weights(clr_batch* h, const double* w) {
   if ((st = apply_noise(h)) != CLR_OK) {
     h->have_series = false;
     return st;
+  }
+  return CLR_OK;
+}
+
+/* ---- a per-sample amplitude model: clr_batch_set_amplitude_basis / _set_amplitudes ---------------------------------- */
+// The log terms of the evaluation in force move to the host before the forming pass overwrites them (amp_eval: 0 the
+// evaluation in force ran without amplitudes, 1 its terms are still the ones in amp_back, 2 they are in host_amp_L)
+static int amplitude_snapshot(clr_batch* h) {
+  if (h->amp_eval != 1) return CLR_OK;
+  HIP_TRY(hipEventSynchronize(h->amp_back_ev.get()));
+  h->host_amp_L.assign(h->amp_back.p, h->amp_back.p + 2 * (size_t)h->B);
+  h->amp_eval = 2;
+  return CLR_OK;
+}
+
+// The scale s of the amplitudes in force into `amp_s`, its log term and flags (fetched asynchronously: amp_back); then the
+// residual and the variances formed again where a mean or a noise model is in force, and the two divisions.
+static int apply_amplitudes(clr_batch* h) {
+  const long N = h->N;
+  const size_t B = (size_t)h->B;
+  int st;
+  if ((st = amplitude_snapshot(h)) != CLR_OK) return st;
+  if ((st = h->amp_s.reserve(B * (size_t)N)) != CLR_OK) return st;
+  if ((st = h->amp_part.reserve(clr::amplitude_scale_workspace(h->B, h->N))) != CLR_OK) return st;
+  if ((st = h->amp_Lf.reserve(2 * B)) != CLR_OK) return st;
+  const size_t na = h->host_amp.size();
+  if ((st = h->amp_dev.reserve(na)) != CLR_OK) return st;
+  // through pinned staging, as the noise weights
+  if (h->amp_ev) HIP_TRY(hipEventSynchronize(h->amp_ev.get()));
+  else HIP_TRY(clr::create_event(h->amp_ev, hipEventDisableTiming));
+  if ((st = h->amp_pin.reserve(na)) != CLR_OK) return st;
+  std::copy(h->host_amp.begin(), h->host_amp.end(), h->amp_pin.p);
+  HIP_TRY(hipMemcpyAsync(h->amp_dev.p, h->amp_pin.p, na * sizeof(double), hipMemcpyHostToDevice, h->stream.get()));
+  HIP_TRY(hipEventRecord(h->amp_ev.get(), h->stream.get()));
+  if (!clr::launch_amplitude_scale(h->amp_basis.p, h->amp_stride, h->amp_dev.p, h->amp_K, h->B, (int)N,
+                                   h->ragged ? h->len_dev.p : nullptr, h->amp_s.p, h->amp_part.p, h->amp_Lf.p, h->stream.get()))
+    return fail(CLR_UNSUPPORTED, "clr_batch_set_amplitudes: B x N / 4096 workgroups do not fit one launch");
+  if (h->amp_back_ev) HIP_TRY(hipEventSynchronize(h->amp_back_ev.get()));
+  else HIP_TRY(clr::create_event(h->amp_back_ev, hipEventDisableTiming));
+  if ((st = h->amp_back.reserve(2 * B)) != CLR_OK) return st;
+  HIP_TRY(hipMemcpyAsync(h->amp_back.p, h->amp_Lf.p, 2 * B * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
+  HIP_TRY(hipEventRecord(h->amp_back_ev.get(), h->stream.get()));
+  h->amp_formed = true;
+  if (h->mean_K > 0 && (st = apply_mean(h, false)) != CLR_OK) return st;
+  if (h->noise_K > 0 && (st = apply_noise(h, false)) != CLR_OK) return st;
+  return amplitude_divide(h, true, true);
+}
+
+// amplitudes in force -> none: the residual and the variances the plan read before them, bit for bit
+static int amplitudes_dropped(clr_batch* h) {
+  if (!h->amp_active) return CLR_OK;
+  int st;
+  if ((st = amplitude_snapshot(h)) != CLR_OK) return st;
+  h->amp_active = h->amp_formed = false;
+  h->host_amp.clear();
+  if (!h->have_series) return CLR_OK;
+  if (h->mean_K > 0) st = apply_mean(h);
+  else { std::swap(h->y, h->y_src); residual_replaced(h, h->y_src_stride); }
+  if (st == CLR_OK) {
+    if (h->noise_K > 0) st = apply_noise(h);
+    else { std::swap(h->diag, h->diag_src); variance_replaced(h, h->diag_src_stride); }
+  }
+  if (st != CLR_OK) h->have_series = false;  // (no half-formed series is ever evaluated: set the series again)
+  return st;
+}
+
+int clr_batch_set_amplitude_basis(clr_batch* h, int K, const double* gamma, long gamma_stride) {
+  int st = require_device(h->device);
+  if (st != CLR_OK) return st;
+  if (K <= 0 || !gamma) {  // remove the amplitude model: the plain plan again
+    if (K < 0) return fail(CLR_INVALID_ARGUMENT, "clr_batch_set_amplitude_basis: K >= 0");
+    if (h->amp_K == 0) return CLR_OK;
+    if ((st = warm_resolve(h, nullptr)) != CLR_OK) return st;  // (an evaluation in flight is settled on ITS series)
+    h->amp_K = 0;
+    return amplitudes_dropped(h);
+  }
+  if (K > CLR_MAX_AMPLITUDE_BASIS)
+    return fail(CLR_INVALID_ARGUMENT, "clr_batch_set_amplitude_basis: at most CLR_MAX_AMPLITUDE_BASIS = 16 basis functions");
+  const size_t per = (size_t)K * (size_t)h->N;
+  if (gamma_stride != 0 && gamma_stride != (long)per)
+    return fail(CLR_INVALID_ARGUMENT, "clr_batch_set_amplitude_basis: gamma_stride is 0 (gamma[K][N], shared) or K * N (gamma[B][K][N])");
+  if (h->have_mean)
+    return fail(CLR_INVALID_ARGUMENT, "clr_batch_set_amplitude_basis: a constant mean is in force (clr_batch_set_mean) -- the constant "
+                                      "mean and the amplitude model are mutually exclusive: remove it first; a constant in data "
+                                      "units is the mean-basis function 1 (clr_batch_set_mean_basis)");
+  const size_t n = gamma_stride ? per * (size_t)h->B : per;
+  // (per-problem lengths in force: a row's tail is never looked at and may hold anything -- of a shared basis the tail past
+  //  the longest problem)
+  const size_t longest = h->ragged ? (size_t)*std::max_element(h->host_len.begin(), h->host_len.end()) : (size_t)h->N;
+  for (size_t r = 0; r < n / (size_t)h->N; ++r) {
+    const size_t len = (h->ragged && gamma_stride) ? (size_t)h->host_len[r / (size_t)K] : longest;
+    for (size_t i = 0; i < len; ++i)
+      if (!std::isfinite(gamma[r * (size_t)h->N + i]))
+        return fail(CLR_INVALID_ARGUMENT, "clr_batch_set_amplitude_basis: a non-finite basis entry");
+  }
+  if ((st = warm_resolve(h, nullptr)) != CLR_OK) return st;
+  HIP_TRY(hipStreamSynchronize(h->stream.get()));  // (a forming pass in flight may still read the previous basis)
+  if ((st = h->amp_basis.reserve(n)) != CLR_OK) return st;
+  HIP_TRY(hipMemcpy(h->amp_basis.p, gamma, n * sizeof(double), hipMemcpyHostToDevice));
+  h->amp_K = K;
+  h->amp_stride = gamma_stride;
+  // a new basis drops the amplitudes in force: zero amplitudes are no neutral start (s = 0), so the plan is the plain plan
+  // until clr_batch_set_amplitudes
+  return amplitudes_dropped(h);
+}
+
+int clr_batch_set_amplitudes(clr_batch* h, const double* a) {
+  int st = require_device(h->device);
+  if (st != CLR_OK) return st;
+  if (h->amp_K == 0) return fail(CLR_INVALID_ARGUMENT, "clr_batch_set_amplitudes: no basis is set (clr_batch_set_amplitude_basis)");
+  if (!a) return fail(CLR_INVALID_ARGUMENT, "clr_batch_set_amplitudes: a is null");
+  const size_t n = (size_t)h->B * h->amp_K;
+  for (size_t i = 0; i < n; ++i)
+    if (!std::isfinite(a[i])) return fail(CLR_INVALID_ARGUMENT, "clr_batch_set_amplitudes: a non-finite amplitude");
+  if (h->amp_active && memcmp(h->host_amp.data(), a, n * sizeof(double)) == 0) return CLR_OK;  // (the series in force are these amplitudes')
+  if ((st = warm_resolve(h, nullptr)) != CLR_OK) return st;  // (an evaluation in flight is settled on ITS series)
+  h->host_amp.assign(a, a + n);
+  if (!h->amp_active && h->have_series) {
+    // the caller's arrays move aside unless a mean / a noise model has moved them already
+    if (h->mean_K == 0) { std::swap(h->y, h->y_src); h->y_src_stride = h->y_stride; }
+    if (h->noise_K == 0) { std::swap(h->diag, h->diag_src); h->diag_src_stride = h->diag_stride; }
+  }
+  h->amp_active = true;
+  if (!h->have_series) return CLR_OK;  // (clr_batch_set_series applies them)
+  if ((st = apply_amplitudes(h)) != CLR_OK) {
+    h->have_series = false;  // (no half-formed series is ever evaluated: set the series again)
+    return st;
+  }
+  return CLR_OK;
+}
+
+int clr_batch_get_log_amplitude_sum(clr_batch* h, double* L) {
+  int st = require_device(h->device);
+  if (st != CLR_OK) return st;
+  if (!L) return fail(CLR_INVALID_ARGUMENT, "clr_batch_get_log_amplitude_sum: L is null");
+  std::fill(L, L + h->B, 0.0);
+  if (!h->amp_active || !h->amp_formed) return CLR_OK;  // (no amplitudes in force, or no series to form them on yet)
+  HIP_TRY(hipEventSynchronize(h->amp_back_ev.get()));
+  std::copy(h->amp_back.p, h->amp_back.p + h->B, L);
+  return CLR_OK;
+}
+
+extern "C++" int amplitude_adjust(clr_batch* h, double* loglike, double* logdet, double* quad, int* status) {
+  if (h->amp_eval == 0) return CLR_OK;
+  const int st = amplitude_snapshot(h);
+  if (st != CLR_OK) return st;
+  const double* L = h->host_amp_L.data();
+  const double* flag = L + h->B;
+  for (size_t b = 0; b < (size_t)h->B; ++b) {
+    if (flag[b] != 0.0) {  // a zero or non-finite s_n inside the problem's length: the draw is refused
+      if (loglike) loglike[b] = NAN;
+      if (logdet) logdet[b] = NAN;
+      if (quad) quad[b] = NAN;
+      if (status) status[b] = CLR_INVALID_ARGUMENT;
+      continue;
+    }
+    if (logdet) logdet[b] = logdet[b] + (L[b] + L[b]);
+    if (loglike) loglike[b] = loglike[b] - L[b];
   }
   return CLR_OK;
 }
@@ -595,16 +792,18 @@ static int set_series_impl(clr_batch* h, const double* t, long t_stride, const d
     h->dtmin = (finite_min < 0.0) ? finite_min : (nan ? NAN : finite_min);
   }
   h->have_series = true;
-  if (h->have_mean || h->mean_K > 0) {  // (the upload went to `y`: it becomes the caller's series, `y` the residual)
+  if (h->have_mean || h->mean_K > 0 || h->amp_active) {  // (the upload went to `y`: it becomes the caller's series, `y` the residual)
     std::swap(h->y, h->y_src);
     h->y_src_stride = y_stride;
-    if ((st = apply_mean(h)) != CLR_OK) { h->have_series = false; return st; }
+    if (!h->amp_active && (st = apply_mean(h)) != CLR_OK) { h->have_series = false; return st; }
   }
-  if (h->noise_K > 0) {  // (the upload went to `diag`: it becomes the caller's diagonal, `diag` the variances)
+  if (h->noise_K > 0 || h->amp_active) {  // (the upload went to `diag`: it becomes the caller's diagonal, `diag` the variances)
     std::swap(h->diag, h->diag_src);
     h->diag_src_stride = diag_stride;
-    if ((st = apply_noise(h)) != CLR_OK) { h->have_series = false; return st; }
+    if (!h->amp_active && (st = apply_noise(h)) != CLR_OK) { h->have_series = false; return st; }
   }
+  // (amplitudes in force: the scale and its log term over the new lengths, then the residual, the variances and both divisions)
+  if (h->amp_active && (st = apply_amplitudes(h)) != CLR_OK) { h->have_series = false; return st; }
   if ((st = warm_scan_spans(h)) != CLR_OK) { h->have_series = false; return st; }
   h->set_series_host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - host_t0).count();
   // a new series: the warm-ups chosen for the previous one's spans do not apply, nor does its history of fallbacks
@@ -1520,6 +1719,7 @@ static int launch_step(clr_batch* h, int materialize, clr::BatchParams& P, const
   hipStream_t s = h->stream.get();
   int st;
   h->evaluated = true;
+  h->amp_eval = h->amp_active ? 1 : 0;  // (whose log term the results of this evaluation carry: amplitude_adjust)
   h->warm_inflight = h->small_inflight = h->rescue_inflight = false;
   if (h->J_general > 0 || h->J > clr::wide_max_width()) {
     // general terms -- and (round 5) celerite-only kernels of widths 65..128, which have no wave-per-problem kernel --: the
@@ -1879,6 +2079,11 @@ int clr_batch_synchronize(clr_batch* h) {
 
 int clr_batch_get_results(clr_batch* h, double* loglike, double* logdet, double* quad,
                           int* status) {
+  const int st = batch_results_scaled(h, loglike, logdet, quad, status);
+  return st != CLR_OK ? st : amplitude_adjust(h, loglike, logdet, quad, status);
+}
+
+extern "C++" int batch_results_scaled(clr_batch* h, double* loglike, double* logdet, double* quad, int* status) {
   int st = require_device(h->device);
   if (st != CLR_OK) return st;
   const size_t B = (size_t)h->B, words = 3 * B + (B + 1) / 2;

@@ -1,11 +1,12 @@
 // celerite_amd/csrc/api_batch_consumers.hip -- C ABI of the batched plans, second part: the consumers of a plan's factor
 // and coefficients (clr_batch_get_factor, _solve, _dot_L, _dot, _predict, _predict_var, _predict_var_recurrence,
 // _one_step_ahead, _forecast, _predict_terms, _predict_cov, _sample_conditional, _leave_one_out, _grad_mean_weights,
-// _fit_mean_weights, _grad_noise_weights) and the helpers they
+// _fit_mean_weights, _grad_noise_weights, _grad_amplitudes) and the helpers they
 // share: the factor and route checks, the frame of one call's device work, prediction points and tiles.
 #include "api_internal.h"
 #include "clr_bmean_kernels.h"
 #include "clr_bnoise_kernels.h"
+#include "clr_bamplitude_kernels.h"
 
 #include <functional>
 #include <limits>
@@ -630,8 +631,13 @@ int clr_batch_grad_mean_weights(clr_batch* h, double* dw, int* status) {
   {
     ConsumerFrame frame{h};  // (untimed: solve_device_ms stays the solve's; the projection has its own events)
     HIP_TRY(hipEventRecord(h->proj_ev[0].get(), h->stream.get()));
-    if (!clr::launch_mean_project(h->basis_dev.p, h->basis_stride, h->bs_rm.p, h->mean_K, h->B, h->N, h->proj_part.p,
-                                  h->proj_out.p, h->stream.get()))
+    // (amplitudes in force: the solve is alpha' = K'^-1 y' of the scaled system, and alpha_y = alpha' / s in data units)
+    const bool launched = h->amp_active
+        ? clr::launch_mean_project_scaled(h->basis_dev.p, h->basis_stride, h->bs_rm.p, h->amp_s.p, h->mean_K, h->B, h->N,
+                                          h->proj_part.p, h->proj_out.p, h->stream.get())
+        : clr::launch_mean_project(h->basis_dev.p, h->basis_stride, h->bs_rm.p, h->mean_K, h->B, h->N, h->proj_part.p,
+                                   h->proj_out.p, h->stream.get());
+    if (!launched)
       return fail(CLR_UNSUPPORTED, "clr_batch_grad_mean_weights: B x N / 4096 workgroups do not fit one launch");
     HIP_TRY(hipEventRecord(h->proj_ev[1].get(), h->stream.get()));
     if ((st = frame.finish(dw, h->proj_out.p, B * K)) != CLR_OK) return st;
@@ -1420,8 +1426,13 @@ int clr_batch_grad_noise_weights(clr_batch* h, double* ds, int* status) {
   {
     ConsumerFrame frame{h};  // (untimed: the projection has its own events)
     HIP_TRY(hipEventRecord(h->proj_ev[0].get(), h->stream.get()));
-    if (!clr::launch_noise_project(h->noise_basis.p, h->noise_stride, h->bs_rm.p, h->loo_c.p, h->noise_K, h->B, h->N,
-                                   h->proj_part.p, h->proj_out.p, h->stream.get()))
+    // (amplitudes in force: diag(K_y^-1) = c' / s^2 and alpha_y = alpha' / s in data units)
+    const bool launched = h->amp_active
+        ? clr::launch_noise_project_scaled(h->noise_basis.p, h->noise_stride, h->bs_rm.p, h->loo_c.p, h->amp_s.p, h->noise_K,
+                                           h->B, h->N, h->proj_part.p, h->proj_out.p, h->stream.get())
+        : clr::launch_noise_project(h->noise_basis.p, h->noise_stride, h->bs_rm.p, h->loo_c.p, h->noise_K, h->B, h->N,
+                                    h->proj_part.p, h->proj_out.p, h->stream.get());
+    if (!launched)
       return fail(CLR_UNSUPPORTED, std::string(entry) + ": B x N / 4096 workgroups do not fit one launch");
     HIP_TRY(hipEventRecord(h->proj_ev[1].get(), h->stream.get()));
     if ((st = frame.finish(ds, h->proj_out.p, B * K)) != CLR_OK) return st;
@@ -1440,6 +1451,60 @@ int clr_batch_grad_noise_weights(clr_batch* h, double* ds, int* status) {
 
 int clr_batch_get_noise_project_ms(const clr_batch* h, double* device_ms) {
   if (device_ms) *device_ms = h->noise_project_ms;
+  return CLR_OK;
+}
+
+// ---- clr_batch_grad_amplitudes: the gradient with respect to the amplitudes of the per-sample amplitude model
+
+// loglike = -1/2 y'^T K'^-1 y' - 1/2 log det K' - sum_n log|s_n| + const with y' = r / s and K' = K + diag(d / s^2): s_n enters
+// through y'_n (d y'_n / d s_n = -y'_n / s_n), d'_n (d d'_n / d s_n = -2 d'_n / s_n) and the log term, so with alpha' =
+// K'^-1 y' and c' = diag(K'^-1)
+//   d loglike / d s_n = (alpha'_n y'_n + d'_n (c'_n - alpha'_n^2) - 1) / s_n ,   da[b][k] = sum_n Gamma_k[b][n] d loglike / d s_n.
+// clr_batch_grad_noise_weights' steps with another per-sample factor: leave-one-out's two device parts, one projection.
+int clr_batch_grad_amplitudes(clr_batch* h, double* da, int* status) {
+  static const char* entry = "clr_batch_grad_amplitudes";
+  int st = require_device(h->device);
+  if (st != CLR_OK) return st;
+  if (h->amp_K == 0) return fail(CLR_INVALID_ARGUMENT, std::string(entry) + ": no basis is set (clr_batch_set_amplitude_basis)");
+  if (!h->amp_active) return fail(CLR_INVALID_ARGUMENT, std::string(entry) + ": no amplitudes are in force (clr_batch_set_amplitudes)");
+  if (!da) return fail(CLR_INVALID_ARGUMENT, std::string(entry) + ": an output array");
+  if ((st = require_celerite_width(h, entry)) != CLR_OK) return st;
+  if ((st = require_factor(h, true)) != CLR_OK) return fail(st, std::string(entry) + ": " + g_last_error);
+  if (h->variance_changed)
+    return fail(CLR_NOT_COMPUTED, std::string(entry) + ": the amplitudes, their basis, the noise weights or the series were replaced "
+                                  "after the materialising run whose factor is in HBM -- that factor is another matrix': "
+                                  "materialise again (clr_batch_enqueue(h, 1))");
+  if ((st = require_route(h, entry)) != CLR_OK) return st;
+  if ((st = leave_one_out_device(h, true, true, nullptr, nullptr, nullptr)) != CLR_OK) return fail(st, std::string(entry) + ": " + g_last_error);
+  const size_t B = (size_t)h->B, K = (size_t)h->amp_K;
+  if ((st = h->proj_part.reserve(clr::mean_project_workspace(h->B, h->N, h->amp_K))) != CLR_OK) return st;
+  if ((st = h->proj_out.reserve(B * K)) != CLR_OK) return st;
+  for (clr::Event& e : h->proj_ev)
+    if (!e) HIP_TRY(clr::create_event(e));
+  {
+    ConsumerFrame frame{h};  // (untimed: the projection has its own events)
+    HIP_TRY(hipEventRecord(h->proj_ev[0].get(), h->stream.get()));
+    // (with amplitudes in force `y` and `diag` are y' and d' -- without the jitter --, both [B][N])
+    if (!clr::launch_amplitude_project(h->amp_basis.p, h->amp_stride, h->bs_rm.p, h->loo_c.p, h->y.p, h->diag.p, h->amp_s.p,
+                                       h->amp_K, h->B, h->N, h->proj_part.p, h->proj_out.p, h->stream.get()))
+      return fail(CLR_UNSUPPORTED, std::string(entry) + ": B x N / 4096 workgroups do not fit one launch");
+    HIP_TRY(hipEventRecord(h->proj_ev[1].get(), h->stream.get()));
+    if ((st = frame.finish(da, h->proj_out.p, B * K)) != CLR_OK) return st;
+  }
+  float ms = 0.f;
+  HIP_TRY(hipEventElapsedTime(&ms, h->proj_ev[0].get(), h->proj_ev[1].get()));
+  h->amp_project_ms = ms;
+  // the statuses of the evaluation in force; a problem without a factor (or whose draw or scale was refused): zeros
+  std::vector<int> stat;
+  if ((st = evaluation_statuses(h, stat)) != CLR_OK) return st;
+  for (size_t b = 0; b < B; ++b)
+    if (stat[b] != CLR_OK) std::fill(da + b * K, da + (b + 1) * K, 0.0);  // (the gradient's quiet semantics)
+  if (status) std::copy(stat.begin(), stat.end(), status);
+  return CLR_OK;
+}
+
+int clr_batch_get_amplitude_project_ms(const clr_batch* h, double* device_ms) {
+  if (device_ms) *device_ms = h->amp_project_ms;
   return CLR_OK;
 }
 
@@ -1483,6 +1548,10 @@ int clr_batch_fit_mean_weights(clr_batch* h, double min_pivot, double* w_hat, do
     return fail(CLR_INVALID_ARGUMENT, "clr_batch_fit_mean_weights: a constant mean is in force (clr_batch_set_mean): the fit is "
                                       "the linear mean's -- make the constant a basis function");
   if (h->mean_K == 0) return fail(CLR_INVALID_ARGUMENT, "clr_batch_fit_mean_weights: no basis is set (clr_batch_set_mean_basis)");
+  if (h->amp_active)
+    return fail(CLR_UNSUPPORTED, "clr_batch_fit_mean_weights: amplitudes are in force (clr_batch_set_amplitudes) -- the fit's "
+                                 "right-hand sides would be Phi / s, which is not built: remove the amplitude model for the fit, "
+                                 "or take clr_batch_grad_mean_weights' gradient");
   if ((st = require_celerite_width(h, "clr_batch_fit_mean_weights")) != CLR_OK) return st;
   if ((st = require_factor(h, true)) != CLR_OK) return st;
   if (h->B > 65535) return fail(CLR_UNSUPPORTED, "clr_batch_fit_mean_weights: at most 65535 problems per plan (a grid axis): shard the batch");

@@ -50,6 +50,21 @@ static int grad_chunk_spans(clr_batch* h) {
 // riders of every chunk from its element, one tangent wave per (direction, chunk) from the scanned start states, and a
 // walk over the chunks per direction (wide_grad_kernels.hip); problems the evaluation sent to the sequential recurrence
 // take the sequential tangent kernel.
+// The amplitude model's log term in the gradient's value (amplitude_adjust: value = value' - L); a problem whose scale was
+// refused gets NaN partials and CLR_INVALID_ARGUMENT, as a draw the kernel program refused does in clr_batch_grad_params.
+// The partials with respect to the coefficients are those of the scaled system, which is the model's likelihood up to L.
+static int amplitude_adjust_grad(clr_batch* h, double* value, double* grad, size_t NG, int* status) {
+  std::vector<int> refused((size_t)h->B, CLR_OK);
+  const int st = amplitude_adjust(h, value, nullptr, nullptr, refused.data());
+  if (st != CLR_OK) return st;
+  for (size_t b = 0; b < (size_t)h->B; ++b) {
+    if (refused[b] == CLR_OK) continue;
+    if (status) status[b] = refused[b];
+    if (grad) std::fill(grad + b * NG, grad + (b + 1) * NG, NAN);
+  }
+  return CLR_OK;
+}
+
 static int wide_batch_grad(clr_batch* h, double* value, double* grad, int* status) {
   const bool general = h->J_general > 0;
   const int Wt = h->J + h->J_general;
@@ -75,6 +90,8 @@ static int wide_batch_grad(clr_batch* h, double* value, double* grad, int* statu
     h->grad_scan_only = true;
     st = clr_batch_enqueue(h, 0);
     h->grad_scan_only = false;
+  } else {
+    h->amp_eval = h->amp_active ? 1 : 0;  // (no evaluation in front: the value below is of the series in force)
   }
   if (st != CLR_OK) return st;
   clr::BatchParams P0, P;
@@ -140,7 +157,7 @@ static int wide_batch_grad(clr_batch* h, double* value, double* grad, int* statu
   }
   h->grad_fallbacks = nfb;
   h->grad_reverse_used = false;
-  return CLR_OK;
+  return amplitude_adjust_grad(h, value, grad, NG, status);
 }
 
 int clr_batch_grad(clr_batch* h, double* value, double* grad, int* status) {
@@ -284,7 +301,8 @@ int clr_batch_grad(clr_batch* h, double* value, double* grad, int* status) {
   }
   std::vector<double> ll(B), ld(B), qd(B), res(B * NG);
   std::vector<int> stt(B), lvl(B);
-  if ((st = clr_batch_get_results(h, ll.data(), ld.data(), qd.data(), stt.data())) != CLR_OK) return st;
+  // (the scaled system's results: the amplitude model's log term is folded into the value at the end)
+  if ((st = batch_results_scaled(h, ll.data(), ld.data(), qd.data(), stt.data())) != CLR_OK) return st;
   HIP_TRY(hipMemcpyAsync(res.data(), h->g_res.p, B * NG * sizeof(double), hipMemcpyDeviceToHost, h->stream.get()));
   HIP_TRY(hipMemcpyAsync(lvl.data(), P.need_exact, B * sizeof(int), hipMemcpyDeviceToHost, h->stream.get()));
   std::vector<double> drift;
@@ -359,7 +377,7 @@ int clr_batch_grad(clr_batch* h, double* value, double* grad, int* status) {
       if (!(h->host_jitter[b] > 2.220446049250313e-16)) grad[b * NG] = 0.0;  // solver.cpp:379-389,419-426
     }
   }
-  return CLR_OK;
+  return amplitude_adjust_grad(h, value, grad, NG, status);
 }
 
 int clr_batch_get_grad_fallbacks(const clr_batch* h, int* count) {
@@ -466,6 +484,9 @@ int clr_batch_grad_mean(clr_batch* h, double* value, double* grad, double* dmean
   if (dmean && h->mean_K > 0)
     return fail(CLR_UNSUPPORTED, "clr_batch_grad_mean: a linear mean is in force (clr_batch_set_mean_basis): its partials are "
                                  "clr_batch_grad_mean_weights'");
+  if (dmean && h->amp_active)
+    return fail(CLR_UNSUPPORTED, "clr_batch_grad_mean: amplitudes are in force (clr_batch_set_amplitudes): a constant in data units "
+                                 "is the mean-basis function 1, its partial clr_batch_grad_mean_weights'");
   const size_t B = (size_t)h->B;
   std::vector<int> stat(B);
   // [B] partials | [B] ints: the problems left to the recurrence below

@@ -301,6 +301,23 @@ struct clr_batch {
   clr::Event noise_ev;
   double noise_project_ms = 0.0;      // device time of the last clr_batch_grad_noise_weights' projection
   bool variance_changed = false;      // the variances in `diag` were replaced since the last materialising run (its factor is another matrix')
+  // clr_batch_set_amplitude_basis / _set_amplitudes: a per-sample amplitude, s[b][n] = sum_k a[b][k] Gamma_k[b][n] (amp_K > 0:
+  // a basis is set; amp_active: amplitudes are in force).  With amplitudes in force `y` holds r / s and `diag` holds d / (s
+  // * s), r and d the residual and the variances the plan would otherwise read: the caller's arrays stay in y_src /
+  // diag_src ("a transform is in force": y_transformed / diag_transformed below), `amp_s` keeps s resident as [B][N], and
+  // amp_L holds sum_n log|s_n| | the flags of problems with a zero or non-finite s_n, fetched behind the forming pass
+  // (amp_ev) and folded into the results on the host (amplitude_adjust)
+  int amp_K = 0;
+  long amp_stride = 0;                // 0: one basis [K][N] for all problems, K * N: [B][K][N]
+  bool amp_active = false;
+  bool amp_formed = false;            // the forming pass has run for the amplitudes in force (a series is set)
+  int amp_eval = 0;                   // the evaluation in force: 0 ran without amplitudes, 1 its log term is amp_back's, 2 host_amp_L's
+  std::vector<double> host_amp_L;     // L[B] | flag[B] of the evaluation in force, once the forming pass has moved on
+  std::vector<double> host_amp;       // [B][K] (empty until clr_batch_set_amplitudes)
+  DevBuf amp_basis, amp_dev, amp_s, amp_part, amp_Lf;
+  clr::PinnedBuffer<double> amp_pin, amp_back;  // staging of the amplitudes' upload; L[B] | flag[B] as downloaded
+  clr::Event amp_ev, amp_back_ev;     // recorded behind the upload / the download
+  double amp_project_ms = 0.0;        // device time of the last clr_batch_grad_amplitudes' projection
   // clr_batch_grad_mean: the narrow reverse sweep sums the adjoint of y per chunk (BatchParams::g_ysum) and reduces it
   // into mean_out; grad_mean_done[b] says which problems it settled (the rest take mean_partial_batch)
   bool grad_want_mean = false;
@@ -442,6 +459,12 @@ struct clr_batch {
 int warm_resolve(clr_batch* h, bool* pin_current);
 // draws the kernel program refused: NaN and CLR_INVALID_ARGUMENT in the arrays given
 void mark_refused(const clr_batch* h, double* a, double* b, double* c, int* status);
+// clr_batch_get_results before the amplitude model's log term: the scaled system's loglike', logdet', quad'
+int batch_results_scaled(clr_batch* h, double* loglike, double* logdet, double* quad, int* status);
+// the amplitude model's log term L = sum_n log|s_n| folded into results of the scaled system, in double on the host:
+// logdet = logdet' + (L + L), loglike = loglike' - L, quad = quad'; a problem with a zero or non-finite s_n inside its
+// length: NaN and CLR_INVALID_ARGUMENT (mark_refused's quiet semantics).  No amplitudes in force: nothing is touched.
+int amplitude_adjust(clr_batch* h, double* loglike, double* logdet, double* quad, int* status);
 
 // ---- what a replaced input of a plan leaves stale: one function per cause, called by the entry points ----------
 namespace {

@@ -106,6 +106,7 @@ struct clr_sharded {
   int n_params = 0;  // of the kernel set by clr_sharded_set_kernel
   int mean_K = 0;    // of the basis set by clr_sharded_set_mean_basis
   int noise_K = 0;   // of the basis set by clr_sharded_set_noise_basis
+  int amp_K = 0;     // of the basis set by clr_sharded_set_amplitude_basis
   std::vector<int> device, lo, hi;
   std::vector<clr_batch*> plan;
   std::vector<std::unique_ptr<Worker>> worker;
@@ -667,6 +668,70 @@ int clr_sharded_get_noise_project_ms(const clr_sharded* h, double* device_ms) {
   for (clr_batch* p : h->plan) {
     double v = 0.0;
     (void)clr_batch_get_noise_project_ms(p, &v);
+    m = std::max(m, v);
+  }
+  if (device_ms) *device_ms = m;
+  return CLR_OK;
+}
+
+/* ---- the amplitude model: clr_batch_set_amplitude_basis / _set_amplitudes / _grad_amplitudes over the shards -------- */
+int clr_sharded_set_amplitude_basis(clr_sharded* h, int K, const double* gamma, long gamma_stride) {
+  const bool remove = K == 0 || !gamma;
+  const long per = (long)K * h->N;
+  if (!remove) {  // (checked here: an invalid basis leaves EVERY shard unchanged)
+    g_sharded_error = "clr_sharded_set_amplitude_basis: 1 <= K <= CLR_MAX_AMPLITUDE_BASIS = 16, gamma_stride 0 or K * N, finite entries";
+    if (K < 0 || K > CLR_MAX_AMPLITUDE_BASIS || (gamma_stride != 0 && gamma_stride != per)) return CLR_INVALID_ARGUMENT;
+    // the lengths in force, as clr_sharded_set_noise_basis: of the one shared basis the tail past the longest problem OF
+    // THE BATCH is never looked at
+    std::vector<int> len((size_t)h->B, h->N);
+    for (size_t s = 0; s < h->plan.size(); ++s) (void)clr_batch_get_lengths(h->plan[s], len.data() + h->lo[s]);
+    const int longest = *std::max_element(len.begin(), len.end());
+    const long rows = gamma_stride ? (long)K * h->B : K;
+    for (long r = 0; r < rows; ++r) {
+      const int upto = gamma_stride ? len[(size_t)(r / K)] : longest;
+      for (int i = 0; i < upto; ++i)
+        if (!std::isfinite(gamma[r * h->N + i])) return CLR_INVALID_ARGUMENT;
+    }
+  }
+  int st = resolve_all(h);  // (an evaluation in flight is settled on ITS series)
+  if (st != CLR_OK) return st;
+  st = h->all([=](int s) {
+    return clr_batch_set_amplitude_basis(h->plan[s], remove ? 0 : K, remove ? nullptr : gamma + h->lo[s] * gamma_stride, gamma_stride);
+  });
+  if (st == CLR_OK) h->amp_K = remove ? 0 : K;
+  return st;
+}
+
+int clr_sharded_set_amplitudes(clr_sharded* h, const double* a) {
+  const long K = h->amp_K;
+  g_sharded_error = "clr_sharded_set_amplitudes: a basis must be set (clr_sharded_set_amplitude_basis) and the amplitudes finite";
+  if (K == 0 || !a) return CLR_INVALID_ARGUMENT;
+  for (long i = 0; i < K * h->B; ++i)
+    if (!std::isfinite(a[i])) return CLR_INVALID_ARGUMENT;
+  const int st = resolve_all(h);
+  if (st != CLR_OK) return st;
+  return h->all([=](int s) { return clr_batch_set_amplitudes(h->plan[s], a + h->lo[s] * K); });
+}
+
+int clr_sharded_get_log_amplitude_sum(clr_sharded* h, double* L) {
+  g_sharded_error = "clr_sharded_get_log_amplitude_sum: an output array";
+  return on_slices(h, L != nullptr, [=](clr_batch* p, long lo) { return clr_batch_get_log_amplitude_sum(p, L + lo); });
+}
+
+int clr_sharded_grad_amplitudes(clr_sharded* h, double* da, int* status) {
+  const long K = h->amp_K;
+  g_sharded_error = "clr_sharded_grad_amplitudes: a basis must be set (clr_sharded_set_amplitude_basis), and an output array";
+  return on_slices(h, K > 0 && da, [=](clr_batch* p, long lo) {
+    return clr_batch_grad_amplitudes(p, da + lo * K, status ? status + lo : nullptr);
+  });
+}
+
+// the projection's device time: the largest over the shards, which run concurrently
+int clr_sharded_get_amplitude_project_ms(const clr_sharded* h, double* device_ms) {
+  double m = 0.0;
+  for (clr_batch* p : h->plan) {
+    double v = 0.0;
+    (void)clr_batch_get_amplitude_project_ms(p, &v);
     m = std::max(m, v);
   }
   if (device_ms) *device_ms = m;

@@ -278,7 +278,7 @@ int clr_batch_set_series(clr_batch* h,
  *   (widths above 8) and plans with general terms, every materialising run, and every consumer of the materialised
  *   factor or of the padded rows: clr_batch_get_factor, _solve, _dot_L, _dot, _predict*, _one_step_ahead, _forecast,
  *   _predict_terms, _predict_cov, _sample_conditional, _leave_one_out, _grad_mean_weights, _fit_mean_weights,
- *   _grad_noise_weights.
+ *   _grad_noise_weights, _grad_amplitudes.
  * clr_batch_get_lengths: the lengths in force (N for every problem of a uniform plan). */
 int clr_batch_set_series_ragged(clr_batch* h,
                                 const double* t, long t_stride,
@@ -594,6 +594,67 @@ int clr_batch_set_noise_basis(clr_batch* h, int K, const double* psi, long psi_s
 int clr_batch_set_noise_weights(clr_batch* h, const double* s);
 int clr_batch_grad_noise_weights(clr_batch* h, double* ds, int* status);
 int clr_batch_get_noise_project_ms(const clr_batch* h, double* device_ms);
+/* A PER-SAMPLE AMPLITUDE MODEL (multi-band): the same latent process f seen with another amplitude per band,
+ *     y_n = s_n f(t_n) + eps_n ,   s[p][n] = sum_k a[p][k] Gamma_k[p][n] ,   K <= CLR_MAX_AMPLITUDE_BASIS basis functions
+ * -- multi-colour photometry of one variable source (Gamma_k the indicator of band k, a_k its amplitude), a radial velocity
+ * next to an activity indicator, a chromatic amplitude law (Gamma a polynomial in wavelength): the rank-one Kronecker case
+ * of multi-band celerite models.  With S = diag(s) the data's covariance is K_y = S K S + D = S (K + S^-1 D S^-1) S, so
+ *     log det K_y = log det K' + 2 sum_n log|s_n| ,   r^T K_y^-1 r = y'^T K'^-1 y' ,   K' = K + diag(d'),
+ *     y'_n = r_n / s_n ,   d'_n = d_n / (s_n * s_n)
+ * and no new factorisation is needed: every route of the plan evaluates the model once the device has rewritten the
+ * series it reads.  An optimiser or sampler step sends B x K amplitudes.
+ *
+ * clr_batch_set_amplitude_basis -- gamma is host [K][N] with gamma_stride == 0 (one basis for all problems) or [B][K][N]
+ * with gamma_stride == K * N; uploaded once, before or after clr_batch_set_series.  Setting a basis alone changes nothing:
+ * zero amplitudes are no neutral start (s = 0), so the plan stays the plain plan until the first clr_batch_set_amplitudes;
+ * a new basis drops the amplitudes in force.  K == 0 or gamma == NULL removes the model and restores the plain plan, bit
+ * for bit.  CLR_INVALID_ARGUMENT, the plan unchanged: a non-finite entry (with per-problem lengths in force: within a
+ * problem's length, of a shared basis up to the longest problem), K > CLR_MAX_AMPLITUDE_BASIS, another stride, a constant
+ * mean in force -- the constant mean (clr_batch_set_mean) and the amplitude model are mutually exclusive, as the two means
+ * are: a constant in data units is the mean-basis function 1; clr_batch_set_mean refuses likewise while an amplitude
+ * basis is set.  A later clr_batch_set_series / _set_series_ragged keeps basis and amplitudes in force and applies them
+ * to the new series.
+ *
+ * clr_batch_set_amplitudes -- a is host [B][K].  The device forms, every product, sum and quotient rounded on its own (no
+ * FMA),
+ *     s  = a[p][0] Gamma_0[n] ,  s = s + a[p][k] Gamma_k[n]  (k = 1 .. K - 1, in this order)
+ *     y' = r / s          r: the caller's y, or the residual of the linear mean in force
+ *     d' = d / (s * s)    d: the caller's diag, or diag_eff of the noise model in force
+ * -- the bits of those NumPy expressions -- and every route reads y' and d'; the plan's scalar jitter is added on top of
+ * d' as before: it is part of the kernel, in latent units.  The caller's arrays stay in HBM untouched (a shared y or diag
+ * becomes per problem), s stays resident as [B][N] doubles.  After clr_batch_set_mean_weights / _set_noise_weights the
+ * division is applied again.  With per-problem lengths the tails stay padding; the tails of Gamma and s are never looked
+ * at.  The factor of an earlier materialising run is that of the earlier amplitudes.  Amplitudes equal to the ones in
+ * force: nothing is done.  CLR_INVALID_ARGUMENT: a non-finite amplitude, or no basis set.
+ *     The same pass sums L[p] = sum_n log|s[p][n]| over the problem's length (fixed slabs of 4096 samples, the slabs'
+ * partials added in slab order, no atomics: a problem's bits depend on neither the batch size, a sharding nor the run);
+ * clr_batch_get_log_amplitude_sum returns it (zeros while no amplitudes are in force).  Every entry that returns a plan's
+ * results -- clr_batch_get_results, hence _evaluate*, the value of clr_batch_grad / _grad_params -- then reports, computed
+ * on the host in double with exactly these operations,
+ *     logdet = logdet' + (L + L) ,   loglike = loglike' - L ,   quad = quad'     (primed: of the system K', y').
+ * A zero or non-finite s_n inside a problem's length: that problem reports NaN and CLR_INVALID_ARGUMENT (the quiet
+ * semantics of a draw the kernel program refuses; its scans ran on the stand-in s_n = 1); no other problem is affected.
+ *
+ * clr_batch_grad_amplitudes -- da host [B][K]: with alpha' = K'^-1 y', c' = diag(K'^-1) and d' without the jitter,
+ *     da[p][k] = d loglike_p / d a[p][k] = sum_n Gamma_k[p][n] (alpha'_n y'_n + d'_n (c'_n - alpha'_n^2) - 1) / s_n ,
+ * from the factor of a materialising run MADE AFTER the amplitudes (and the basis, the noise weights, the series) were set:
+ * CLR_NOT_COMPUTED otherwise.  clr_batch_grad_noise_weights' steps, domain, refusals (naming this entry) and status
+ * semantics; clr_batch_get_amplitude_project_ms reports the projection's device time.
+ *     With amplitudes in force clr_batch_grad_mean_weights returns sum_n Phi_k alpha'_n / s_n and
+ * clr_batch_grad_noise_weights 1/2 sum_n Psi_k (alpha'_n^2 - c'_n) / s_n^2 -- the data-unit alpha_y = alpha' / s and
+ * diag(K_y^-1) = c' / s^2 --; without amplitudes their bits are unchanged.  clr_batch_fit_mean_weights returns
+ * CLR_UNSUPPORTED while amplitudes are in force (its right-hand sides would be Phi / s); so does clr_batch_grad_mean's
+ * partial with respect to a constant mean.
+ *     The factor's consumers run on the system in force, K' and y': clr_batch_predict*, _forecast, _predict_terms,
+ * _predict_cov and _sample_conditional return the posterior of the LATENT process f, exactly (k*^T S K_y^-1 r = k*^T K'^-1
+ * y', k** - k*^T S K_y^-1 S k* = k** - k*^T K'^-1 k*): a band's curve is a_band f.  clr_batch_solve(b) is K'^-1 b, _dot and
+ * _dot_L multiply by K' and its factor; leave-one-out and the one-step-ahead innovations are those of the scaled samples. */
+#define CLR_MAX_AMPLITUDE_BASIS 16
+int clr_batch_set_amplitude_basis(clr_batch* h, int K, const double* gamma, long gamma_stride);
+int clr_batch_set_amplitudes(clr_batch* h, const double* a);
+int clr_batch_get_log_amplitude_sum(clr_batch* h, double* L);
+int clr_batch_grad_amplitudes(clr_batch* h, double* da, int* status);
+int clr_batch_get_amplitude_project_ms(const clr_batch* h, double* device_ms);
 /* clr_batch_fit_mean_weights -- the weights that MAXIMISE the log-likelihood of every problem at the coefficients in
  * force.  The log-likelihood is exactly quadratic in the weights, so they need no optimiser: with r = y - Phi w0 the
  * residual at the weights w0 in force,
@@ -1063,6 +1124,15 @@ int clr_sharded_set_noise_basis(clr_sharded* h, int K, const double* psi, long p
 int clr_sharded_set_noise_weights(clr_sharded* h, const double* s);
 int clr_sharded_grad_noise_weights(clr_sharded* h, double* ds, int* status);
 int clr_sharded_get_noise_project_ms(const clr_sharded* h, double* device_ms);  /* the largest over the shards */
+/* The amplitude model over the shards (clr_batch_set_amplitude_basis / _set_amplitudes / _get_log_amplitude_sum /
+ * _grad_amplitudes): every shard takes its slice of gamma (gamma_stride K * N) or the one basis (0), of a[B][K], L[B] and
+ * da[B][K]; an invalid basis or amplitude leaves every shard unchanged.  The results are those of the unsharded plan, bit
+ * for bit. */
+int clr_sharded_set_amplitude_basis(clr_sharded* h, int K, const double* gamma, long gamma_stride);
+int clr_sharded_set_amplitudes(clr_sharded* h, const double* a);
+int clr_sharded_get_log_amplitude_sum(clr_sharded* h, double* L);
+int clr_sharded_grad_amplitudes(clr_sharded* h, double* da, int* status);
+int clr_sharded_get_amplitude_project_ms(const clr_sharded* h, double* device_ms);  /* the largest over the shards */
 /* clr_batch_fit_mean_weights over the whole batch: every shard fits its slice; the same bits as the unsharded plan */
 int clr_sharded_fit_mean_weights(clr_sharded* h, double min_pivot, double* w_hat, double* cov, double* gram,
                                  double* quad_profiled, double* logdet_gram, int* status);
