@@ -148,6 +148,10 @@ def _load():
     lib.clr_sharded_sample_conditional.argtypes = [C.c_void_p, C.c_int, _dp, C.c_long, C.c_int, _dp, C.c_double, C.c_double, _dp, _ip]
     lib.clr_batch_set_conditional_tile.argtypes = [C.c_void_p, C.c_int]
     lib.clr_sharded_set_conditional_tile.argtypes = [C.c_void_p, C.c_int]
+    lib.clr_batch_information.argtypes = [C.c_void_p, C.c_int, _dp, _ip]
+    lib.clr_sharded_information.argtypes = [C.c_void_p, C.c_int, _dp, _ip]
+    lib.clr_batch_set_information_tile.argtypes = [C.c_void_p, C.c_int]
+    lib.clr_sharded_set_information_tile.argtypes = [C.c_void_p, C.c_int]
     lib.clr_gram_solve.argtypes = [C.c_int, C.c_int, _dp, _dp, C.c_double] + [_dp] * 4 + [_ip]
     lib.clr_kernel_create.argtypes = [C.c_int, _ip, C.c_int, _dp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
     lib.clr_kernel_destroy.argtypes = [C.c_void_p]
@@ -1099,6 +1103,7 @@ class BatchedGP(object):
         p = np.ascontiguousarray(params, dtype=np.float64)
         if p.shape != (self.B, prog.n_params):
             raise ValueError("dimension mismatch")
+        self._last_params = p                              # (information_parameters: the Jacobian at these rows)
         return p
 
     def evaluate_parameters(self, params, mean=None, mean_weights=None, noise_weights=None):
@@ -1489,6 +1494,46 @@ class BatchedGP(object):
             return value, grad, dmean, st
         _check(_load().clr_batch_grad(self._h, _ptr(value), _ptr(grad), st.ctypes.data_as(_ip)))
         return value, grad, st
+
+    def information(self, mean_partial=False):
+        """``(info[B, M, M], status[B])``: the information matrix of every problem at the coefficients and on the series
+        in force (``clr_batch_information``; Fisher scoring on the innovations form), ``M = 1 + 2 J_real + 4 J_comp`` in
+        the order of :meth:`grad_log_likelihood`'s columns; ``mean_partial=True``: ``M + 1`` with the constant mean
+        last.  Symmetric, positive semi-definite; its expectation over data drawn from the model is the Fisher
+        information -- it is not the Hessian.  A problem that is not ``CLR_OK`` is all NaN with its status; ``jitter <=
+        2.2e-16`` zeroes the jitter row and column.  Narrow plans with celerite terms; the blocks of linear-mean, noise
+        and amplitude weights are not covered.  Chain to kernel parameters with :func:`chain_information`."""
+        M = 1 + 2 * self.J_real + 4 * self.J_comp + (1 if mean_partial else 0)
+        info, st = np.empty((self.B, M, M)), np.empty(self.B, dtype=np.int32)
+        self._information(int(bool(mean_partial)), info, st)
+        return info, st
+
+    def _information(self, mean_partial, info, st):
+        _check(_load().clr_batch_information(self._h, mean_partial, _ptr(info), st.ctypes.data_as(_ip)))
+
+    def set_information_tile(self, problems=0):
+        """Problems per tile of :meth:`information` (``clr_batch_set_information_tile``); 0: as many as hold their rows
+        in 1 GiB."""
+        _check(_load().clr_batch_set_information_tile(self._h, int(problems)))
+
+    def information_device_ms(self):
+        """Device time of the last :meth:`information` in ms (``clr_batch_get_information_ms``)."""
+        ms = C.c_double()
+        lib = _load()
+        lib.clr_batch_get_information_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+        _check(lib.clr_batch_get_information_ms(self._h, C.byref(ms)))
+        return ms.value
+
+    def information_parameters(self, mean_partial=False):
+        """``(info[B, P(+1), P(+1)], status[B])`` in the kernel's parameters at the rows of the last
+        :meth:`evaluate_parameters`: :func:`chain_information` of :meth:`information` with the program's Jacobian there
+        (exact for this form: no second derivative of a coefficient formula enters).  A draw the program refused is NaN."""
+        prog, p = getattr(self, "kernel_program", None), getattr(self, "_last_params", None)
+        if prog is None or p is None:
+            raise RuntimeError("no parameters are in force: call set_kernel and evaluate_parameters first")
+        info, st = self.information(mean_partial)
+        jac, jj, _ = prog.jacobian(p, status=True)
+        return chain_information(info, jac, jj, mean_partial), st
 
     def set_grad_mode(self, mode="reverse", stored_state_distance=0, drift_tolerance=0.0):
         """``"reverse"`` (default: one sweep for all partials), ``"forward"`` (one tangent per partial) or
@@ -1899,6 +1944,16 @@ class ShardedBatchedGP(object):
         lib.clr_sharded_grad.argtypes = [C.c_void_p, _dp, _dp, _ip]
         self._ok(lib.clr_sharded_grad(self._h, _ptr(value), _ptr(grad), st.ctypes.data_as(_ip)))
         return value, grad, st
+
+    information = BatchedGP.information
+    information_parameters = BatchedGP.information_parameters
+
+    def _information(self, mean_partial, info, st):
+        self._ok(_load().clr_sharded_information(self._h, mean_partial, _ptr(info), st.ctypes.data_as(_ip)))
+
+    def set_information_tile(self, problems=0):
+        """:meth:`BatchedGP.set_information_tile` on every shard."""
+        self._ok(_load().clr_sharded_set_information_tile(self._h, int(problems)))
 
     def enqueue(self):
         self._ok(_load().clr_sharded_enqueue(self._h))
@@ -2426,3 +2481,25 @@ def chain_gradient(grad, jac, jitter_jac, dmean=None):
     if dmean.shape[0] != full.shape[0]:
         raise ValueError("dimension mismatch")
     return np.concatenate([full, dmean], axis=1)
+
+
+def chain_information(info, jac, jitter_jac, mean_partial=False):
+    """The information matrix in the kernel's parameters, ``[B, P, P]``, from the batched coefficient matrix ``info``
+    (``[B, M, M]``, ``BatchedGP.information``) and the tables of :func:`kernel_coefficient_jacobian_table`: the bilinear
+    twin of :func:`chain_gradient` -- per draw ``T = [jitter_jac | jac]`` (``[P, M]``) and ``T info T^T``.
+    ``mean_partial=True``: ``info`` is ``[B, M + 1, M + 1]`` with the constant mean last, which passes through;
+    ``[B, P + 1, P + 1]``."""
+    info = np.asarray(info, dtype=np.float64)
+    jac = np.asarray(jac, dtype=np.float64)
+    jitter_jac = np.asarray(jitter_jac, dtype=np.float64)
+    extra = 1 if mean_partial else 0
+    if (info.ndim != 3 or jac.ndim != 3 or jitter_jac.shape != jac.shape[:2] or info.shape[0] != jac.shape[0]
+            or info.shape[1] != info.shape[2] or info.shape[1] != 1 + jac.shape[2] + extra):
+        raise ValueError("dimension mismatch")
+    B, P = jac.shape[:2]
+    T = np.zeros((B, P + extra, info.shape[1]))
+    T[:, :P, 0] = jitter_jac
+    T[:, :P, 1:1 + jac.shape[2]] = jac
+    if mean_partial:
+        T[:, P, -1] = 1.0
+    return np.einsum("bpi,bij,bqj->bpq", T, info, T)

@@ -4,6 +4,7 @@
 //   api_batch.hip   clr_batch_*: plans, HBM residency, path selection, evaluation, results
 //   api_batch_consumers.hip  clr_batch_*: the consumers of a plan's factor and coefficients (solve .. grad_noise_weights)
 //   api_grad.hip    clr_batch_grad*: the gradient entry points
+//   api_information.hip  clr_batch_information: the information matrix of every problem
 //   api_kernels.hip the small kernels the plans launch themselves (finalize, relayouts, factor de-interleave)
 // Here: error reporting, the device buffer types, the two handle structs, and the functions that turn a plan's state into
 // kernel parameters (used by the evaluation and by the gradient).  Everything is internal to libcelerite_hip.so.
@@ -352,6 +353,12 @@ struct clr_batch {
   int grad_forward_reruns = 0;        // ... and the problems redone by the forward-mode kernels
   bool grad_reverse_used = false;
   std::vector<double> host_jitter;    // per problem, as set (the reference zeroes d/d jitter at jitter <= eps)
+  // clr_batch_information (clr_binfo_kernels.h): the tangent states of every (gradient chunk, direction); a tile's rows;
+  // its Gram pass' slab partials with the tile's matrices behind them.  Scratch of one call: nothing in them is cached
+  DevBuf i_tan, i_rows, i_part;
+  int information_tile = 0;           // clr_batch_set_information_tile: problems per tile (0: automatic)
+  clr::Event info_ev[2];              // ... its two timing events, created by the first call
+  double information_ms = 0.0;        // device time of the last call, from its evaluation to its last Gram pass
   bool grad_scan_only = false;        // the evaluation inside clr_batch_grad: by the scan, its start states are needed
   int grad_fallbacks = 0;             // problems of the last gradient that took the sequential kernel
   double cert_resid = 1e-11;          // end-state mismatch of the chunked replay that still counts as consistent

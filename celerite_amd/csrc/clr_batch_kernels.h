@@ -1032,6 +1032,7 @@ __global__ void __launch_bounds__(64) warm_check_kernel(const BatchParams P) {
 #include "clr_bfilter_kernels.h"
 #include "clr_bterms_kernels.h"
 #include "clr_bcond_kernels.h"
+#include "clr_binfo_kernels.h"
 namespace clr {
 
 // One table entry per (JR, JC): host-callable launchers.
@@ -1047,6 +1048,9 @@ struct BatchLaunchers {
   void (*warm)(const BatchParams&, hipStream_t);  // warm_kernel + warm_check_kernel
   void (*grad)(const BatchParams&, hipStream_t);  // riders + tangents + walk over the chunks (needs P.fast_trig)
   void (*grad_reverse)(const BatchParams&, hipStream_t);  // riders + record, adjoint walk, reverse sweep, reduction
+  // the information matrix (clr_binfo_kernels.h).  what = 0: riders, zero-start tangents and the walk for the whole plan
+  // (-> I.tan); what = 1: the rows of the tile I.b0 .. I.b0 + I.nb by the chunked route, what = 2: by the sequential form
+  void (*information)(const BatchParams&, const BInfoParams& I, int what, hipStream_t);
   // K^-1 b for all problems and right-hand sides from the materialised factor (clr_bsolve_kernels.h): S.xT in / out
   void (*bsolve)(const BatchParams&, BSolveParams S, hipStream_t);
   // L z for all problems and right-hand sides from the materialised factor (clr_bdotl_kernels.h): S.xT in / out
@@ -1433,8 +1437,24 @@ struct BatchImpl {
     hipLaunchKernelGGL((grad_reduce_slab_kernel<JR + 2 * JC>), dim3(nslab, P.B), dim3(256), 0, s, P, Sh::NG);
     hipLaunchKernelGGL((grad_reduce_kernel<JR + 2 * JC>), dim3(P.B), dim3(64), 0, s, P, Sh::NG, nslab);
   }
+  static void information(const BatchParams& P, const BInfoParams& I, int what, hipStream_t s) {
+    using Sh = GradShape<JR, JC>;
+    const unsigned gx = (P.g_nchunk + 63) / 64, gz = Sh::GROUPS + (I.mean ? 1 : 0);
+    if (what == 0) {
+      hipLaunchKernelGGL((grad_riders_kernel<JR, JC, true>), dim3(gx, P.B), dim3(64), 0, s, P);
+      hipLaunchKernelGGL((info_chunk_kernel<JR, JC, true>), dim3(gx, P.B, gz), dim3(64), 0, s, P, I, 0);
+      const long n = (long)P.B * I.M;
+      hipLaunchKernelGGL((info_walk_kernel<JR + 2 * JC>), dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, P, I);
+    } else if (what == 1) {
+      hipLaunchKernelGGL((info_chunk_kernel<JR, JC, true>), dim3(gx, I.nb, gz), dim3(64), 0, s, P, I, 1);
+    } else if (P.fast_trig) {
+      hipLaunchKernelGGL((info_chunk_kernel<JR, JC, true>), dim3(1, I.nb, gz), dim3(64), 0, s, P, I, 2);
+    } else {
+      hipLaunchKernelGGL((info_chunk_kernel<JR, JC, false>), dim3(1, I.nb, gz), dim3(64), 0, s, P, I, 2);
+    }
+  }
   static BatchLaunchers table() {
-    return BatchLaunchers{&summarize, &prefix, &correct, &replay, &sequential, &compose_check, &warm, &grad, &grad_reverse,
+    return BatchLaunchers{&summarize, &prefix, &correct, &replay, &sequential, &compose_check, &warm, &grad, &grad_reverse, &information,
                           &bsolve, &bdotl, &bdot, &bpredvar, &binvdiag, &bpredvar_rec, &bfilter, &bterms, &bcond, &expand, Widths<JR, JC>::ELEM, Widths<JR, JC>::START};
   }
 };

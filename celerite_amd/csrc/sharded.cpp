@@ -531,6 +531,23 @@ int clr_sharded_grad(clr_sharded* h, double* value, double* grad, int* status) {
   });
 }
 
+// the information matrix of every problem at the coefficients in force: clr_batch_information on every shard concurrently
+int clr_sharded_information(clr_sharded* h, int mean_partial, double* info, int* status) {
+  const long M = 1 + 2 * (long)h->J_real + 4 * (long)h->J_comp + (mean_partial ? 1 : 0);
+  if (!info) return CLR_INVALID_ARGUMENT;
+  const int st0 = resolve_all(h);
+  if (st0 != CLR_OK) return st0;
+  return h->all([=](int s) {
+    const long lo = h->lo[s];
+    return clr_batch_information(h->plan[s], mean_partial, info + lo * M * M, status ? status + lo : nullptr);
+  });
+}
+
+int clr_sharded_set_information_tile(clr_sharded* h, int problems) {
+  for (clr_batch* p : h->plan) clr_batch_set_information_tile(p, problems);
+  return CLR_OK;
+}
+
 int clr_sharded_evaluate(clr_sharded* h, const double* jitter, const double* a_real, const double* c_real,
                          const double* a_comp, const double* b_comp, const double* c_comp,
                          const double* d_comp, double* loglike, double* logdet, double* quad, int* status) {

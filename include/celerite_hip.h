@@ -941,6 +941,34 @@ int clr_batch_grad(clr_batch* h, double* value, double* grad, int* status);
  * dmean = sum_n x1_n x_n / D_n; one workgroup per problem, sequential in n. */
 int clr_batch_grad_mean(clr_batch* h, double* value, double* grad, double* dmean, int* status);
 int clr_batch_get_grad_fallbacks(const clr_batch* h, int* count);
+/* The information matrix of every problem at the coefficients and on the series in force (Fisher scoring, Harvey 1989
+ * section 3.4).  With z = L^-1 r the one-step-ahead innovations and D their variances,
+ * loglike = -1/2 sum_n (log D_n + z_n^2 / D_n + log 2 pi), and for two directions i, j
+ *     info[b][i][j] = sum_n 1/2 (d_i D_n / D_n)(d_j D_n / D_n) + (d_i z_n)(d_j z_n) / D_n :
+ * first-order tangents only, a Gram matrix of 2 N numbers per direction -- positive semi-definite by construction, its
+ * D half independent of the data, its expectation over data drawn from the model the Fisher information
+ * 1/2 tr(K^-1 K_i K^-1 K_j).  It is NOT the Hessian of the log-likelihood (no second derivative enters).
+ * info is [B][M][M] row-major, M = 1 + 2 J_real + 4 J_comp (+ 1 with mean_partial), the directions in the order of
+ * clr_batch_grad's columns (jitter, a_real, c_real, a_comp, b_comp, c_comp, d_comp), then the constant mean (d D = 0,
+ * d r = -1); status is [B] (may be null).  The residual, variances and amplitude-scaled series in force are what every
+ * route reads, as for clr_batch_grad.  Written symmetric bit for bit.  A problem whose status is not CLR_OK (not positive
+ * definite, a draw or a scale refused) gets an all-NaN matrix and its status, the others are unaffected; a problem with
+ * jitter <= DBL_EPSILON gets a zero jitter row and column (the rule of the gradient's column).
+ * Narrow plans (widths 1..8), celerite terms, any N >= 1, per-problem lengths included (problem b's matrix is that of its
+ * first n_b samples); wide plans and general terms: CLR_UNSUPPORTED.  Parallel in n on chunked plans (the chunks'
+ * tangent start states from a walk over the gradient's riders, then every chunk again for its rows, then the Gram pass
+ * in slabs of a fixed size and order: no atomics, a problem's bits depend on neither the batch, the tile nor a sharding);
+ * problems the scan sent to the sequential recurrence, and every problem under clr_batch_set_exact, take a sequential
+ * form.  The rows of a tile of problems (16 M bytes per sample and problem) live in scratch of at most 1 GiB, the tiles
+ * run one after another; clr_batch_set_information_tile: problems per tile (0: automatic).  The blocks of linear-mean,
+ * noise and amplitude WEIGHTS are not covered (the mean weights' own block is clr_batch_fit_mean_weights' Gram matrix);
+ * mean_partial with a linear mean or amplitudes in force: CLR_UNSUPPORTED.  The plan's results, gradient state and any
+ * materialised factor are left as they were.  Synchronous. */
+int clr_batch_information(clr_batch* h, int mean_partial, double* info, int* status);
+int clr_batch_set_information_tile(clr_batch* h, int problems);
+/* Device time of the last clr_batch_information in ms (HIP events on the plan's stream): from its evaluation to the last
+ * tile's Gram pass, the tiles' downloads and host round trips in between included. */
+int clr_batch_get_information_ms(const clr_batch* h, double* ms);
 /* How clr_batch_grad differentiates.  mode 0 (default): REVERSE mode -- the riders pass also records w, D, x per
  * sample and the state every K steps, the adjoint at every chunk end follows from the riders in a walk backwards over
  * the chunks, and ONE reverse sweep per chunk yields all partials (cost ~4x an evaluation instead of ~20x; needs
@@ -1098,6 +1126,10 @@ int clr_sharded_get_results(clr_sharded* h, double* loglike, double* logdet, dou
 /* clr_batch_grad on every shard concurrently (coefficients in force: clr_sharded_set_coefficients); grad is
  * [B][1 + 2 J_real + 4 J_comp]. */
 int clr_sharded_grad(clr_sharded* h, double* value, double* grad, int* status);
+/* clr_batch_information on every shard concurrently: info is [B][M][M], M = 1 + 2 J_real + 4 J_comp (+ 1 with
+ * mean_partial); clr_batch_set_information_tile on every shard. */
+int clr_sharded_information(clr_sharded* h, int mean_partial, double* info, int* status);
+int clr_sharded_set_information_tile(clr_sharded* h, int problems);
 /* One optimiser / MCMC evaluation: new coefficients in, B log-likelihoods out
  * (set_coefficients + enqueue + get_results on every shard concurrently). */
 int clr_sharded_evaluate(clr_sharded* h, const double* jitter, const double* a_real, const double* c_real,
