@@ -549,7 +549,8 @@ bool lazy_phases_ok(const clr_batch* h) {
   return sel_max(h->dmax, h->floor_dmax) * sel_max(h->tmax, h->floor_tmax) < CLR_LAZY_PHASE_LIMIT;
 }
 bool lazy_eligible(const clr_batch* h) {
-  // |c dx| < 2^-7 at every step: Psi stays within [0.88, 1] over the 16 steps between renormalisations;
+  // |c dx| < 2^-7 at every step: Psi stays within [0.6, 1] over the 64 steps between renormalisations
+  // (CLR_SPLIT_RENORM, clr_split_kernels.h);
   // |d dx| < 2^-5: the per-step rotation of the (cos, sin) pairs uses a short Taylor series
   const double cmax = sel_max(h->cmax, h->floor_cmax), dmax = sel_max(h->dmax, h->floor_dmax),
                dxmax = sel_max(h->dxmax, h->floor_dxmax);
