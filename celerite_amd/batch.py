@@ -983,6 +983,7 @@ class BatchedGP(object):
         except ValueError:
             raise ValueError("dimension mismatch")
         jit = np.ascontiguousarray(np.broadcast_to(np.asarray(jitter, dtype=np.float64), (self.B,)))
+        self._last_params = None                           # (tables replace what parameters formed: information_parameters)
         _check(_load().clr_batch_set_coefficients(self._h, _ptr(jit), *[_ptr(b) for b in blocks]))
 
     def set_general(self, A, U, V):
@@ -1064,6 +1065,7 @@ class BatchedGP(object):
             tabs.append(a)
         jit = np.ascontiguousarray(np.broadcast_to(np.asarray(jitter, dtype=np.float64), (B,)))
         ll, ld, q, st = np.empty(B), np.empty(B), np.empty(B), np.empty(B, dtype=np.int32)
+        self._last_params = None
         if mean is not None:
             m, stride = _mean_arg(mean, B)
             _check(_load().clr_batch_evaluate_mean(self._h, m.ctypes.data, stride, jit.ctypes.data,
@@ -1089,6 +1091,7 @@ class BatchedGP(object):
             raise ValueError("dimension mismatch: the kernel has (J_real, J_comp) = (%d, %d), the plan (%d, %d)"
                              % (prog.J_real, prog.J_comp, self.J_real, self.J_comp))
         self._set_kernel_handle(prog)
+        self._last_params = None                           # (clr_batch_set_kernel: no parameters are in force)
         self.kernel_program = prog
         self.kernel = prog.kernel
         return prog
@@ -1103,7 +1106,6 @@ class BatchedGP(object):
         p = np.ascontiguousarray(params, dtype=np.float64)
         if p.shape != (self.B, prog.n_params):
             raise ValueError("dimension mismatch")
-        self._last_params = p                              # (information_parameters: the Jacobian at these rows)
         return p
 
     def evaluate_parameters(self, params, mean=None, mean_weights=None, noise_weights=None):
@@ -1120,8 +1122,10 @@ class BatchedGP(object):
         p = self._params_arg(params)
         ll, ld, q, st = np.empty(self.B), np.empty(self.B), np.empty(self.B), np.empty(self.B, dtype=np.int32)
         m, stride = _mean_arg(mean, self.B)
+        self._last_params = None
         _check(_load().clr_batch_evaluate_params(self._h, p.ctypes.data, None if m is None else m.ctypes.data, stride,
                                                  ll.ctypes.data, ld.ctypes.data, q.ctypes.data, st.ctypes.data))
+        self._last_params = p                              # (information_parameters: the Jacobian at these rows)
         return ll, ld, q, st
 
     def grad_parameters(self, mean_partial=False):
@@ -1527,10 +1531,13 @@ class BatchedGP(object):
     def information_parameters(self, mean_partial=False):
         """``(info[B, P(+1), P(+1)], status[B])`` in the kernel's parameters at the rows of the last
         :meth:`evaluate_parameters`: :func:`chain_information` of :meth:`information` with the program's Jacobian there
-        (exact for this form: no second derivative of a coefficient formula enters).  A draw the program refused is NaN."""
+        (exact for this form: no second derivative of a coefficient formula enters).  A draw the program refused is NaN.
+        Refused wherever :meth:`grad_parameters` is: behind :meth:`set_coefficients`, :meth:`evaluate` or :meth:`set_kernel`
+        the coefficients in force are not those parameters' any more, until the next :meth:`evaluate_parameters`."""
         prog, p = getattr(self, "kernel_program", None), getattr(self, "_last_params", None)
         if prog is None or p is None:
-            raise RuntimeError("no parameters are in force: call set_kernel and evaluate_parameters first")
+            raise RuntimeError("no parameters are in force: the coefficients in force were not formed from parameters "
+                               "(call set_kernel and evaluate_parameters first)")
         info, st = self.information(mean_partial)
         jac, jj, _ = prog.jacobian(p, status=True)
         return chain_information(info, jac, jj, mean_partial), st
@@ -1855,6 +1862,7 @@ class ShardedBatchedGP(object):
 
     def set_coefficients(self, a_real, c_real, a_comp, b_comp, c_comp, d_comp, jitter=0.0):
         jit, blocks = self._coeff_blocks(a_real, c_real, a_comp, b_comp, c_comp, d_comp, jitter)
+        self._last_params = None
         self._ok(_load().clr_sharded_set_coefficients(self._h, _ptr(jit), *[_ptr(b) for b in blocks]))
 
     def set_mean(self, mu):
@@ -1988,6 +1996,7 @@ class ShardedBatchedGP(object):
             self.set_noise_weights(noise_weights)
         jit, blocks = self._coeff_blocks(a_real, c_real, a_comp, b_comp, c_comp, d_comp, jitter)
         ll, ld, q, st = self._out()
+        self._last_params = None
         if mean is not None:
             m, stride = _mean_arg(mean, self.B)
             self._ok(_load().clr_sharded_evaluate_mean(self._h, _ptr(m), stride, _ptr(jit), *(
@@ -2014,8 +2023,10 @@ class ShardedBatchedGP(object):
         p = self._params_arg(params)
         ll, ld, q, st = self._out()
         m, stride = _mean_arg(mean, self.B)
+        self._last_params = None
         self._ok(_load().clr_sharded_evaluate_params(self._h, _ptr(p), None if m is None else _ptr(m), stride,
                                                      _ptr(ll), _ptr(ld), _ptr(q), st.ctypes.data_as(_ip)))
+        self._last_params = p
         return ll, ld, q, st
 
     def grad_parameters(self, mean_partial=False):

@@ -667,11 +667,8 @@ int clr_batch_get_log_amplitude_sum(clr_batch* h, double* L) {
   return CLR_OK;
 }
 
-extern "C++" int amplitude_adjust(clr_batch* h, double* loglike, double* logdet, double* quad, int* status) {
-  if (h->amp_eval == 0) return CLR_OK;
-  const int st = amplitude_snapshot(h);
-  if (st != CLR_OK) return st;
-  const double* L = h->host_amp_L.data();
+// `L`: the log terms and, behind them, the flags of B problems
+static void amplitude_fold(const clr_batch* h, const double* L, double* loglike, double* logdet, double* quad, int* status) {
   const double* flag = L + h->B;
   for (size_t b = 0; b < (size_t)h->B; ++b) {
     if (flag[b] != 0.0) {  // a zero or non-finite s_n inside the problem's length: the draw is refused
@@ -684,6 +681,23 @@ extern "C++" int amplitude_adjust(clr_batch* h, double* loglike, double* logdet,
     if (logdet) logdet[b] = logdet[b] + (L[b] + L[b]);
     if (loglike) loglike[b] = loglike[b] - L[b];
   }
+}
+
+// The log term of the EVALUATION in force, into its results
+extern "C++" int amplitude_adjust(clr_batch* h, double* loglike, double* logdet, double* quad, int* status) {
+  if (h->amp_eval == 0) return CLR_OK;
+  const int st = amplitude_snapshot(h);
+  if (st != CLR_OK) return st;
+  amplitude_fold(h, h->host_amp_L.data(), loglike, logdet, quad, status);
+  return CLR_OK;
+}
+
+// The log term of the AMPLITUDES in force, into a value formed from the series in force with no evaluation in front (the
+// sequential plan gradient of widths 33..64): the evaluation in force, its results and amp_eval stay as they are
+extern "C++" int amplitude_adjust_in_force(clr_batch* h, double* loglike, int* status) {
+  if (!h->amp_active || !h->amp_formed) return CLR_OK;
+  HIP_TRY(hipEventSynchronize(h->amp_back_ev.get()));
+  amplitude_fold(h, h->amp_back.p, loglike, nullptr, nullptr, status);
   return CLR_OK;
 }
 

@@ -53,9 +53,12 @@ static int grad_chunk_spans(clr_batch* h) {
 // The amplitude model's log term in the gradient's value (amplitude_adjust: value = value' - L); a problem whose scale was
 // refused gets NaN partials and CLR_INVALID_ARGUMENT, as a draw the kernel program refused does in clr_batch_grad_params.
 // The partials with respect to the coefficients are those of the scaled system, which is the model's likelihood up to L.
-static int amplitude_adjust_grad(clr_batch* h, double* value, double* grad, size_t NG, int* status) {
+// `in_force`: the value was formed from the series in force with no evaluation in front -- its log term is that of the
+// amplitudes in force, and the evaluation in force is not touched.
+static int amplitude_adjust_grad(clr_batch* h, double* value, double* grad, size_t NG, int* status, bool in_force = false) {
   std::vector<int> refused((size_t)h->B, CLR_OK);
-  const int st = amplitude_adjust(h, value, nullptr, nullptr, refused.data());
+  const int st = in_force ? amplitude_adjust_in_force(h, value, refused.data())
+                          : amplitude_adjust(h, value, nullptr, nullptr, refused.data());
   if (st != CLR_OK) return st;
   for (size_t b = 0; b < (size_t)h->B; ++b) {
     if (refused[b] == CLR_OK) continue;
@@ -86,12 +89,10 @@ static int wide_batch_grad(clr_batch* h, double* value, double* grad, int* statu
   // The evaluation behind the gradient must hand out FINAL values: no level-1 problem may be left pending for a side
   // plan (defer_runs) -- the walk reads ll / status straight from the device, before any resolve could run
   int st = CLR_OK;
-  if (!seq_all) {
+  if (!seq_all) {  // (seq_all: no evaluation in front -- the value below is of the series in force)
     h->grad_scan_only = true;
     st = clr_batch_enqueue(h, 0);
     h->grad_scan_only = false;
-  } else {
-    h->amp_eval = h->amp_active ? 1 : 0;  // (no evaluation in front: the value below is of the series in force)
   }
   if (st != CLR_OK) return st;
   clr::BatchParams P0, P;
@@ -157,7 +158,7 @@ static int wide_batch_grad(clr_batch* h, double* value, double* grad, int* statu
   }
   h->grad_fallbacks = nfb;
   h->grad_reverse_used = false;
-  return amplitude_adjust_grad(h, value, grad, NG, status);
+  return amplitude_adjust_grad(h, value, grad, NG, status, seq_all);
 }
 
 int clr_batch_grad(clr_batch* h, double* value, double* grad, int* status) {

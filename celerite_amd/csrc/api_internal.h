@@ -472,6 +472,9 @@ int batch_results_scaled(clr_batch* h, double* loglike, double* logdet, double* 
 // logdet = logdet' + (L + L), loglike = loglike' - L, quad = quad'; a problem with a zero or non-finite s_n inside its
 // length: NaN and CLR_INVALID_ARGUMENT (mark_refused's quiet semantics).  No amplitudes in force: nothing is touched.
 int amplitude_adjust(clr_batch* h, double* loglike, double* logdet, double* quad, int* status);
+// ... and the log term of the amplitudes IN FORCE into a value that was formed from the series in force with no evaluation
+// in front (the sequential plan gradient of a one-chunk plan of widths 33..64): amp_eval and the results stay untouched.
+int amplitude_adjust_in_force(clr_batch* h, double* loglike, int* status);
 
 // ---- what a replaced input of a plan leaves stale: one function per cause, called by the entry points ----------
 namespace {

@@ -32,6 +32,12 @@ History dependences ``fresh()`` pins (neither plan may depend on an "auto" decis
     evaluation's differs from the materialising run's in the last bits: the walks' ``fit_mean_weights`` runs a plain
     evaluation first, on both plans.
 
+  * ``results()`` returns the evaluation in force, and which call ran it is history: the model keeps ``evaluated`` -- the
+    last call that ran an evaluation (evaluate, materialize, enqueue, the coefficient and parameter gradients, the
+    information matrix, kernel_params, fit_mean_weights' plain evaluation) with the state it ran in -- and ``Results`` is
+    drawn only while input setters or ``set_chunks`` alone came since.  The gradient of a one-chunk plan of widths 33..64
+    runs no evaluation (``gradient_evaluates``): ``results()`` behind it is the earlier evaluation's.
+
 ``"undefined"`` today (the documentation says "materialise again", the code does not refuse; called, not compared -- a
 finding for a later issue):
   * every consumer of a REFERENCE-layout factor after the series, the coefficients or the variances (noise basis, noise
@@ -39,16 +45,16 @@ finding for a later issue):
   * ``grad_mean_weights`` and ``fit_mean_weights`` on such a factor likewise (they go through ``batch_solve_impl``).
 ``grad_noise_weights`` does refuse it (``variance_changed``) and is modelled as a refusal.
 """
-import copy
-
 import numpy as np
 
 from _cases import coeffs_of, synthetic
 from _noise_cases import host_diag, noise_basis, noise_weights
+from _amplitude_cases import amplitudes, band_basis, host_scale, host_series, log_sum, smooth_basis
 
 kernel_factory = None     # set by the GPU test: (J_real, J_comp) -> a ``celerite_amd.terms`` kernel of that shape
 
-MEAN_K, NOISE_K, M_POINTS = 2, 3, 7
+MEAN_K, NOISE_K, AMP_K, M_POINTS = 2, 3, 3, 7
+ZERO_PROBLEM = 2          # ``amplitudes_zero``: the problem whose scale is zero on one band (every family has B >= 3)
 
 
 def make_kernel(terms, JR, JC):
@@ -99,7 +105,18 @@ FAMILIES = {
                        lengths=((1000, 512, 999, 700, 641), (300, 1000, 513, 511, 77)), flayouts=("reference",)),
     "wide": _family(3, 600, 1, 10, chunks=(5, 3), layouts=("staged",), consumers=WIDE_CONSUMERS, flayouts=("reference",)),
     "sharded": _family(5, 601, 2, 1, layouts=("staged",), consumers=("solve",), flayouts=("reference",), sharded=True),
+    # width 35 below auto_chunks' 128 samples per chunk: ONE chunk, so the plan gradient is the sequential tangent kernel on
+    # the resident series with no evaluation in front (api_grad.hip: seq_all)
+    "wide 64 one chunk": _family(3, 120, 1, 17, chunks=(1,), layouts=("staged",), mat=False, consumers=(),
+                                 flayouts=("reference",)),
 }
+
+
+def gradient_evaluates(fam):
+    """Whether ``grad_log_likelihood`` runs an evaluation of its own in the family: not on a one-chunk plan of widths
+    33..64, whose gradient leaves the results of the evaluation in force as they are."""
+    c = FAMILIES[fam]
+    return not (c["JR"] + 2 * c["JC"] > 32 and c["chunks"] == (1,))
 
 
 # ---- the arrays of a state: functions of (family, seed, k) ----------------------------------------------------------
@@ -217,6 +234,45 @@ def psi_weights(fam, seed, k):
 
 
 @_cached
+def gamma(fam, seed, kind, k):
+    """The amplitude basis, (K, N) or (B, K, N): band indicators for an even ``k``, the non-indicator basis for an odd one;
+    ``kind`` "nan": per problem, NaN past the longest length a problem has in any of the family's sets (psi_nan_tails)."""
+    c = FAMILIES[fam]
+    per = kind != "shared"
+    out = (band_basis if k % 2 == 0 else smooth_basis)(c["B"], c["N"], AMP_K, per, seed=10 * seed + k)
+    if kind == "nan":
+        out = np.array(out, copy=True)
+        for b, n in enumerate(np.max(c["lengths"], axis=0)):
+            out[b, :, n:] = np.nan
+    return out
+
+
+def gamma_of(state):
+    return gamma(state.fam, state.seed, *state.gam)
+
+
+@_cached
+def amplitude_values(fam, seed, k, zero_band):
+    """Amplitudes ``k`` (B, K); ``zero_band`` >= 0: problem ZERO_PROBLEM's amplitude of that band is zero, ``AMP_K``: all of
+    its amplitudes are."""
+    a = amplitudes(FAMILIES[fam]["B"], AMP_K, seed=30 * seed + k)
+    if zero_band >= 0:
+        a[ZERO_PROBLEM, zero_band if zero_band < AMP_K else slice(None)] = 0.0
+    return a
+
+
+def amplitudes_of(state):
+    """The amplitudes in force.  The deliberate zero: on an indicator basis the band of problem ZERO_PROBLEM's first sample,
+    which is inside every length -- a zero amplitude IS a zero scale on the band's samples; on the non-indicator basis, where
+    one zero amplitude leaves a small scale and no zero, all of the problem's amplitudes."""
+    band = -1
+    if state.amp_zero:
+        G = gamma_of(state)
+        band = int(np.argmax((G[ZERO_PROBLEM] if G.ndim == 3 else G)[:, 0])) if state.gam[1] % 2 == 0 else AMP_K
+    return amplitude_values(state.fam, state.seed, state.amp, band)
+
+
+@_cached
 def points(fam, seed):
     t = _base(fam, seed)["t"]
     lo, hi = t.min(), t.max()
@@ -246,6 +302,14 @@ class PlanState(object):
         self.psi, self.nw = None, 0
         # the coefficients: ("draw" | "bzero" | "fast", k) tables with their jitter, or ("kernel", k) parameter rows
         self.coef = ("draw", 0)
+        # the amplitude model: the basis, None or ("shared" | "per" | "nan", k); the amplitudes in force, None or an index,
+        # and whether problem ZERO_PROBLEM carries a zero scale
+        self.gam, self.amp, self.amp_zero = None, None, False
+        # whether a kernel has ever been handed to the plan (``kernel_params``): grad_parameters / information_parameters
+        self.kernel_seen = False
+        # the evaluation in force: ``(kind, k, the state it ran in)`` of the last operation that ran one (None: none yet), and
+        # whether only input setters or set_chunks came since (``results`` is drawn while they did)
+        self.evaluated, self.results_kept = None, False
         # the settings
         self.chunks, self.layout = c["chunks"][0], layout or c["layouts"][0]
         self.summarize = c["summarize"][0] if summarize is None else summarize
@@ -257,7 +321,9 @@ class PlanState(object):
         self.step = 0
 
     def copy(self):
-        return copy.copy(self)
+        n = PlanState.__new__(PlanState)
+        n.__dict__.update(self.__dict__)
+        return n
 
     @property
     def cfg(self):
@@ -266,6 +332,15 @@ class PlanState(object):
     @property
     def ragged(self):
         return self.lengths is not None
+
+    @property
+    def kernel_in_force(self):
+        """The coefficients in force were formed from kernel parameters (the C side's ``kp_in_force``)."""
+        return self.coef[0] == "kernel"
+
+    def gam_class(self):
+        """None, "nan" (NaN past the lengths) or "set"."""
+        return None if self.gam is None else ("nan" if self.gam[0] == "nan" else "set")
 
     def lens(self):
         return None if self.lengths is None else self.cfg["lengths"][self.lengths]
@@ -302,8 +377,11 @@ def host_model(w, Phi):
 
 
 def effective(state):
-    """``(t, variances, residual, lengths)`` as NumPy forms them -- ``_noise_cases.host_diag`` and test_gpu_batch_linear_mean's
-    ``y - host_model(w, Phi)`` -- each a list of B rows truncated to the problem's length."""
+    """``(t, variances, residual, lengths, L)`` as NumPy forms them -- ``_noise_cases.host_diag`` and
+    test_gpu_batch_linear_mean's ``y - host_model(w, Phi)``, and with amplitudes in force ``_amplitude_cases.host_series`` of
+    the two on ``host_scale``: ``r / s`` and ``d / (s * s)`` -- each a list of B rows truncated to the problem's length;
+    ``L[B]``: ``_amplitude_cases.log_sum`` of the scale over each length (zeros without amplitudes).  A problem with a zero
+    scale has non-finite rows and a non-finite ``L``: the library refuses it."""
     c = state.cfg
     B, N = c["B"], c["N"]
     t, diag, y = series(state.fam, state.seed, state.ser)
@@ -317,8 +395,14 @@ def effective(state):
     elif state.phi is not None:
         y = y - host_model(mean_weights(state.fam, state.seed, state.mw), mean_basis(state.fam, state.phi))
     lens = state.lens() or (N,) * B
+    L = np.zeros(B)
+    if state.amp is not None:
+        s = host_scale(amplitudes_of(state), gamma_of(state))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            y, diag = host_series(y, diag, s)
+            L = log_sum(s, lens)[0]
     return ([t[b, :n] for b, n in enumerate(lens)], [diag[b, :n] for b, n in enumerate(lens)],
-            [y[b, :n] for b, n in enumerate(lens)], lens)
+            [y[b, :n] for b, n in enumerate(lens)], lens, L)
 
 
 # ---- a plan built directly at a state -------------------------------------------------------------------------------
@@ -356,7 +440,7 @@ def _mean_value(state):
 
 def fresh(state, cls):
     """A plan straight at ``state``, in the canonical order: every setting, the bases, the series, the constant mean and
-    the weights, the coefficients or the kernel.  ``cls(B, N, J_real, J_comp)`` creates it; a setter the class does not
+    the weights (the amplitudes last of them), the coefficients or the kernel.  ``cls(B, N, J_real, J_comp)`` creates it; a setter the class does not
     have (a sharded plan's layout, small mode, factor layout, ...) is skipped."""
     c = state.cfg
     plan = cls(c["B"], c["N"], c["JR"], c["JC"])
@@ -372,16 +456,22 @@ def fresh(state, cls):
             plan.set_mean_basis(mean_basis(state.fam, state.phi))
         if state.psi is not None and state.psi[0] != "nan":
             plan.set_noise_basis(psi_of(state))
+        if state.gam is not None and state.gam[0] != "nan":
+            plan.set_amplitude_basis(gamma_of(state))
         t, diag, y, lens = arrays(state)
         plan.set_series(t, diag, y, lengths=lens)
         if state.psi is not None and state.psi[0] == "nan":      # (accepted only with the lengths in force)
             plan.set_noise_basis(psi_of(state))
+        if state.gam is not None and state.gam[0] == "nan":
+            plan.set_amplitude_basis(gamma_of(state))
         if state.mean is not None:
             plan.set_mean(_mean_value(state))
         if state.phi is not None:
             plan.set_mean_weights(mean_weights(state.fam, state.seed, state.mw))
         if state.psi is not None:
             plan.set_noise_weights(psi_weights(state.fam, state.seed, state.nw))
+        if state.amp is not None:
+            plan.set_amplitudes(amplitudes_of(state))
         _set_coefficients(plan, state)
     except Exception:
         plan.close()
@@ -395,8 +485,10 @@ RAGGED = "per-problem lengths"
 
 class Op(object):
     kind = None
-    observes = None      # "eval", "mat", "grad" or "consumer": the class of an observation
+    observes = None      # "eval", "mat", "grad", "info" or "consumer": the class of an observation
     settings = False     # a settings operation: the family's route assertion follows it
+    ks = (0,)            # the values of k under which legality, expectation or the abstract state after the call differ
+    input_setter = False # series, means, noise, amplitudes, coefficients: settles an evaluation in flight "on ITS series"
 
     def __init__(self, k=0):
         self.k = int(k)
@@ -413,10 +505,22 @@ class Op(object):
     def apply(self, s):
         """The state after the call (a refused or undefined call leaves the model's state as it was)."""
         n = s.copy()
-        if self.expect(s) == "ok":
+        e = self.expect(s)
+        if e == "ok":
             self.change(n)
+        # the evaluation in force and whether ``results`` still returns it: a refused call leaves the plan as it was
+        if self.evaluates(s):
+            n.evaluated, n.results_kept = (self.kind, self.k, s), True
+        elif (e == "ok" and not (self.input_setter or self.keeps_results)) or e == "undefined":
+            n.results_kept = False
         n.step = s.step + 1
         return n
+
+    keeps_results = False   # neither an evaluation nor a setter, and the results in HBM stay the evaluation's
+
+    def evaluates(self, s):
+        """Whether the call runs an evaluation whose results ``results()`` then returns."""
+        return False
 
     def change(self, n):
         pass
@@ -433,6 +537,7 @@ def _series_changed(n, ragged_before):
 
 class _SetSeries(Op):
     """``set_series``; the subclasses say what changes.  Called with the arrays of the state after the change."""
+    input_setter = True
 
     def change(self, n):
         ragged = n.ragged
@@ -505,40 +610,50 @@ class SeriesNoLengths(_SetSeries):
     kind = "series_no_lengths"       # the lengths cleared: a uniform plan again
 
     def legal(self, s):
-        return s.ragged and (s.psi is None or s.psi[0] != "nan")
+        return s.ragged and (s.psi is None or s.psi[0] != "nan") and (s.gam is None or s.gam[0] != "nan")
 
     def move(self, n):
         n.lengths = None
         n.ser = 1 + self.k % 9
 
 
-class MeanConst(Op):
+class _Mean(Op):
+    input_setter, ks = True, (0, 1)
+
+
+class MeanConst(_Mean):
     kind = "mean_const"
 
     def legal(self, s):
         return s.phi is None and s.mean != ("const", self.k % 4)
 
+    def expect(self, s):
+        return "ok" if s.gam is None else "refuses:an amplitude basis is set"
+
     def change(self, n):
         n.mean = ("const", self.k % 4)
 
-    def call(self, plan):
-        plan.set_mean(_mean_value(self.apply_to))
+    def call(self, plan):      # (the value of the call, not of the state behind it: a refused call leaves no mean there)
+        plan.set_mean(float(mean_values(self.before.fam, self.before.seed, self.k % 4)[0]))
 
 
-class MeanPer(Op):
+class MeanPer(_Mean):
     kind = "mean_per"
 
     def legal(self, s):
         return s.phi is None and s.mean != ("per", self.k % 4)
 
+    def expect(self, s):
+        return "ok" if s.gam is None else "refuses:an amplitude basis is set"
+
     def change(self, n):
         n.mean = ("per", self.k % 4)
 
     def call(self, plan):
-        plan.set_mean(_mean_value(self.apply_to))
+        plan.set_mean(mean_values(self.before.fam, self.before.seed, self.k % 4))
 
 
-class MeanNone(Op):
+class MeanNone(_Mean):
     kind = "mean_none"
 
     def legal(self, s):
@@ -551,7 +666,7 @@ class MeanNone(Op):
         plan.set_mean(None)
 
 
-class MeanBasis(Op):
+class MeanBasis(_Mean):
     kind = "mean_basis"              # a new basis starts from zero weights
 
     def legal(self, s):
@@ -564,7 +679,7 @@ class MeanBasis(Op):
         plan.set_mean_basis(mean_basis(self.apply_to.fam, self.apply_to.phi))
 
 
-class MeanBasisNone(Op):
+class MeanBasisNone(_Mean):
     kind = "mean_basis_none"
 
     def legal(self, s):
@@ -577,7 +692,7 @@ class MeanBasisNone(Op):
         plan.set_mean_basis(None)
 
 
-class MeanWeights(Op):
+class MeanWeights(_Mean):
     kind = "mean_weights"
 
     def legal(self, s):
@@ -596,7 +711,7 @@ def _variance_changed(n):
 
 
 class _NoiseBasis(Op):
-    per = None
+    per, input_setter = None, True
 
     def change(self, n):
         n.psi, n.nw = (self.per, self.k % 3), 0
@@ -622,7 +737,7 @@ class NoiseBasisNanTails(_NoiseBasis):
 
 
 class NoiseBasisNone(Op):
-    kind = "noise_basis_none"
+    kind, input_setter = "noise_basis_none", True
 
     def legal(self, s):
         return s.psi is not None
@@ -636,7 +751,7 @@ class NoiseBasisNone(Op):
 
 
 class NoiseWeights(Op):
-    kind = "noise_weights"
+    kind, input_setter = "noise_weights", True
 
     def legal(self, s):
         return s.psi is not None
@@ -651,7 +766,7 @@ class NoiseWeights(Op):
 
 
 class NoiseWeightsZero(Op):
-    kind = "noise_weights_zero"
+    kind, input_setter = "noise_weights_zero", True
 
     def legal(self, s):
         return s.psi is not None and s.nw != 0
@@ -665,6 +780,7 @@ class NoiseWeightsZero(Op):
 
 
 class NoiseWeightsSame(Op):
+    input_setter = True
     kind = "noise_weights_same"      # the weights already in force: clr_batch_set_noise_weights' early return, nothing changes
 
     def legal(self, s):
@@ -675,8 +791,83 @@ class NoiseWeightsSame(Op):
         plan.set_noise_weights(psi_weights(s.fam, s.seed, s.nw).copy())
 
 
+class _AmplitudeBasis(Op):
+    """``set_amplitude_basis``: a new basis drops the amplitudes in force -- the plan reads the plain series again."""
+    per, input_setter = None, True
+
+    def expect(self, s):
+        return "ok" if s.mean is None else "refuses:a constant mean is in force"
+
+    def change(self, n):
+        if n.amp is not None:
+            _variance_changed(n)      # (amplitudes_dropped: the residual and the variances formed again)
+        n.gam, n.amp, n.amp_zero = (self.per, self.k % 4), None, False
+
+    def call(self, plan):      # (the basis of the call: a refused call leaves none in the state behind it)
+        plan.set_amplitude_basis(gamma(self.before.fam, self.before.seed, self.per, self.k % 4))
+
+
+class AmplitudeBasisShared(_AmplitudeBasis):
+    kind, per = "amplitude_basis_shared", "shared"
+
+
+class AmplitudeBasisPer(_AmplitudeBasis):
+    kind, per = "amplitude_basis_per", "per"
+
+
+class AmplitudeBasisNanTails(_AmplitudeBasis):
+    kind, per = "amplitude_basis_nan_tails", "nan"    # NaN past the lengths: legal only while lengths are in force
+
+    def legal(self, s):
+        return s.ragged
+
+
+class AmplitudeBasisNone(Op):
+    kind, input_setter = "amplitude_basis_none", True
+
+    def legal(self, s):
+        return s.gam is not None
+
+    def change(self, n):
+        if n.amp is not None:
+            _variance_changed(n)
+        n.gam, n.amp, n.amp_zero = None, None, False
+
+    def call(self, plan):
+        plan.set_amplitude_basis(None)
+
+
+class Amplitudes(Op):
+    kind, input_setter, zero = "amplitudes", True, False
+
+    def legal(self, s):
+        return s.gam is not None
+
+    def change(self, n):
+        n.amp = 1 + self.k % 6 if 1 + self.k % 6 != n.amp else 1 + (self.k + 1) % 6
+        n.amp_zero = self.zero
+        _variance_changed(n)
+
+    def call(self, plan):
+        plan.set_amplitudes(amplitudes_of(self.apply_to))
+
+
+class AmplitudesZero(Amplitudes):
+    kind, zero = "amplitudes_zero", True     # problem ZERO_PROBLEM gets one zero band inside its length: NaN, CLR_INVALID_ARGUMENT
+
+
+class AmplitudesSame(Op):
+    kind, input_setter = "amplitudes_same", True   # the amplitudes already in force: clr_batch_set_amplitudes' early return
+
+    def legal(self, s):
+        return s.amp is not None
+
+    def call(self, plan):
+        plan.set_amplitudes(amplitudes_of(self.apply_to).copy())
+
+
 class _Coefficients(Op):
-    variant = None
+    variant, input_setter, ks = None, True, (0, 1)
 
     def legal(self, s):
         return s.coef != (self.variant, self.k % 8)
@@ -704,9 +895,16 @@ class CoefFast(_Coefficients):
 class KernelParams(_Coefficients):
     kind, variant = "kernel_params", "kernel"     # set_kernel and evaluate_parameters: the coefficients formed on the device
 
+    def change(self, n):
+        _Coefficients.change(self, n)
+        n.kernel_seen = True
+
+    def evaluates(self, s):
+        return True
+
 
 class _Setting(Op):
-    settings = True
+    settings, ks = True, (0, 1, 2)
     field = options = method = None
 
     def value(self, s):
@@ -729,6 +927,7 @@ class _Setting(Op):
 
 class SetChunks(_Setting):
     kind, field, options, method, same_allowed = "set_chunks", "chunks", "chunks", "set_chunks", True
+    keeps_results = True              # (tests/test_gpu_batch.py: the results of the evaluation in force stay readable)
 
     def change(self, n):
         _Setting.change(self, n)
@@ -781,12 +980,18 @@ class SetExact(_Setting):
 class Enqueue(Op):
     kind = "enqueue"                 # an evaluation left in flight: the next operation settles it first
 
+    def evaluates(self, s):
+        return True
+
     def call(self, plan):
         plan.enqueue()
 
 
 class Evaluate(Op):
     kind, observes = "evaluate", "eval"
+
+    def evaluates(self, s):
+        return True
 
     def call(self, plan):
         return plan.log_likelihood()
@@ -805,6 +1010,9 @@ class Materialize(Op):
         n.factor, n.f_lean = n.step, n.flayout == "lean"
         n.f_inputs = n.f_var = n.f_settings = False      # (factor_written)
 
+    def evaluates(self, s):
+        return self.expect(s) == "ok"
+
     def call(self, plan):
         return plan.materialize() if hasattr(plan, "materialize") else plan.log_likelihood(True)
 
@@ -812,11 +1020,104 @@ class Materialize(Op):
 class Gradient(Op):
     kind, observes = "grad_log_likelihood", "grad"
 
+    keeps_results = True     # (where it runs no evaluation -- gradient_evaluates -- it leaves the one in force as it is)
+
     def legal(self, s):
         return s.cfg["JR"] + 2 * s.cfg["JC"] <= 8 or not s.ragged
 
+    def evaluates(self, s):
+        return gradient_evaluates(s.fam)
+
     def call(self, plan):
         return plan.grad_log_likelihood()
+
+
+class Results(Op):
+    """``plan.results()`` with no evaluation of its own: what a fresh plan at the state of the evaluation in force returns
+    from ``results()`` directly behind the same call (``reference``), whatever input setter or ``set_chunks`` came since
+    -- the calls that reach amplitude_snapshot, pin_results and warm_resolve."""
+    kind, observes, keeps_results = "results", "eval", True
+
+    def legal(self, s):
+        return s.evaluated is not None and s.results_kept
+
+    def call(self, plan):
+        return plan.results()
+
+    def reference(self, make):
+        """The expected arrays: ``make(state)`` builds a fresh plan (the caller closes it)."""
+        kind, k, at = self.before.evaluated
+        other = make(at)
+        ev = bind(KINDS[kind](k), at)
+        if ev.kind == "consumer" and ev.expected == "ok":
+            other.log_likelihood(True)
+        try:
+            ev.call(other)
+        except (RuntimeError, ValueError):
+            assert ev.expected != "ok", (kind, k)
+        return other.results()
+
+
+def _width(s):
+    return s.cfg["JR"] + 2 * s.cfg["JC"]
+
+
+NOT_FROM_PARAMETERS = "refuses:the coefficients in force were not formed from parameters"
+
+
+def _information_expect(s, mean_partial):
+    if _width(s) > 8:
+        return "refuses:narrow plans (widths 1..8)"
+    if mean_partial and s.phi is not None:
+        return "refuses:a linear mean is in force"
+    if mean_partial and s.amp is not None:
+        return "refuses:amplitudes are in force"
+    return "ok"
+
+
+class Information(Op):
+    kind, observes, ks = "information", "info", (0, 1)     # k chooses mean_partial; the factor in HBM stays as it was
+
+    def expect(self, s):
+        return _information_expect(s, self.k % 2 == 1)
+
+    def evaluates(self, s):
+        return self.expect(s) == "ok"
+
+    def call(self, plan):
+        return plan.information(mean_partial=self.k % 2 == 1)
+
+
+class GradParameters(Op):
+    kind, observes, keeps_results = "grad_parameters", "grad", True
+
+    def legal(self, s):
+        return s.kernel_seen and Gradient(self.k).legal(s)
+
+    def expect(self, s):
+        return "ok" if s.kernel_in_force else NOT_FROM_PARAMETERS
+
+    def evaluates(self, s):
+        return self.expect(s) == "ok" and gradient_evaluates(s.fam)
+
+    def call(self, plan):
+        return plan.grad_parameters()
+
+
+class InformationParameters(Op):
+    kind, observes, ks = "information_parameters", "info", (0, 1)
+
+    def legal(self, s):
+        return s.kernel_seen
+
+    def expect(self, s):
+        return _information_expect(s, self.k % 2 == 1) if s.kernel_in_force else NOT_FROM_PARAMETERS
+
+    def evaluates(self, s):
+        return self.expect(s) == "ok"
+
+    def call(self, plan):
+        return plan.information_parameters(mean_partial=self.k % 2 == 1)
 
 
 def _factor_expect(s, entry=""):
@@ -859,7 +1160,24 @@ class GradNoiseWeights(Op):
         return plan.grad_noise_weights()
 
 
+class GradAmplitudes(Op):
+    kind, observes = "grad_amplitudes", "grad"
+
+    def legal(self, s):
+        return s.amp is not None and (s.cfg["mat"] or s.ragged) and s.factor_state() != "settings"
+
+    def expect(self, s):
+        e = _factor_expect(s)
+        if e in ("ok", "undefined") and s.f_var:
+            return "refuses:materialise again"          # (variance_changed)
+        return e
+
+    def call(self, plan):
+        return plan.grad_amplitudes()
+
+
 class Consumer(Op):
+    ks = (0, 6, 10)                              # (fit_mean_weights, the consumer that evaluates: the wide and the narrow list's)
     kind, observes = "consumer", "consumer"      # k chooses one of the family's consumers; points and right-hand sides fixed per walk
 
     def name(self, s):
@@ -872,10 +1190,15 @@ class Consumer(Op):
         return (bool(s.cfg["consumers"]) or s.ragged) and s.factor_state() != "settings"
 
     def expect(self, s):
+        if self.name(s) == "fit_mean_weights" and s.phi is not None and s.amp is not None:
+            return "refuses:amplitudes are in force"    # (before the factor is looked at)
         return _factor_expect(s)
 
+    def evaluates(self, s):
+        return self.name(s) == "fit_mean_weights" and s.phi is not None     # (its plain evaluation runs whatever follows)
+
     def call(self, plan):
-        s = self.apply_to
+        s = self.before
         name, xs, z = self.name(s), points(s.fam, s.seed), rhs(s.fam, s.seed)
         basis = mean_basis_at_points(s.fam, s.phi) if s.phi is not None else None
         if name == "solve":
@@ -897,10 +1220,12 @@ class Consumer(Op):
 
 OPS = [SeriesNew, SeriesYStride, SeriesDStride, SeriesLengths, SeriesNoLengths, MeanConst, MeanPer, MeanNone, MeanBasis,
        MeanBasisNone, MeanWeights, NoiseBasisShared, NoiseBasisPer, NoiseBasisNanTails, NoiseBasisNone, NoiseWeights, NoiseWeightsZero,
-       NoiseWeightsSame, CoefDraw, CoefBZero, CoefFast, KernelParams, SetChunks, SetLayout, SetSummarize, SetFactorLayout,
-       SetRescue, SetExact, Enqueue, Evaluate, Materialize, Gradient, GradMeanWeights, GradNoiseWeights, Consumer]
+       NoiseWeightsSame, AmplitudeBasisShared, AmplitudeBasisPer, AmplitudeBasisNanTails, AmplitudeBasisNone, Amplitudes,
+       AmplitudesSame, AmplitudesZero, CoefDraw, CoefBZero, CoefFast, KernelParams, SetChunks, SetLayout, SetSummarize,
+       SetFactorLayout, SetRescue, SetExact, Enqueue, Evaluate, Results, Materialize, Gradient, GradMeanWeights,
+       GradNoiseWeights, GradAmplitudes, GradParameters, Information, InformationParameters, Consumer]
 KINDS = {op.kind: op for op in OPS}
-OBSERVATION_CLASSES = ("eval", "mat", "grad", "consumer")
+OBSERVATION_CLASSES = ("eval", "mat", "grad", "info", "consumer")
 
 
 def flatten(result):
@@ -953,62 +1278,71 @@ def _candidates(state, k):
 def _abstract(s):
     """What the legality and the expectation of every kind depend on (besides the family)."""
     return (s.factor_state(), s.f_var, s.phi is None, s.psi and s.psi[0], s.mean is None, s.ragged, s.nw == 0, s.summarize > 0,
-            s.flayout)
+            s.flayout, s.gam_class(), s.amp is None, s.kernel_seen, s.kernel_in_force,
+            s.evaluated is not None and s.results_kept)
 
 
-_REACHABLE = {}
+_REACHABLE, _GRAPH = {}, {}
+
+
+def _graph(fam):
+    """The family's graph over the abstract state, from its first state: ``edges[key] = [(kind, key behind the call), ...]`` of
+    the calls that are legal and compared there (every value of k that matters: ``Op.ks``), in the order of ``OPS``."""
+    if fam not in _GRAPH:
+        first = initial(fam, 0)
+        edges, frontier = {_abstract(first): None}, [first]
+        while frontier:
+            nxt = []
+            for st in frontier:
+                out = []
+                for cls in OPS:
+                    for k in cls.ks:
+                        op = cls(k)
+                        if not op.legal(st) or op.expect(st) != "ok":
+                            continue
+                        after = op.apply(st)
+                        key = _abstract(after)
+                        if key not in edges:      # (what can follow is a function of the abstract state: explored once)
+                            edges[key] = None
+                            nxt.append(after)
+                        if (op.kind, key) not in out:
+                            out.append((op.kind, key))
+                edges[_abstract(st)] = out
+            frontier = nxt
+        _GRAPH[fam] = edges, dict((key, set(kind for kind, _ in out)) for key, out in edges.items())
+    return _GRAPH[fam]
 
 
 def reachable_pairs(fam):
     """Every ordered pair (kind_i, kind_j) that can legally be adjacent in the family, both calls compared: a breadth-first
     search from the family's first state over the abstract state, not over what the walks happened to visit."""
     if fam not in _REACHABLE:
-        pairs, seen, frontier = set(), set(), [initial(fam, 0)]
-        while frontier:
-            nxt = []
-            for st in frontier:
-                for k in range(4):
-                    for cls in OPS:
-                        op = cls(k)
-                        if not op.legal(st) or op.expect(st) != "ok":
-                            continue
-                        after = op.apply(st)
-                        for cls2 in OPS:
-                            if any(cls2(k2).legal(after) and cls2(k2).expect(after) == "ok" for k2 in range(4)):
-                                pairs.add((op.kind, cls2.kind))
-                        key = _abstract(after)
-                        if key not in seen:
-                            seen.add(key)
-                            nxt.append(after)
-            frontier = nxt
-        _REACHABLE[fam] = pairs
+        edges, ok = _graph(fam)
+        _REACHABLE[fam] = set((kind, then) for out in edges.values() for kind, key in out for then in ok[key])
     return _REACHABLE[fam]
 
 
-def _path_to(state, target, then, k, depth=4):
+def _path_to(state, target, then, depth=4):
     """The shortest sequence of kinds, each an "ok" call, from ``state`` to a call of kind ``target`` after which a call of
-    kind ``then`` is legal and compared."""
-    follow = KINDS[then](k)
-    seen, frontier = {_abstract(state)}, [(state, [])]
+    kind ``then`` is legal and compared: a search of the family's graph, not of states."""
+    edges, ok = _graph(state.fam)
+    start = _abstract(state)
+    seen, frontier = {start}, [(start, [])]
     for _ in range(depth):
         nxt = []
-        for st, path in frontier:
-            for cls in OPS:
-                op = cls(k)
-                if not op.legal(st) or op.expect(st) != "ok":
-                    continue
-                after = op.apply(st)
-                if op.kind == target and follow.legal(after) and follow.expect(after) == "ok":
-                    return path + [op.kind]
-                key = _abstract(after)
+        for at, path in frontier:
+            for kind, key in edges.get(at) or ():
+                if kind == target and then in ok[key]:
+                    return path + [kind]
                 if key not in seen:
                     seen.add(key)
-                    nxt.append((after, path + [op.kind]))
+                    nxt.append((key, path + [kind]))
         frontier = nxt
     return None
 
 
-_RARE = ("consumer", "grad_mean_weights", "grad_noise_weights", "materialize")
+_RARE = ("consumer", "grad_mean_weights", "grad_noise_weights", "grad_amplitudes", "materialize", "results", "grad_parameters",
+         "information_parameters")
 
 
 def _walk_one(fam, seed, steps, covered, possible):
@@ -1048,7 +1382,7 @@ def _walk_one(fam, seed, steps, covered, possible):
                 left = sorted(p for p in possible - covered if not p[0].endswith("!") and p[0] != "start")
                 at = int(rng.randint(0, len(left))) if left else 0
                 for a, b in (left[at:] + left[:at])[:6]:
-                    plan = _path_to(state, a, b, k) or []
+                    plan = _path_to(state, a, b) or []
                     if plan:
                         break
             if plan:
@@ -1064,11 +1398,11 @@ def _walk_one(fam, seed, steps, covered, possible):
 
 
 # Steps per walk and walks per family: the smallest counts at which the walks meet tests/test_plan_walk_cpu.py's coverage
-# conditions (650 to 1100 pairs of kinds per family); more seeds, not longer walks.  LITERAL: further sequences per family,
+# conditions (1100 to 2000 pairs of kinds per family); more seeds, not longer walks.  LITERAL: further sequences per family,
 # ``(seed, [(name, k), ...])``, run and counted like the walks -- regressions, and pairs the generator does not reach.
 STEPS = 80
-SEEDS = {"narrow": 27, "role split 8": 21, "role split 7": 20, "warm": 12, "one launch": 14, "lengths": 21, "wide": 19,
-         "sharded": 17}
+SEEDS = {"narrow": 58, "role split 8": 45, "role split 7": 45, "warm": 30, "one launch": 31, "lengths": 45, "wide": 39,
+         "sharded": 40, "wide 64 one chunk": 28}
 LITERAL = {
     "narrow": [
         # the residual and the variances both pending, then the caller's stride changes (y, then diag) under both bases
@@ -1085,6 +1419,35 @@ LITERAL = {
         (3, [("materialize", 0), ("consumer", 0), ("series_lengths", 0), ("consumer", 0), ("evaluate", 0), ("materialize", 0),
              ("grad_log_likelihood", 0), ("series_no_lengths", 0), ("consumer", 0), ("evaluate", 0), ("materialize", 0),
              ("consumer", 0), ("consumer", 8)]),
+        # amplitudes arriving and leaving with no other transform, under a mean basis, under both, under a noise basis (the
+        # first to arrive moves the caller's array aside, the last to leave moves it back); then the other order: the mean
+        # and the noise basis arrive while amplitudes are in force and are removed while they stay
+        (1, [("amplitude_basis_shared", 0), ("amplitudes", 1), ("evaluate", 0), ("amplitude_basis_none", 0), ("evaluate", 0),
+             ("mean_basis", 0), ("mean_weights", 1), ("amplitude_basis_per", 1), ("amplitudes", 2), ("evaluate", 0),
+             ("amplitude_basis_none", 0), ("evaluate", 0), ("noise_basis_per", 0), ("noise_weights", 1),
+             ("amplitude_basis_shared", 2), ("amplitudes", 3), ("evaluate", 0), ("amplitude_basis_none", 0), ("evaluate", 0),
+             ("mean_basis_none", 0), ("amplitude_basis_per", 3), ("amplitudes", 4), ("evaluate", 0), ("amplitude_basis_none", 0),
+             ("evaluate", 0), ("noise_basis_none", 0), ("amplitude_basis_shared", 0), ("amplitudes", 5), ("mean_basis", 1),
+             ("mean_weights", 2), ("evaluate", 0), ("consumer", 10), ("results", 0), ("noise_basis_shared", 1), ("noise_weights", 2), ("evaluate", 0),
+             ("mean_basis_none", 0), ("evaluate", 0), ("noise_basis_none", 0), ("evaluate", 0), ("materialize", 0),
+             ("grad_amplitudes", 0)]),
+        # results() behind every kind of setter while the evaluation in force is one with amplitudes: its log term is
+        # snapshotted before the forming pass overwrites it (amp_eval, amplitude_snapshot)
+        (2, [("amplitude_basis_per", 0), ("amplitudes", 1), ("evaluate", 0), ("results", 0), ("amplitudes", 2), ("results", 0),
+             ("evaluate", 0), ("series_new", 0), ("results", 0), ("evaluate", 0), ("amplitude_basis_none", 0), ("results", 0),
+             ("evaluate", 0), ("noise_basis_shared", 0), ("amplitude_basis_shared", 1), ("amplitudes", 3), ("enqueue", 0),
+             ("noise_weights", 1), ("results", 0), ("evaluate", 0), ("coef_draw", 1), ("set_chunks", 1), ("results", 0),
+             ("evaluate", 0)]),
+        # a zero scale on one problem and new amplitudes directly behind it (the flags clear again); the caller's strides of y
+        # and of diag changed, lengths set and cleared, all with amplitudes in force
+        (3, [("noise_basis_shared", 0), ("amplitude_basis_shared", 2), ("amplitudes", 1), ("evaluate", 0), ("amplitudes_zero", 0),
+             ("evaluate", 0), ("amplitudes_zero", 1), ("amplitudes", 3), ("evaluate", 0), ("series_y_stride", 0), ("evaluate", 0), ("series_d_stride", 0),
+             ("evaluate", 0), ("amplitudes_same", 0), ("series_lengths", 0), ("evaluate", 0), ("information", 0),
+             ("series_no_lengths", 0), ("evaluate", 0), ("grad_log_likelihood", 0), ("results", 0)]),
+        # information_parameters behind tables that replaced what the parameters formed: refused as grad_parameters is
+        (0, [("kernel_params", 1), ("information_parameters", 0), ("grad_parameters", 0), ("coef_draw", 1),
+             ("information_parameters", 0), ("evaluate", 0), ("grad_parameters", 0), ("evaluate", 0), ("kernel_params", 2),
+             ("information_parameters", 1), ("results", 0)]),
     ],
     "role split 8": [
         # the same through the summarize mode: single wave (no copy read) -> role split
@@ -1099,6 +1462,19 @@ LITERAL = {
         # a basis with NaN past the lengths: the padded tail of the variances must be restored behind every forming pass
         (1, [("series_lengths", 0), ("noise_basis_nan_tails", 0), ("evaluate", 0), ("noise_weights", 1), ("evaluate", 0),
              ("grad_log_likelihood", 0), ("series_lengths", 1), ("noise_weights", 2), ("evaluate", 0)]),
+        # an amplitude basis with NaN past the lengths, amplitudes in force while the lengths change and are cleared
+        (2, [("series_lengths", 0), ("amplitude_basis_nan_tails", 0), ("amplitudes", 1), ("evaluate", 0), ("series_lengths", 1),
+             ("results", 0), ("evaluate", 0), ("amplitude_basis_per", 1), ("amplitudes", 2), ("series_no_lengths", 0),
+             ("evaluate", 0), ("grad_log_likelihood", 0)]),
+    ],
+    "wide 64 one chunk": [
+        # the gradient of a one-chunk plan of widths 33..64 runs no evaluation: results() behind it is the evaluation in
+        # force with ITS amplitudes' log term, not the one of the amplitudes set since ...
+        (0, [("amplitude_basis_shared", 0), ("amplitudes", 1), ("evaluate", 0), ("amplitudes", 2), ("grad_log_likelihood", 0),
+             ("results", 0), ("evaluate", 0)]),
+        # ... nor no log term at all when the basis was removed in between
+        (0, [("amplitude_basis_shared", 0), ("amplitudes", 1), ("evaluate", 0), ("amplitude_basis_none", 0),
+             ("grad_log_likelihood", 0), ("results", 0), ("evaluate", 0)]),
     ],
 }
 

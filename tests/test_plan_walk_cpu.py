@@ -57,8 +57,8 @@ def test_every_adjacent_pair_of_kinds_is_visited(fam):
 
 @pytest.mark.parametrize("fam", FAMILIES)
 def test_every_kind_comes_directly_before_every_class_of_observation(fam):
-    """... compared observations: a plain evaluation, a materialising one, a gradient, a consumer -- wherever the family
-    has the class at all and the kind leaves it legal (a consumer is never legal directly behind ``set_chunks``)."""
+    """... compared observations: a plain evaluation (``results`` among them), a materialising one, a gradient, an
+    information matrix, a consumer -- wherever the family has the class at all and the kind leaves it legal (a consumer is never legal directly behind ``set_chunks``)."""
     before, could, refused_then_observed, refused = set(), set(), set(), set()
     for ops in _walks(fam):
         for op, nxt in zip(ops[:-1], ops[1:]):
@@ -88,11 +88,51 @@ def test_refusals_stay_rare_and_every_walk_ends_in_a_compared_observation(fam):
         assert ops[-1].observes and ops[-1].expected == "ok"
         seen.update(pm.label(op) for op in ops)
     # the refusals the code's own rules give do occur
-    want = {"narrow": ["consumer!", "grad_noise_weights!", "grad_mean_weights!"],
-            "lengths": ["materialize!", "consumer!", "set_summarize_mode!"], "wide": ["series_lengths!"],
-            "warm": ["series_lengths!"], "one launch": ["series_lengths!"], "role split 8": ["series_lengths!"]}
+    want = {"narrow": ["consumer!", "grad_noise_weights!", "grad_mean_weights!", "grad_amplitudes!", "mean_const!", "mean_per!",
+                       "amplitude_basis_shared!", "amplitude_basis_per!", "information!", "grad_parameters!",
+                       "information_parameters!"],
+            "lengths": ["materialize!", "consumer!", "set_summarize_mode!", "grad_amplitudes!", "amplitude_basis_nan_tails!"],
+            "wide": ["series_lengths!", "information!", "grad_parameters!", "information_parameters!", "grad_amplitudes!"],
+            "warm": ["series_lengths!", "information!", "grad_parameters!", "information_parameters!"],
+            "one launch": ["series_lengths!", "mean_const!"], "role split 8": ["series_lengths!", "grad_amplitudes!"],
+            "sharded": ["information_parameters!", "grad_parameters!"],
+            "wide 64 one chunk": ["series_lengths!", "information!", "information_parameters!", "grad_parameters!"]}
     for lab in want.get(fam, []):
         assert lab in seen, (fam, lab)
+
+
+class _Recorder(object):
+    """Stands in for a plan: takes every call and keeps its name."""
+    B = 0
+
+    def __init__(self):
+        self.calls = []
+
+    def __getattr__(self, name):
+        def method(*args, **kwargs):
+            self.calls.append(name)
+        return method
+
+
+@pytest.mark.parametrize("fam", FAMILIES)
+def test_every_call_of_every_walk_forms_its_arguments(fam):
+    """... also a call the model expects to be refused, whose state behind it holds nothing of what the call passes."""
+    from celerite_amd import terms
+    saved = pm.kernel_factory
+    pm.kernel_factory = lambda JR, JC: pm.make_kernel(terms, JR, JC)
+    try:
+        for ops in _walks(fam):
+            plan = _Recorder()
+            for op in ops:
+                n = len(plan.calls)
+                op.call(plan)
+                assert len(plan.calls) > n, op
+                if op.kind == "results":
+                    made = []
+                    op.reference(lambda at: made.append(pm.fresh(at, lambda *shape: _Recorder())) or made[-1])
+                    assert made[0].calls[-1] == "results" and made[0].calls.count("results") == 1
+    finally:
+        pm.kernel_factory = saved
 
 
 def test_the_compositions_the_walks_are_for_occur():
@@ -140,8 +180,43 @@ def test_the_compositions_the_walks_are_for_occur():
     assert some("narrow", lambda ops, i, op: i >= 1 and op.kind == "kernel_params" and ops[i - 1].kind == "coef_draw")
     # every setter with an evaluation in flight
     for kind in ("series_new", "mean_const", "mean_basis", "mean_weights", "noise_basis_per", "noise_weights", "coef_draw",
-                 "kernel_params", "set_chunks", "set_layout", "set_rescue"):
+                 "kernel_params", "set_chunks", "set_layout", "set_rescue", "amplitude_basis_shared", "amplitude_basis_per",
+                 "amplitude_basis_none", "amplitudes", "amplitudes_same", "amplitudes_zero"):
         assert some("narrow", lambda ops, i, op: i >= 1 and op.kind == kind and ops[i - 1].kind == "enqueue"), kind
+    # ---- the amplitude model: "the first transform to arrive moves the caller's array aside, the last to leave moves it back"
+    bases = ("amplitude_basis_shared", "amplitude_basis_per", "amplitude_basis_nan_tails", "amplitude_basis_none")
+    ok = lambda op: op.expected == "ok"
+    for mean in (False, True):
+        for noise in (False, True):
+            under = lambda s: (s.phi is not None) == mean and (s.psi is not None) == noise
+            # amplitudes arriving and leaving under each combination of a mean basis and a noise basis ...
+            assert some("narrow", lambda ops, i, op: op.kind == "amplitudes" and op.before.amp is None and under(op.before)), (mean, noise)
+            assert some("narrow", lambda ops, i, op: op.kind in bases and ok(op) and op.before.amp is not None and under(op.before)), (mean, noise)
+    # ... and in the other order: the mean basis, the noise basis arriving while amplitudes are in force, and removed while they stay
+    for kind in ("mean_basis", "noise_basis_shared", "noise_basis_per", "mean_basis_none", "noise_basis_none"):
+        assert some("narrow", lambda ops, i, op: op.kind == kind and ok(op) and op.before.amp is not None
+                    and (not kind.endswith("none") or op.apply_to.amp is not None)), kind
+    # results() directly behind a setter, the evaluation in force one with amplitudes (amplitude_snapshot, pin_results)
+    for kind in ("amplitudes", "amplitude_basis_none", "series_new", "noise_weights"):
+        assert some("narrow", lambda ops, i, op: i >= 1 and op.kind == "results" and ops[i - 1].kind == kind and ok(ops[i - 1])
+                    and op.before.evaluated[2].amp is not None), kind
+    # new amplitudes directly behind a zero scale (the per-problem flags clear again), then a compared evaluation
+    assert some("narrow", lambda ops, i, op: 1 <= i < len(ops) - 1 and op.kind == "amplitudes" and ops[i - 1].kind == "amplitudes_zero"
+                and ops[i + 1].observes == "eval" and ok(ops[i + 1]))
+    # a stride change of y and of diag, lengths set and cleared, with amplitudes in force
+    for kind in ("series_y_stride", "series_d_stride", "series_lengths", "series_no_lengths"):
+        assert some("narrow", lambda ops, i, op: op.kind == kind and ok(op) and op.before.amp is not None), kind
+    assert some("lengths", lambda ops, i, op: op.kind == "series_no_lengths" and op.before.amp is not None)
+    # fit_mean_weights refused under amplitudes, whatever the factor's state
+    assert some("narrow", lambda ops, i, op: op.kind == "consumer" and op.expected == "refuses:amplitudes are in force")
+    # the parameter calls behind tables that replaced what the parameters formed (refused), and behind new parameters
+    for kind in ("grad_parameters", "information_parameters"):
+        assert some("narrow", lambda ops, i, op: op.kind == kind and op.expected == pm.NOT_FROM_PARAMETERS)
+        assert some("narrow", lambda ops, i, op: op.kind == kind and ok(op))
+    # the one-chunk plan of width 35: results() behind a gradient that runs no evaluation, new amplitudes or none in between
+    for kind in ("amplitudes", "amplitude_basis_none"):
+        assert some("wide 64 one chunk", lambda ops, i, op: i >= 2 and op.kind == "results" and ops[i - 1].kind == "grad_log_likelihood"
+                    and ops[i - 2].kind == kind and op.before.evaluated[2].amp is not None), kind
 
 
 def test_the_model_follows_the_code_s_rules_for_the_factor():
@@ -168,6 +243,54 @@ def test_the_model_follows_the_code_s_rules_for_the_factor():
         pm.replay("narrow", 0, [("materialize", 0), ("set_exact", 1), ("consumer", 0)])   # (the factor is the old settings')
 
 
+def test_the_amplitudes_the_walks_draw_keep_the_scale_away_from_zero():
+    """``min |s| >= _amplitude_cases.S_MIN`` within every length, for every basis and every amplitudes the walks can draw
+    (kind, ``k % 4``, index 1..6, every seed a family uses); the deliberate zero is zero on ZERO_PROBLEM alone, inside its
+    shortest length."""
+    from _amplitude_cases import S_MIN, host_scale
+    for fam in FAMILIES:
+        c = pm.FAMILIES[fam]
+        seeds = set(range(pm.SEEDS[fam])) | set(seed for seed, _ in pm.LITERAL.get(fam, []))
+        kinds = ("shared", "per") + (("nan",) if c["lengths"] else ())
+        shortest = np.min(c["lengths"], axis=0) if c["lengths"] else [c["N"]] * c["B"]
+        for seed in sorted(seeds):
+            for kind in kinds:
+                for k in range(4):
+                    G = pm.gamma(fam, seed, kind, k)
+                    for a in range(1, 7):
+                        s = np.abs(host_scale(pm.amplitude_values(fam, seed, a, -1), G))
+                        assert np.nanmin(s) >= S_MIN, (fam, seed, kind, k, a, np.nanmin(s))
+                        if kind == "nan":
+                            assert not np.isnan(s[:, :int(np.min(np.max(c["lengths"], axis=0)))]).any() and np.isnan(s[:, -1]).any()
+                    st = pm.PlanState(fam, seed)
+                    st.gam, st.amp, st.amp_zero = (kind, k), 1 + k, True
+                    s = np.abs(host_scale(pm.amplitudes_of(st), G))
+                    z = pm.ZERO_PROBLEM
+                    assert (s[z, :shortest[z]] == 0.0).any() and np.nanmin(np.delete(s, z, axis=0)) >= S_MIN, (fam, seed, kind, k)
+
+
+def test_effective_with_amplitudes_is_the_host_formed_series_and_its_log_term():
+    import math
+    fam, seed = "lengths", 2
+    s = pm.PlanState(fam, seed)
+    s.ser, s.lengths, s.phi, s.mw, s.psi, s.nw, s.gam, s.amp = 3, 0, 0, 2, ("shared", 1), 3, ("nan", 1), 4
+    plain = s.copy()
+    plain.gam, plain.amp = None, None
+    t0, d0, r0, lens0, L0 = pm.effective(plain)
+    t, d, r, lens, L = pm.effective(s)
+    a, G = pm.amplitude_values(fam, seed, 4, -1), pm.gamma(fam, seed, "nan", 1)
+    assert tuple(lens) == tuple(lens0) == pm.FAMILIES[fam]["lengths"][0] and not L0.any() and G.shape == (5, 3, 1000)
+    for b, n in enumerate(lens):
+        sc = (a[b, 0] * G[b, 0] + a[b, 1] * G[b, 1]) + a[b, 2] * G[b, 2]
+        assert np.array_equal(r[b], r0[b] / sc[:n]) and np.array_equal(d[b], d0[b] / (sc[:n] * sc[:n])) and np.array_equal(t[b], t0[b])
+        assert L[b] == math.fsum(np.log(np.abs(sc[:n]))) and np.isfinite(L[b]) and L[b] != 0.0
+    # the deliberate zero: that problem's rows and its L are not finite, the others are as without it
+    s.gam, s.amp_zero = ("per", 2), True
+    t, d, r, lens, L = pm.effective(s)
+    z = pm.ZERO_PROBLEM
+    assert not np.isfinite(L[z]) and not np.isfinite(d[z]).all() and all(np.isfinite(L[b]) and np.isfinite(d[b]).all() for b in range(5) if b != z)
+
+
 def test_effective_is_the_numpy_statement_of_the_residual_and_the_variances():
     fam, seed = "lengths", 3
     s = pm.PlanState(fam, seed)
@@ -178,7 +301,7 @@ def test_effective_is_the_numpy_statement_of_the_residual_and_the_variances():
     resid = y - (w[:, 0, None] * Phi[0] + w[:, 1, None] * Phi[1])
     var = diag + ((sw[:, 0, None] * Psi[:, 0] + sw[:, 1, None] * Psi[:, 1]) + sw[:, 2, None] * Psi[:, 2])
     assert np.array_equal(var, host_diag(diag, sw, Psi)) and (var > 0).all() and not np.array_equal(var, diag)
-    et, ed, ey, lens = pm.effective(s)
+    et, ed, ey, lens, _ = pm.effective(s)
     assert tuple(lens) == pm.FAMILIES[fam]["lengths"][1] == (300, 1000, 513, 511, 77)
     for b, n in enumerate(lens):
         assert et[b].shape == (n,) and np.array_equal(et[b], t[b, :n])
@@ -191,7 +314,7 @@ def test_effective_is_the_numpy_statement_of_the_residual_and_the_variances():
     s.y_shared, s.d_shared, s.mean, s.psi, s.nw = True, True, ("per", 3), ("shared", 1), 2
     t, diag, y = pm.series("narrow", 2, 0)
     mu, sw, Psi = pm.mean_values("narrow", 2, 3), pm.psi_weights("narrow", 2, 2), pm.psi("narrow", 2, False, 1)
-    et, ed, ey, lens = pm.effective(s)
+    et, ed, ey, lens, _ = pm.effective(s)
     assert Psi.shape == (3, 601) and set(lens) == {601}
     for b in range(5):
         assert np.array_equal(ey[b], y[0] - mu[b])
@@ -219,7 +342,7 @@ def test_the_double_oracle_is_no_truth_at_1e_10_on_the_near_singular_problem():
         tabs = pm.host_coefficients(state)
     finally:
         pm.kernel_factory = saved
-    t, d, r, _ = pm.effective(state)
+    t, d, r, _, _ = pm.effective(state)
     own = {}
     for b in (cfg["ill"], 0):
         co = [x[b] for x in tabs[:6]]
