@@ -140,6 +140,13 @@ def _load():
     lib.clr_sharded_one_step_ahead.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _ip]
     lib.clr_batch_forecast.argtypes = [C.c_void_p, C.c_int, _dp, C.c_long, _dp, _dp]
     lib.clr_sharded_forecast.argtypes = [C.c_void_p, C.c_int, _dp, C.c_long, _dp, _dp]
+    for pre in ("clr_batch", "clr_sharded"):
+        getattr(lib, pre + "_periodogram").argtypes = [C.c_void_p, C.c_int, _dp, C.c_long, C.c_double, C.c_int, C.c_double,
+                                                       _dp, _dp, _dp, _dp, _ip]
+        getattr(lib, pre + "_set_periodogram_tile").argtypes = [C.c_void_p, C.c_int]
+    lib.clr_batch_get_periodogram_ms.argtypes = [C.c_void_p, _dp]
+    lib.clr_sharded_get_periodogram_ms.argtypes = [C.c_void_p, _dp]
+    lib.clr_batch_debug_get_periodogram_block.argtypes = [C.c_void_p, _ip]
     lib.clr_batch_predict_terms.argtypes = [C.c_void_p, C.c_int, _dp, C.c_long, C.c_int, C.c_void_p, _dp, _dp]
     lib.clr_sharded_predict_terms.argtypes = [C.c_void_p, C.c_int, _dp, C.c_long, C.c_int, C.c_void_p, _dp, _dp]
     lib.clr_batch_predict_cov.argtypes = [C.c_void_p, C.c_int, _dp, C.c_long, _dp]
@@ -509,6 +516,54 @@ def _one_step_ahead(plan, name, check, b):
     z, D, st = np.empty(shape), np.empty((plan.B, plan.N)), np.empty(plan.B, dtype=np.int32)
     check(getattr(_load(), name)(plan._h, int(nrhs), bp, _ptr(z), _ptr(D), st.ctypes.data_as(_ip)))
     return OneStepAhead(z, D, st)
+
+
+class Periodogram(collections.namedtuple("Periodogram", ["power", "coef", "cov", "status", "gram"])):
+    """The periodogram under a plan's covariance (``periodogram``): per problem and trial frequency ``power[B, F]``, the
+    gain in maximised log-likelihood of the sinusoid; ``coef[B, F, K]`` the fitted amplitudes of ``(cos, sin)`` --
+    ``(1, cos, sin)`` with the offset --; ``cov[B, F, K, K]`` their covariance ``G^-1``; ``status[B, F]``; ``gram[B, F, K + 1,
+    K + 1]`` = ``[[G, d], [d^T, q]]`` with ``return_gram=True``, else ``None``.  Refused entries are NaN."""
+    __slots__ = ()
+
+    @property
+    def amplitude(self):
+        """``hypot`` of the (cos, sin) coefficients: the amplitude of ``A cos(w tau) + B sin(w tau)``."""
+        return np.hypot(self.coef[..., -2], self.coef[..., -1])
+
+    @property
+    def phase(self):
+        """``phi`` of ``amplitude * cos(w tau + phi)`` = ``A cos(w tau) + B sin(w tau)``: ``arctan2(-B, A)``."""
+        return np.arctan2(-self.coef[..., -1], self.coef[..., -2])
+
+
+def _periodogram_args(B, omega, offset, t_ref, min_pivot):
+    """The arguments of ``periodogram`` of both plan classes, checked before the library is touched:
+    ``(omega, stride, F, t_ref, min_pivot, K)``."""
+    omega = _f64(omega)
+    if omega.ndim == 1:
+        stride = 0
+    elif omega.ndim == 2 and omega.shape[0] == B:
+        stride = omega.shape[1]
+    else:
+        raise ValueError("dimension mismatch")
+    if not np.all(np.isfinite(omega)):
+        raise ValueError("the frequencies must be finite")
+    t_ref = float(t_ref)
+    if not np.isfinite(t_ref):
+        raise ValueError("t_ref must be finite")
+    return omega, stride, omega.shape[-1], t_ref, _check_min_pivot(min_pivot), (3 if offset else 2)
+
+
+def _periodogram(plan, name, check, omega, offset, t_ref, min_pivot, return_gram):
+    """``periodogram`` of both plan classes."""
+    omega, stride, F, t_ref, p, K = _periodogram_args(plan.B, omega, offset, t_ref, min_pivot)
+    B = plan.B
+    power, coef, cov = np.empty((B, F)), np.empty((B, F, K)), np.empty((B, F, K, K))
+    gram = np.empty((B, F, K + 1, K + 1)) if return_gram else None
+    st = np.empty((B, F), dtype=np.int32)
+    check(getattr(_load(), name)(plan._h, int(F), _ptr(omega), stride, t_ref, 1 if offset else 0, p, _ptr(power), _ptr(coef),
+                                 _ptr(cov), None if gram is None else _ptr(gram), st.ctypes.data_as(_ip)))
+    return Periodogram(power, coef, cov, st, gram)
 
 
 def _forecast(plan, name, check, xs, return_var, mean_basis):
@@ -1253,6 +1308,35 @@ class BatchedGP(object):
         one-step-ahead prediction of sample n (:meth:`one_step_ahead`: ``y_n - innovation_n``, ``variance_n - diag_n -
         jitter``).  One forward pass over the series plus O(J^2) per point; tiles follow :meth:`set_predict_tile`."""
         return _forecast(self, "clr_batch_forecast", _check, xs, return_var, mean_basis)
+
+    def periodogram(self, omega, offset=False, t_ref=0.0, min_pivot=1e-10, return_gram=False):
+        """The periodogram under the plan's covariance, a :class:`Periodogram` (``clr_batch_periodogram``): at every
+        trial angular frequency ``omega`` -- ``(F,)`` shared by all problems or ``(B, F)`` -- the generalised-least-squares
+        fit of ``A cos(omega (t - t_ref)) + B sin(omega (t - t_ref))``, plus a constant with ``offset=True``, to the
+        residual in force with ``K^-1`` as the metric, from the factor of the last materialising run.  ``power`` is the
+        log-likelihood the fit gains over the model without the sinusoid; ``coef`` holds ``(A, B)`` -- ``(offset, A, B)``
+        --, ``cov`` their covariance; ``.amplitude`` and ``.phase`` follow from them.  A frequency whose normal matrix
+        is not positive definite to ``min_pivot`` (``omega = 0``; with the offset, one far below ``1 / T``) has status
+        ``CLR_NOT_POSITIVE_DEFINITE`` and NaN there.  Two forward walks over the series per block of frequencies with
+        the columns formed on the fly: nothing is uploaded but ``omega``; narrow plans (widths 1..8), chunked."""
+        return _periodogram(self, "clr_batch_periodogram", _check, omega, offset, t_ref, min_pivot, return_gram)
+
+    def set_periodogram_tile(self, frequencies=0):
+        """Frequencies per tile of :meth:`periodogram` (``clr_batch_set_periodogram_tile``); 0: automatic.  The results
+        do not depend on it."""
+        _check(_load().clr_batch_set_periodogram_tile(self._h, int(frequencies)))
+
+    def periodogram_ms(self):
+        """Device time of the last :meth:`periodogram`'s kernels, ms."""
+        ms = C.c_double(0.0)
+        _check(_load().clr_batch_get_periodogram_ms(self._h, C.byref(ms)))
+        return ms.value
+
+    def periodogram_block(self):
+        """Frequencies one lane of :meth:`periodogram`'s walks carries at this width (a test hook)."""
+        n = C.c_int(0)
+        _check(_load().clr_batch_debug_get_periodogram_block(self._h, C.byref(n)))
+        return n.value
 
     def predict_terms(self, xs, groups=None, return_var=False):
         """Component separation: the posterior of the process of each GROUP of kernel terms, ``E[f_g(x) | y] = k_g*^T
@@ -2128,6 +2212,21 @@ class ShardedBatchedGP(object):
     def forecast(self, xs, return_var=False, mean_basis=None):
         """The causal forecast of every problem at ``xs`` (as :meth:`BatchedGP.forecast`), every shard on its slice."""
         return _forecast(self, "clr_sharded_forecast", lambda st: self._ok(st), xs, return_var, mean_basis)
+
+    def periodogram(self, omega, offset=False, t_ref=0.0, min_pivot=1e-10, return_gram=False):
+        """The periodogram under the plan's covariance (as :meth:`BatchedGP.periodogram`), every shard on its slice: the
+        unsharded plan's bits."""
+        return _periodogram(self, "clr_sharded_periodogram", lambda st: self._ok(st), omega, offset, t_ref, min_pivot, return_gram)
+
+    def set_periodogram_tile(self, frequencies=0):
+        """Frequencies per tile of :meth:`periodogram` on every shard."""
+        self._ok(_load().clr_sharded_set_periodogram_tile(self._h, int(frequencies)))
+
+    def periodogram_ms(self):
+        """Device time of the last :meth:`periodogram`'s kernels: the largest over the shards, which run concurrently."""
+        ms = C.c_double(0.0)
+        self._ok(_load().clr_sharded_get_periodogram_ms(self._h, C.byref(ms)))
+        return ms.value
 
     def predict_terms(self, xs, groups=None, return_var=False):
         """The posterior of each group of kernel terms at ``xs`` (as :meth:`BatchedGP.predict_terms`), every shard on

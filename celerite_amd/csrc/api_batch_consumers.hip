@@ -1,7 +1,7 @@
 // celerite_amd/csrc/api_batch_consumers.hip -- C ABI of the batched plans, second part: the consumers of a plan's factor
 // and coefficients (clr_batch_get_factor, _solve, _dot_L, _dot, _predict, _predict_var, _predict_var_recurrence,
 // _one_step_ahead, _forecast, _predict_terms, _predict_cov, _sample_conditional, _leave_one_out, _grad_mean_weights,
-// _fit_mean_weights, _grad_noise_weights, _grad_amplitudes) and the helpers they
+// _fit_mean_weights, _grad_noise_weights, _grad_amplitudes, _periodogram) and the helpers they
 // share: the factor and route checks, the frame of one call's device work, prediction points and tiles.
 #include "api_internal.h"
 #include "clr_bmean_kernels.h"
@@ -1651,6 +1651,132 @@ int clr_batch_fit_mean_weights(clr_batch* h, double min_pivot, double* w_hat, do
     if (quad_profiled) quad_profiled[b] = evaluated ? o[K + K * K] : nan;
     if (logdet_gram) logdet_gram[b] = evaluated ? o[K + K * K + 1] : nan;
     if (status) status[b] = evaluated ? solve_status[b] : stat[b];
+  }
+  return CLR_OK;
+}
+
+// ---- clr_batch_periodogram: the sinusoid fit under the plan's covariance at every trial frequency (clr_bperiodogram_kernels.h)
+
+int clr_batch_set_periodogram_tile(clr_batch* h, int frequencies) {
+  h->periodogram_tile = frequencies > 0 ? frequencies : 0;
+  return CLR_OK;
+}
+
+int clr_batch_get_periodogram_ms(const clr_batch* h, double* device_ms) {
+  if (device_ms) *device_ms = h->periodogram_ms;
+  return CLR_OK;
+}
+
+int clr_batch_debug_get_periodogram_block(const clr_batch* h, int* frequencies) {
+  if (frequencies) *frequencies = h->launch ? h->launch->periodogram_block : 0;
+  return CLR_OK;
+}
+
+// For every problem and trial frequency: the bordered Gram matrix of the columns (cos, sin) or (1, cos, sin) and the
+// residual in force under K^-1, and the small solve of clr_batch_fit_mean_weights on it.  The residual (and the constant
+// column) are whitened once by the forward pass of clr_batch_one_step_ahead (the chunk maps under clr_batch_solve's
+// validity rule); a tile of frequencies at a time -- as many as fit predict_tile's 1 GiB, or the caller's -- runs the two
+// walks of clr_bperiodogram_kernels.h and the reduction.  Nothing goes up but the frequencies.
+int clr_batch_periodogram(clr_batch* h, int F, const double* omega, long omega_stride, double t_ref, int offset, double min_pivot,
+                          double* power, double* coef, double* cov, double* gram, int* status) {
+  int st = require_device(h->device);
+  if (st != CLR_OK) return st;
+  const char* e = "clr_batch_periodogram";
+  if (F < 0 || (F > 0 && !omega)) return fail(CLR_INVALID_ARGUMENT, std::string(e) + ": F >= 0 and the frequencies");
+  if (omega_stride != 0 && omega_stride != F)
+    return fail(CLR_INVALID_ARGUMENT, std::string(e) + ": the frequencies' stride is 0 (shared by all problems) or F");
+  if (!power && !coef && !cov && !gram && !status) return fail(CLR_INVALID_ARGUMENT, std::string(e) + ": at least one output array");
+  if (!std::isfinite(t_ref)) return fail(CLR_INVALID_ARGUMENT, std::string(e) + ": t_ref is finite");
+  if (!std::isfinite(min_pivot) || min_pivot < 0.0 || min_pivot >= 1.0)
+    return fail(CLR_INVALID_ARGUMENT, std::string(e) + ": min_pivot is finite and in [0, 1)");
+  const size_t B = (size_t)h->B, Ff = (size_t)F, nsrc = omega_stride == 0 ? 1 : B;
+  for (size_t i = 0; i < nsrc * Ff; ++i)
+    if (!std::isfinite(omega[i])) return fail(CLR_INVALID_ARGUMENT, std::string(e) + ": the frequencies are finite");
+  if ((st = refuse_ragged(h, e)) != CLR_OK) return st;
+  if (h->J_general > 0)
+    return fail(CLR_UNSUPPORTED, std::string(e) + " covers celerite-only plans: with general terms, fit (cos, sin) as a linear mean "
+                                 "through the object API's solves");
+  if (!h->launch)
+    return fail(CLR_UNSUPPORTED, std::string(e) + " covers narrow plans (widths 1..8): a wide plan takes clr_batch_set_mean_basis with "
+                                 "(cos, sin) and clr_batch_fit_mean_weights per frequency");
+  if (h->amp_active)
+    return fail(CLR_UNSUPPORTED, std::string(e) + ": amplitudes are in force (clr_batch_set_amplitudes) -- the resident series are y / s, "
+                                 "where a sinusoid in observed units is none: remove the amplitude model for the scan");
+  if (F == 0) return CLR_OK;
+  if ((st = require_factor(h, true)) != CLR_OK) return st;
+  if (h->B > 65535) return fail(CLR_UNSUPPORTED, std::string(e) + ": at most 65535 problems per plan (a grid axis): shard the batch");
+  Route route;
+  route.chunk_hint = " (shorter series: clr_batch_fit_mean_weights with (cos, sin) as the basis)";
+  if ((st = require_route(h, e, route)) != CLR_OK) return st;
+  clr::BatchParams P;
+  if ((st = consumer_params(h, false, P)) != CLR_OK) return st;
+  const size_t J = (size_t)h->J, nc = (size_t)h->nchunk, cells = (size_t)h->L * nc, nz = offset ? 2 : 1;
+  const size_t K = offset ? 3 : 2, K1 = K + 1;
+  // a frequency's scratch: the offsets and start states of its two columns, its chunks' sums
+  const size_t per_f = B * nc * (4 * J + clr::BPG_SUMS);
+  const size_t budget = (size_t)1 << 27;  // doubles (predict_tile's)
+  size_t R = h->periodogram_tile > 0 ? (size_t)h->periodogram_tile : std::max<size_t>(1, budget / per_f);
+  R = std::min(std::min<size_t>(R, 32767), Ff);  // (the frequency blocks ride on grid.z; 2 R right-hand sides)
+  DevBuf dom, dpart, dbase, dbpart, dpower, dcoef, dcov, dgram;
+  DevArray<int> dstat;
+  if ((st = h->bs_x.reserve(B * nz * cells)) != CLR_OK) return st;
+  if ((st = h->bs_M.reserve(B * nc * J * J)) != CLR_OK) return st;
+  if ((st = h->bs_off.reserve(B * std::max(nz, 2 * R) * nc * J)) != CLR_OK) return st;
+  if ((st = h->bs_starts.reserve(B * std::max(nz, 2 * R) * nc * J)) != CLR_OK) return st;
+  if ((st = dpart.reserve(B * R * nc * clr::BPG_SUMS)) != CLR_OK) return st;
+  if ((st = dbpart.reserve(B * nc * 3)) != CLR_OK) return st;
+  if ((st = dbase.reserve(B * 3)) != CLR_OK) return st;
+  if (power && (st = dpower.reserve(B * Ff)) != CLR_OK) return st;
+  if (coef && (st = dcoef.reserve(B * Ff * K)) != CLR_OK) return st;
+  if (cov && (st = dcov.reserve(B * Ff * K * K)) != CLR_OK) return st;
+  if (gram && (st = dgram.reserve(B * Ff * K1 * K1)) != CLR_OK) return st;
+  if ((st = dstat.reserve(B * Ff)) != CLR_OK) return st;
+  std::vector<int> fstat(B * Ff);
+  const double keep_solve_ms = h->solve_device_ms;
+  {
+    ConsumerFrame frame{h};
+    hipStream_t s = h->stream.get();
+    if ((st = upload(dom, omega, nsrc * Ff, s)) != CLR_OK) return st;
+    HIP_TRY(frame.start());
+    // z_r (and z_1) in bs_x: the residual in force and the constant column, whitened in place
+    const clr::BSolveParams Q = narrow_solve_begin(h, frame, (int)nz);
+    clr::launch_relayout(h->y.p, h->y_stride, h->bs_x.p, (long)(nz * cells), h->B, h->N, h->L, h->nchunk, 0, s);
+    if (offset) clr::launch_fill_rows(h->bs_x.p + cells, (long)(nz * cells), h->B, (long)cells, 1.0, s);
+    clr::BFilterParams Z{};
+    Z.nrhs = (int)nz; Z.lean = Q.lean; Z.have_M = Q.have_M;
+    Z.xT = Z.zT = Q.xT; Z.M = Q.M; Z.off = Q.off; Z.starts = Q.starts;
+    h->launch->bfilter(P, Z, 0, s);
+    clr::launch_periodogram_base(h->bs_x.p, h->D.p, (int)nz, h->B, h->N, h->L, h->nchunk, dbpart.p, dbase.p, s);
+    clr::BPeriodogramParams S{};
+    S.lean = Q.lean; S.offset = offset ? 1 : 0;
+    S.omega_stride = omega_stride; S.t_ref = t_ref;
+    S.zT = h->bs_x.p; S.M = h->bs_M.p; S.off = h->bs_off.p; S.starts = h->bs_starts.p; S.part = dpart.p;
+    const clr::PeriodogramOut out{power ? dpower.p : nullptr, coef ? dcoef.p : nullptr, cov ? dcov.p : nullptr,
+                                  gram ? dgram.p : nullptr, dstat.p};
+    for (size_t f0 = 0; f0 < Ff; f0 += R) {
+      S.nf = (int)std::min(R, Ff - f0);
+      S.omega = dom.p + f0;
+      h->launch->bperiodogram(P, S, s);
+      clr::launch_periodogram_reduce(dpart.p, dbase.p, h->B, S.nf, h->nchunk, S.offset, min_pivot, (long)Ff, (long)f0, out, s);
+    }
+    HIP_TRY(frame.stop());
+    HIP_TRY(hipGetLastError());
+    if (power) HIP_TRY(hipMemcpyAsync(power, dpower.p, B * Ff * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (coef) HIP_TRY(hipMemcpyAsync(coef, dcoef.p, B * Ff * K * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (cov) HIP_TRY(hipMemcpyAsync(cov, dcov.p, B * Ff * K * K * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (gram) HIP_TRY(hipMemcpyAsync(gram, dgram.p, B * Ff * K1 * K1 * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(fstat.data(), dstat.p, B * Ff * sizeof(int), hipMemcpyDeviceToHost, s));
+    if ((st = frame.finish()) != CLR_OK) return st;
+  }
+  h->periodogram_ms = h->solve_device_ms;
+  h->solve_device_ms = keep_solve_ms;  // (it stays the solve's)
+  // the statuses of the evaluation in force come first: a problem without a factor is NaN at every frequency
+  if ((st = nan_rows_without_factor(h, {{power, Ff}, {coef, Ff * K}, {cov, Ff * K * K}, {gram, Ff * K1 * K1}})) != CLR_OK) return st;
+  if (status) {
+    std::vector<int> stat;
+    if ((st = evaluation_statuses(h, stat)) != CLR_OK) return st;
+    for (size_t b = 0; b < B; ++b)
+      for (size_t f = 0; f < Ff; ++f) status[b * Ff + f] = stat[b] == CLR_OK ? fstat[b * Ff + f] : stat[b];
   }
   return CLR_OK;
 }

@@ -416,7 +416,9 @@ struct clr_batch {
   DevBuf pv_S;
   bool pv_S_valid = false, loo_Q_valid = false;
   int predict_tile = 0;                         // clr_batch_set_predict_tile: prediction points per tile of the point consumers (predict_tile; 0: automatic)
-  int conditional_tile = 0;                     // clr_batch_set_conditional_tile: problems per tile of clr_batch_predict_cov / _sample_conditional (0: automatic)
+  int periodogram_tile = 0;                     // clr_batch_set_periodogram_tile: frequencies per tile of clr_batch_periodogram (0: automatic)
+  double periodogram_ms = 0.0;                  // device time of the last clr_batch_periodogram's kernels
+  int conditional_tile = 0;                   // clr_batch_set_conditional_tile: problems per tile of clr_batch_predict_cov / _sample_conditional (0: automatic)
   clr::Event bs_ev[2];                          // ... its two timing events, created by the first solve, kept for the plan's life
   int factor_layout = 0;      // clr_batch_set_factor_layout: 0 the reference's four arrays, 1 lean (W, D; phi, u regenerated)
   bool factor_is_lean = false;  // what the factor in HBM holds (set by the materialising run that wrote it)

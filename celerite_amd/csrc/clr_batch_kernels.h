@@ -1030,6 +1030,7 @@ __global__ void __launch_bounds__(64) warm_check_kernel(const BatchParams P) {
 #include "clr_binvdiag_kernels.h"
 #include "clr_bpredvar_rec_kernels.h"
 #include "clr_bfilter_kernels.h"
+#include "clr_bperiodogram_kernels.h"
 #include "clr_bterms_kernels.h"
 #include "clr_bcond_kernels.h"
 #include "clr_binfo_kernels.h"
@@ -1069,6 +1070,9 @@ struct BatchLaunchers {
   // points (S.npts > 0) the mean (S.mean) and variance (S.var) at each given the samples strictly before it
   // (clr_bfilter_kernels.h); `xfast`: the points' phases stay below CLR_FAST_TRIG_LIMIT
   void (*bfilter)(const BatchParams&, BFilterParams S, int xfast, hipStream_t);
+  // the periodogram's sums of one tile of frequencies for all problems from the materialised factor
+  // (clr_bperiodogram_kernels.h): S.omega -> S.part; the chunk maps S.M are formed
+  void (*bperiodogram)(const BatchParams&, BPeriodogramParams S, hipStream_t);
   // the posterior mean (S.mean) and variance (S.var) of every group of kernel terms for all problems at one tile of SORTED
   // points (clr_bterms_kernels.h); `xfast`: the points' phases stay below CLR_FAST_TRIG_LIMIT
   void (*bterms)(const BatchParams&, BTermsParams S, int xfast, hipStream_t);
@@ -1080,6 +1084,7 @@ struct BatchLaunchers {
   // lean factor of problem b (replay mode 3) -> the reference's storage, phi and u regenerated (t: the problem's row-major times)
   void (*expand)(const BatchParams&, int b, const double* t, double* phi, double* u, double* W, double* D, hipStream_t);
   int elem_doubles, start_doubles;
+  int periodogram_block;  // frequencies per lane of the periodogram's walks (bperiodogram_block)
 };
 
 bool launch_summarize_split(const BatchParams& P, int JR, int JC, hipStream_t s);
@@ -1322,6 +1327,22 @@ struct BatchImpl {
   static void bfilter(const BatchParams& P, BFilterParams S, int xfast, hipStream_t s) {
     lean_fast(S.lean, P, [&](auto L, auto F) { bfilter_go<L(), F()>(P, S, xfast, s); });
   }
+  // the periodogram's sums of one tile of frequencies: the zero-start walk's end offsets, the solve's forward walk over
+  // the chunks with the tile's 2 nf columns as right-hand sides, the walk from the start states with the sums
+  template <bool LEAN, bool FAST>
+  static void bperiodogram_go(const BatchParams& P, const BPeriodogramParams& S, hipStream_t s) {
+    constexpr int J = JR + 2 * JC, FB = bperiodogram_block(J);
+    const dim3 grid((P.nchunk + 63) / 64, P.B, (S.nf + FB - 1) / FB), pgrid((unsigned)(((long)P.B * 2 * S.nf + 63) / 64));
+    hipLaunchKernelGGL((bperiodogram_walk_kernel<JR, JC, LEAN, FAST, FB, false>), grid, dim3(64), 0, s, P, S);
+    BSolveParams Q;
+    Q.nrhs = 2 * S.nf; Q.r = 0; Q.lean = S.lean; Q.have_M = 1;
+    Q.xT = nullptr; Q.M = S.M; Q.off = S.off; Q.starts = S.starts;
+    hipLaunchKernelGGL((bsolve_prefix_kernel<J, false>), pgrid, dim3(64), 0, s, P, Q);
+    hipLaunchKernelGGL((bperiodogram_walk_kernel<JR, JC, LEAN, FAST, FB, true>), grid, dim3(64), 0, s, P, S);
+  }
+  static void bperiodogram(const BatchParams& P, BPeriodogramParams S, hipStream_t s) {
+    lean_fast(S.lean, P, [&](auto L, auto F) { bperiodogram_go<L(), F()>(P, S, s); });
+  }
   // component separation at one tile of sorted points: the points' features; with S.mean, unless an earlier tile of the
   // call has formed them, the chunks' start states of b and p (the two passes of the batched dot on alpha, offsets and
   // walks) and the two mean replays; with S.var, unless formed, the start states of S and Q exactly as bpredvar_rec_go,
@@ -1455,7 +1476,8 @@ struct BatchImpl {
   }
   static BatchLaunchers table() {
     return BatchLaunchers{&summarize, &prefix, &correct, &replay, &sequential, &compose_check, &warm, &grad, &grad_reverse, &information,
-                          &bsolve, &bdotl, &bdot, &bpredvar, &binvdiag, &bpredvar_rec, &bfilter, &bterms, &bcond, &expand, Widths<JR, JC>::ELEM, Widths<JR, JC>::START};
+                          &bsolve, &bdotl, &bdot, &bpredvar, &binvdiag, &bpredvar_rec, &bfilter, &bperiodogram, &bterms, &bcond, &expand, Widths<JR, JC>::ELEM, Widths<JR, JC>::START,
+                          bperiodogram_block(JR + 2 * JC)};
   }
 };
 

@@ -130,4 +130,23 @@ void launch_gram_solve(const double* gram, const double* w0, double min_pivot, i
 size_t gram_solve_workspace(int B, int K);  // doubles of `work`
 inline size_t gram_solve_out_doubles(int K) { return (size_t)K + (size_t)K * K + 2; }
 
+// ---- clr_batch_periodogram: what does not depend on the plan's width (the walks: clr_bperiodogram_kernels.h)
+// `rows` rows of `cells` doubles, `stride` apart, all set to v (the constant column, chunk-interleaved)
+void launch_fill_rows(double* dst, long stride, int rows, long cells, double v, hipStream_t s);
+// base[b] = (q, G_00, d_0) = sum_n (z_r z_r, z_1 z_1, z_1 z_r)[n] / D_n from the chunk-interleaved whitened columns
+// zT [B][nz][L][nchunk] (nz = 1: q alone) and the factor's D [B][L][nchunk]: per chunk, then the chunks in order;
+// part: B * nchunk * 3 doubles
+void launch_periodogram_base(const double* zT, const double* D, int nz, int B, int N, int L, int nchunk, double* part, double* base,
+                             hipStream_t s);
+// One thread per (problem, frequency of the tile): the chunks' sums [B][nf][nchunk][7] (cc, cs, ss, cr, sr, c1, s1) added in
+// chunk order, the bordered matrix [[G, d], [d^T, q]] of the columns (c, s) or (1, c, s), mirrored, and the small solve
+// (clr_gram_solve.h, w0 = 0).  Frequency f of the tile goes to entry b * F + f0 + f of the outputs; any may be null.
+// power = 1/2 ((d_0 coef_0 + d_1 coef_1) + ...), with the offset less 1/2 d_0^2 / G_00, every operation rounded on its own.
+struct PeriodogramOut {
+  double *power, *coef, *cov, *gram;
+  int* status;
+};
+void launch_periodogram_reduce(const double* part, const double* base, int B, int nf, int nchunk, int offset, double min_pivot,
+                               long F, long f0, const PeriodogramOut& out, hipStream_t s);
+
 }  // namespace clr

@@ -150,7 +150,113 @@ __global__ void __launch_bounds__(64) gram_solve_kernel(const double* __restrict
                          work + b * gram_solve_work(K));
 }
 
+__global__ void __launch_bounds__(256) fill_rows_kernel(double* __restrict__ dst, long stride, long cells, double v) {
+  double* row = dst + (long)blockIdx.y * stride;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < cells; i += (long)gridDim.x * 256) row[i] = v;
+}
+
+// one thread per (problem, chunk): the chunk's share of q, G_00, d_0
+__global__ void __launch_bounds__(64) periodogram_base_kernel(const double* __restrict__ zT, const double* __restrict__ D, int nz,
+                                                              int N, int L, int nchunk, double* __restrict__ part) {
+  const int b = blockIdx.y, c = blockIdx.x * 64 + threadIdx.x;
+  if (c >= nchunk) return;
+  const long cells = (long)L * nchunk;
+  const double* zr = zT + (long)b * nz * cells + c;
+  const double* z1 = zr + cells;
+  const double* d = D + (long)b * cells + c;
+  const int last = (N - c * L < L) ? N - c * L : L;
+  double q = 0.0, g00 = 0.0, d0 = 0.0;
+  for (int i = 0; i < last; ++i) {
+    const double dn = d[(long)i * nchunk], r = zr[(long)i * nchunk];
+    q = q + (r * r) / dn;
+    if (nz > 1) {
+      const double o = z1[(long)i * nchunk];
+      g00 = g00 + (o * o) / dn;
+      d0 = d0 + (o * r) / dn;
+    }
+  }
+  double* p = part + ((long)b * nchunk + c) * 3;
+  p[0] = q; p[1] = g00; p[2] = d0;
+}
+
+__global__ void __launch_bounds__(64) periodogram_base_finish_kernel(const double* __restrict__ part, int B, int nchunk,
+                                                                     double* __restrict__ base) {
+  const int b = blockIdx.x * 64 + threadIdx.x;
+  if (b >= B) return;
+  double s[3] = {0.0, 0.0, 0.0};
+  for (int c = 0; c < nchunk; ++c)
+    for (int i = 0; i < 3; ++i) s[i] = s[i] + part[((long)b * nchunk + c) * 3 + i];
+  for (int i = 0; i < 3; ++i) base[(long)b * 3 + i] = s[i];
+}
+
+template <int K>  // 2: the columns (c, s); 3: (1, c, s)
+__global__ void __launch_bounds__(64) periodogram_reduce_kernel(const double* __restrict__ part, const double* __restrict__ base, int B,
+                                                                int nf, int nchunk, double min_pivot, long F, long f0,
+                                                                const PeriodogramOut out) {
+  constexpr bool offset = K == 3;
+  const long idx = (long)blockIdx.x * 64 + threadIdx.x;
+  if (idx >= (long)B * nf) return;
+  const long b = idx / nf, f = idx % nf, o = b * F + f0 + f;
+  double s[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  const double* p = part + idx * nchunk * 7;
+  for (int c = 0; c < nchunk; ++c)
+    for (int i = 0; i < 7; ++i) s[i] = s[i] + p[(long)c * 7 + i];
+  const double q = base[b * 3], g00 = base[b * 3 + 1], d0 = base[b * 3 + 2];
+  constexpr int K1 = K + 1;
+  double S[K1 * K1];
+  // the upper triangle, mirrored below: columns (c, s) or (1, c, s), then the border (d, q)
+  constexpr int ic = offset ? 1 : 0, is = ic + 1;
+  if (offset) {
+    S[0] = g00; S[0 * K1 + ic] = s[5]; S[0 * K1 + is] = s[6]; S[0 * K1 + K] = d0;
+  }
+  S[ic * K1 + ic] = s[0]; S[ic * K1 + is] = s[1]; S[ic * K1 + K] = s[3];
+  S[is * K1 + is] = s[2]; S[is * K1 + K] = s[4];
+  S[K * K1 + K] = q;
+  for (int i = 0; i < K1; ++i)
+    for (int j = 0; j < i; ++j) S[i * K1 + j] = S[j * K1 + i];
+  if (out.gram)
+    for (int i = 0; i < K1 * K1; ++i) out.gram[o * K1 * K1 + i] = S[i];
+  const double zero[3] = {0.0, 0.0, 0.0};
+  double w[3], cv[9], quad, ld, work[15];
+  const int st = gram_solve(K, S, zero, min_pivot, w, cv, &quad, &ld, work);
+  const double nan = __builtin_nan("");
+  double pw = nan;
+  if (st == 0) {
+    pw = S[0 * K1 + K] * w[0] + S[1 * K1 + K] * w[1];
+    if (offset) pw = (pw + S[2 * K1 + K] * w[2]) - (d0 * d0) / g00;
+    pw = 0.5 * pw;
+  } else {
+    for (int i = 0; i < K; ++i) w[i] = nan;  // (gram_solve leaves w0 there)
+  }
+  if (out.power) out.power[o] = pw;
+  if (out.coef)
+    for (int i = 0; i < K; ++i) out.coef[o * K + i] = w[i];
+  if (out.cov)
+    for (int i = 0; i < K * K; ++i) out.cov[o * K * K + i] = cv[i];
+  if (out.status) out.status[o] = st;
+}
+
 }  // namespace
+
+void launch_fill_rows(double* dst, long stride, int rows, long cells, double v, hipStream_t s) {
+  const dim3 grid((unsigned)std::min<long>((cells + 255) / 256, 1024), (unsigned)rows);
+  hipLaunchKernelGGL(fill_rows_kernel, grid, dim3(256), 0, s, dst, stride, cells, v);
+}
+
+void launch_periodogram_base(const double* zT, const double* D, int nz, int B, int N, int L, int nchunk, double* part, double* base,
+                             hipStream_t s) {
+  hipLaunchKernelGGL(periodogram_base_kernel, dim3((unsigned)((nchunk + 63) / 64), (unsigned)B), dim3(64), 0, s, zT, D, nz, N, L, nchunk,
+                     part);
+  hipLaunchKernelGGL(periodogram_base_finish_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, part, B, nchunk, base);
+}
+
+void launch_periodogram_reduce(const double* part, const double* base, int B, int nf, int nchunk, int offset, double min_pivot,
+                               long F, long f0, const PeriodogramOut& out, hipStream_t s) {
+  const long n = (long)B * nf;
+  const dim3 grid((unsigned)((n + 63) / 64));
+  if (offset) hipLaunchKernelGGL(periodogram_reduce_kernel<3>, grid, dim3(64), 0, s, part, base, B, nf, nchunk, min_pivot, F, f0, out);
+  else hipLaunchKernelGGL(periodogram_reduce_kernel<2>, grid, dim3(64), 0, s, part, base, B, nf, nchunk, min_pivot, F, f0, out);
+}
 
 void launch_fit_rhs_interleaved(const FitRhs& R, int c0, int nr, int B, int L, int nchunk, double* dst, long cells, hipStream_t s) {
   const dim3 grid((L + 31) / 32, (nchunk + 31) / 32, (unsigned)(B * nr));

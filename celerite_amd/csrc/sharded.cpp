@@ -916,6 +916,37 @@ int clr_sharded_set_conditional_tile(clr_sharded* h, int problems) {
   return CLR_OK;
 }
 
+// clr_batch_periodogram, every shard on its slice (a (problem, frequency)'s result does not depend on the sharding); the
+// other arguments are checked by the shards
+int clr_sharded_periodogram(clr_sharded* h, int F, const double* omega, long omega_stride, double t_ref, int offset,
+                            double min_pivot, double* power, double* coef, double* cov, double* gram, int* status) {
+  const long Ff = F, K = offset ? 3 : 2, K1 = K + 1;
+  g_sharded_error = "clr_sharded_periodogram: F >= 0, the frequencies with stride 0 or F, and at least one output array";
+  return on_slices(h, F >= 0 && (F == 0 || omega) && (omega_stride == 0 || omega_stride == F) && (power || coef || cov || gram || status),
+                   [=](clr_batch* p, long lo) {
+    return clr_batch_periodogram(p, F, omega ? omega + lo * omega_stride : nullptr, omega_stride, t_ref, offset, min_pivot,
+                                 at(power, lo * Ff), at(coef, lo * Ff * K), at(cov, lo * Ff * K * K), at(gram, lo * Ff * K1 * K1),
+                                 at(status, lo * Ff));
+  });
+}
+
+int clr_sharded_set_periodogram_tile(clr_sharded* h, int frequencies) {
+  for (clr_batch* p : h->plan) clr_batch_set_periodogram_tile(p, frequencies);
+  return CLR_OK;
+}
+
+// the scan's device time: the largest over the shards, which run concurrently
+int clr_sharded_get_periodogram_ms(const clr_sharded* h, double* device_ms) {
+  double m = 0.0;
+  for (clr_batch* p : h->plan) {
+    double v = 0.0;
+    (void)clr_batch_get_periodogram_ms(p, &v);
+    m = std::max(m, v);
+  }
+  if (device_ms) *device_ms = m;
+  return CLR_OK;
+}
+
 int clr_sharded_run_timed(clr_sharded* h, int steps, double* shard_ms /* [nshards] or NULL */) {
   // (a timing tool: every shard times its own steps and settles them by its own counts)
   const int st0 = resolve_all(h);

@@ -784,6 +784,42 @@ int clr_batch_one_step_ahead(clr_batch* h, int nrhs, const double* b, double* in
  * the sharding, bit for bit.  A NaN point gives NaN; rows of problems whose status is not CLR_OK are NaN.
  * clr_batch_get_solve_ms then reports this call's device time. */
 int clr_batch_forecast(clr_batch* h, int M, const double* xs, long xs_stride, double* mean, double* var);
+/* The periodogram under the plan's covariance: for every problem b and F trial angular frequencies the generalised-
+ * least-squares fit of A cos(w tau) + B sin(w tau), tau_n = t_n - t_ref, plus a constant with `offset` != 0, to the
+ * residual in force r (as clr_batch_one_step_ahead's b == NULL) with K^-1 as the metric, from the factor of the last
+ * materialising run.  omega host [F] shared by all problems (omega_stride 0) or [B][F] (omega_stride F), the xs /
+ * xs_stride convention of the point consumers.  The columns are c_n = cos(w tau_n), s_n = sin(w tau_n) evaluated as one
+ * subtraction, one product and the library's sincos; X = (c, s), K = 2, or X = (1, c, s), K = 3.  With G = X^T K^-1 X,
+ * d = X^T K^-1 r, q = r^T K^-1 r:
+ *     gram   [B][F][K+1][K+1] = [[G, d], [d^T, q]] -- clr_gram_solve's layout, its symmetric part stored symmetric;
+ *     coef   [B][F][K]        = G^-1 d: the fitted amplitudes, the offset first (on top of the mean in force);
+ *     cov    [B][F][K][K]     = G^-1;
+ *     power  [B][F]           = 1/2 d^T coef, with the offset less 1/2 d_0^2 / G_00: the gain in maximised log-likelihood
+ *                               over the model without the sinusoid (not clamped at 0);
+ *     status [B][F].
+ * Any output may be NULL, not all.  The small solve is clr_batch_fit_mean_weights' (unit-diagonal scaling, unpivoted
+ * Cholesky, min_pivot), per (b, f), the bits of clr_gram_solve on the returned gram; power is the sum above from left to
+ * right, every operation rounded on its own.  A (b, f) whose G has a diagonal entry that is not positive, or a pivot of the
+ * scaled G not above zero or below min_pivot (w = 0; with the offset a frequency far below 1 / T), has status
+ * CLR_NOT_POSITIVE_DEFINITE, coef, cov and power NaN and its gram returned; no other entry changes.  The status of the
+ * evaluation in force comes first: where it is not CLR_OK it is the status of every frequency of the problem, whose other
+ * outputs are NaN.  With K = L diag(D) L^T every inner product is sum_n z_x[n] z_y[n] / D_n, z_x = L^-1 x: the columns are
+ * formed on the fly from the resident times, whitened by the forward recurrence of clr_batch_one_step_ahead and folded
+ * into running sums (csrc/clr_bperiodogram_kernels.h) -- nothing is uploaded but the frequencies, no right-hand side is
+ * written.  A noise model in force is part of the factor.  A result's bits depend on the plan's chunking and on nothing
+ * else: not on F, the tile, the batch, the sharding or the frequency's place in omega.
+ * CLR_INVALID_ARGUMENT, the plan unchanged: F < 0, omega NULL with F > 0, a stride other than 0 or F, a non-finite
+ * frequency or t_ref, min_pivot outside [0, 1), all outputs NULL.  F == 0: CLR_OK, nothing written.  CLR_NOT_COMPUTED
+ * without a materialising run.  CLR_UNSUPPORTED: wide plans (widths 9..64; take clr_batch_set_mean_basis with (cos, sin)
+ * and clr_batch_fit_mean_weights per frequency), general terms, unchunked plans (N < 128), per-problem lengths, amplitudes
+ * in force (the resident series are y / s), B > 65535. */
+int clr_batch_periodogram(clr_batch* h, int F, const double* omega, long omega_stride, double t_ref, int offset, double min_pivot,
+                          double* power, double* coef, double* cov, double* gram, int* status);
+/* Frequencies per tile of clr_batch_periodogram; 0 (the default): as many as fit 1 GiB of scratch.  Results do not depend
+ * on it. */
+int clr_batch_set_periodogram_tile(clr_batch* h, int frequencies);
+/* Device time of the last clr_batch_periodogram's kernels (HIP events; no copies). */
+int clr_batch_get_periodogram_ms(const clr_batch* h, double* device_ms);
 /* Component separation: the posterior of the process of a GROUP of kernel terms, for G groups at M points per problem,
  * from the factor of the last materialising run:  mean_g(x) = k_g*^T K^-1 r  and  var_g(x) = k_g(0) - k_g*^T K^-1 k_g*,
  * where k_g is the sum of the group's terms and K the full kernel with its diagonal.  groups host [G][T], T = J_real +
@@ -1200,6 +1236,11 @@ int clr_sharded_predict_cov(clr_sharded* h, int M, const double* xs, long xs_str
 int clr_sharded_sample_conditional(clr_sharded* h, int M, const double* xs, long xs_stride, int size, const double* normals,
                                    double regularize, double min_pivot, double* draws, int* status);
 int clr_sharded_set_conditional_tile(clr_sharded* h, int problems);
+/* clr_batch_periodogram, every shard its slice of omega (when per problem) and of the outputs: the unsharded plan's bits. */
+int clr_sharded_periodogram(clr_sharded* h, int F, const double* omega, long omega_stride, double t_ref, int offset,
+                            double min_pivot, double* power, double* coef, double* cov, double* gram, int* status);
+int clr_sharded_set_periodogram_tile(clr_sharded* h, int frequencies);
+int clr_sharded_get_periodogram_ms(const clr_sharded* h, double* device_ms); /* the largest over the shards */
 /* `steps` back-to-back evaluations on every shard concurrently (HIP events per shard);
  * shard_ms[s] = that shard's first-to-last event time. */
 int clr_sharded_run_timed(clr_sharded* h, int steps, double* shard_ms);

@@ -47,6 +47,10 @@ int clr_batch_debug_compose_check(clr_batch* h, int group, double* max_rel_diff,
  * pivots).  Returns per-problem log det / quadratic form and the kernel's time for the whole batch. */
 int clr_batch_fp32_probe(clr_batch* h, double* logdet, double* quad, double* ms);
 
+/* Frequencies a lane of clr_batch_periodogram's walks carries at the plan's width (tests: results must not depend on how a
+ * list of frequencies falls into such blocks); 0 on a wide plan. */
+int clr_batch_debug_get_periodogram_block(const clr_batch* h, int* frequencies);
+
 #ifdef __cplusplus
 }
 #endif
